@@ -9,15 +9,22 @@ A "step" is ONE SJD iteration (= one transformer forward over the draft window +
 Where the K timed steps sit: the cost of a step grows with the KV length, so the decode first runs an UNTIMED lead-in (real SJD
 iterations from the prompt) until the KV length is such that the W warm-up + K timed steps are centred on the mean KV length of
 a whole image (P + image/2 = 1240 for 768x768; `--kv-center 0` times from the prompt as round 1 did).  At N=1 the same decode
-then continues to the end of the image, so the line also carries the MEASURED whole-image NFE / tokens/s (`whole_image`) and
-ms/step at KV lengths {64, 1216, 2368} (`per_kv`), plus bounded side legs: `floor` (1 / ms_per_step), `acceptance_probe_unscaled_embeddings` (plain random embeddings),
-`torch_baseline` (the reference's data flow in PyTorch-ROCm ops on the same weights at the same KV length: `vs_baseline`), and
-`cpu_baseline` (the oracle's scheduler step on the host cores).
+then continues to the end of the image, so the line also carries the MEASURED whole-image NFE / tokens/s (`whole_image`).  When one
+image holds fewer than W + K steps, the timed region goes on over fresh decodes of the same prompt until exactly K steps are timed.
 
-python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run stops there.  `--full` adds everything else the benchmark measures: the live kernel figures (`roofline`, `roofline_k1`),
+ms/step at KV lengths {64, 1216, 2368} (`per_kv`), and the bounded side legs: `ar_baseline`, the other BASELINE.json configurations
+(`other_configs`), `floor` (1 / ms_per_step), `acceptance_probe_unscaled_embeddings` (plain random embeddings), `torch_baseline` (the
+reference's data flow in PyTorch-ROCm ops on the same weights at the same KV length: `vs_baseline`), and `cpu_baseline` (the oracle's
+scheduler step on the host cores).
+
+python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
    N > 1 without a torch.distributed environment: re-executes itself under `python -m torch.distributed.run --nproc-per-node N`
    (one rank per GPU, RCCL); under the driver's own torchrun launch it reads RANK / LOCAL_RANK / WORLD_SIZE.  Prompt i -> rank i
    (weak scaling), no collective inside the decode, ONE all_gather of [tokens, steps, seconds] at the end.
+   --dump-outputs DIR: after the timed steps, the token sequence the decode hands its caller at the end of the last timed step
+   (DIR/tokens.npy) and that step's window (DIR/last_step_window.npy: accepted tokens, then the drafts carried on; and
+   DIR/last_step_accepted.npy), as float64.  Inputs are seeded: the same arguments give the same inputs in every run.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -79,6 +86,11 @@ def parse(argv=None):
                          "(prompt i keeps seed 1234 + i whatever N is; one all_gather at the end).  0 = the default per-rank K-step bench")
     ap.add_argument("--no-pin", action="store_true", help="multi-rank runs: do not pin each rank to its GPU's NUMA node")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the compact emu3_8b / anole7b records (BASELINE configs 3 and 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (kernel rooflines, per-KV table, AR / PyTorch / CPU baselines, other configurations, "
+                         "acceptance probe); the --no-* switches above thin this out.  Default: only the headline figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed decode computed in its last step as DIR/<name>.npy (float64 token ids)")
     return ap.parse_args(argv)
 
 
@@ -691,14 +703,18 @@ def main():
             raise SystemExit("--total-prompts decodes one prompt at a time per GPU (use --queue-prompts with --prompts-per-gpu)")
         eng.decode(prompt, spec, copy.deepcopy(grammar0), cfg, warmup_iters=0, timed_iters=args.warmup + 8)      # untimed: graph captures, allocations
         per_prompt = []
+        seqs = {}
 
         def decode_one(i):
             wi = workload_of(args, margs, rank, device, prompt_index=i)
             seq_i, st_i = eng.decode(wi["prompt"], wi["spec"], wi["grammar"], wi["cfg"])
             per_prompt.append((i, st_i.total_tokens, st_i.nfe, bool(seq_i[-1] in wi["cfg"].eos_token_ids)))
+            seqs[f"tokens_prompt{i}"] = seq_i
             return st_i.total_tokens, st_i.nfe
 
         q = run_prompt_queue(args.total_prompts, decode_one, sync=torch.cuda.synchronize, device=device)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, seqs, rank, world)
         if rank == 0:
             out = {"metric": "accepted image-tokens/s (SJD, whole images, prompt queue over the ranks; BASELINE.json config 4's shape)",
                    "value": round(q["tokens_per_s"], 2), "unit": "image-tokens/s", "n_gpus": world, "steps": int(q["steps"]), "warmup": args.warmup,
@@ -741,6 +757,8 @@ def main():
         torch.cuda.synchronize()
         capture_s = time.perf_counter() - t_cap0
     t_wall0 = time.perf_counter()
+    dumped = {}
+    extra_images = 0
     if PP > 1:
         res = eng.decode_many(prompts, specs, [copy.deepcopy(grammar) for _ in range(len(prompts))], cfg, warmup_iters=args.warmup,
                               timed_iters=args.steps, on_timed_start=sync_all, on_timed_end=sync_all)
@@ -750,17 +768,56 @@ def main():
         stats.host_seconds, stats.sync_seconds = rs["host_seconds"], rs["sync_seconds"]
         stats.timed_host_seconds, stats.timed_sync_seconds = rs["host_seconds"], rs["sync_seconds"]
         stats.kv_len_start = P
+        for i, (seq_i, _) in enumerate(res):                     # decode_many stops at the end of the timed region
+            dumped[f"tokens_prompt{i}"] = seq_i
     else:
+        def end_of_region(log, barrier):
+            # the last timed step's window as K4 left it in the state mirror (accepted tokens first, then the drafts carried on), and how many
+            # iterations had run: the sequence at this point is rebuilt from the decode's result below
+            def cb():
+                barrier()
+                if log:
+                    n_rows, m = log[-1][1], log[-1][2]
+                    st_ = eng.state.view
+                    dumped["last_step_window"] = [int(st_.tokens[i]) for i in range(n_rows)]
+                    dumped["last_step_accepted"] = [m if n_rows > 1 else 1]
+                    dumped["_iterations"] = len(log)
+            return cb
+
         seq, stats = eng.decode(prompt, spec, grammar, cfg, warmup_iters=args.warmup, timed_iters=args.steps, on_timed_start=sync_all,
-                                on_timed_end=sync_all, lead_in_kv=lead_in_kv, continue_after=whole_image, iter_log=iter_log)
+                                on_timed_end=end_of_region(iter_log, sync_all), lead_in_kv=lead_in_kv, continue_after=whole_image,
+                                iter_log=iter_log)
         if not stats.timed_region_reached:          # the image ended before the region opened: keep the other ranks' two barriers matched
             sync_all()
             sync_all()
+            raise SystemExit(f"rank {rank}: the image ended before the {args.warmup} warm-up steps were over: no step was timed")
+        # emitted tokens per iteration: one for the prefill, the accepted length after it (SJDEngine.decode)
+        seq_end = list(seq[:len(prompt) + sum(1 if r[1] <= 1 else r[2] for r in iter_log[:dumped.get("_iterations", len(iter_log))])])
+        # --steps K is the number of timed steps: when this image ended first, the region goes on over fresh decodes of the same prompt
+        # (their prefill steps included; no barriers, as ranks need different numbers of them)
+        while stats.timed_nfe < args.steps:
+            log_x = []
+            seq_end, st_x = eng.decode(prompt, spec, copy.deepcopy(grammar0), cfg, warmup_iters=0, timed_iters=args.steps - stats.timed_nfe,
+                                       on_timed_start=torch.cuda.synchronize, on_timed_end=end_of_region(log_x, torch.cuda.synchronize),
+                                       iter_log=log_x)
+            stats.seconds += st_x.seconds
+            stats.tokens += st_x.tokens
+            stats.timed_nfe += st_x.timed_nfe
+            stats.timed_host_seconds += st_x.timed_host_seconds
+            stats.timed_sync_seconds += st_x.timed_sync_seconds
+            stats.kv_len = st_x.kv_len
+            extra_images += 1
+        dumped.pop("_iterations", None)
+        dumped["tokens"] = seq_end
     decode_wall = time.perf_counter() - t_wall0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dumped, rank, world)
     kv_mid = (stats.kv_len_start + stats.kv_len) // 2
-    prof = measure_k1(args, model, attn, device, kv_len=kv_mid)
-    pair = measure_k1_pair(args, model, attn, device, kv_len=kv_mid) if args.prompts_per_gpu == 1 else None
-    prof_g1 = measure_g1(args, model, device) if (args.gemm == "sjd" and not args.no_fused) else None
+    prof = pair = prof_g1 = None
+    if args.full:
+        prof = measure_k1(args, model, attn, device, kv_len=kv_mid)
+        pair = measure_k1_pair(args, model, attn, device, kv_len=kv_mid) if args.prompts_per_gpu == 1 else None
+        prof_g1 = measure_g1(args, model, device) if (args.gemm == "sjd" and not args.no_fused) else None
     # whole image of this rank: from the end of the prefill iteration to the last iteration (host clock after each iteration's sync)
     img_tok = img_nfe = 0
     img_s = 0.0
@@ -822,22 +879,25 @@ def main():
                               "tokens_per_s_incl_capture": round((n_tok - 1) / (t_img + capture_s), 2),
                               "finished": bool(seq[-1] in cfg.eos_token_ids),
                               "reference_published_nfe": "1009-1115 (hardware unstated, BASELINE.md)" if args.model == "lumina7b" else None}
-        pts = [P, P + n_img // 2 - 24, P + n_img - 112] if args.model != "lumina7b" else [64, 1216, 2368]
-        out["per_kv"] = per_kv_table(iter_log, pts)
-        for S in pts:
-            if str(S) in out["per_kv"]:
-                k1 = measure_k1(args, model, attn, device, kv_len=S)
-                out["per_kv"][str(S)].update({"k1_us": round(k1["avg_ms"] * 1e3, 2), "k1_GBps": round(k1["gbps"], 1)})
+        if args.full:
+            pts = [P, P + n_img // 2 - 24, P + n_img - 112] if args.model != "lumina7b" else [64, 1216, 2368]
+            out["per_kv"] = per_kv_table(iter_log, pts)
+            for S in pts:
+                if str(S) in out["per_kv"]:
+                    k1 = measure_k1(args, model, attn, device, kv_len=S)
+                    out["per_kv"][str(S)].update({"k1_us": round(k1["avg_ms"] * 1e3, 2), "k1_GBps": round(k1["gbps"], 1)})
 
         # (rounds 1-3 counted the hipGraph captures inside `value`; the old basis stays readable next to the new one)
         out["value_incl_capture"] = out["whole_image"]["tokens_per_s_incl_capture"] if world == 1 else None
+    if extra_images:
+        out["config"]["timed_region_extra_decodes"] = extra_images
     out["schema"] = 5           # 5: value_incl_capture, roofline.rocprof_avg_us, torch_baseline over >= 64 steps
     r_main, r_k1 = roofline_blocks(args, prof, prof_g1, pair)
     if r_main is not None:
         out["roofline"] = r_main
     if r_k1 is not None:
         out["roofline_k1"] = r_k1
-    side_legs = (world == 1 and PP == 1)
+    side_legs = (world == 1 and PP == 1 and args.full)
     gpu_sched_ms = None
     if side_legs and not args.no_graph:
         try:
@@ -933,6 +993,14 @@ def main():
     if dist.is_initialized():
         dist.destroy_process_group()
     _print_line(out)
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64 (names carry _rank<r> when several ranks write)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def _print_line(out):

@@ -87,3 +87,20 @@ def test_per_kv_table_uses_window_iterations_near_each_point(bench):
     assert set(tab) == {"64", "1216", "2368"}
     assert tab["64"]["ms_per_step"] < tab["1216"]["ms_per_step"] < tab["2368"]["ms_per_step"]
     assert abs(tab["1216"]["ms_per_step"] - (4.0 + 1.216)) < 0.1
+
+
+def test_plain_run_is_lean_and_full_is_opt_in(bench):
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "out_dir"])
+    assert a.full is True and a.dump_outputs == "out_dir"
+
+
+def test_dump_outputs_writes_float64_npy(bench, tmp_path):
+    np = pytest.importorskip("numpy")
+    bench.dump_outputs(str(tmp_path / "d"), {"tokens": [1, 8197, 65535], "last_step_accepted": [3]})
+    t = np.load(tmp_path / "d" / "tokens.npy")
+    assert t.dtype == np.float64 and t.tolist() == [1.0, 8197.0, 65535.0]
+    assert np.load(tmp_path / "d" / "last_step_accepted.npy").tolist() == [3.0]
+    bench.dump_outputs(str(tmp_path / "d"), {"tokens": [5]}, rank=1, world=2)
+    assert np.load(tmp_path / "d" / "tokens_rank1.npy").tolist() == [5.0]

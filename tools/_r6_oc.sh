@@ -5,7 +5,7 @@ O=gpurun_out
 ALL="--no-floor --no-torch-baseline --no-ar-baseline --no-cpu-baseline --no-whole-image"
 for keep in floor torch-baseline ar-baseline cpu-baseline whole-image; do
   FL=$(echo $ALL | sed "s/--no-$keep//")
-  python bench.py --steps 64 --warmup 8 $FL > $O/r6_oc_$keep.json 2> $O/r6_oc_$keep.err
+  python bench.py --full --steps 64 --warmup 8 $FL > $O/r6_oc_$keep.json 2> $O/r6_oc_$keep.err
   python - <<PY
 import json
 try:

@@ -2,7 +2,7 @@
 # G1w for 33..64-row windows on the uncompressed stream: Emu3-8B in fp16 (BASELINE config 3 as worded), end to end, same box
 cd ${GRAFT_REPO_ROOT:-.}
 O=gpurun_out
-B="python bench.py --model emu3_8b --window 32 --steps 64 --warmup 8 --no-floor --no-torch-baseline --no-ar-baseline --no-cpu-baseline --no-whole-image --no-other-configs"
+B="python bench.py --full --model emu3_8b --window 32 --steps 64 --warmup 8 --no-floor --no-torch-baseline --no-ar-baseline --no-cpu-baseline --no-whole-image --no-other-configs"
 T='{"qkv":[1024,4,1],"o":[512,4,1],"gate_up":[2048,8,1],"down":[1792,4,1]}'
 run() {
   name=$1; shift

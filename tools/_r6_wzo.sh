@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 O=gpurun_out
 python -m pytest tests/test_gpu_glue.py -x -q -m gpu -k "g1z" 2>&1 | tail -2
-B="python bench.py --steps 64 --warmup 8 --no-floor --no-torch-baseline --no-ar-baseline --no-cpu-baseline --no-whole-image --no-other-configs"
+B="python bench.py --full --steps 64 --warmup 8 --no-floor --no-torch-baseline --no-ar-baseline --no-cpu-baseline --no-whole-image --no-other-configs"
 run() { name=$1; shift
   env "$@" > $O/r6_wzo_$name.json 2> $O/r6_wzo_$name.err
   python - <<PY
