@@ -9,6 +9,9 @@ import os
 MAX_WINDOW = 64
 MAX_RANGES = 4
 DTYPE_BF16, DTYPE_F16, DTYPE_F32 = 0, 1, 2
+# mode bits in the high bits of the glue kernels' dtype argument (include/sjd_hip.h)
+F1_POST_NORM = 0x100
+QKN_SHARDS_SHIFT = 16
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("SJD_HIP_LIB") or os.path.join(_HERE, "libsjd_hip.so")      # SJD_HIP_LIB: an instrumented build (tools/phase_trace.py)

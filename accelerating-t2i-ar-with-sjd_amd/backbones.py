@@ -270,6 +270,8 @@ class ChameleonArgs:
     rope_theta: float = 10000.0
     qk_norm: bool = True          # Chameleon/Lumina/Anole: True; Emu3 (Llama): False
     max_position_embeddings: int = 4096
+    swin_norm: bool = False       # ChameleonSwinDecoderLayer (modeling_chameleon.py:670-735): the RMSNorm after each sublayer, not before it
+    model_parallel_size: int = 1  # shards of the QK-norm gain / bias ([mp, head_dim], each row repeat-interleaved over heads / mp heads)
 
 
 class _CRMSNorm(nn.Module):
@@ -287,17 +289,21 @@ class _CRMSNorm(nn.Module):
 
 class _HeadLayerNorm(nn.Module):
     """ChameleonLayerNorm (modeling_chameleon.py:198-219): stats over head_dim, per-head gamma/beta.
-    weight/bias are stored [model_parallel_size=1, head_dim] and repeat-interleaved over heads."""
+    weight/bias are stored [model_parallel_size, head_dim]; row r serves heads [r * n_heads / mp, (r + 1) * n_heads / mp)."""
 
-    def __init__(self, head_dim, n_heads):
+    def __init__(self, head_dim, n_heads, model_parallel_size=1):
         super().__init__()
-        self.weight = nn.Parameter(torch.ones(1, head_dim))
-        self.bias = nn.Parameter(torch.zeros(1, head_dim))
+        if model_parallel_size < 1 or n_heads % model_parallel_size:
+            raise ValueError(f"model_parallel_size {model_parallel_size} must divide the {n_heads} heads of the QK-norm")
+        self.weight = nn.Parameter(torch.ones(model_parallel_size, head_dim))
+        self.bias = nn.Parameter(torch.zeros(model_parallel_size, head_dim))
         self.head_dim, self.n_heads = head_dim, n_heads
+        self.heads_per_shard = n_heads // model_parallel_size
 
     def forward(self, x):       # x [..., n_heads, head_dim]
         x = F.layer_norm(x, (self.head_dim,), None, None, eps=1e-5)
-        return x * self.weight.repeat_interleave(self.n_heads, dim=0) + self.bias.repeat_interleave(self.n_heads, dim=0)
+        return (x * self.weight.repeat_interleave(self.heads_per_shard, dim=0)
+                + self.bias.repeat_interleave(self.heads_per_shard, dim=0))
 
 
 class _CAttention(nn.Module):
@@ -310,8 +316,8 @@ class _CAttention(nn.Module):
         self.v_proj = nn.Linear(a.hidden_size, self.num_kv * self.head_dim, bias=False)
         self.o_proj = nn.Linear(a.hidden_size, a.hidden_size, bias=False)
         if a.qk_norm:
-            self.q_norm = _HeadLayerNorm(self.head_dim, self.num_heads)
-            self.k_norm = _HeadLayerNorm(self.head_dim, self.num_kv)
+            self.q_norm = _HeadLayerNorm(self.head_dim, self.num_heads, a.model_parallel_size)
+            self.k_norm = _HeadLayerNorm(self.head_dim, self.num_kv, a.model_parallel_size)
 
 
 class _CMLP(nn.Module):
@@ -350,6 +356,10 @@ def _rotate_half(x):
 class ChameleonBackbone(nn.Module):
     def __init__(self, args: ChameleonArgs, attn=None):
         super().__init__()
+        mp = args.model_parallel_size
+        if mp < 1 or args.num_attention_heads % mp or args.num_key_value_heads % mp:
+            raise ValueError(f"model_parallel_size {mp} must divide both num_attention_heads {args.num_attention_heads} and "
+                             f"num_key_value_heads {args.num_key_value_heads}")
         self.args = args
         self.model = _CModel(args)
         self.lm_head = nn.Linear(args.hidden_size, args.vocab_size, bias=False)
@@ -364,6 +374,8 @@ class ChameleonBackbone(nn.Module):
 
     def setup_cache(self, batch, s_max, dtype=None, device=None):
         p = self.lm_head.weight
+        if self.args.swin_norm and dtype is not None and str(dtype).startswith("torch.float8"):
+            raise ValueError("an fp8 KV cache is not served for swin-norm backbones (swin_norm=True): use a 16-bit cache")
         self.cache = StaticKVCache(self.n_layers, batch, self.n_kv_heads, s_max, self.head_dim, dtype or p.dtype,
                                    device or p.device)
         self.buffers_version = getattr(self, "buffers_version", 0) + 1      # captured hipGraphs hold the old cache's addresses
@@ -408,6 +420,11 @@ class ChameleonBackbone(nn.Module):
     # the same on the 12-bit stream (Emu3 in bf16, round 4): 256-workgroup launches for q|k|v and o, step-major packing -- 11.75 / 10.25 / 19.85 us
     # against 12.15 / 10.66 / 20.19 (tools/g1z_bench.py --sweep --emu3 --rows 64, profiles/r4_g1z_sweep_emu3_64rows.jsonl)
     G1_CFG_EMU3_Z = dict(qkv=(512, 6, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(896, 8, True))
+    # 30B-class Chameleon (hidden 8192, intermediate 22016, GQA 64 / 8: q|k|v 10240 columns, gate|up 44032, down K 22016); chunks <= 2560 so that
+    # the 32-row window stages its chunk in LDS.  The fastest shapes of `tools/swin30b_bench.py --sweep` at 32 rows on one MI355X
+    # (profiles/g1_30b_sweep.jsonl), us per launch uncompressed / 12-bit: q|k|v 30.4 / 25.2, o 23.8 / 20.3, gate|up 120.5 / 98.9, down 62.9 / 50.4
+    G1_CFG_30B = dict(qkv=(1536, 8, True), o=(1536, 8, False), gate_up=(2048, 8, True), down=(1536, 8, False))
+    G1_CFG_30B_Z = dict(qkv=(1792, 8, True), o=(1280, 8, True), gate_up=(2048, 8, True), down=(1536, 8, True))
 
     # Weight prefetch plan of the G1 window forward: projection -> (workgroups of the prefetch kernel, when it is issued).  The packed
     # weights of projection j+1 are read into the Infinity Cache on a side stream (a parallel branch of the forward hipGraph)
@@ -464,12 +481,15 @@ class ChameleonBackbone(nn.Module):
         a matrix that does not fit the format (fp16, or a unit with too many out-of-window weights) stays uncompressed."""
         self._ops = ops
         self._gemm = gemm
-        self._fold_norm = bool(fold_norm) and gemm == "sjd"
+        # swin-norm layers have no norm in front of a projection: nothing to fold (the unfolded window path, F1 in its post-norm form)
+        self._fold_norm = bool(fold_norm) and gemm == "sjd" and not self.args.swin_norm
         if compress is None:
             compress = _os.environ.get("SJD_G1Z", "1") != "0"
         self.compress = bool(compress) and gemm == "sjd"
         if "G1_CFG" not in self.__dict__:      # the caller has not chosen launch shapes: take the tuned set of the architecture
-            if self.n_kv_heads != self.n_heads:
+            if self.args.hidden_size >= 8192:
+                self.G1_CFG = dict(self.G1_CFG_30B_Z if self.compress and self.lm_head.weight.dtype == torch.bfloat16 else self.G1_CFG_30B)
+            elif self.n_kv_heads != self.n_heads:
                 self.G1_CFG = dict(self.G1_CFG_EMU3)
             elif self.compress and self.lm_head.weight.dtype == torch.bfloat16:
                 self.G1_CFG = dict(self.G1_CFG_Z)
@@ -597,14 +617,14 @@ class ChameleonBackbone(nn.Module):
         ops, H, Hkv, D = self._ops, self.n_heads, self.n_kv_heads, self.head_dim
         return ops.qknorm_rope_append(qkv, self.cache.k[li], self.cache.v[li], *qn, self._inv_freq32, pos, B, n, H, Hkv, D, params,
                                       kv_len if params is None else 0, kv_scale=self.attn.scale_of(li) if hasattr(self.attn, "scale_of") else (1.0, 1.0),
-                                      dtype=self.lm_head.weight.dtype, row_norm=row_norm)
+                                      dtype=self.lm_head.weight.dtype, row_norm=row_norm, qk_shards=self.args.model_parallel_size)
 
     def _attention_block(self, qkv_part, li, qn, pos, B, n, params, kv_len, key_start, row_norm=None):
         """QK-norm + RoPE + KV append + draft-window attention of one layer on the G1 partials of the q|k|v projection: kernel K1F (one
         launch) for the multi-head 16-row window, F2 then K1 (+ combine) otherwise."""
         ops, H, Hkv, D = self._ops, self.n_heads, self.n_kv_heads, self.head_dim
         ks_ok = isinstance(key_start, torch.Tensor) and key_start.is_cuda and key_start.dtype == torch.int32
-        if getattr(self, "k1_fused", _K1_FUSED_DEFAULT) and ks_ok and ops.fused_attention_ok(B, n, H, Hkv, D, self.cache.k.dtype):
+        if getattr(self, "k1_fused", _K1_FUSED_DEFAULT) and ks_ok and not self.args.swin_norm and self.args.model_parallel_size == 1 and ops.fused_attention_ok(B, n, H, Hkv, D, self.cache.k.dtype):
             ns, ws = 1, None
             if getattr(self, "k1_fused_split", _K1_FUSED_SPLIT_DEFAULT):       # K1Fs: the split form (F2 + k1_partial in one launch, then k1_combine)
                 ns = self.attn._resolve_split(B, Hkv, n, H)
@@ -693,17 +713,25 @@ class ChameleonBackbone(nn.Module):
         h = self.model.embed_tokens(tokens).view(T, -1).contiguous()
         pos = positions.reshape(T).contiguous()
         delta = None
+        swin = self.args.swin_norm
         for li, layer in enumerate(self.model.layers):
             a = layer.self_attn
-            x = ops.add_rmsnorm(h, delta, layer.input_layernorm.weight, eps)
+            # swin-norm: the projection reads h itself; each sublayer ends in ONE F1 launch in its post-norm form (h += norm(sublayer))
+            x = h if swin else ops.add_rmsnorm(h, delta, layer.input_layernorm.weight, eps)
             qkv = g1(x, "qkv", (H + 2 * Hkv) * D, hid)
             qn = (a.q_norm.weight, a.q_norm.bias, a.k_norm.weight, a.k_norm.bias) if self.args.qk_norm else (None,) * 4
             o = self._attention_block(qkv, li, qn, pos, B, n, params, kv_len, key_start)
             attn_out = g1(o.view(T, H * D), "o", hid, H * D)
-            x = ops.add_rmsnorm(h, attn_out, layer.post_attention_layernorm.weight, eps)
+            if swin:
+                x = ops.add_rmsnorm_post(h, attn_out, layer.input_layernorm.weight, eps)
+            else:
+                x = ops.add_rmsnorm(h, attn_out, layer.post_attention_layernorm.weight, eps)
             gu = g1(x, "gate_up", 2 * inter, hid)
             act = ops.silu_mul(gu, rows=T, dtype=h.dtype)
             delta = g1(act, "down", hid, inter)
+            if swin:
+                ops.add_rmsnorm_post(h, delta, layer.post_attention_layernorm.weight, eps)
+                delta = None
         x = ops.add_rmsnorm(h, delta, self.model.norm.weight, eps)
         return _head_logits(self.lm_head, x, cols).view(B, n, -1)
 
@@ -716,7 +744,7 @@ class ChameleonBackbone(nn.Module):
                                      and all(c[1] in self.G1_WIDE_TILES for c in self.G1_CFG.values()))):
             if self._fold_norm:
                 return self._forward_window_g1_folded(tokens, positions, kv_len, key_start, cols, head_partials)
-            return self._forward_window_g1(tokens, positions, kv_len, key_start, cols)
+            return self._forward_window_g1(tokens, positions, kv_len, key_start, cols)     # (swin-norm backbones: always here)
         ops, B, n = self._ops, tokens.shape[0], tokens.shape[1]
         T, eps = B * n, self.args.rms_norm_eps
         H, Hkv, D = self.n_heads, self.n_kv_heads, self.head_dim
@@ -724,15 +752,21 @@ class ChameleonBackbone(nn.Module):
         h = self.model.embed_tokens(tokens).view(T, -1).contiguous()
         pos = positions.reshape(T).contiguous()
         delta = None
+        swin = self.args.swin_norm
         for li, layer in enumerate(self.model.layers):
             a = layer.self_attn
             qkv_w, gu_w = self._fused[li]
-            x = ops.add_rmsnorm(h, delta, layer.input_layernorm.weight, eps)
+            x = h if swin else ops.add_rmsnorm(h, delta, layer.input_layernorm.weight, eps)
             qkv = F.linear(x, qkv_w)
             qn = (a.q_norm.weight, a.q_norm.bias, a.k_norm.weight, a.k_norm.bias) if self.args.qk_norm else (None,) * 4
             q = _chk(f"prefill L{li} q", self._f2(_chk(f"prefill L{li} qkv", qkv), li, qn, pos, B, n, params, kv_len))
             o = _chk(f"prefill L{li} attention", self.attn.attend(li, q, self.cache, kv_len, key_start))
             attn_out = F.linear(o.view(T, H * D), a.o_proj.weight)
+            if swin:           # (the swin-norm order: the norms sit behind the sublayers, h is the next projection's input)
+                x = _chk(f"prefill L{li} norm1", ops.add_rmsnorm_post(h, attn_out, layer.input_layernorm.weight, eps))
+                ops.add_rmsnorm_post(h, _chk(f"prefill L{li} mlp", F.linear(ops.silu_mul(F.linear(x, gu_w)), layer.mlp.down_proj.weight)),
+                                     layer.post_attention_layernorm.weight, eps)
+                continue
             x = _chk(f"prefill L{li} norm2", ops.add_rmsnorm(h, attn_out, layer.post_attention_layernorm.weight, eps))
             delta = _chk(f"prefill L{li} mlp", F.linear(ops.silu_mul(F.linear(x, gu_w)), layer.mlp.down_proj.weight))
         x = ops.add_rmsnorm(h, delta, self.model.norm.weight, eps)
@@ -749,7 +783,7 @@ class ChameleonBackbone(nn.Module):
         cos, sin = self._rope(positions, h.dtype)
         for li, layer in enumerate(self.model.layers):
             a = layer.self_attn
-            x = layer.input_layernorm(h)
+            x = h if self.args.swin_norm else layer.input_layernorm(h)
             q = a.q_proj(x).view(B, n, a.num_heads, a.head_dim)
             k = a.k_proj(x).view(B, n, a.num_kv, a.head_dim)
             v = a.v_proj(x).view(B, n, a.num_kv, a.head_dim)
@@ -758,12 +792,20 @@ class ChameleonBackbone(nn.Module):
             q = q * cos + _rotate_half(q) * sin          # modeling_chameleon.py:175-176
             k = k * cos + _rotate_half(k) * sin
             o = self.attn(li, q, k, v, self.cache, kv_len, key_start)
+            if self.args.swin_norm:          # modeling_chameleon.py:717-728: sublayer output (dtype), fp32 norm cast to dtype, gain, residual add
+                h = h + layer.input_layernorm(a.o_proj(o.reshape(B, n, -1)))
+                h = h + layer.post_attention_layernorm(layer.mlp(h))
+                continue
             h = h + a.o_proj(o.reshape(B, n, -1))
             h = h + layer.mlp(layer.post_attention_layernorm(h))
         return _head_logits(self.lm_head, self.model.norm(h), cols)   # modeling_chameleon.py:1560-1561
 
 
 LUMINA_7B = ChameleonArgs()
+# the Chameleon-30B form (swin-norm layers, QK-norm gains in four shards: convert_chameleon_weights_to_hf.py's 30B branch).  The shapes were
+# not checked against a released config.json: every test and tool takes them from here, so a correction is this one line
+CHAMELEON_30B = ChameleonArgs(vocab_size=65536, hidden_size=8192, intermediate_size=22016, num_hidden_layers=48, num_attention_heads=64,
+                              num_key_value_heads=8, model_parallel_size=4, swin_norm=True)
 EMU3_8B = ChameleonArgs(vocab_size=184622, hidden_size=4096, intermediate_size=14336, num_hidden_layers=32,
                         num_attention_heads=32, num_key_value_heads=8, rms_norm_eps=1e-5, rope_theta=1000000.0,
                         qk_norm=False, max_position_embeddings=9216)

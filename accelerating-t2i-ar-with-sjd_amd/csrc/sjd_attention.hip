@@ -1757,7 +1757,11 @@ static int k1_dispatch(const void *q, const void *k_cache, const void *v_cache, 
         return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
     }
     const int G = H / H_kv;
-    if (!(G == 1 || G == 2 || G == 4)) return SJD_ERR_UNSUPPORTED;
+    // group 8 (the 30B-class Chameleon, 64 / 8 heads): one draft window of <= 16 rows is 8 (head, chunk) pairs -- the LDS-DMA ring kernel with
+    // eight waves; 17..32 rows (two chunks) run on k1_partial with eight waves, one per head of the group (key parts 1); four-wave k1_partial
+    // (SJD_K1_WAVES=4) has no wave per head there and declines
+    if (!(G == 1 || G == 2 || G == 4 || G == 8)) return SJD_ERR_UNSUPPORTED;
+    if (G == 8 && k1_waves() != 8 && !(D == 128 && n_rows <= K1_ROWS && !getenv("SJD_K1_NO_SHARED"))) return SJD_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
 #define SJD_K1_CASE(DT_, D_) \
     if (dtype == DT_ && D == D_) return launch_attention<DT_, D_>(q, k_cache, v_cache, out, B, n_rows, H, H_kv, S_max, key_start, params, kv_len, n_split, workspace, s, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, ticket, colsplit);

@@ -84,7 +84,9 @@ __device__ __forceinline__ float wave_sum(float v)
 // ------------------------------------------------------------------------------------------------ F1
 // one 256-thread workgroup per row; hidden % 8 == 0 and hidden <= 256*8*MAXV
 // `part` (optional): fp32 split-K partials [n_chunks, 32, hidden] of the producing G1 projection; delta = dtype(sum_c part[c]).
-template <int DT>
+// POST (swin-norm layers, ChameleonSwinDecoderLayer): the norm applies to the sublayer output, not to h --
+//   h = dtype(h + dtype(w * dtype(delta * rsqrt(mean(delta^2) + eps))))   (delta or part required, y is not written)
+template <int DT, bool POST = false>
 __global__ __launch_bounds__(256) void f1_add_rmsnorm(unsigned short *__restrict__ h, const unsigned short *__restrict__ delta,
                                                       const unsigned short *__restrict__ w, unsigned short *__restrict__ y,
                                                       int hidden, float eps, const float *__restrict__ part, int n_chunks, int prows)
@@ -95,10 +97,11 @@ __global__ __launch_bounds__(256) void f1_add_rmsnorm(unsigned short *__restrict
     const unsigned short *dr = delta ? delta + (size_t)row * hidden : nullptr;
     constexpr int MAXV = 4;
     float x[MAXV][8];
+    float hp[POST ? MAXV : 1][8];                  // POST: h itself (x holds the rounded sublayer output)
     float ss = 0.f;
     int nv = 0;
     for (int c = threadIdx.x * 8; c < hidden && nv < MAXV; c += 256 * 8, ++nv) {
-        unpack8<DT>(*reinterpret_cast<const u32x4 *>(hr + c), x[nv]);
+        unpack8<DT>(*reinterpret_cast<const u32x4 *>(hr + c), POST ? hp[POST ? nv : 0] : x[nv]);
         if (dr || part) {
             float d[8];
             if (part) {
@@ -130,9 +133,14 @@ __global__ __launch_bounds__(256) void f1_add_rmsnorm(unsigned short *__restrict
             } else {
                 unpack8<DT>(*reinterpret_cast<const u32x4 *>(dr + c), d);
             }
+            if constexpr (POST) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) x[nv][j] = Cvt<DT>::to_f(Cvt<DT>::from_f(x[nv][j] + d[j]));   // residual add rounds to the activation dtype
-            *reinterpret_cast<u32x4 *>(hr + c) = pack8<DT>(x[nv]);
+                for (int j = 0; j < 8; ++j) x[nv][j] = d[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) x[nv][j] = Cvt<DT>::to_f(Cvt<DT>::from_f(x[nv][j] + d[j]));   // residual add rounds to the activation dtype
+                *reinterpret_cast<u32x4 *>(hr + c) = pack8<DT>(x[nv]);
+            }
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) ss += x[nv][j] * x[nv][j];
@@ -148,14 +156,20 @@ __global__ __launch_bounds__(256) void f1_add_rmsnorm(unsigned short *__restrict
         unpack8<DT>(*reinterpret_cast<const u32x4 *>(w + c), wv);
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = wv[j] * Cvt<DT>::to_f(Cvt<DT>::from_f(x[nv][j] * inv));   // weight * hidden.to(dtype)
-        *reinterpret_cast<u32x4 *>(y + (size_t)row * hidden + c) = pack8<DT>(o);
+        if constexpr (POST) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = Cvt<DT>::to_f(Cvt<DT>::from_f(hp[nv][j] + Cvt<DT>::to_f(Cvt<DT>::from_f(o[j]))));   // residual + norm, both rounded
+            *reinterpret_cast<u32x4 *>(hr + c) = pack8<DT>(o);
+        } else {
+            *reinterpret_cast<u32x4 *>(y + (size_t)row * hidden + c) = pack8<DT>(o);
+        }
     }
 }
 
 // F1 for a G1 producer: the residual delta arrives as fp32 split-K partials [n_chunks, 32, hidden].  Only `rows` (<= 32)
 // workgroups exist, so the kernel is bound by how many loads ONE CU keeps in flight: 1024 threads, 4 columns each per 4096-column
-// stripe, and all chunk loads of a stripe are issued before the first add.
-template <int DT>
+// stripe, and all chunk loads of a stripe are issued before the first add.  POST: the swin-norm form of f1_add_rmsnorm (h is written last).
+template <int DT, bool POST = false>
 __global__ __launch_bounds__(1024) void f1p_add_rmsnorm(unsigned short *__restrict__ h, const float *__restrict__ part, int n_chunks,
                                                         const unsigned short *__restrict__ w, unsigned short *__restrict__ y,
                                                         int hidden, float eps, int prows)
@@ -167,10 +181,12 @@ __global__ __launch_bounds__(1024) void f1p_add_rmsnorm(unsigned short *__restri
     unsigned short *hr = h + (size_t)row * hidden;
     const size_t cstride = (size_t)prows * hidden;
     float x[MAXS][4];
+    uint2 hkeep[POST ? MAXS : 1];                  // POST: h as loaded (x holds the rounded sublayer output)
     float ss = 0.f;
     int ns = 0;
     for (int c = threadIdx.x * 4; c < hidden && ns < MAXS; c += 4096, ++ns) {
         const uint2 hv = *reinterpret_cast<const uint2 *>(hr + c);
+        if constexpr (POST) hkeep[ns] = hv;
         const float *p0 = part + (size_t)row * hidden + c;
         float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
         for (int c0 = 0; c0 < n_chunks; c0 += MAXC) {
@@ -185,6 +201,15 @@ __global__ __launch_bounds__(1024) void f1p_add_rmsnorm(unsigned short *__restri
         const float hx[4] = {Cvt<DT>::to_f((unsigned short)(hv.x & 0xffffu)), Cvt<DT>::to_f((unsigned short)(hv.x >> 16)),
                              Cvt<DT>::to_f((unsigned short)(hv.y & 0xffffu)), Cvt<DT>::to_f((unsigned short)(hv.y >> 16))};
         const float dd[4] = {d0, d1, d2, d3};
+        if constexpr (POST) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                x[ns][j] = Cvt<DT>::to_f(Cvt<DT>::from_f(dd[j]));                         // the sublayer output rounds to the activation dtype
+                ss += x[ns][j] * x[ns][j];
+            }
+            (void)hx;
+            continue;
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float dj = Cvt<DT>::to_f(Cvt<DT>::from_f(dd[j]));                       // projection output rounds to the activation dtype
@@ -211,10 +236,17 @@ __global__ __launch_bounds__(1024) void f1p_add_rmsnorm(unsigned short *__restri
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = ww[j] * Cvt<DT>::to_f(Cvt<DT>::from_f(x[ns][j] * inv));
+        if constexpr (POST) {                      // h + dtype(gain * norm), rounded like the reference's residual add
+            const uint2 hv = hkeep[ns];
+            const float hx[4] = {Cvt<DT>::to_f((unsigned short)(hv.x & 0xffffu)), Cvt<DT>::to_f((unsigned short)(hv.x >> 16)),
+                                 Cvt<DT>::to_f((unsigned short)(hv.y & 0xffffu)), Cvt<DT>::to_f((unsigned short)(hv.y >> 16))};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = hx[j] + Cvt<DT>::to_f(Cvt<DT>::from_f(o[j]));
+        }
         uint2 yo;
         yo.x = (unsigned)Cvt<DT>::from_f(o[0]) | ((unsigned)Cvt<DT>::from_f(o[1]) << 16);
         yo.y = (unsigned)Cvt<DT>::from_f(o[2]) | ((unsigned)Cvt<DT>::from_f(o[3]) << 16);
-        *reinterpret_cast<uint2 *>(y + (size_t)row * hidden + c) = yo;
+        *reinterpret_cast<uint2 *>((POST ? hr : y + (size_t)row * hidden) + c) = yo;
     }
 }
 
@@ -336,7 +368,7 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
     const unsigned short *__restrict__ kn_w, const unsigned short *__restrict__ kn_b, const float *__restrict__ inv_freq,
     const long *__restrict__ positions, int B, int n, int H, int H_kv, int S_max, const sjd_iter_params *__restrict__ params,
     int kv_len_arg, const float *__restrict__ part, int n_chunks, int prows, float k_inv, float v_inv,
-    const float *__restrict__ row_sumsq, int rs_slices, float rs_inv_hidden, float rs_eps)
+    const float *__restrict__ row_sumsq, int rs_slices, float rs_inv_hidden, float rs_eps, int hps_q, int hps_k)
 {
     SJD_TRG(1, 0);
     constexpr int HALF = D / 2;
@@ -363,7 +395,11 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
     const bool has_norm = gw_ != nullptr && (is_q || is_k);           // (wave-uniform)
     const int la = active ? lane : 0;
     unsigned short nw0 = 0, nw1 = 0, nb0 = 0, nb1 = 0;
-    if (has_norm) { nw0 = gw_[la]; nw1 = gw_[la + HALF]; nb0 = gb_[la]; nb1 = gb_[la + HALF]; }
+    if (has_norm) {
+        const int hps = is_q ? hps_q : hps_k;                 // sharded gains ([mp, D], swin-norm checkpoints): row head / heads_per_shard
+        const size_t nrow = hps ? (size_t)(hl / hps) * D : 0; //   (a scalar offset: the loads stay where they are)
+        nw0 = gw_[nrow + la]; nw1 = gw_[nrow + la + HALF]; nb0 = gb_[nrow + la]; nb1 = gb_[nrow + la + HALF];
+    }
     const float ifr = inv_freq[la];
     const long posv = positions[tok];
     if (part) {                                               // fp32 split-K partials of the qkv projection (G1)
@@ -514,15 +550,18 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
 // dependent round trips.  Here a wave takes HPW consecutive heads of one kind (q, k or v) of its token: the planes of all HPW heads are requested
 // together, the angle is computed once.  Element for element the arithmetic of f2_qknorm_rope_append (same sums in chunk order, same roundings),
 // so q and the cache rows are bit-identical; used for windows of more than 64 rows read from split-K partials.
-template <int DT, int D, bool KV8, int HPW>
+// SHARD (sharded QK-norm gains, [mp, D]): the HPW heads of a wave may belong to different shards, so each head loads its own row (all in
+// the same early batch); without it one row serves the wave, as before.
+template <int DT, int D, bool KV8, int HPW, bool SHARD = false>
 __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
     unsigned short *__restrict__ q_out, unsigned short *__restrict__ k_cache, unsigned short *__restrict__ v_cache,
     const unsigned short *__restrict__ qn_w, const unsigned short *__restrict__ qn_b, const unsigned short *__restrict__ kn_w,
     const unsigned short *__restrict__ kn_b, const float *__restrict__ inv_freq, const long *__restrict__ positions, int B, int n, int H, int H_kv,
     int S_max, const sjd_iter_params *__restrict__ params, int kv_len_arg, const float *__restrict__ part, int n_chunks, int prows, float k_inv,
-    float v_inv, const float *__restrict__ row_sumsq, int rs_slices, float rs_inv_hidden, float rs_eps)
+    float v_inv, const float *__restrict__ row_sumsq, int rs_slices, float rs_inv_hidden, float rs_eps, int hps_q, int hps_k)
 {
     constexpr int HALF = D / 2;
+    constexpr int NG = SHARD ? HPW : 1;                       // gain / bias rows held per lane
     const int lane = threadIdx.x & 63;
     const int gw = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int heads = H + 2 * H_kv, groups = heads / HPW;
@@ -538,8 +577,16 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
     const unsigned short *gw_ = is_q ? qn_w : kn_w, *gb_ = is_q ? qn_b : kn_b;
     const bool has_norm = gw_ != nullptr && (is_q || is_k);
     const int la = active ? lane : 0;
-    unsigned short nw0 = 0, nw1 = 0, nb0 = 0, nb1 = 0;
-    if (has_norm) { nw0 = gw_[la]; nw1 = gw_[la + HALF]; nb0 = gb_[la]; nb1 = gb_[la + HALF]; }
+    unsigned short nw0[NG], nw1[NG], nb0[NG], nb1[NG];
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        nw0[j] = 0; nw1[j] = 0; nb0[j] = 0; nb1[j] = 0;
+        if (has_norm) {
+            const int hps = is_q ? hps_q : hps_k;
+            const size_t nrow = (SHARD && hps) ? (size_t)((hl0 + j) / hps) * D : 0;
+            nw0[j] = gw_[nrow + la]; nw1[j] = gw_[nrow + la + HALF]; nb0[j] = gb_[nrow + la]; nb1[j] = gb_[nrow + la + HALF];
+        }
+    }
     const float ifr = inv_freq[la];
     const long posv = positions[tok];
     float ssv[8];
@@ -567,7 +614,9 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
     int kv_len = kv_len_arg, n_unused_ = 0;
     if (params) sjdi_kv_rows(params, b, &kv_len, &n_unused_);
 #ifndef F2_NO_PIN
-    asm volatile("" :: "v"(nw0), "v"(nw1), "v"(nb0), "v"(nb1), "v"(ifr), "s"(posv));
+#pragma unroll
+    for (int j = 0; j < NG; ++j) asm volatile("" :: "v"(nw0[j]), "v"(nw1[j]), "v"(nb0[j]), "v"(nb1[j]));
+    asm volatile("" :: "v"(ifr), "s"(posv));
 #endif
     float ss_tot = 0.f;                                       // row_sumsq_total's order
 #pragma unroll
@@ -603,9 +652,10 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
         return;
     }
     if (gw_ != nullptr) {                                     // per-head LayerNorm over head_dim (eps 1e-5)
-        const float w0 = Cvt<DT>::to_f(nw0), w1 = Cvt<DT>::to_f(nw1), b0 = Cvt<DT>::to_f(nb0), b1 = Cvt<DT>::to_f(nb1);
 #pragma unroll
         for (int j = 0; j < HPW; ++j) {
+            const int jg = SHARD ? j : 0;
+            const float w0 = Cvt<DT>::to_f(nw0[jg]), w1 = Cvt<DT>::to_f(nw1[jg]), b0 = Cvt<DT>::to_f(nb0[jg]), b1 = Cvt<DT>::to_f(nb1[jg]);
             const float mean = wave_sum(active ? x0[j] + x1[j] : 0.f) / (float)D;
             const float d0 = x0[j] - mean, d1 = x1[j] - mean;
             const float var = wave_sum(active ? d0 * d0 + d1 * d1 : 0.f) / (float)D;
@@ -706,26 +756,32 @@ __global__ __launch_bounds__(256) void f3_silu_mul(const unsigned short *__restr
 extern "C" int sjd_add_rmsnorm(void *h, const void *delta, const void *weight, void *y, int rows, int hidden, float eps, int dtype,
                                const float *part, int n_chunks, void *stream)
 {
+    const int mode = dtype & ~SJD_DTYPE_MASK;
+    dtype &= SJD_DTYPE_MASK;
+    if (mode & ~SJD_F1_POST_NORM) return SJD_ERR_UNSUPPORTED;
+    const bool post = (mode & SJD_F1_POST_NORM) != 0;
     if (part && (rows > 256 || n_chunks < 1)) return SJD_ERR_BAD_ARG;
+    if (post && !delta && !part) return SJD_ERR_BAD_ARG;         // the post-norm form normalises the sublayer output: there must be one
     const int prows = ((rows + 31) / 32) * 32;      // row padding of the G1 partials
-    if (!h || !weight || !y || rows < 1 || hidden < 8 || (hidden % 8) != 0 || hidden > 256 * 8 * 4) return SJD_ERR_BAD_ARG;
+    // (hidden <= 8192 for the 256-thread kernel; the post-norm form of the 1024-thread plane kernel serves up to 16384)
+    const int hidden_cap = (post && part) ? 16384 : 256 * 8 * 4;
+    if (!h || !weight || (!y && !post) || rows < 1 || hidden < 8 || (hidden % 8) != 0 || hidden > hidden_cap) return SJD_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (part && (hidden % 4) == 0 && hidden <= 16384 && (dtype == SJD_DTYPE_BF16 || dtype == SJD_DTYPE_F16)) {
-        if (dtype == SJD_DTYPE_BF16)
-            hipLaunchKernelGGL(f1p_add_rmsnorm<SJD_DTYPE_BF16>, dim3(rows), dim3(1024), 0, s, (unsigned short *)h, part, n_chunks,
-                               (const unsigned short *)weight, (unsigned short *)y, hidden, eps, prows);
-        else
-            hipLaunchKernelGGL(f1p_add_rmsnorm<SJD_DTYPE_F16>, dim3(rows), dim3(1024), 0, s, (unsigned short *)h, part, n_chunks,
-                               (const unsigned short *)weight, (unsigned short *)y, hidden, eps, prows);
+#define SJD_F1P(DT_, POST_) hipLaunchKernelGGL((f1p_add_rmsnorm<DT_, POST_>), dim3(rows), dim3(1024), 0, s, (unsigned short *)h, part, n_chunks, \
+                                               (const unsigned short *)weight, (unsigned short *)y, hidden, eps, prows)
+        if (dtype == SJD_DTYPE_BF16) { if (post) SJD_F1P(SJD_DTYPE_BF16, true); else SJD_F1P(SJD_DTYPE_BF16, false); }
+        else { if (post) SJD_F1P(SJD_DTYPE_F16, true); else SJD_F1P(SJD_DTYPE_F16, false); }
+#undef SJD_F1P
         return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
     }
-    if (dtype == SJD_DTYPE_BF16)
-        hipLaunchKernelGGL(f1_add_rmsnorm<SJD_DTYPE_BF16>, dim3(rows), dim3(256), 0, s, (unsigned short *)h, (const unsigned short *)delta,
-                           (const unsigned short *)weight, (unsigned short *)y, hidden, eps, part, n_chunks, prows);
-    else if (dtype == SJD_DTYPE_F16)
-        hipLaunchKernelGGL(f1_add_rmsnorm<SJD_DTYPE_F16>, dim3(rows), dim3(256), 0, s, (unsigned short *)h, (const unsigned short *)delta,
-                           (const unsigned short *)weight, (unsigned short *)y, hidden, eps, part, n_chunks, prows);
+#define SJD_F1(DT_, POST_) hipLaunchKernelGGL((f1_add_rmsnorm<DT_, POST_>), dim3(rows), dim3(256), 0, s, (unsigned short *)h,                \
+                                              (const unsigned short *)delta, (const unsigned short *)weight, (unsigned short *)y, hidden, eps, \
+                                              part, n_chunks, prows)
+    if (dtype == SJD_DTYPE_BF16) { if (post) SJD_F1(SJD_DTYPE_BF16, true); else SJD_F1(SJD_DTYPE_BF16, false); }
+    else if (dtype == SJD_DTYPE_F16) { if (post) SJD_F1(SJD_DTYPE_F16, true); else SJD_F1(SJD_DTYPE_F16, false); }
     else return SJD_ERR_UNSUPPORTED;
+#undef SJD_F1
     return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
 }
 
@@ -734,6 +790,12 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
                      int dtype, const sjd_iter_params *params, int kv_len, const float *part, int n_chunks, bool kv8, float k_scale,
                      float v_scale, const sjd_row_norm *rn, void *stream)
 {
+    // the mode bits of `dtype`: SJD_QKN_SHARDS(mp) -- QK-norm gain / bias stored [mp, D], head h of q uses row h / (H / mp), of k h / (H_kv / mp)
+    if (dtype & ~(SJD_DTYPE_MASK | SJD_QKN_SHARDS_MASK)) return SJD_ERR_UNSUPPORTED;
+    const int shards = (dtype & SJD_QKN_SHARDS_MASK) >> SJD_QKN_SHARDS_SHIFT;
+    dtype &= SJD_DTYPE_MASK;
+    if (shards > 1 && (H % shards != 0 || H_kv % shards != 0)) return SJD_ERR_BAD_ARG;
+    const int hps_q = shards > 1 ? H / shards : 0, hps_k = shards > 1 ? H_kv / shards : 0;     // heads per shard (0: one shared row)
     if (part && (B * n > 256 || n_chunks < 1)) return SJD_ERR_BAD_ARG;
     if (rn && (!part || !rn->sumsq || rn->slices < 1 || rn->hidden < 1)) return SJD_ERR_BAD_ARG;
     const int prows = ((B * n + 31) / 32) * 32;
@@ -747,13 +809,14 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
     const bool rows_ok = !(f2r_env && f2r_env[0] == '0');
     if (rows_ok && part && B * n > 64 && (H % 4) == 0 && (H_kv % 4) == 0 && D == 128 && dtype == SJD_DTYPE_BF16) {
         const dim3 g2((B * n * ((H + 2 * H_kv) / 4) + 3) / 4);
-#define SJD_F2R(KV8_)                                                                                                                      \
-        hipLaunchKernelGGL((f2_qknorm_rope_append_rows<SJD_DTYPE_BF16, 128, KV8_, 4>), g2, block, 0, s, (unsigned short *)q_out,           \
+#define SJD_F2R(KV8_, SH_)                                                                                                                 \
+        hipLaunchKernelGGL((f2_qknorm_rope_append_rows<SJD_DTYPE_BF16, 128, KV8_, 4, SH_>), g2, block, 0, s, (unsigned short *)q_out,      \
                            (unsigned short *)k_cache, (unsigned short *)v_cache, (const unsigned short *)qn_w, (const unsigned short *)qn_b, \
                            (const unsigned short *)kn_w, (const unsigned short *)kn_b, inv_freq, (const long *)positions, B, n, H, H_kv,    \
                            S_max, params, kv_len, part, n_chunks, prows, kv8 ? 1.0f / k_scale : 1.0f, kv8 ? 1.0f / v_scale : 1.0f,          \
-                           rn ? rn->sumsq : nullptr, rn ? rn->slices : 0, rn ? 1.0f / (float)rn->hidden : 0.f, rn ? rn->eps : 0.f)
-        if (kv8) SJD_F2R(true); else SJD_F2R(false);
+                           rn ? rn->sumsq : nullptr, rn ? rn->slices : 0, rn ? 1.0f / (float)rn->hidden : 0.f, rn ? rn->eps : 0.f, hps_q, hps_k)
+        if (shards > 1) { if (kv8) SJD_F2R(true, true); else SJD_F2R(false, true); }
+        else { if (kv8) SJD_F2R(true, false); else SJD_F2R(false, false); }
 #undef SJD_F2R
         return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
     }
@@ -764,7 +827,7 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
                            (const unsigned short *)qn_b, (const unsigned short *)kn_w, (const unsigned short *)kn_b, inv_freq,              \
                            (const long *)positions, B, n, H, H_kv, S_max, params, kv_len, part, n_chunks, prows,                           \
                            kv8 ? 1.0f / k_scale : 1.0f, kv8 ? 1.0f / v_scale : 1.0f, rn ? rn->sumsq : nullptr, rn ? rn->slices : 0,         \
-                           rn ? 1.0f / (float)rn->hidden : 0.f, rn ? rn->eps : 0.f);                                                       \
+                           rn ? 1.0f / (float)rn->hidden : 0.f, rn ? rn->eps : 0.f, hps_q, hps_k);                                         \
         return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;                                                                   \
     }
     SJD_F2_CASE(SJD_DTYPE_BF16, 128, false)

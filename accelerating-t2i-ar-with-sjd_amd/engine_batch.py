@@ -42,6 +42,10 @@ class _Slot:
 
 class SJDBatchEngine:
     def __init__(self, backbone, vocab_size, device, n_prompts, max_window=16, n_batch=2, use_graph=True, narrow_head=True, head_partials=True):
+        bargs = getattr(backbone, "args", None)
+        if getattr(bargs, "swin_norm", False) or getattr(bargs, "model_parallel_size", 1) != 1:
+            raise ValueError("SJDBatchEngine does not serve swin-norm backbones (swin_norm=True or model_parallel_size > 1, the 30B-class "
+                             "Chameleon form): decode them one prompt at a time with SJDEngine / FlexARInferenceSolver")
         L.load()                                   # fail loudly if the HIP extension is missing
         if max_window > L.MAX_WINDOW:
             raise ValueError(f"max_window {max_window} > {L.MAX_WINDOW}")

@@ -80,7 +80,8 @@ class FlexARInferenceSolver:
                                 num_key_value_heads=cfg.get("num_key_value_heads", cfg["num_attention_heads"]),
                                 rms_norm_eps=cfg.get("rms_norm_eps", 1e-5), rope_theta=cfg.get("rope_theta", 10000.0),
                                 qk_norm=bool(cfg.get("qk_norm", str(cfg.get("model_type", "chameleon")).lower().startswith("chameleon"))),
-                                max_position_embeddings=cfg.get("max_position_embeddings", 4096))
+                                max_position_embeddings=cfg.get("max_position_embeddings", 4096),
+                                swin_norm=bool(cfg.get("swin_norm", False)), model_parallel_size=int(cfg.get("model_parallel_size", 1)))
         model = BB.ChameleonBackbone(args)
         sd = {}
         for f in sorted(os.listdir(model_path)):

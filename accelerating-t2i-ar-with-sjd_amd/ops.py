@@ -825,6 +825,17 @@ def add_rmsnorm(h, delta, weight, eps):
     return y
 
 
+def add_rmsnorm_post(h, delta, weight, eps):
+    """F1 in the swin-norm order (ChameleonSwinDecoderLayer): h [T, hidden] += dtype(weight * dtype(rmsnorm(delta))) in place, delta = a
+    sublayer output (a tensor, or the Partials of a G1 projection); returns h, which is the next projection's input as it stands."""
+    T, hidden = h.shape
+    d, part, nc = _part_args(delta)
+    assert delta is not None and h.is_contiguous() and (d is None or d.is_contiguous()) and weight.is_contiguous()
+    L.check(L.load().sjd_add_rmsnorm(_ptr(h), _ptr(d), _ptr(weight), None, T, hidden, float(eps), _dtype_code(h.dtype) | L.F1_POST_NORM,
+                                    part, nc, _stream()), "sjd_add_rmsnorm")
+    return h
+
+
 def _row_norm(row_norm):
     """(sumsq [slices, R] fp32, hidden, eps) -> ctypes pointer to an sjd_row_norm (or None)"""
     if row_norm is None:
@@ -837,11 +848,12 @@ def _row_norm(row_norm):
 
 
 def qknorm_rope_append(qkv, k_cache, v_cache, qn_w, qn_b, kn_w, kn_b, inv_freq, positions, B, n, H, H_kv, D, params, kv_len,
-                       kv_scale=(1.0, 1.0), dtype=None, row_norm=None):
+                       kv_scale=(1.0, 1.0), dtype=None, row_norm=None, qk_shards=1):
     """qkv [B*n, (H+2Hkv)*D] (tensor or G1 Partials) -> q [B,n,H,D]; k/v rows are written into k_cache/v_cache [B,Hkv,S,D].
     An fp8 cache (dtype FP8) receives fp8(x / scale) with kv_scale = (k, v); `dtype` = the activation dtype (needed with Partials
     into an fp8 cache, where no 16-bit tensor is around to tell).  row_norm = (sumsq, hidden, eps): the projection ran on the
-    un-normalised residual stream with the norm gain folded into its weight; the row scale is applied here (folded-norm path)."""
+    un-normalised residual stream with the norm gain folded into its weight; the row scale is applied here (folded-norm path).
+    qk_shards = mp > 1: the QK-norm gains / biases are [mp, D] (model_parallel_size mp), head h of q uses row h // (H // mp), of k h // (Hkv // mp)."""
     t, part, nc = _part_args(qkv)
     assert (t is None or t.is_contiguous()) and positions.is_contiguous() and positions.dtype == torch.int64
     assert inv_freq.dtype == torch.float32 and inv_freq.is_contiguous()
@@ -851,7 +863,8 @@ def qknorm_rope_append(qkv, k_cache, v_cache, qn_w, qn_b, kn_w, kn_b, inv_freq, 
     q = torch.empty(B, n, H, D, dtype=act, device=k_cache.device)
     L.check(L.load().sjd_qknorm_rope_append_ex(_ptr(t), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(qn_w), _ptr(qn_b), _ptr(kn_w),
                                               _ptr(kn_b), _ptr(inv_freq), _ptr(positions), B, n, H, H_kv, D, k_cache.shape[2],
-                                              _dtype_code(act), int(fp8), float(kv_scale[0]), float(kv_scale[1]), _row_norm(row_norm),
+                                              _dtype_code(act) | (int(qk_shards) << L.QKN_SHARDS_SHIFT if qk_shards > 1 else 0), int(fp8),
+                                              float(kv_scale[0]), float(kv_scale[1]), _row_norm(row_norm),
                                               params.ptr if params is not None else None, int(kv_len), part, nc, _stream()),
             "sjd_qknorm_rope_append")
     return q

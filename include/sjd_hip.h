@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define SJD_VERSION 100
+#define SJD_VERSION 101
 #define SJD_MAX_WINDOW 64      /* max draft-window length L (reference max_num_new_tokens: 16 / 32 by default, a free CLI argument of eval_model.py:76;
                                   64 = one wavefront of accept tests in K4, 128 forward rows with CFG) */
 #define SJD_MAX_RANGES 4
@@ -33,6 +33,23 @@ extern "C" {
 #define SJD_DTYPE_BF16 0
 #define SJD_DTYPE_F16 1
 #define SJD_DTYPE_F32 2        /* K1/K3 only: exact-fp32 VALU variant for small parity runs (not a performance path) */
+
+/* Mode bits in the high bits of the `dtype` argument of the glue entry points (version 101).  dtype & SJD_DTYPE_MASK is the dtype code
+ * above; a value without mode bits selects the plain kernels, bit for bit as before.  An entry point given a bit it does not know returns
+ * SJD_ERR_UNSUPPORTED.
+ *   SJD_F1_POST_NORM      sjd_add_rmsnorm: the swin-norm order of ChameleonSwinDecoderLayer (reference modeling_chameleon.py:670-735),
+ *                         h += dtype(weight * dtype(rmsnorm(delta)))  with delta = dtype(sum of the planes `part`) or the dense `delta` (one
+ *                         of them required); every step rounds to `dtype` where ChameleonRMSNorm and the residual add do.  y is not
+ *                         written (may be NULL): h is the next projection's input as it stands.  rows <= 256 with planes; hidden <= 16384
+ *                         with planes, <= 8192 with a dense delta.
+ *   SJD_QKN_SHARDS(mp)    sjd_qknorm_rope_append / _ex / _fp8: the QK-norm gain and bias are stored [mp, D] (ChameleonLayerNorm with
+ *                         model_parallel_size mp, modeling_chameleon.py:198-219); q head h uses row h / (H / mp), k head h row h / (H_kv / mp).
+ *                         mp must divide H and H_kv (SJD_ERR_BAD_ARG otherwise); mp 0 or 1 = one shared [D] row. */
+#define SJD_DTYPE_MASK 0xff
+#define SJD_F1_POST_NORM 0x100
+#define SJD_QKN_SHARDS_SHIFT 16
+#define SJD_QKN_SHARDS_MASK (0xff << SJD_QKN_SHARDS_SHIFT)
+#define SJD_QKN_SHARDS(mp) ((int)(mp) << SJD_QKN_SHARDS_SHIFT)
 
 /* One row of the "3-dim" logits processors, reduced to what the kernels need.  Built on the host from
  * integer grammar state; replaces MultiTokensVLLogitsProcessor / MultiTokensInterleavedTopKLogitsWarper /
