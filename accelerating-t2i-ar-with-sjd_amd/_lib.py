@@ -11,6 +11,7 @@ MAX_RANGES = 4
 DTYPE_BF16, DTYPE_F16, DTYPE_F32 = 0, 1, 2
 # mode bits in the high bits of the glue kernels' dtype argument (include/sjd_hip.h)
 F1_POST_NORM = 0x100
+F2_ROPE_TABLE = 0x200
 QKN_SHARDS_SHIFT = 16
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -131,6 +131,15 @@ def _rope_2d_table(grid_size, n_elem, base, cls_token_num):
     return torch.cat([torch.zeros(cls_token_num, n_elem // 2, 2), cache])
 
 
+def _rope_table_extended(freqs, s_max):
+    """the (cos, sin) table F2 reads on the fused path: one row per cache position (>= s_max rows); the rows past cls + grid^2 repeat the
+    last real row, which is what forward_embeds' positions.clamp(max=len - 1) reads there"""
+    f = freqs.float()
+    if s_max > f.shape[0]:
+        f = torch.cat([f, f[-1:].expand(s_max - f.shape[0], -1, -1)])
+    return f.contiguous()
+
+
 def _apply_rope_interleaved(x, freqs):
     """llamagen.py:457-467.  x [B,n,H,D], freqs [B or 1,n,D/2,2]"""
     xs = x.float().reshape(*x.shape[:-1], -1, 2)
@@ -230,6 +239,7 @@ class LlamaGenBackbone(nn.Module):
                                    device or p.device)
         self.buffers_version = getattr(self, "buffers_version", 0) + 1
         self.freqs = self.freqs.to(p.device)
+        self._rope_ext = _rope_table_extended(self.freqs, s_max)
         return self.cache
 
     def embed_condition(self, cond):
@@ -253,8 +263,101 @@ class LlamaGenBackbone(nn.Module):
             h = h + layer.feed_forward(layer.ffn_norm(h))
         return _head_logits(self.output, self.norm(h), cols)
 
-    def forward_window(self, tokens, positions, kv_len, key_start, cols=None):
+    def forward_window(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
+        """head_partials: on the fused G1 window path return an ops.HeadOut (the output head's split-K partials for kernel K2) instead
+        of fp32 logits; longer inputs (prefill) run forward_embeds and return logits as usual."""
+        if getattr(self, "_ops", None) is not None and tokens.shape[0] * tokens.shape[1] <= 64:
+            return self._forward_window_g1(tokens, positions, kv_len, key_start, cols, head_partials)
         return self.forward_embeds(self.tok_embeddings(tokens), positions, kv_len, key_start, cols=cols)
+
+    # G1 launch shapes of the window forward (<= 64 rows): (split-K chunk, column tiles per workgroup, step-major packing) per projection and for
+    # the output head.  `tools/llamagen_bench.py --sweep` at 32 rows, GPT-XL (profiles/llamagen_g1_sweep.jsonl): per projection the fastest shape
+    # with at most eight split-K planes (one batch of plane loads in F1r / F2 / F3), us per launch q|k|v 5.36, o 4.46, gate|up 6.64, down 6.35,
+    # head 10.09 (the launch-alone optimum, KC 128, is 0.3 - 1.4 us faster but leaves 10 - 28 planes for the consumer to sum)
+    G1_CFG_LLAMAGEN = dict(qkv=(256, 2, True), o=(256, 2, False), gate_up=(320, 2, False), down=(512, 2, False))
+    HEAD_CFG = (640, 4, True)
+
+    def enable_fused(self, ops, gemm="sjd"):
+        """Switch draft windows of <= 64 rows to the hand-written HIP path: per layer F1r, G1 q|k|v, F2 (the interleaved rotary from a
+        table, SJD_F2_ROPE_TABLE), K1, G1 o, F1r, G1 gate|up (+ F3, or G1s where ops.gateup_silu_ok allows), G1 down; then the output head
+        on G1, whose split-K partials K2 reads (head_partials).  The RMSNorm gains are folded into packed copies of the weights (the
+        norm becomes a row scale applied by F2 / F3 / K2, as ChameleonBackbone's folded path does).  w1 / w3 are concatenated once into
+        [w1; w3] (gate | up) and re-pointed at its halves (state dict unchanged).  The prefill and longer inputs stay on forward_embeds.
+        `ops` is sjd_amd.ops.  Raises ValueError for what the kernels do not serve."""
+        if gemm != "sjd":
+            raise ValueError(f"LlamaGenBackbone.enable_fused serves gemm='sjd' only (the G1 weight-streaming kernels), got gemm={gemm!r}")
+        dt = self.output.weight.dtype
+        if dt not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"LlamaGenBackbone.enable_fused needs 16-bit weights (bf16 or fp16), got {dt}")
+        if self.head_dim not in (64, 128):
+            raise ValueError(f"LlamaGenBackbone.enable_fused: head_dim {self.head_dim} is not served (F2's table rotary takes head_dim 64 or 128)")
+        if "G1_CFG" not in self.__dict__:
+            self.G1_CFG = dict(self.G1_CFG_LLAMAGEN)
+        c = self.G1_CFG
+        fold = lambda w, g: (w.float() * g.float()[None, :]).to(w.dtype)      # W' = W diag(gamma)
+        self._packed, self._fused = [], []
+        with torch.no_grad():
+            for layer in self.layers:
+                a, f = layer.attention, layer.feed_forward
+                gu = torch.cat([f.w1.weight, f.w3.weight], dim=0).contiguous()           # gate | up: F3 / G1s read the gate half first
+                ni = f.w1.weight.shape[0]
+                f.w1.weight.data, f.w3.weight.data = gu[:ni], gu[ni:]
+                self._fused.append(gu)
+                self._packed.append(dict(qkv=ops.pack_weight(fold(a.wqkv.weight, layer.attention_norm.weight), c["qkv"][0], c["qkv"][2]),
+                                         o=ops.pack_weight(a.wo.weight, c["o"][0], c["o"][2]),
+                                         gate_up=ops.pack_weight(fold(gu, layer.ffn_norm.weight), c["gate_up"][0], c["gate_up"][2]),
+                                         down=ops.pack_weight(f.w2.weight, c["down"][0], c["down"][2])))
+            wf = fold(self.output.weight, self.norm.weight)
+            pad = (-wf.shape[0]) % 32
+            if pad:          # (columns past the vocabulary are never read: K2's rules end at V)
+                wf = torch.cat([wf, wf[-1:].expand(pad, -1)], dim=0)
+            self._head_cols = wf.shape[0]
+            self._packed_head = ops.pack_weight(wf, self.HEAD_CFG[0], self.HEAD_CFG[2])
+            del wf
+        self._ops = ops
+        self.supports_head_partials = True
+        self.buffers_version = getattr(self, "buffers_version", 0) + 1          # captured hipGraphs hold the packed weights' addresses
+        return self
+
+    def packed_bytes(self):
+        """bytes of packed weights one fused window forward streams (every layer and the whole output head)"""
+        per = sum(w.numel() * w.element_size() for d in self._packed for w in d.values())
+        return per + self._packed_head.numel() * self._packed_head.element_size()
+
+    def _forward_window_g1(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
+        ops, B, n = self._ops, tokens.shape[0], tokens.shape[1]
+        T, eps, cfg = B * n, self.args.norm_eps, self.G1_CFG
+        H, Hkv, D, hid = self.n_heads, self.n_kv_heads, self.head_dim, self.args.dim
+        inter = self._fused[0].shape[0] // 2
+        params = getattr(self.attn, "params", None)
+        kv_arg = kv_len if params is None else 0
+        g1 = lambda x_, li, name, N_, K_: ops.skinny_gemm(x_, self._packed[li][name], N_, K_, cfg[name][0], cfg[name][1], cfg[name][2])
+        fuse_mlp = ops.gateup_silu_ok(T, inter, hid, cfg["gate_up"][0])
+        h = self.tok_embeddings(tokens).view(T, -1).contiguous()
+        pos = positions.reshape(T).contiguous()
+        delta = None                        # the down projection's split-K planes, summed by the next F1r
+        for li in range(self.n_layers):
+            kc, vc = self.cache.k[li], self.cache.v[li]
+            rn = (ops.residual_sumsq(h, delta), hid, eps)
+            qkv = g1(h, li, "qkv", (H + 2 * Hkv) * D, hid)
+            q = ops.qknorm_rope_append(qkv, kc, vc, None, None, None, None, None, pos, B, n, H, Hkv, D, params, kv_arg, dtype=h.dtype,
+                                       row_norm=rn, rope_table=self._rope_ext)
+            o = self.attn.attend(li, q, self.cache, kv_len, key_start)
+            rn = (ops.residual_sumsq(h, g1(o.view(T, H * D), li, "o", hid, H * D)), hid, eps)
+            if fuse_mlp:
+                act = ops.gateup_silu(h, self._packed[li]["gate_up"], inter, hid, cfg["gate_up"][2], row_norm=rn)
+            else:
+                act = ops.silu_mul(g1(h, li, "gate_up", 2 * inter, hid), rows=T, dtype=h.dtype, row_norm=rn)
+            delta = g1(act, li, "down", hid, inter)
+        if head_partials:
+            sumsq = ops.residual_sumsq(h, delta)
+            lo, hi = cols if cols is not None else (0, self.vocab_size)
+            lo32, hi32 = (lo // 32) * 32, min(self._head_cols, ((hi + 31) // 32) * 32)
+            part = ops.skinny_gemm_cols(h, self._packed_head, self._head_cols, hid, self.HEAD_CFG[0], lo32, hi32 - lo32, self.HEAD_CFG[1],
+                                        self.HEAD_CFG[2])
+            return ops.HeadOut(part, lo32, n if T > n else 0, h.dtype, row_norm=(sumsq, hid, eps))
+        x = ops.add_rmsnorm(h, delta, self.norm.weight, eps)
+        return _head_logits(self.output, x, cols).view(B, n, -1)
 
 
 # ------------------------------------------------------------------------------------------ Chameleon / Llama

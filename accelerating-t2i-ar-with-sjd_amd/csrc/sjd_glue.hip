@@ -359,9 +359,11 @@ __device__ __forceinline__ float row_sumsq_total(const float *__restrict__ row_s
 // qkv: [T, (H + 2*Hkv) * D] fused projection output (T = B*n tokens).  One wave64 per (token, head); D in {64,128}.
 // Lane l owns the rotate-half pair (d = l', d + D/2) for l' = l (+64*k).  positions: int64 [T].
 // KV8: the cache holds OCP fp8 e4m3 bytes (value = fp8 * scale); k/v rows are quantised on the way in (q stays 16-bit)
+// TBL (SJD_F2_ROPE_TABLE, LlamaGen): the interleaved 2-D rotary of reference llamagen.py:457-467 -- lane l owns the pair (2l, 2l + 1), and
+// `inv_freq` is an fp32 table [S_rows >= S_max, D/2, 2] of (cos, sin), row p serving position p (positions clamp to [0, S_max - 1]).  No QK-norm.
 __device__ __forceinline__ unsigned char f2_to_fp8(float x) { return (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(x, x, 0, false) & 0xff); }
 
-template <int DT, int D, bool KV8>
+template <int DT, int D, bool KV8, bool TBL = false>
 __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
     const unsigned short *__restrict__ qkv, unsigned short *__restrict__ q_out, unsigned short *__restrict__ k_cache,
     unsigned short *__restrict__ v_cache, const unsigned short *__restrict__ qn_w, const unsigned short *__restrict__ qn_b,
@@ -373,6 +375,7 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
     SJD_TRG(1, 0);
     constexpr int HALF = D / 2;
     constexpr int PPL = HALF / 64 > 0 ? HALF / 64 : 1;       // pairs per lane (D=128: 1, D=64: lanes 32..63 idle)
+    constexpr int EST = TBL ? 2 : 1, E1 = TBL ? 1 : HALF;    // the lane's pair: elements (EST * lane, EST * lane + E1)
     const int lane = threadIdx.x & 63;
     // the wave index as a SCALAR: everything derived from it (token, head, batch row) is uniform, so kv_len and the position come through
     // the scalar cache instead of as 64-lane vector loads the partial loads would queue behind
@@ -400,14 +403,22 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
         const size_t nrow = hps ? (size_t)(hl / hps) * D : 0; //   (a scalar offset: the loads stay where they are)
         nw0 = gw_[nrow + la]; nw1 = gw_[nrow + la + HALF]; nb0 = gb_[nrow + la]; nb1 = gb_[nrow + la + HALF];
     }
-    const float ifr = inv_freq[la];
     const long posv = positions[tok];
+    float ifr, tsn = 0.f;                                     // TBL: (cos, sin) of the table row; the rotate-half form: the lane's frequency
+    if constexpr (TBL) {
+        const long prow = posv < 0 ? 0 : (posv < S_max ? posv : (long)S_max - 1);
+        const float2 cs2 = reinterpret_cast<const float2 *>(inv_freq)[(size_t)prow * HALF + la];
+        ifr = cs2.x;
+        tsn = cs2.y;
+    } else {
+        ifr = inv_freq[la];
+    }
     if (part) {                                               // fp32 split-K partials of the qkv projection (G1)
         // Entry sequence written for the memory system (ISA, late round 2: the kernel used to run through five dependent round trips --
         // two batches of kernel arguments, batch_rows, kv_len as a vector load with a full wait, the row statistics -- before the partial
         // loads went out).  Now: the row statistics and the first eight partial planes are requested back to back with unconditional
         // (clamped) loads, THEN kv_len is fetched (one scalar round trip, under the vector one), then the sums in the usual order.
-        const size_t ncol = (size_t)heads * D, col = (size_t)hh * D + (active ? lane : 0);
+        const size_t ncol = (size_t)heads * D, col = (size_t)hh * D + (active ? EST * lane : 0);
         float ssv[8], v0[8], v1[8];
         const float *ssp = row_sumsq ? row_sumsq : part;
 #pragma unroll
@@ -421,7 +432,7 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
                 if (q < 2) {
                     const float *pp = part + ((size_t)min(q, n_chunks - 1) * prows + tok) * ncol + col;
                     v0[q] = pp[0];
-                    v1[q] = pp[HALF];
+                    v1[q] = pp[E1];
                 }
             }
         } else if (n_chunks <= 4) {
@@ -431,7 +442,7 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
                 if (q < 4) {
                     const float *pp = part + ((size_t)min(q, n_chunks - 1) * prows + tok) * ncol + col;
                     v0[q] = pp[0];
-                    v1[q] = pp[HALF];
+                    v1[q] = pp[E1];
                 }
             }
         } else {
@@ -439,13 +450,14 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
             for (int q = 0; q < 8; ++q) {
                 const float *pp = part + ((size_t)min(q, n_chunks - 1) * prows + tok) * ncol + col;
                 v0[q] = pp[0];
-                v1[q] = pp[HALF];
+                v1[q] = pp[E1];
             }
         }
         int n_unused_ = 0;
         if (params) sjdi_kv_rows(params, b, &kv_len, &n_unused_);
 #ifndef F2_NO_PIN          // (A/B aid: without the pin the compiler sinks the early loads back to their uses -- the round-5 schedule)
         asm volatile("" :: "v"(nw0), "v"(nw1), "v"(nb0), "v"(nb1), "v"(ifr), "s"(posv));      // (keeps the early loads early: the compiler sinks them to their uses otherwise)
+        if constexpr (TBL) asm volatile("" :: "v"(tsn));
 #endif
         float ss_tot = 0.f;                                   // row_sumsq_total: batches of eight slices in order, missing slices add zero
 #pragma unroll
@@ -467,7 +479,7 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
                 if (c0 + q < n_chunks) {
                     const float *pp = part + ((size_t)(c0 + q) * prows + tok) * ncol + col;
                     w0[q] = pp[0];
-                    w1[q] = pp[HALF];
+                    w1[q] = pp[E1];
                 }
 #pragma unroll
             for (int q = 0; q < 8; ++q)
@@ -485,8 +497,8 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
     } else {
         if (params) kv_len = sjdi_params_of(params, b)->kv_len;
         if (active) {
-            x0 = Cvt<DT>::to_f(src[lane]);
-            x1 = Cvt<DT>::to_f(src[lane + HALF]);
+            x0 = Cvt<DT>::to_f(src[EST * lane]);
+            x1 = Cvt<DT>::to_f(src[EST * lane + E1]);
         }
     }
     // Where the row goes.  This used to sit -- with its early return for rows beyond the cache -- in front of the partial loads above,
@@ -503,8 +515,8 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
     }
     if (!is_q && !is_k) {                                     // V: plain copy into the cache
         if (active) {
-            if (KV8) { dst8[lane] = f2_to_fp8(x0 * q8); dst8[lane + HALF] = f2_to_fp8(x1 * q8); }
-            else { dst[lane] = Cvt<DT>::from_f(x0); dst[lane + HALF] = Cvt<DT>::from_f(x1); }
+            if (KV8) { dst8[EST * lane] = f2_to_fp8(x0 * q8); dst8[EST * lane + E1] = f2_to_fp8(x1 * q8); }
+            else { dst[EST * lane] = Cvt<DT>::from_f(x0); dst[EST * lane + E1] = Cvt<DT>::from_f(x1); }
         }
         return;
     }
@@ -522,7 +534,18 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
             x1 = Cvt<DT>::to_f(Cvt<DT>::from_f(x1));
         }
     }
-    if (active) {
+    if constexpr (TBL) {
+        if (active) {
+#pragma clang fp contract(off)
+            // out0 = x0 c - x1 s, out1 = x1 c + x0 s: each product and each sum rounded to fp32 as the separate ATen ops do, then ONE rounding
+            // to the activation dtype (.type_as(x)); condition rows (c = s = 0) give zeros.  The pragma keeps the products out of an FMA (the
+            // header's __fmul_rn / __fadd_rn are plain operators compiled under the file's contraction setting, and they fuse once inlined)
+            const float o0 = x0 * ifr - x1 * tsn;
+            const float o1 = x1 * ifr + x0 * tsn;
+            dst[2 * lane] = Cvt<DT>::from_f(o0);
+            dst[2 * lane + 1] = Cvt<DT>::from_f(o1);
+        }
+    } else if (active) {
         const float ang = (float)posv * ifr;
         float sn, cs;
         sincosf(ang, &sn, &cs);
@@ -790,10 +813,14 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
                      int dtype, const sjd_iter_params *params, int kv_len, const float *part, int n_chunks, bool kv8, float k_scale,
                      float v_scale, const sjd_row_norm *rn, void *stream)
 {
-    // the mode bits of `dtype`: SJD_QKN_SHARDS(mp) -- QK-norm gain / bias stored [mp, D], head h of q uses row h / (H / mp), of k h / (H_kv / mp)
-    if (dtype & ~(SJD_DTYPE_MASK | SJD_QKN_SHARDS_MASK)) return SJD_ERR_UNSUPPORTED;
+    // the mode bits of `dtype`: SJD_QKN_SHARDS(mp) -- QK-norm gain / bias stored [mp, D], head h of q uses row h / (H / mp), of k h / (H_kv / mp);
+    // SJD_F2_ROPE_TABLE -- LlamaGen's interleaved rotary from a (cos, sin) table in `inv_freq`
+    if (dtype & ~(SJD_DTYPE_MASK | SJD_QKN_SHARDS_MASK | SJD_F2_ROPE_TABLE)) return SJD_ERR_UNSUPPORTED;
     const int shards = (dtype & SJD_QKN_SHARDS_MASK) >> SJD_QKN_SHARDS_SHIFT;
+    const bool table = (dtype & SJD_F2_ROPE_TABLE) != 0;
     dtype &= SJD_DTYPE_MASK;
+    if (table && (qn_w || qn_b || kn_w || kn_b)) return SJD_ERR_BAD_ARG;      // (LlamaGen has no QK-norm)
+    if (table && (kv8 || B * n > 64 || (D != 64 && D != 128))) return SJD_ERR_UNSUPPORTED;
     if (shards > 1 && (H % shards != 0 || H_kv % shards != 0)) return SJD_ERR_BAD_ARG;
     const int hps_q = shards > 1 ? H / shards : 0, hps_k = shards > 1 ? H_kv / shards : 0;     // heads per shard (0: one shared row)
     if (part && (B * n > 256 || n_chunks < 1)) return SJD_ERR_BAD_ARG;
@@ -829,6 +856,23 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
                            kv8 ? 1.0f / k_scale : 1.0f, kv8 ? 1.0f / v_scale : 1.0f, rn ? rn->sumsq : nullptr, rn ? rn->slices : 0,         \
                            rn ? 1.0f / (float)rn->hidden : 0.f, rn ? rn->eps : 0.f, hps_q, hps_k);                                         \
         return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;                                                                   \
+    }
+    if (table) {
+#define SJD_F2T_CASE(DT_, D_)                                                                                                              \
+        if (dtype == DT_ && D == D_) {                                                                                                     \
+            hipLaunchKernelGGL((f2_qknorm_rope_append<DT_, D_, false, true>), grid, block, 0, s, (const unsigned short *)qkv,              \
+                               (unsigned short *)q_out, (unsigned short *)k_cache, (unsigned short *)v_cache, nullptr, nullptr, nullptr,   \
+                               nullptr, inv_freq, (const long *)positions, B, n, H, H_kv, S_max, params, kv_len, part, n_chunks, prows,    \
+                               1.0f, 1.0f, rn ? rn->sumsq : nullptr, rn ? rn->slices : 0, rn ? 1.0f / (float)rn->hidden : 0.f,             \
+                               rn ? rn->eps : 0.f, 0, 0);                                                                                  \
+            return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;                                                              \
+        }
+        SJD_F2T_CASE(SJD_DTYPE_BF16, 128)
+        SJD_F2T_CASE(SJD_DTYPE_F16, 128)
+        SJD_F2T_CASE(SJD_DTYPE_BF16, 64)
+        SJD_F2T_CASE(SJD_DTYPE_F16, 64)
+#undef SJD_F2T_CASE
+        return SJD_ERR_UNSUPPORTED;
     }
     SJD_F2_CASE(SJD_DTYPE_BF16, 128, false)
     SJD_F2_CASE(SJD_DTYPE_F16, 128, false)

@@ -848,14 +848,21 @@ def _row_norm(row_norm):
 
 
 def qknorm_rope_append(qkv, k_cache, v_cache, qn_w, qn_b, kn_w, kn_b, inv_freq, positions, B, n, H, H_kv, D, params, kv_len,
-                       kv_scale=(1.0, 1.0), dtype=None, row_norm=None, qk_shards=1):
+                       kv_scale=(1.0, 1.0), dtype=None, row_norm=None, qk_shards=1, rope_table=None):
     """qkv [B*n, (H+2Hkv)*D] (tensor or G1 Partials) -> q [B,n,H,D]; k/v rows are written into k_cache/v_cache [B,Hkv,S,D].
     An fp8 cache (dtype FP8) receives fp8(x / scale) with kv_scale = (k, v); `dtype` = the activation dtype (needed with Partials
     into an fp8 cache, where no 16-bit tensor is around to tell).  row_norm = (sumsq, hidden, eps): the projection ran on the
     un-normalised residual stream with the norm gain folded into its weight; the row scale is applied here (folded-norm path).
-    qk_shards = mp > 1: the QK-norm gains / biases are [mp, D] (model_parallel_size mp), head h of q uses row h // (H // mp), of k h // (Hkv // mp)."""
+    qk_shards = mp > 1: the QK-norm gains / biases are [mp, D] (model_parallel_size mp), head h of q uses row h // (H // mp), of k h // (Hkv // mp).
+    rope_table: LlamaGen's interleaved 2-D rotary (SJD_F2_ROPE_TABLE) from an fp32 (cos, sin) table [S_rows >= S_max, D/2, 2], row p serving
+    position p; inv_freq is ignored then and the QK-norm arguments must be None."""
     t, part, nc = _part_args(qkv)
     assert (t is None or t.is_contiguous()) and positions.is_contiguous() and positions.dtype == torch.int64
+    mode = 0
+    if rope_table is not None:
+        assert rope_table.dtype == torch.float32 and rope_table.is_contiguous() and rope_table.shape[1:] == (D // 2, 2)
+        assert rope_table.shape[0] >= k_cache.shape[2], "the rotary table needs a row per cache position"
+        inv_freq, mode = rope_table, L.F2_ROPE_TABLE
     assert inv_freq.dtype == torch.float32 and inv_freq.is_contiguous()
     fp8 = k_cache.dtype == FP8
     act = dtype or (t.dtype if t is not None else k_cache.dtype)
@@ -863,7 +870,7 @@ def qknorm_rope_append(qkv, k_cache, v_cache, qn_w, qn_b, kn_w, kn_b, inv_freq, 
     q = torch.empty(B, n, H, D, dtype=act, device=k_cache.device)
     L.check(L.load().sjd_qknorm_rope_append_ex(_ptr(t), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(qn_w), _ptr(qn_b), _ptr(kn_w),
                                               _ptr(kn_b), _ptr(inv_freq), _ptr(positions), B, n, H, H_kv, D, k_cache.shape[2],
-                                              _dtype_code(act) | (int(qk_shards) << L.QKN_SHARDS_SHIFT if qk_shards > 1 else 0), int(fp8),
+                                              _dtype_code(act) | (int(qk_shards) << L.QKN_SHARDS_SHIFT if qk_shards > 1 else 0) | mode, int(fp8),
                                               float(kv_scale[0]), float(kv_scale[1]), _row_norm(row_norm),
                                               params.ptr if params is not None else None, int(kv_len), part, nc, _stream()),
             "sjd_qknorm_rope_append")

@@ -33,6 +33,7 @@ def main():
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--window", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--fused", action="store_true", help="draft windows on the hand-written HIP path (LlamaGenBackbone.enable_fused)")
     ap.add_argument("--out", default="sample.png")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -53,6 +54,8 @@ def main():
         gpt.load_state_dict(ck.get("model", ck), strict=False)
     else:
         synthetic.fill_state_dict_device(gpt, seed=0, embed_token_scale=0.5)
+    if a.fused:
+        gpt.enable_fused(ops, gemm="sjd")
     jac = dict(jacobi_loop_interval_l=1, jacobi_loop_interval_r=latent ** 2 - a.window - 2, max_num_new_tokens=a.window,
                guidance_scale=a.cfg_scale, seed=a.seed, multi_token_init_scheme="random", do_cfg=True, image_top_k=a.top_k,
                text_top_k=10, prefix_token_sampler_scheme="speculative_jacobi")

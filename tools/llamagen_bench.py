@@ -1,0 +1,229 @@
+#!/usr/bin/env python3
+"""LlamaGen on one MI355X: the ATen window forward against the fused HIP path (LlamaGenBackbone.enable_fused).
+
+  --sweep   G1 launch shapes of the four per-layer projections and the output head of one preset (default GPT-XL) at a 32-row window
+            (window 16, CFG): us per launch from a hipGraph of back-to-back launches over enough weight copies that each streams from HBM.
+            One JSON line per shape; the fastest per projection is what LlamaGenBackbone.G1_CFG_LLAMAGEN / HEAD_CFG hold.
+  --ab      ms per SJD step, ATen against fused, for GPT-B c2i 256px, GPT-XL t2i 512px (120 caption rows, left-padded) and GPT-XXL t2i 512px
+            on synthetic weights (window 16, CFG, bf16): both legs in the same process on the same weights, timed in alternation over
+            --rounds rounds (median reported), captured hipGraphs in both; then one whole image per leg (tokens/s) and the packed bytes one
+            fused step streams / step time / 8 TB/s.
+  --step    the fused step alone (one preset, --steps timed iterations): what the rocprofv3 by-shape table is taken from.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+import sjd_amd.backbones as BB  # noqa: E402
+import sjd_amd.ops as ops  # noqa: E402
+
+PRESETS = {"GPT-B": (12, 12, 768), "GPT-L": (24, 16, 1024), "GPT-XL": (36, 20, 1280), "GPT-XXL": (48, 24, 1536)}
+CONFIGS = [("GPT-B", "c2i", 256), ("GPT-XL", "t2i", 512), ("GPT-XXL", "t2i", 512)]
+PEAK_TBPS = 8.0
+CAP_PAD = 7            # left-padded caption rows of the t2i runs (key_start)
+
+
+def _args(preset, model_type, image_size):
+    n_layer, n_head, dim = PRESETS[preset]
+    latent = image_size // 16
+    return BB.LlamaGenArgs(dim=dim, n_layer=n_layer, n_head=n_head, vocab_size=16384, block_size=latent * latent, model_type=model_type,
+                           cls_token_num=1 if model_type == "c2i" else 120, num_classes=1000, caption_dim=2048)
+
+
+def _graph_us(fn, n):
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        fn(0)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for i in range(n):
+            fn(i)
+    g.replay()
+    torch.cuda.synchronize()
+    res = []
+    for _ in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        res.append(e0.elapsed_time(e1) * 1e3 / n)
+    return min(res)
+
+
+def sweep(args):
+    a = _args(args.preset, "t2i", 512)
+    D = a.dim // a.n_head
+    ff = int(2 * (4 * a.dim) / 3)
+    inter = ff if ff % a.multiple_of == 0 else ff + a.multiple_of - (ff % a.multiple_of)
+    shapes = dict(qkv=(3 * a.n_head * D, a.dim), o=(a.dim, a.dim), gate_up=(2 * inter, a.dim), down=(a.dim, inter), head=(a.vocab_size, a.dim))
+    dev = torch.device("cuda:0")
+    M = args.rows
+    g = torch.Generator(device=dev).manual_seed(1)
+    best = {}
+    for name, (N, K) in shapes.items():
+        copies = max(2, -(-768 * 2**20 // (N * K * 2)))        # > 0.75 GB in flight: past the 256 MB Infinity Cache
+        ws = [(torch.randn(N, K, generator=g, device=dev) / K ** 0.5).to(torch.bfloat16) for _ in range(copies)]
+        x = torch.randn(M, K, generator=g, device=dev).to(torch.bfloat16)
+        for kc in (128, 256, 320, 512, 640, 1280):
+            if kc > K:
+                continue
+            for sm in (True, False):
+                packed = [ops.pack_weight(w, kc, sm) for w in ws]
+                for waves in (1, 2, 4, 8):
+                    try:
+                        if name == "head":
+                            fn = lambda i: ops.skinny_gemm_cols(x, packed[i % copies], N, K, kc, 0, N, waves, sm)
+                        else:
+                            fn = lambda i: ops.skinny_gemm(x, packed[i % copies], N, K, kc, waves, sm)
+                        us = _graph_us(fn, 2 * copies)
+                    except Exception as e:          # a launch shape the kernel declines
+                        print(json.dumps(dict(proj=name, kc=kc, waves=waves, step_major=sm, error=str(e)[:80])), flush=True)
+                        continue
+                    rec = dict(preset=args.preset, proj=name, N=N, K=K, rows=M, kc=kc, waves=waves, step_major=sm, us=round(us, 2),
+                               tbps=round(N * K * 2 / us / 1e6, 3))
+                    print(json.dumps(rec), flush=True)
+                    if name not in best or us < best[name]["us"]:
+                        best[name] = rec
+                del packed
+        del ws
+        torch.cuda.empty_cache()
+    for name, r in best.items():
+        print(json.dumps(dict(best=name, preset=args.preset, cfg=[r["kc"], r["waves"], r["step_major"]], us=r["us"], tbps=r["tbps"])), flush=True)
+
+
+def _make(preset, model_type, image_size, dev):
+    import sjd_amd.synthetic as synthetic
+    a = _args(preset, model_type, image_size)
+    with torch.device(dev):
+        m = BB.LlamaGenBackbone(a, attn=ops.HipWindowAttention()).to(torch.bfloat16).eval()
+    synthetic.fill_state_dict_device(m, seed=0, embed_token_scale=0.5)
+    return m
+
+
+class _Leg:
+    """one backbone (ATen or fused) with its cache, prefill and engine"""
+
+    def __init__(self, model, window, dev, seed=3):
+        from sjd_amd.engine import SJDEngine
+        self.m, self.window, self.dev = model, window, dev
+        a = model.args
+        self.T, self.N = a.cls_token_num, a.block_size
+        g = torch.Generator(device=dev).manual_seed(seed)
+        if a.model_type == "c2i":
+            self.cond = torch.tensor([207, a.num_classes], device=dev)
+            self.ks = torch.zeros(2, dtype=torch.int32, device=dev)
+        else:
+            cap = (torch.randn(1, self.T, a.caption_dim, generator=g, device=dev) * 0.5).to(torch.bfloat16)
+            self.cond = torch.cat([cap, torch.zeros_like(cap) + model.cls_embedding.uncond_embedding.to(cap.dtype)])
+            self.ks = torch.full((2,), CAP_PAD, dtype=torch.int32, device=dev)          # left-padded caption: the first rows are hidden
+        self.s_max = ((self.T + self.N + window + 32 + 31) // 32) * 32
+        model.setup_cache(batch=2, s_max=self.s_max)
+        self.eng = SJDEngine(model, a.vocab_size, dev, max_window=window, use_graph=True)
+
+    def prefill(self):
+        m = self.m
+        m.attn.params = None
+        pos = torch.arange(self.T, device=self.dev)[None].repeat(2, 1)
+        lg = m.forward_embeds(m.embed_condition(self.cond), pos, 0, self.ks)
+        return int(lg[0, -1].argmax())
+
+    def decode(self, warmup=0, steps=None):
+        from sjd_amd.engine import SJDConfig, WindowSpec
+        from sjd_amd.grammar import TopKTopPGrammar
+        first = self.prefill()
+        T, N, w = self.T, self.N, self.window
+        cfg = SJDConfig(jacobi_loop_interval_l=1, jacobi_loop_interval_r=N - w - 2, max_num_new_tokens=w, guidance_scale=4.0, seed=3,
+                        max_length=N)
+        spec = WindowSpec(first_tokens=torch.tensor([[first], [first]], device=self.dev),
+                          first_positions=torch.full((2, 1), T, dtype=torch.long, device=self.dev), key_start=self.ks,
+                          pos_offset=torch.zeros(2, dtype=torch.long), kv_base=T)
+        kw = {} if steps is None else dict(warmup_iters=warmup, timed_iters=steps, on_timed_start=torch.cuda.synchronize,
+                                           on_timed_end=torch.cuda.synchronize)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        seq, st = self.eng.decode([first], spec, TopKTopPGrammar(1000, 1.0), cfg, **kw)
+        torch.cuda.synchronize()
+        return seq, st, time.time() - t0
+
+
+def ab(args):
+    dev = torch.device("cuda:0")
+    out = []
+    for preset, mt, size in CONFIGS:
+        if args.only and preset not in args.only.split(","):
+            continue
+        aten = _make(preset, mt, size, dev)
+        fused = _make(preset, mt, size, dev)
+        fused.load_state_dict(aten.state_dict())
+        fused.enable_fused(ops, gemm="sjd")
+        legs = dict(aten=_Leg(aten, args.window, dev), fused=_Leg(fused, args.window, dev))
+        ms = {k: [] for k in legs}
+        for _ in range(args.rounds):
+            for k, leg in legs.items():
+                _, st, _ = leg.decode(args.warmup, args.steps)
+                ms[k].append(1e3 * st.seconds / max(1, st.timed_nfe))
+        whole = {}
+        for k, leg in legs.items():
+            seq, st, wall = leg.decode()
+            whole[k] = dict(tokens=len(seq) - 1, nfe=st.nfe, seconds=round(wall, 3), tokens_per_s=round((len(seq) - 1) / wall, 1))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        nbytes = fused.packed_bytes()
+        rec = dict(preset=preset, model_type=mt, image_size=size, window=args.window, cfg=True, dtype="bf16",
+                   cls_token_num=fused.args.cls_token_num, key_start=int(legs["fused"].ks[0]), layers=fused.n_layers,
+                   ms_per_step=dict(aten=round(med["aten"], 3), fused=round(med["fused"], 3)),
+                   ms_per_step_rounds={k: [round(x, 3) for x in v] for k, v in ms.items()},
+                   speedup=round(med["aten"] / med["fused"], 2), whole_image=whole,
+                   packed_gb_per_step=round(nbytes / 1e9, 3),
+                   fused_fraction_of_8tbps=round(nbytes / (med["fused"] * 1e-3) / (PEAK_TBPS * 1e12), 3),
+                   g1_cfg=fused.G1_CFG, head_cfg=list(fused.HEAD_CFG))
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+        del legs, aten, fused
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+def step(args):
+    dev = torch.device("cuda:0")
+    preset, mt, size = next(c for c in CONFIGS if c[0] == args.preset)
+    m = _make(preset, mt, size, dev)
+    m.enable_fused(ops, gemm="sjd")
+    leg = _Leg(m, args.window, dev)
+    _, st, _ = leg.decode(args.warmup, args.steps)
+    print(json.dumps(dict(preset=preset, ms_per_step=round(1e3 * st.seconds / max(1, st.timed_nfe), 3), timed_steps=st.timed_nfe)), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--ab", action="store_true")
+    ap.add_argument("--step", action="store_true")
+    ap.add_argument("--preset", default="GPT-XL", choices=list(PRESETS))
+    ap.add_argument("--only", default="")
+    ap.add_argument("--rows", type=int, default=32)
+    ap.add_argument("--window", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    if args.sweep:
+        sweep(args)
+    if args.ab:
+        ab(args)
+    if args.step:
+        step(args)
+
+
+if __name__ == "__main__":
+    main()
