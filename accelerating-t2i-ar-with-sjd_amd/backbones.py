@@ -266,7 +266,7 @@ class LlamaGenBackbone(nn.Module):
     def forward_window(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
         """head_partials: on the fused G1 window path return an ops.HeadOut (the output head's split-K partials for kernel K2) instead
         of fp32 logits; longer inputs (prefill) run forward_embeds and return logits as usual."""
-        if getattr(self, "_ops", None) is not None and tokens.shape[0] * tokens.shape[1] <= 64:
+        if getattr(self, "_ops", None) is not None and tokens.shape[0] * tokens.shape[1] <= getattr(self, "_fused_rows", 64):
             return self._forward_window_g1(tokens, positions, kv_len, key_start, cols, head_partials)
         return self.forward_embeds(self.tok_embeddings(tokens), positions, kv_len, key_start, cols=cols)
 
@@ -276,9 +276,21 @@ class LlamaGenBackbone(nn.Module):
     # head 10.09 (the launch-alone optimum, KC 128, is 0.3 - 1.4 us faster but leaves 10 - 28 planes for the consumer to sum)
     G1_CFG_LLAMAGEN = dict(qkv=(256, 2, True), o=(256, 2, False), gate_up=(320, 2, False), down=(512, 2, False))
     HEAD_CFG = (640, 4, True)
+    # Several prompts per forward (SJDBatchEngine): 65..128 and 129..256 window rows run on G1's sub-tiled kernels / kernel G1w, whose workgroups
+    # take 2, 3, 4, 6 or 8 column tiles.  The packed layout depends on the split-K chunk, so the set is chosen when the weights are packed:
+    # enable_fused(..., max_rows=128 / 256); forward_window then serves windows of up to that many rows on the HIP path.
+    # `tools/llamagen_bench.py --sweep --rows 128 / 256`, GPT-XL (profiles/llamagen_g1_sweep_128rows.jsonl, _256rows.jsonl): per projection the
+    # fastest shape with at most eight planes -- us per launch at 128 rows q|k|v 6.92, o 5.36, gate|up 8.68, down 7.27, head 12.54; at 256 rows
+    # 9.80, 8.16, 12.31, 11.18, 17.87 (the 32-row set at 256 rows would still run: every tile count above is one kernel G1w takes)
+    G1_CFG_LLAMAGEN_128ROW = dict(qkv=(320, 2, False), o=(256, 2, False), gate_up=(320, 4, True), down=(512, 2, False))
+    HEAD_CFG_128ROW = (640, 4, True)
+    G1_CFG_LLAMAGEN_256ROW = dict(qkv=(256, 4, False), o=(256, 2, False), gate_up=(320, 4, True), down=(512, 4, False))
+    HEAD_CFG_256ROW = (640, 4, True)
+    G1_WIDE_TILES = (2, 3, 4, 6, 8)
 
-    def enable_fused(self, ops, gemm="sjd"):
-        """Switch draft windows of <= 64 rows to the hand-written HIP path: per layer F1r, G1 q|k|v, F2 (the interleaved rotary from a
+    def enable_fused(self, ops, gemm="sjd", max_rows=64):
+        """Switch draft windows of <= max_rows rows (64, 128 or 256: rows = prompts per forward x CFG batch x window; 256 needs bf16, what
+        kernel G1 serves) to the hand-written HIP path: per layer F1r, G1 q|k|v, F2 (the interleaved rotary from a
         table, SJD_F2_ROPE_TABLE), K1, G1 o, F1r, G1 gate|up (+ F3, or G1s where ops.gateup_silu_ok allows), G1 down; then the output head
         on G1, whose split-K partials K2 reads (head_partials).  The RMSNorm gains are folded into packed copies of the weights (the
         norm becomes a row scale applied by F2 / F3 / K2, as ChameleonBackbone's folded path does).  w1 / w3 are concatenated once into
@@ -291,6 +303,19 @@ class LlamaGenBackbone(nn.Module):
             raise ValueError(f"LlamaGenBackbone.enable_fused needs 16-bit weights (bf16 or fp16), got {dt}")
         if self.head_dim not in (64, 128):
             raise ValueError(f"LlamaGenBackbone.enable_fused: head_dim {self.head_dim} is not served (F2's table rotary takes head_dim 64 or 128)")
+        if max_rows not in (64, 128, 256):
+            raise ValueError(f"LlamaGenBackbone.enable_fused: max_rows is 64, 128 or 256 (the three sets of G1 launch shapes), got {max_rows!r}")
+        if max_rows > 128 and dt != torch.bfloat16:
+            raise ValueError("LlamaGenBackbone.enable_fused: kernel G1 serves fp16 windows of at most 128 rows; max_rows=256 needs bf16 weights")
+        if max_rows > 64:            # (the default keeps packing exactly what it packed before: a G1_CFG / HEAD_CFG set by the caller still wins)
+            sfx = f"_{max_rows}ROW"
+            if "G1_CFG" not in self.__dict__:
+                self.G1_CFG = dict(getattr(self, "G1_CFG_LLAMAGEN" + sfx))
+            if "HEAD_CFG" not in self.__dict__:
+                self.HEAD_CFG = tuple(getattr(self, "HEAD_CFG" + sfx))
+            bad = [k for k, c_ in list(self.G1_CFG.items()) + [("head", self.HEAD_CFG)] if c_[1] not in self.G1_WIDE_TILES]
+            if bad:
+                raise ValueError(f"windows of more than 64 rows take {self.G1_WIDE_TILES} column tiles per workgroup; offending launch shapes: {bad}")
         if "G1_CFG" not in self.__dict__:
             self.G1_CFG = dict(self.G1_CFG_LLAMAGEN)
         c = self.G1_CFG
@@ -315,6 +340,7 @@ class LlamaGenBackbone(nn.Module):
             self._packed_head = ops.pack_weight(wf, self.HEAD_CFG[0], self.HEAD_CFG[2])
             del wf
         self._ops = ops
+        self._fused_rows = self.max_rows = int(max_rows)
         self.supports_head_partials = True
         self.buffers_version = getattr(self, "buffers_version", 0) + 1          # captured hipGraphs hold the packed weights' addresses
         return self

@@ -575,7 +575,12 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
 // so q and the cache rows are bit-identical; used for windows of more than 64 rows read from split-K partials.
 // SHARD (sharded QK-norm gains, [mp, D]): the HPW heads of a wave may belong to different shards, so each head loads its own row (all in
 // the same early batch); without it one row serves the wave, as before.
-template <int DT, int D, bool KV8, int HPW, bool SHARD = false>
+// TBL (SJD_F2_ROPE_TABLE, LlamaGen's windows of 65..256 rows): lane l owns the interleaved pair (2l, 2l + 1) of each of its HPW heads -- one
+// 8-byte load per plane and head, one packed 32-bit store per head -- and the (cos, sin) of its pair comes from row `position` of the table in
+// `inv_freq`, read ONCE per wave.  The table row's address hangs on the position, so the order of requests is: position (scalar), the first
+// four planes of all HPW heads (they do not need it), then the table row -- one vector round trip with the planes, not one in front of them.
+// No QK-norm, no fp8 cache; the arithmetic of the one-head kernel's TBL branch element for element (no FMA contraction).
+template <int DT, int D, bool KV8, int HPW, bool SHARD = false, bool TBL = false>
 __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
     unsigned short *__restrict__ q_out, unsigned short *__restrict__ k_cache, unsigned short *__restrict__ v_cache,
     const unsigned short *__restrict__ qn_w, const unsigned short *__restrict__ qn_b, const unsigned short *__restrict__ kn_w,
@@ -595,7 +600,8 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
     const int hl0 = is_q ? hh0 : (is_k ? hh0 - H : hh0 - H - H_kv);
     const float q8 = is_k ? k_inv : v_inv;
     const bool active = lane < HALF;
-    const size_t ncol = (size_t)heads * D, col = (size_t)hh0 * D + (active ? lane : 0);
+    constexpr int EST = TBL ? 2 : 1;                          // the lane's pair starts at element EST * lane (TBL: (2l, 2l + 1); else (l, l + HALF))
+    const size_t ncol = (size_t)heads * D, col = (size_t)hh0 * D + (active ? EST * lane : 0);
     // (the norm parameters, the rotary frequency and the position in front of the planes: see f2_qknorm_rope_append)
     const unsigned short *gw_ = is_q ? qn_w : kn_w, *gb_ = is_q ? qn_b : kn_b;
     const bool has_norm = gw_ != nullptr && (is_q || is_k);
@@ -610,7 +616,8 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
             nw0[j] = gw_[nrow + la]; nw1[j] = gw_[nrow + la + HALF]; nb0[j] = gb_[nrow + la]; nb1[j] = gb_[nrow + la + HALF];
         }
     }
-    const float ifr = inv_freq[la];
+    float ifr = 0.f, tsn = 0.f;                               // TBL: (cos, sin) of the table row; the rotate-half form: the lane's frequency
+    if constexpr (!TBL) ifr = inv_freq[la];
     const long posv = positions[tok];
     float ssv[8];
     const float *ssp = row_sumsq ? row_sumsq : part;
@@ -625,7 +632,20 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
         for (int q = 0; q < 4; ++q) {
             const float *pp = part + ((size_t)min(c0 + q, n_chunks - 1) * prows + tok) * ncol + col;
 #pragma unroll
-            for (int j = 0; j < HPW; ++j) { v0[q][j] = pp[j * D]; v1[q][j] = pp[j * D + HALF]; }
+            for (int j = 0; j < HPW; ++j) {
+                if constexpr (TBL) {
+                    const float2 pr = *reinterpret_cast<const float2 *>(pp + j * D);
+                    v0[q][j] = pr.x; v1[q][j] = pr.y;
+                } else { v0[q][j] = pp[j * D]; v1[q][j] = pp[j * D + HALF]; }
+            }
+        }
+        if constexpr (TBL) {
+            if (c0 == 0) {                                    // the table row, behind the first batch of planes (positions clamp to the table)
+                const long prow = posv < 0 ? 0 : (posv < S_max ? posv : (long)S_max - 1);
+                const float2 cs2 = reinterpret_cast<const float2 *>(inv_freq)[(size_t)prow * HALF + la];
+                ifr = cs2.x;
+                tsn = cs2.y;
+            }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -640,6 +660,7 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
 #pragma unroll
     for (int j = 0; j < NG; ++j) asm volatile("" :: "v"(nw0[j]), "v"(nw1[j]), "v"(nb0[j]), "v"(nb1[j]));
     asm volatile("" :: "v"(ifr), "s"(posv));
+    if constexpr (TBL) asm volatile("" :: "v"(tsn));
 #endif
     float ss_tot = 0.f;                                       // row_sumsq_total's order
 #pragma unroll
@@ -666,7 +687,10 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
 #pragma unroll
             for (int j = 0; j < HPW; ++j) {
                 const size_t off = (((size_t)b * H_kv + hl0 + j) * S_max + rrow) * D;
-                if (KV8) {
+                if constexpr (TBL) {
+                    *reinterpret_cast<unsigned *>(v_cache + off + 2 * lane) =
+                        (unsigned)Cvt<DT>::from_f(x0[j]) | ((unsigned)Cvt<DT>::from_f(x1[j]) << 16);
+                } else if (KV8) {
                     unsigned char *d8 = reinterpret_cast<unsigned char *>(v_cache) + off;
                     d8[lane] = f2_to_fp8(x0[j] * q8); d8[lane + HALF] = f2_to_fp8(x1[j] * q8);
                 } else { v_cache[off + lane] = Cvt<DT>::from_f(x0[j]); v_cache[off + lane + HALF] = Cvt<DT>::from_f(x1[j]); }
@@ -692,7 +716,22 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
             }
         }
     }
-    if (active) {
+    if constexpr (TBL) {
+        if (active) {
+#pragma clang fp contract(off)
+            // out0 = x0 c - x1 s, out1 = x1 c + x0 s: every product and sum rounded to fp32, ONE rounding to the activation dtype (see the
+            // one-head kernel); condition rows (c = s = 0) give zeros
+#pragma unroll
+            for (int j = 0; j < HPW; ++j) {
+                const float o0 = x0[j] * ifr - x1[j] * tsn;
+                const float o1 = x1[j] * ifr + x0[j] * tsn;
+                const unsigned pk = (unsigned)Cvt<DT>::from_f(o0) | ((unsigned)Cvt<DT>::from_f(o1) << 16);
+                unsigned short *dst = is_q ? q_out + ((size_t)tok * H + hl0 + j) * D
+                                           : k_cache + (((size_t)b * H_kv + hl0 + j) * S_max + rrow) * D;
+                *reinterpret_cast<unsigned *>(dst + 2 * lane) = pk;
+            }
+        }
+    } else if (active) {
         const float ang = (float)posv * ifr;
         float sn, cs;
         sincosf(ang, &sn, &cs);
@@ -820,7 +859,8 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
     const bool table = (dtype & SJD_F2_ROPE_TABLE) != 0;
     dtype &= SJD_DTYPE_MASK;
     if (table && (qn_w || qn_b || kn_w || kn_b)) return SJD_ERR_BAD_ARG;      // (LlamaGen has no QK-norm)
-    if (table && (kv8 || B * n > 64 || (D != 64 && D != 128))) return SJD_ERR_UNSUPPORTED;
+    // (table mode above 64 rows reads split-K planes only: the many-row windows come from G1; a dense source stays refused)
+    if (table && (kv8 || (B * n > 64 && !part) || (D != 64 && D != 128))) return SJD_ERR_UNSUPPORTED;
     if (shards > 1 && (H % shards != 0 || H_kv % shards != 0)) return SJD_ERR_BAD_ARG;
     const int hps_q = shards > 1 ? H / shards : 0, hps_k = shards > 1 ? H_kv / shards : 0;     // heads per shard (0: one shared row)
     if (part && (B * n > 256 || n_chunks < 1)) return SJD_ERR_BAD_ARG;
@@ -834,7 +874,25 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
     // more than 64 rows of split-K partials: HPW heads per wave (f2_qknorm_rope_append_rows); SJD_F2_ROWS=0 keeps the one-head kernel (A/B aid)
     const char *f2r_env = getenv("SJD_F2_ROWS");              // (read per launch: the parity test flips it inside one process)
     const bool rows_ok = !(f2r_env && f2r_env[0] == '0');
-    if (rows_ok && part && B * n > 64 && (H % 4) == 0 && (H_kv % 4) == 0 && D == 128 && dtype == SJD_DTYPE_BF16) {
+    if (rows_ok && table && part && B * n > 64 && (H % 4) == 0 && (H_kv % 4) == 0) {      // (other head counts: the one-head table kernel below)
+        const dim3 g2((B * n * ((H + 2 * H_kv) / 4) + 3) / 4);
+#define SJD_F2RT_CASE(DT_, D_)                                                                                                             \
+        if (dtype == DT_ && D == D_) {                                                                                                     \
+            hipLaunchKernelGGL((f2_qknorm_rope_append_rows<DT_, D_, false, 4, false, true>), g2, block, 0, s, (unsigned short *)q_out,     \
+                               (unsigned short *)k_cache, (unsigned short *)v_cache, nullptr, nullptr, nullptr, nullptr, inv_freq,         \
+                               (const long *)positions, B, n, H, H_kv, S_max, params, kv_len, part, n_chunks, prows, 1.0f, 1.0f,           \
+                               rn ? rn->sumsq : nullptr, rn ? rn->slices : 0, rn ? 1.0f / (float)rn->hidden : 0.f, rn ? rn->eps : 0.f, 0,  \
+                               0);                                                                                                         \
+            return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;                                                              \
+        }
+        SJD_F2RT_CASE(SJD_DTYPE_BF16, 128)
+        SJD_F2RT_CASE(SJD_DTYPE_F16, 128)
+        SJD_F2RT_CASE(SJD_DTYPE_BF16, 64)
+        SJD_F2RT_CASE(SJD_DTYPE_F16, 64)
+#undef SJD_F2RT_CASE
+        return SJD_ERR_UNSUPPORTED;
+    }
+    if (rows_ok && !table && part && B * n > 64 && (H % 4) == 0 && (H_kv % 4) == 0 && D == 128 && dtype == SJD_DTYPE_BF16) {
         const dim3 g2((B * n * ((H + 2 * H_kv) / 4) + 3) / 4);
 #define SJD_F2R(KV8_, SH_)                                                                                                                 \
         hipLaunchKernelGGL((f2_qknorm_rope_append_rows<SJD_DTYPE_BF16, 128, KV8_, 4, SH_>), g2, block, 0, s, (unsigned short *)q_out,      \

@@ -87,6 +87,11 @@ class WindowSpec:
     key_start: torch.Tensor               # int32 [B_cfg]: first visible cache row per batch row
     pos_offset: torch.Tensor              # int64 [B_cfg]: RoPE position = cache row + pos_offset
     kv_base: int = 0                      # cache rows valid before `_sample` starts (LlamaGen: cond tokens)
+    # SJDBatchEngine, LlamaGen: the slot's conditioning, embedded ([B_cfg, T, dim]: class / caption embeddings, cond row first).  When set the
+    # admission prefills it into the slot's cache rows [0, T) with backbone.forward_embeds and draws the FIRST image token from the last row's
+    # logits (llamagen_solver.sample with the prompt's own generator); first_tokens / first_positions are ignored (may be None), kv_base = T.
+    cond_embeds: Optional[torch.Tensor] = None
+    cond_sampling: Optional[dict] = None  # cfg_scale, temperature, top_k, top_p, sample_logits of that first draw (LlamaGenSolver.prefill)
 
 
 @dataclass

@@ -52,6 +52,18 @@ class SJDBatchEngine:
         if n_prompts * n_batch * max_window > 256:
             raise ValueError("the window forward (G1, F1-F3) serves at most 256 rows: n_prompts * n_batch * max_window <= 256")
         rows = n_prompts * n_batch * max_window
+        if hasattr(backbone, "tok_embeddings") and hasattr(backbone, "embed_condition"):          # LlamaGen
+            # its window forward leaves the HIP path above the row count the weights were packed for (LlamaGenBackbone.forward_window) and
+            # would fall onto ATen silently: not bit-identical to the oracle replays, and no head partials for K2
+            if getattr(backbone, "_ops", None) is None:
+                raise ValueError("SJDBatchEngine serves a LlamaGen backbone on the fused HIP path only: call "
+                                 f"model.enable_fused(ops, gemm='sjd', max_rows=...) first ({rows} window rows per forward here)")
+            if backbone.output.weight.dtype == torch.float16 and rows > 128:
+                raise ValueError(f"kernel G1 serves fp16 windows of at most 128 rows: n_prompts * n_batch * max_window = {rows} > 128 "
+                                 "(use bf16 weights, or fewer prompts per forward)")
+            if getattr(backbone, "max_rows", 64) < rows:
+                raise ValueError(f"the backbone was packed for windows of at most max_rows={getattr(backbone, 'max_rows', 64)} rows, but "
+                                 f"n_prompts * n_batch * max_window = {rows}: call enable_fused(ops, gemm='sjd', max_rows={128 if rows <= 128 else 256})")
         if rows > 128 and getattr(backbone, "_gemm", None) == "sjd" and getattr(backbone, "_packed", None):
             # 129..256 window rows run on kernel G1w (csrc/sjd_gemm_wide.h): the uncompressed packing, 2 / 3 / 4 / 6 / 8 column tiles per
             # workgroup for every projection AND the output head.  Anything else used to fall onto the library-GEMM prefill path silently
@@ -351,6 +363,11 @@ class SJDBatchEngine:
         attn = getattr(self.backbone, "attn", None)
         full_cache = self.backbone.cache
         results = [None] * N
+        pre_seeds = None
+        if seeds is None and cfg.seed is None and any(getattr(sp, "cond_embeds", None) is not None for sp in specs):
+            # no seed: the N per-prompt seeds are drawn from the default generator UP FRONT, in prompt order -- a prompt's first token (drawn at
+            # its admission) then depends neither on the number of slots nor on which slot finished first
+            pre_seeds = [int(t) for t in torch.randint(0, 2 ** 62, (N,), device=dev, generator=default_gen).tolist()]
         next_prompt = 0
         emitted_total = 0                 # tokens appended to any prompt's sequence so far (the timed region counts its increase)
         cur = 0
@@ -362,10 +379,36 @@ class SJDBatchEngine:
             j, s = next_prompt, self.slots[i]
             next_prompt += 1
             s.prompt_index = j
-            s.X = [int(t) for t in prompts[j]]
-            s.P = len(s.X)
             seed = (seeds[j] if seeds is not None else (None if cfg.seed is None else cfg.seed + j))
-            if seed is None:
+            cond = getattr(specs[j], "cond_embeds", None)
+            self.key_start[i * nb:(i + 1) * nb].copy_(specs[j].key_start.to(device=dev, dtype=torch.int32))
+            first_tok = None
+            if cond is not None:
+                # LlamaGen: the conditioning rows go into the slot's cache rows [0, T) through the ATen prefill (as the solo path's), the
+                # first image token comes from the last row's logits, drawn from the PROMPT's generator (seed + j, or its up-front seed)
+                from .llamagen_solver import sample as _lg_sample
+                sk = dict(specs[j].cond_sampling or {})
+                scale = float(sk.pop("cfg_scale", self._guidance))
+                T = cond.shape[1]
+                if specs[j].kv_base != T:
+                    raise ValueError(f"WindowSpec.cond_embeds has {T} rows but kv_base = {specs[j].kv_base}: the window starts behind the conditioning")
+                self.backbone.cache = _CacheView(full_cache, i * nb, (i + 1) * nb)
+                try:
+                    lg = self.backbone.forward_embeds(cond.to(dev), torch.arange(T, device=dev)[None].repeat(cond.shape[0], 1), 0,
+                                                      self.key_start[i * nb:(i + 1) * nb])
+                finally:
+                    self.backbone.cache = full_cache
+                if nb > 1 and scale > 1.0:
+                    lg = lg[1:2] + (lg[0:1] - lg[1:2]) * scale
+                else:
+                    lg = lg[0:1]
+                g0 = torch.Generator(dev).manual_seed(seed if seed is not None else pre_seeds[j])
+                first_tok = int(_lg_sample(lg, generator=g0, **sk)[0][0, 0])
+            s.X = [int(t) for t in prompts[j]] if first_tok is None else [first_tok]
+            s.P = len(s.X)
+            if seed is None and pre_seeds is not None:
+                s.gen = torch.Generator(dev).manual_seed(pre_seeds[j])
+            elif seed is None:
                 # no seed given: every slot needs its OWN Philox stream.  Sharing the device's default generator (round 3) handed every slot
                 # the same (seed, offset) pair -- identical prompts in a batch then drew identical noise.  A per-slot seed is
                 # drawn FROM the default generator instead: it advances with every admission, and torch.manual_seed still reproduces a run.
@@ -381,7 +424,6 @@ class SJDBatchEngine:
             s.n, s.kv_len, s.cur_len, s.n_prev, s.m_prev = 1, specs[j].kv_base, s.P, 1, 1
             s.carried, s.carried_amax, s.last_amax, s.finished, s.harvested, s.stats = [], [], None, False, False, DecodeStats()
             s.t_admit = time.perf_counter()
-            self.key_start[i * nb:(i + 1) * nb].copy_(specs[j].key_start.to(device=dev, dtype=torch.int32))
             self.pos_offset[i * nb:(i + 1) * nb].copy_(specs[j].pos_offset.to(device=dev, dtype=torch.int64))
             if s.cpu_gen is not None:
                 torch.randint(0, cfg.img_vocab_n, (1, 0), generator=s.cpu_gen)
@@ -391,7 +433,11 @@ class SJDBatchEngine:
             s.params.upload()
             if self.hook is not None:
                 self._observer_noise(s, 1, scheme)
-            tokens, positions = specs[j].first_tokens.to(dev), specs[j].first_positions.to(dev)
+            if first_tok is None:
+                tokens, positions = specs[j].first_tokens.to(dev), specs[j].first_positions.to(dev)
+            else:                                # the window starts as the solo path's: the first image token at position T
+                tokens = torch.full((nb, 1), first_tok, dtype=torch.long, device=dev)
+                positions = torch.full((nb, 1), specs[j].kv_base, dtype=torch.long, device=dev)
             from .engine import SJDEngine
             SJDEngine._calibrate_fp8(self, tokens, positions, self.key_start[i * nb:(i + 1) * nb])      # (an fp8 cache nobody calibrated: once per backbone)
             self.backbone.cache = _CacheView(full_cache, i * nb, (i + 1) * nb)

@@ -27,9 +27,10 @@ def top_k_top_p_filtering(logits, top_k: int = 0, top_p: float = 1.0, filter_val
     return logits
 
 
-def sample(logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, sample_logits=True, noise_device=None):
+def sample(logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, sample_logits=True, noise_device=None, generator=None):
     """Behaviour of reference LS:75-84: last row / temperature -> filtering -> softmax -> one draw from the GLOBAL generator of the
-    logits' device (noise_device="cpu": draw on the CPU generator instead -- replays the reference's CPU run on a GPU backbone)."""
+    logits' device (noise_device="cpu": draw on the CPU generator instead -- replays the reference's CPU run on a GPU backbone).
+    generator: draw from this torch.Generator instead (one per prompt when several prompts share a forward); None = the global one."""
     dev = logits.device
     if noise_device is not None:
         logits = logits.float().to(noise_device)
@@ -37,7 +38,12 @@ def sample(logits, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
     if top_k > 0 or top_p < 1.0:
         last = top_k_top_p_filtering(last, top_k=top_k, top_p=top_p)
     probs = last.softmax(dim=-1)
-    idx = torch.multinomial(probs, num_samples=1) if sample_logits else probs.argmax(dim=-1, keepdim=True)
+    if not sample_logits:
+        idx = probs.argmax(dim=-1, keepdim=True)
+    elif generator is None:
+        idx = torch.multinomial(probs, num_samples=1)
+    else:
+        idx = torch.multinomial(probs, num_samples=1, generator=generator)
     return idx.to(dev), probs.to(dev)
 
 
@@ -141,8 +147,10 @@ def renew_llamagen(model_class):
 class LlamaGenSolver:
     """reference LS:349-470"""
 
-    def __init__(self, model, image_top_k, image_top_p, noise_device=None):
+    def __init__(self, model, image_top_k, image_top_p, noise_device=None, prompts_per_forward=None):
         self.model = model
+        # generate() with several prompts: how many share one window forward (None: as many as the kernels' row limit allows)
+        self.prompts_per_forward = prompts_per_forward
         self.image_top_k = image_top_k
         self.image_top_p = image_top_p
         # None: every draw on the model's device, as the reference does.  "cpu": the first-token draw and the SJD noise streams come
@@ -173,6 +181,8 @@ class LlamaGenSolver:
     @torch.no_grad()
     def generate(self, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cfg_interval=-1, **sampling_kwargs):
         model = self.model
+        if cond.shape[0] > 1:
+            return self._generate_many(cond, max_new_tokens, emb_masks, cfg_scale, **sampling_kwargs)
         if model.model_type == 'c2i':
             cond_combined = torch.cat([cond, torch.ones_like(cond) * model.num_classes]) if cfg_scale > 1.0 else cond
             T = 1
@@ -202,6 +212,66 @@ class LlamaGenSolver:
                                 synced_gpus=False, streamer=None, logits_warper=None, use_cache=True,
                                 attention_mask=torch.ones((1, T + 1), device=cond.device), past_key_values=None,
                                 cache_position=T + 1)
+        generated = outputs[:, -max_new_tokens:]
+        model.clear_kvcache()
+        return generated
+
+    def slots_for(self, n_prompts, n_batch):
+        """prompts per window forward: prompts_per_forward, or what the kernels' row limit allows (256 rows in bf16, 128 in fp16)"""
+        model = self.model
+        rows_limit = 256 if model.output.weight.dtype == torch.bfloat16 else 128
+        slots = self.prompts_per_forward or max(1, rows_limit // (n_batch * model.max_num_new_tokens))
+        return max(1, min(int(slots), n_prompts))
+
+    def _generate_many(self, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, **sampling_kwargs):
+        """N > 1 prompts (class ids [N], or caption embeddings [N, T, C] with emb_masks [N, T]): slots_for(N) of them share every window
+        forward (SJDBatchEngine), the rest enter as slots finish.  Returns LongTensor [N, max_new_tokens] in prompt order."""
+        from .engine import WindowSpec
+        model = self.model
+        N, dev = cond.shape[0], cond.device
+        if getattr(model, "_ops", None) is None:
+            raise ValueError(f"generate() with {N} prompts runs on the fused HIP path only: call model.enable_fused(ops, gemm='sjd', "
+                             "max_rows=128 or 256) first, or generate one prompt per call")
+        if self.noise_device is not None:
+            raise ValueError(f"generate() with {N} prompts draws its noise in the kernels: noise_device={self.noise_device!r} is served for "
+                             "one prompt per call only (use noise_device=None)")
+        do_cfg = bool(model.do_cfg) and (model.guidance_scale != 1)
+        if do_cfg != (cfg_scale > 1.0):
+            raise ValueError(f"cfg_scale {cfg_scale} at prefill must match do_cfg / guidance_scale of the sampler (do_cfg={do_cfg})")
+        nb = 2 if do_cfg else 1
+        if model.model_type == 'c2i':
+            T = 1
+        elif model.model_type == 't2i':
+            T = cond.shape[1]
+        else:
+            raise Exception("please check model type")
+        if emb_masks is not None:
+            assert emb_masks.shape[0] == N and emb_masks.shape[-1] == T
+        slots = self.slots_for(N, nb)
+        s_max = ((T + max_new_tokens + model.max_num_new_tokens + 32 + 31) // 32) * 32
+        model.setup_cache(batch=slots * nb, s_max=s_max)
+        for e in getattr(model, "_sjd_engines", {}).values():
+            e.reset_graphs()
+        model._sjd_key_start = None
+        model.sjd_noise_device = None
+        specs = []
+        for j in range(N):
+            c = cond[j:j + 1]
+            if model.model_type == 'c2i':
+                cc = torch.cat([c, torch.ones_like(c) * model.num_classes]) if nb > 1 else c
+            else:
+                cc = torch.cat([c, torch.zeros_like(c) + model.cls_embedding.uncond_embedding]) if nb > 1 else c
+            if emb_masks is not None:            # left-padded caption masks: every prompt its own hidden key prefix (LS:403-412)
+                ks = (emb_masks[j:j + 1].long().cumsum(-1) == 0).sum(-1).to(torch.int32).repeat(nb)
+            else:
+                ks = torch.zeros(nb, dtype=torch.int32)
+            specs.append(WindowSpec(first_tokens=None, first_positions=None, key_start=ks, pos_offset=torch.zeros(nb, dtype=torch.long),
+                                    kv_base=T, cond_embeds=model.embed_condition(cc), cond_sampling=dict(cfg_scale=cfg_scale, **sampling_kwargs)))
+        from transformers import GenerationConfig
+        generation_config = GenerationConfig(max_new_tokens=T + max_new_tokens, max_length=T + max_new_tokens, temperature=1.0,
+                                             top_k=None, do_sample=True, return_dict_in_generate=False)
+        outputs = model._sample_many(specs, [self.create_logits_processor() for _ in range(N)], [MaxlenCriteria(max_new_tokens)],
+                                     generation_config, slots)
         generated = outputs[:, -max_new_tokens:]
         model.clear_kvcache()
         return generated

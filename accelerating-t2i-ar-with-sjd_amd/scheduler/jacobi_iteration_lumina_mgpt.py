@@ -370,6 +370,56 @@ def renew_sampler(model_class):
             print("tokens length: ", len(seq))
             return torch.tensor([seq], dtype=torch.long, device=dev)
 
+        @torch.no_grad()
+        def _sample_many(self, specs, logits_processors, stopping_criteria, generation_config, n_slots):
+            """Several LlamaGen prompts through ONE window forward per iteration (SJDBatchEngine): specs[j] carries prompt j's conditioning
+            (WindowSpec.cond_embeds: the engine prefills it into a slot's cache rows and draws the first image token), logits_processors[j]
+            its processor list.  n_slots prompts share a forward; further prompts enter as slots finish (continuous batching).  The cache
+            for n_slots x CFG rows must be allocated.  Prompt j's generators are seeded self.seed + j.  Returns LongTensor [N, tokens] in
+            prompt order; self.last_sjd_stats = the N DecodeStats."""
+            from ..engine_batch import SJDBatchEngine
+            if self.prefix_token_sampler_scheme not in ("speculative_jacobi", "jacobi"):
+                raise ValueError(f"prefix_token_sampler_scheme: {self.prefix_token_sampler_scheme}")
+            if getattr(self, "sjd_noise_device", None) is not None:
+                raise ValueError("several prompts per forward draw their noise in the kernels: noise_device must be None (decode one prompt "
+                                 "per call to replay a CPU noise stream)")
+            N = len(specs)
+            dev = specs[0].cond_embeds.device
+            do_cfg = bool(self.do_cfg) and (self.guidance_scale != 1)
+            do_sample = bool(getattr(generation_config, "do_sample", True))
+            eos, max_len = _stopping_to_limits(stopping_criteria, generation_config)
+            grammars = []
+            for procs in logits_processors:
+                g = grammar_from_processors(list(procs or []), prompt_len=1, max_length=max_len, vocab_size=getattr(self, "vocab_size", None))
+                if getattr(g, "V", 0) is None:
+                    g.V = self.vocab_size
+                grammars.append(g)
+            cfg = SJDConfig(jacobi_loop_interval_l=self.jacobi_loop_interval_l, jacobi_loop_interval_r=self.jacobi_loop_interval_r,
+                            max_num_new_tokens=self.max_num_new_tokens, guidance_scale=self.guidance_scale, seed=self.seed,
+                            do_cfg=do_cfg, prefix_token_sampler_scheme=self.prefix_token_sampler_scheme,
+                            multi_token_init_scheme=self.multi_token_init_scheme, img_vocab_lo=self.img_vocab_range[0],
+                            img_vocab_n=self.img_vocab_range[1] - self.img_vocab_range[0], max_length=max_len, eos_token_ids=eos,
+                            do_sample=do_sample)
+            B = 2 if do_cfg else 1
+            need = specs[0].kv_base + max_len + self.max_num_new_tokens + 32
+            if self.cache is None or self.cache.k.shape[1] != B * n_slots or self.cache.s_max < need:
+                have = None if self.cache is None else (int(self.cache.k.shape[1]), int(self.cache.s_max))
+                raise ValueError(f"KV cache (batch, rows) = {have} does not fit {n_slots} slots x batch {B} with {need} rows each")
+            if getattr(self, "attn", None) is None:
+                self.attn = ops.HipWindowAttention()
+            key = ("many", n_slots, B, self.max_num_new_tokens, str(dev))
+            eng = self._sjd_engines.get(key)
+            if eng is None:
+                eng = self._sjd_engines[key] = SJDBatchEngine(self, self.vocab_size, dev, n_slots, max_window=self.max_num_new_tokens, n_batch=B,
+                                                              use_graph=getattr(self, "sjd_use_graph", True))
+            results = eng.decode_many([[] for _ in range(N)], specs, grammars, cfg)
+            self.last_sjd_stats = [st for _, st in results]
+            for seq, st in results:
+                print("Time elapsed inner: ", st.seconds)                                                # JL:1218-1220, once per prompt
+                print("gen loop num (NFE): ", st.nfe)
+                print("tokens length: ", len(seq))
+            return torch.tensor([seq for seq, _ in results], dtype=torch.long, device=dev)
+
     if not hasattr(model_class, "generate"):
         # this package's backbones are plain nn.Modules: give them the HF-shaped entry point the drivers call
         # (`model.generate(input_ids, generation_config, logits_processor=..., attention_mask=..., neg_input_ids=...)`)

@@ -5,6 +5,7 @@ reference's import lines.  Checkpoints: pass --gpt-ckpt / --vq-ckpt (the referen
 without them both networks get synthetic weights, which exercises every step but of course draws noise.
 
     python examples/llamagen_c2i.py --class-id 207 --out sample.png
+    python examples/llamagen_c2i.py --fused --class-id 207 1 980 417 --out grid.png      # four images per forward: grid_207.png, grid_1.png, ...
 """
 import argparse
 import os
@@ -20,14 +21,16 @@ from llamagen.tokenizer.tokenizer_image.vq_model import VQ_models  # noqa: E402 
 from scheduler.jacobi_iteration_lumina_mgpt import renew_sampler  # noqa: E402          (test_llamagen.py:21)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpt-model", default="GPT-B", choices=list(GPT_models))
     ap.add_argument("--gpt-ckpt", default=None)
     ap.add_argument("--vq-model", default="VQ-16", choices=list(VQ_models))
     ap.add_argument("--vq-ckpt", default=None)
     ap.add_argument("--image-size", type=int, default=256)
-    ap.add_argument("--class-id", type=int, default=207)
+    ap.add_argument("--class-id", type=int, nargs="+", default=[207],
+                    help="one ImageNet class, or several: they share the window forwards (needs --fused) and one PNG is written per label")
+    ap.add_argument("--prompts-per-forward", type=int, default=None, help="several labels: how many share a forward (default: what 256 rows hold)")
     ap.add_argument("--cfg-scale", type=float, default=4.0)
     ap.add_argument("--top-k", type=int, default=1000)
     ap.add_argument("--top-p", type=float, default=1.0)
@@ -35,7 +38,22 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fused", action="store_true", help="draft windows on the hand-written HIP path (LlamaGenBackbone.enable_fused)")
     ap.add_argument("--out", default="sample.png")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    if len(a.class_id) > 1 and not a.fused:
+        ap.error("several --class-id labels are decoded together on the fused HIP path: add --fused")
+    return a
+
+
+def out_paths(out, class_ids):
+    """one label: `out` itself; several: <stem>_<label><ext> per label (a repeated label gets its index as well)"""
+    if len(class_ids) == 1:
+        return [out]
+    stem, ext = os.path.splitext(out)
+    return [f"{stem}_{c}{ext}" if class_ids.count(c) == 1 else f"{stem}_{c}_{i}{ext}" for i, c in enumerate(class_ids)]
+
+
+def main():
+    a = parse_args()
     dev = torch.device("cuda:0")
     import sjd_amd.ops as ops
     import sjd_amd.synthetic as synthetic
@@ -55,7 +73,8 @@ def main():
     else:
         synthetic.fill_state_dict_device(gpt, seed=0, embed_token_scale=0.5)
     if a.fused:
-        gpt.enable_fused(ops, gemm="sjd")
+        rows = (a.prompts_per_forward or len(a.class_id)) * 2 * a.window          # prompts x CFG pair x window rows per forward
+        gpt.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256))
     jac = dict(jacobi_loop_interval_l=1, jacobi_loop_interval_r=latent ** 2 - a.window - 2, max_num_new_tokens=a.window,
                guidance_scale=a.cfg_scale, seed=a.seed, multi_token_init_scheme="random", do_cfg=True, image_top_k=a.top_k,
                text_top_k=10, prefix_token_sampler_scheme="speculative_jacobi")
@@ -64,21 +83,25 @@ def main():
     gpt.__class__ = renew_sampler(gpt.__class__)
     gpt._init_new_params(**jac)
 
-    solver = LlamaGenSolver(model=gpt, image_top_k=a.top_k, image_top_p=a.top_p)
+    solver = LlamaGenSolver(model=gpt, image_top_k=a.top_k, image_top_p=a.top_p, prompts_per_forward=a.prompts_per_forward)
     torch.manual_seed(a.seed)
     t0 = time.time()
-    index_sample = solver.generate(torch.tensor([a.class_id], device=dev), latent ** 2, None, cfg_scale=a.cfg_scale, temperature=1.0,
+    index_sample = solver.generate(torch.tensor(a.class_id, device=dev), latent ** 2, None, cfg_scale=a.cfg_scale, temperature=1.0,
                                    top_k=a.top_k, top_p=a.top_p, sample_logits=True)
     torch.cuda.synchronize()
     dt = time.time() - t0
-    st = gpt.last_sjd_stats
-    print(f"{index_sample.shape[1]} image tokens in {st.nfe} forward passes ({index_sample.shape[1] / max(st.nfe, 1):.2f} tokens/step), {dt:.2f} s")
+    stats = gpt.last_sjd_stats if isinstance(gpt.last_sjd_stats, list) else [gpt.last_sjd_stats]
+    n_tok = index_sample.numel()
+    for c, st in zip(a.class_id, stats):
+        print(f"class {c}: {index_sample.shape[1]} image tokens in {st.nfe} forward passes ({index_sample.shape[1] / max(st.nfe, 1):.2f} tokens/step)")
+    print(f"{n_tok} image tokens in {dt:.2f} s ({n_tok / dt:.0f} tokens/s)")
 
-    samples = vq.decode_code(index_sample.reshape(-1), (1, 8, latent, latent))          # [-1, 1]   (test_llamagen.py:182)
     from sjd_amd.detokenizers import to_uint8
     from PIL import Image
-    Image.fromarray(to_uint8(samples)[0].cpu().numpy()).save(a.out)
-    print(f"wrote {a.out} ({samples.shape[-1]}x{samples.shape[-2]})")
+    for row, path in zip(index_sample, out_paths(a.out, a.class_id)):
+        samples = vq.decode_code(row.reshape(-1), (1, 8, latent, latent))                # [-1, 1]   (test_llamagen.py:182)
+        Image.fromarray(to_uint8(samples)[0].cpu().numpy()).save(path)
+        print(f"wrote {path} ({samples.shape[-1]}x{samples.shape[-2]})")
 
 
 if __name__ == "__main__":

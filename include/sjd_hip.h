@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define SJD_VERSION 102
+#define SJD_VERSION 103
 #define SJD_MAX_WINDOW 64      /* max draft-window length L (reference max_num_new_tokens: 16 / 32 by default, a free CLI argument of eval_model.py:76;
                                   64 = one wavefront of accept tests in K4, 128 forward rows with CFG) */
 #define SJD_MAX_RANGES 4
@@ -34,7 +34,7 @@ extern "C" {
 #define SJD_DTYPE_F16 1
 #define SJD_DTYPE_F32 2        /* K1/K3 only: exact-fp32 VALU variant for small parity runs (not a performance path) */
 
-/* Mode bits in the high bits of the `dtype` argument of the glue entry points (version 101; SJD_F2_ROPE_TABLE: 102).  dtype & SJD_DTYPE_MASK is the dtype code
+/* Mode bits in the high bits of the `dtype` argument of the glue entry points (version 101; SJD_F2_ROPE_TABLE: 102, its 65..256 rows: 103).  dtype & SJD_DTYPE_MASK is the dtype code
  * above; a value without mode bits selects the plain kernels, bit for bit as before.  An entry point given a bit it does not know returns
  * SJD_ERR_UNSUPPORTED.
  *   SJD_F1_POST_NORM      sjd_add_rmsnorm: the swin-norm order of ChameleonSwinDecoderLayer (reference modeling_chameleon.py:670-735),
@@ -50,7 +50,11 @@ extern "C" {
  *                         the caller guarantees S_rows >= S_max (positions clamp to [0, S_max - 1]).  Elements (2i, 2i+1) pair up:
  *                         out0 = x0 c - x1 s, out1 = x1 c + x0 s, each product and sum rounded to fp32, then once to `dtype` -- bit for
  *                         bit the ATen ops on the same 16-bit q / k.  v and the K/V append as without the bit.  QK-norm pointers:
- *                         SJD_ERR_BAD_ARG; an fp8 cache, B*n > 64 or D not 64 / 128: SJD_ERR_UNSUPPORTED. */
+ *                         SJD_ERR_BAD_ARG; an fp8 cache or D not 64 / 128: SJD_ERR_UNSUPPORTED.  Rows: B*n <= 64 from a dense `qkv` or
+ *                         from split-K planes; 64 < B*n <= 256 (version 103) from split-K planes only (`part` != NULL) -- a dense source
+ *                         with more than 64 rows stays SJD_ERR_UNSUPPORTED.  Above 64 rows a wave serves four consecutive heads of one
+ *                         kind when H and H_kv are multiples of 4 (one head per wave otherwise, or with SJD_F2_ROWS=0 in the
+ *                         environment); both forms write the same bits. */
 #define SJD_DTYPE_MASK 0xff
 #define SJD_F1_POST_NORM 0x100
 #define SJD_F2_ROPE_TABLE 0x200

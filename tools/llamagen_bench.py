@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """LlamaGen on one MI355X: the ATen window forward against the fused HIP path (LlamaGenBackbone.enable_fused).
 
-  --sweep   G1 launch shapes of the four per-layer projections and the output head of one preset (default GPT-XL) at a 32-row window
-            (window 16, CFG): us per launch from a hipGraph of back-to-back launches over enough weight copies that each streams from HBM.
+  --sweep   G1 launch shapes of the four per-layer projections and the output head of one preset (default GPT-XL) at a --rows-row window
+            (default 32: window 16, CFG; 128 / 256: four / eight prompts per forward, column-tile counts of kernel G1w, at most eight planes): us per launch from a hipGraph of back-to-back launches over enough weight copies that each streams from HBM.
             One JSON line per shape; the fastest per projection is what LlamaGenBackbone.G1_CFG_LLAMAGEN / HEAD_CFG hold.
   --ab      ms per SJD step, ATen against fused, for GPT-B c2i 256px, GPT-XL t2i 512px (120 caption rows, left-padded) and GPT-XXL t2i 512px
             on synthetic weights (window 16, CFG, bf16): both legs in the same process on the same weights, timed in alternation over
             --rounds rounds (median reported), captured hipGraphs in both; then one whole image per leg (tokens/s) and the packed bytes one
             fused step streams / step time / 8 TB/s.
+  --batch   several prompts per forward (SJDBatchEngine): for the same three configurations ms per SJD step and accepted image tokens/s per GPU
+            at 1 (SJDEngine on the default packing: the one-prompt path), 2, 4 and 8 prompts per forward (packed with max_rows 64 / 128 / 256),
+            all legs in one process on the same weights, timed in alternation over --rounds rounds (median and the per-round values reported),
+            the fraction of 8 TB/s each step streams; then F2's table rotary at 256 rows, GPT-XL shape: four heads per wave against one
+            (SJD_F2_ROWS=0), us per launch from a hipGraph of back-to-back launches.
   --step    the fused step alone (one preset, --steps timed iterations): what the rocprofv3 by-shape table is taken from.
 """
 import argparse
@@ -73,11 +78,11 @@ def sweep(args):
         ws = [(torch.randn(N, K, generator=g, device=dev) / K ** 0.5).to(torch.bfloat16) for _ in range(copies)]
         x = torch.randn(M, K, generator=g, device=dev).to(torch.bfloat16)
         for kc in (128, 256, 320, 512, 640, 1280):
-            if kc > K:
+            if kc > K or (M > 64 and -(-K // kc) > 8):       # (the wider sets: at most eight split-K planes, the limit the 32-row set observes)
                 continue
             for sm in (True, False):
                 packed = [ops.pack_weight(w, kc, sm) for w in ws]
-                for waves in (1, 2, 4, 8):
+                for waves in ((1, 2, 4, 8) if M <= 64 else (2, 3, 4, 6, 8)):       # (above 64 rows: the column-tile counts of kernel G1w)
                     try:
                         if name == "head":
                             fn = lambda i: ops.skinny_gemm_cols(x, packed[i % copies], N, K, kc, 0, N, waves, sm)
@@ -193,10 +198,122 @@ def ab(args):
             json.dump(out, f, indent=1)
 
 
+class _BatchLeg:
+    """P prompts per forward on one fused backbone (its own cache and engine); every prompt its own conditioning"""
+
+    def __init__(self, model, P, window, dev):
+        from sjd_amd.engine_batch import SJDBatchEngine
+        self.m, self.P, self.window, self.dev = model, P, window, dev
+        a = model.args
+        self.T, self.N = a.cls_token_num, a.block_size
+        self.s_max = ((self.T + self.N + window + 32 + 31) // 32) * 32
+        model.setup_cache(batch=2 * P, s_max=self.s_max)
+        self.eng = SJDBatchEngine(model, a.vocab_size, dev, P, max_window=window, use_graph=True)
+
+    def decode(self, warmup, steps):
+        from sjd_amd.engine import SJDConfig, WindowSpec
+        from sjd_amd.grammar import TopKTopPGrammar
+        m, a, T, N, w, dev = self.m, self.m.args, self.T, self.N, self.window, self.dev
+        specs = []
+        for j in range(self.P):
+            if a.model_type == "c2i":
+                cond, ks = torch.tensor([(207 + 101 * j) % 1000, a.num_classes], device=dev), torch.zeros(2, dtype=torch.int32)
+            else:
+                cap = (torch.randn(1, T, a.caption_dim, generator=torch.Generator().manual_seed(3 + j)) * 0.5).to(dev, torch.bfloat16)
+                cond = torch.cat([cap, torch.zeros_like(cap) + m.cls_embedding.uncond_embedding.to(cap.dtype)])
+                ks = torch.full((2,), CAP_PAD, dtype=torch.int32)
+            specs.append(WindowSpec(first_tokens=None, first_positions=None, key_start=ks, pos_offset=torch.zeros(2, dtype=torch.long), kv_base=T,
+                                    cond_embeds=m.embed_condition(cond), cond_sampling=dict(cfg_scale=4.0, top_k=1000, top_p=1.0)))
+        cfg = SJDConfig(jacobi_loop_interval_l=1, jacobi_loop_interval_r=N - w - 2, max_num_new_tokens=w, guidance_scale=4.0, seed=3, max_length=N)
+        self.eng.decode_many([[] for _ in specs], specs, [TopKTopPGrammar(1000, 1.0) for _ in specs], cfg, warmup_iters=warmup, timed_iters=steps,
+                             on_timed_start=torch.cuda.synchronize, on_timed_end=torch.cuda.synchronize)
+        rs = self.eng.run_stats
+        return 1e3 * rs["seconds"] / max(1, rs["timed_iterations"]), rs["tokens"] / rs["seconds"]
+
+
+def _f2_ab(dev, rows=256, H=20, D=64, hid=1280):
+    """F2's table rotary at `rows` rows, GPT-XL shape, planes source: us per launch, four heads per wave against one (SJD_F2_ROWS=0)"""
+    g = torch.Generator(device=dev).manual_seed(2)
+    S, N, n = 1216, 3 * H * D, 16
+    B = rows // n
+    table = BB._rope_table_extended(BB._rope_2d_table(32, D, 10000, 120).to(dev), S)
+    copies = 24
+    parts = [ops.Partials(torch.randn(5, rows, N, generator=g, device=dev), 5, N) for _ in range(copies)]       # (K 1280 in chunks of 256)
+    kc = torch.zeros(B, H, S, D, dtype=torch.bfloat16, device=dev)
+    vc = torch.zeros_like(kc)
+    pos = (400 + torch.arange(n, device=dev))[None].repeat(B, 1).reshape(-1).contiguous()
+    ss = torch.rand(3, rows, device=dev) * hid
+    out = {}
+    for name, env in (("rows_kernel", None), ("one_head_kernel", "0"), ("rows_kernel_again", None)):
+        if env is None:
+            os.environ.pop("SJD_F2_ROWS", None)
+        else:
+            os.environ["SJD_F2_ROWS"] = env
+        fn = lambda i: ops.qknorm_rope_append(parts[i % copies], kc, vc, None, None, None, None, None, pos, B, n, H, H, D, None, 400,
+                                              dtype=torch.bfloat16, row_norm=(ss, hid, 1e-5), rope_table=table)
+        out[name] = round(_graph_us(fn, 4 * copies), 2)
+    os.environ.pop("SJD_F2_ROWS", None)
+    return dict(shape=dict(rows=rows, H=H, D=D, planes=5), us_per_launch=out)
+
+
+def batch(args):
+    dev = torch.device("cuda:0")
+    out = dict(configs=[], window=args.window, cfg=True, dtype="bf16", rounds=args.rounds, steps=args.steps, warmup=args.warmup)
+    for preset, mt, size in CONFIGS:
+        if args.only and preset not in args.only.split(","):
+            continue
+        base = _make(preset, mt, size, dev)
+        models = {1: base}
+        for P in (2, 4, 8):
+            models[P] = _make(preset, mt, size, dev)
+            models[P].load_state_dict(base.state_dict())
+        for P, m in models.items():
+            rows = P * 2 * args.window
+            m.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256))
+        legs = {1: _Leg(base, args.window, dev)}
+        legs.update({P: _BatchLeg(models[P], P, args.window, dev) for P in (2, 4, 8)})
+        ms, tps = {P: [] for P in legs}, {P: [] for P in legs}
+        for _ in range(args.rounds):
+            for P, leg in legs.items():
+                if P == 1:
+                    _, st, _ = leg.decode(args.warmup, args.steps)
+                    ms[P].append(1e3 * st.seconds / max(1, st.timed_nfe))
+                    tps[P].append(st.tokens / st.seconds)
+                else:
+                    a_, b_ = leg.decode(args.warmup, args.steps)
+                    ms[P].append(a_)
+                    tps[P].append(b_)
+        med_ms = {P: statistics.median(v) for P, v in ms.items()}
+        med_tps = {P: statistics.median(v) for P, v in tps.items()}
+        rec = dict(preset=preset, model_type=mt, image_size=size, layers=base.n_layers,
+                   ms_per_step={str(P): round(v, 3) for P, v in med_ms.items()},
+                   tokens_per_s={str(P): round(v, 1) for P, v in med_tps.items()},
+                   ms_per_step_rounds={str(P): [round(x, 3) for x in v] for P, v in ms.items()},
+                   tokens_per_s_rounds={str(P): [round(x, 1) for x in v] for P, v in tps.items()},
+                   tokens_per_s_vs_one_prompt={str(P): round(med_tps[P] / med_tps[1], 2) for P in legs},
+                   fraction_of_8tbps={str(P): round(models[P].packed_bytes() / (med_ms[P] * 1e-3) / (PEAK_TBPS * 1e12), 3) for P in legs},
+                   g1_cfg={str(P): [models[P].G1_CFG, list(models[P].HEAD_CFG)] for P in legs})
+        print(json.dumps(rec), flush=True)
+        out["configs"].append(rec)
+        del legs, models, base
+        torch.cuda.empty_cache()
+    out["f2_table_256rows"] = _f2_ab(dev)
+    print(json.dumps(out["f2_table_256rows"]), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def step(args):
     dev = torch.device("cuda:0")
     preset, mt, size = next(c for c in CONFIGS if c[0] == args.preset)
     m = _make(preset, mt, size, dev)
+    if args.prompts > 1:
+        rows = args.prompts * 2 * args.window
+        m.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256))
+        ms, tps = _BatchLeg(m, args.prompts, args.window, dev).decode(args.warmup, args.steps)
+        print(json.dumps(dict(preset=preset, prompts=args.prompts, ms_per_step=round(ms, 3), tokens_per_s=round(tps, 1))), flush=True)
+        return
     m.enable_fused(ops, gemm="sjd")
     leg = _Leg(m, args.window, dev)
     _, st, _ = leg.decode(args.warmup, args.steps)
@@ -208,6 +325,8 @@ def main():
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--ab", action="store_true")
     ap.add_argument("--step", action="store_true")
+    ap.add_argument("--batch", action="store_true")
+    ap.add_argument("--prompts", type=int, default=1, help="--step: prompts per forward (SJDBatchEngine above 1)")
     ap.add_argument("--preset", default="GPT-XL", choices=list(PRESETS))
     ap.add_argument("--only", default="")
     ap.add_argument("--rows", type=int, default=32)
@@ -221,6 +340,8 @@ def main():
         sweep(args)
     if args.ab:
         ab(args)
+    if args.batch:
+        batch(args)
     if args.step:
         step(args)
 
