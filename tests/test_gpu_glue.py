@@ -841,3 +841,119 @@ def test_mlp_pair_matches_g1sz_then_g1z(dev, M, I, KC_dn, step_major_dn, with_no
     for y, part in outs:
         assert torch.equal(y.view(torch.int16), y_ref.view(torch.int16)) and torch.equal(part.data.view(torch.int32), p_ref.view(torch.int32))
     assert ops.mlp_pair_timeouts() == t0
+
+
+# ------------------------------------------------------------------------------------------------ F2 under a blob array
+def _f2_blob_ids():
+    from tests.blob_array_cases import F2_BLOB_CASES
+    out = []
+    for c in F2_BLOB_CASES:
+        for dt in c[11]:
+            for flag in c[12]:
+                out.append(pytest.param(c, dt, flag, id=f"{c[0]}-{dt}" + (f"-rows{flag}" if flag is not None else "")))
+    return out
+
+
+@pytest.mark.parametrize("case,dt,rows_flag", _f2_blob_ids())
+def test_f2_blob_array(dev, monkeypatch, case, dt, rows_flag):
+    """F2 with several prompts per launch: batch row b appends its K/V rows at the kv_len of blob b // nb (sjdi_kv_rows in the two split-K
+    kernels, sjdi_params_of for a dense source).  q is bit-identical to the same call with a host kv_len (q does not depend on it); slot
+    j's K/V rows sit at [kv_j, kv_j + n) and are the bytes of a launch of that slot alone with host kv_len; every other cache row still
+    holds the sentinel the caches were filled with.  Rotate-half with and without per-head QK-norm, folded row_norm, SJD_QKN_SHARDS, dense
+    and split-K sources, the one-head and the four-heads-per-wave kernel (SJD_F2_ROWS), 16-bit and fp8 caches, slots in both orders.
+    The dense QK-norm variant is also held against the ATen sequence test_f2_qknorm_rope_append uses, at its tolerance."""
+    import sjd_amd.ops as ops
+    import sjd_amd._lib as L
+    from sjd_amd.backbones import _rotate_half
+    from tests.blob_array_cases import F2_SLOT_KV
+    name, nb, n, slots, H, Hkv, n_chunks, qk_norm, folded, shards, fp8, _, _ = case
+    dtype = torch.bfloat16 if dt == "bf16" else torch.float16
+    if rows_flag is not None:
+        monkeypatch.setenv("SJD_F2_ROWS", rows_flag)
+    D, S, hid = 128, 1152, 4096
+    B, ncol = nb * slots, (H + 2 * Hkv) * D
+    T = B * n
+    g = torch.Generator().manual_seed(len(name) + 31 * slots)
+    if n_chunks:
+        planes = torch.zeros(n_chunks, ops._prows(T), ncol)
+        planes[:, :T] = torch.randn(n_chunks, T, ncol, generator=g)
+        dense = None
+    else:
+        assert T <= 64
+        dense = torch.randn(T, ncol, generator=g).to(dtype)
+    sumsq = torch.rand(3, ops._prows(T), generator=g).add(0.5).mul(hid / 3.0) if folded else None
+    w = lambda a: (a + 0.2 * torch.randn(shards, D, generator=g)).to(dtype).to(dev)
+    args = (w(1.0), w(0.0), w(1.0), w(0.0)) if qk_norm else (None,) * 4
+    inv = (1.0 / (10000.0 ** (torch.arange(0, D, 2).float() / D))).to(dev)
+    scale = (0.05, 0.03)
+
+    def sentinel(rows, r0=0):    # a different value in every batch row; fp8: raw bytes
+        if fp8:
+            return (0x31 + r0 + torch.arange(rows, dtype=torch.uint8, device=dev).view(rows, 1, 1, 1)).expand(rows, Hkv, S, D).contiguous().view(ops.FP8)
+        return (100.0 + r0 + torch.arange(rows, device=dev).view(rows, 1, 1, 1)).expand(rows, Hkv, S, D).to(dtype).contiguous()
+    raw = lambda t: t.view(torch.uint8) if fp8 else t.view(torch.int16)
+
+    def launch(r0, rows, kc, vc, pos, params, kv_len):
+        """F2 over batch rows [r0, r0 + rows) of the source"""
+        t0, t1 = r0 * n, (r0 + rows) * n
+        if dense is not None:
+            src = dense[t0:t1].contiguous().to(dev)
+            rn = None
+        else:
+            pl = torch.zeros(n_chunks, ops._prows(t1 - t0), ncol)
+            pl[:, :t1 - t0] = planes[:, t0:t1]
+            src = ops.Partials(pl.to(dev), n_chunks, ncol)
+            rn = None
+            if folded:
+                ss = torch.ones(3, ops._prows(t1 - t0))
+                ss[:, :t1 - t0] = sumsq[:, t0:t1]
+                rn = (ss.to(dev), hid, 1e-5)
+        return ops.qknorm_rope_append(src, kc, vc, *args, inv, pos[r0:r0 + rows].reshape(-1).contiguous().to(dev), rows, n, H, Hkv, D, params, kv_len,
+                                      kv_scale=scale, dtype=dtype, row_norm=rn, qk_shards=shards)
+
+    for kvs in (F2_SLOT_KV[:slots], F2_SLOT_KV[:slots][::-1]):
+        kv_rows = torch.tensor(kvs).repeat_interleave(nb)
+        pos = kv_rows[:, None] + torch.arange(n)[None] - 3 * (torch.arange(B) % nb)[:, None] + 40
+        params = ops.BlobArray(L.IterParams, slots, dev)
+        for j, kv in enumerate(kvs):
+            v_ = params.blobs[j].view
+            v_.kv_len, v_.n_rows, v_.batch_rows = kv, n, nb
+        params.upload()
+        kc, vc = sentinel(B), sentinel(B)
+        q = launch(0, B, kc, vc, pos, params, 0)
+        kh, vh = sentinel(B), sentinel(B)
+        q_host = launch(0, B, kh, vh, pos, None, 40)
+        torch.cuda.synchronize()
+        assert torch.equal(q.view(torch.int16), q_host.view(torch.int16)) and q.float().abs().sum() > 0
+        sk = sv = sentinel(B)
+        untouched = torch.ones(B, S, dtype=torch.bool, device=dev)
+        for j, kv in enumerate(kvs):
+            lo, hi = j * nb, (j + 1) * nb
+            ck, cv = sentinel(nb, lo), sentinel(nb, lo)
+            qs = launch(lo, nb, ck, cv, pos, None, kv)
+            torch.cuda.synchronize()
+            assert torch.equal(qs.view(torch.int16), q[lo:hi].view(torch.int16)), f"slot {j}: q"
+            for got, solo, sent in ((kc, ck, sk), (vc, cv, sv)):
+                assert torch.equal(raw(got[lo:hi, :, kv:kv + n]), raw(solo[:, :, kv:kv + n])), f"slot {j} (kv_len {kv}): rows are not those of the slot's own launch"
+                assert not torch.equal(raw(got[lo:hi, :, kv:kv + n]), raw(sent[lo:hi, :, kv:kv + n])), f"slot {j}: nothing appended at kv_len {kv}"
+                assert torch.equal(raw(solo[:, :, :kv]), raw(sent[lo:hi, :, :kv])) and torch.equal(raw(solo[:, :, kv + n:]), raw(sent[lo:hi, :, kv + n:]))
+            untouched[lo:hi, kv:kv + n] = False
+        m = untouched[:, None, :, None].expand(B, Hkv, S, D)
+        assert torch.equal(raw(kc)[m], raw(sk)[m]) and torch.equal(raw(vc)[m], raw(sv)[m]), "a cache row outside every [kv_j, kv_j + n) lost the sentinel"
+        if dense is not None and qk_norm and not fp8:       # against the unfused ATen sequence (test_f2_qknorm_rope_append), at its tolerance
+            from sjd_amd.backbones import _HeadLayerNorm
+            qn, kn = _HeadLayerNorm(D, H).to(dev).to(dtype), _HeadLayerNorm(D, Hkv).to(dev).to(dtype)
+            qn.weight.data, qn.bias.data, kn.weight.data, kn.bias.data = args
+            x = dense.to(dev).view(B, n, H + 2 * Hkv, D)
+            qr, kr, vr = qn(x[:, :, :H]), kn(x[:, :, H:H + Hkv]), x[:, :, H + Hkv:]
+            fr = pos.to(dev)[:, :, None].float() * inv[None, None, :]
+            emb = torch.cat((fr, fr), dim=-1)
+            cos, sin = emb.cos().to(dtype)[:, :, None, :], emb.sin().to(dtype)[:, :, None, :]
+            qr, kr = qr * cos + _rotate_half(qr) * sin, kr * cos + _rotate_half(kr) * sin
+            tol = dict(atol=4e-2, rtol=4e-2)
+            torch.testing.assert_close(q.float(), qr.float(), **tol)
+            for b in range(B):
+                kv = int(kv_rows[b])
+                torch.testing.assert_close(kc[b, :, kv:kv + n].float(), kr[b].transpose(0, 1).float(), **tol)
+                assert torch.equal(vc[b, :, kv:kv + n], vr[b].transpose(0, 1))
+            assert (q.float() - qr.float()).abs().mean() < 4e-3

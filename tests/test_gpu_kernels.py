@@ -17,6 +17,8 @@ pytestmark = pytest.mark.gpu
 from oracle import sjd_oracle as O
 from oracle.attention_ref import OracleWindowAttention
 from tests.helpers import make_pq
+from tests import blob_array_cases as BA
+from tests.blob_array_cases import attention_fp64
 
 
 @pytest.fixture(scope="module")
@@ -331,28 +333,14 @@ def test_k1_k3_attention(dev, case, n_split):
     assert err[vis].mean() < 3e-3, f"mean err {err[vis].mean()}"
     assert (got[~vis] == 0).all()
     # The kernel's rounding points restated (the fp8 test does the same for its P): scores and the softmax sum are
-    # fp32, each probability is rounded ONCE to the 16-bit MFMA operand type before P.V (relative error <= u = 2^-8 bf16 / 2^-11 fp16: half an ulp,
-    # whatever running maximum it was taken against), the output is rounded once more.  So element by element
-    #     |out - exact| <= u * (sum_j p_j |v_jd|  +  |exact_d|)            (+ fp16: N * 2^-25 max|v| for subnormal probabilities)
-    # with exact = fp64 attention over the same 16-bit operands -- about two output ulps; a wrong tile edge, mask bit or split merge
-    # is orders of magnitude above it, where the 3e-2 above would hide it.
-    u = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
-    G = H // Hkv
-    Kd, Vd = ref_cache.k[0].double(), ref_cache.v[0].double()
-    for b in range(B):
-        for i in range(n):
-            lo, hi = key_start[b], kv_len + i + 1
-            if hi <= lo:
-                continue
-            for h in range(H):
-                kk, vv = Kd[b, h // G, lo:hi], Vd[b, h // G, lo:hi]
-                p = torch.softmax((kk @ q[b, i, h].double()) / D ** 0.5, dim=0)
-                exact = (p[:, None] * vv).sum(0)
-                bound = u * 1.05 * ((p[:, None] * vv.abs()).sum(0) + exact.abs()) + 2e-6
-                if dtype == torch.float16:
-                    bound = bound + (hi - lo) * 2.0 ** -25 * float(vv.abs().max())
-                e = (got[b, i, h].double() - exact).abs()
-                assert (e <= bound).all(), f"{name} b{b} row{i} head{h}: err {float(e.max()):.3e} over the rounding bound {float(bound[e.argmax()]):.3e}"
+    # fp32, each probability is rounded ONCE to the 16-bit MFMA operand type before P.V, the output is rounded once more -- the element-wise
+    # bound of tests/blob_array_cases.py::attention_fp64 (about two output ulps; a wrong tile edge, mask bit or split merge is orders of
+    # magnitude above it, where the 3e-2 above would hide it).
+    exact, bound, _ = attention_fp64(q, ref_cache.k[0], ref_cache.v[0], kv_len, n, key_start, dtype)
+    e = (got.double() - exact).abs()
+    over = e > bound
+    over[~vis] = False
+    assert not over.any(), f"{name}: err {float(e[over].max()):.3e} over the rounding bound at {over.nonzero()[0].tolist()} (batch row, row, head, column)"
 
 
 _DIRECT_SCRIPT = r"""
@@ -942,3 +930,334 @@ def test_slot_launches_equal_one_launch_per_slot(dev, n_slots, n_batch, fold):
         for i in range(n_slots):
             st = b_["state"].blobs[i].view
             assert 1 <= st.m <= max(1, b_["params"].blobs[i].view.n_rows)
+
+
+# ------------------------------------------------------------------------------------------------ several prompts per launch (blob array)
+# One launch serves P slots x nb batch rows, every slot with its own kv_len / n_rows in its sjd_iter_params blob (batch_rows = nb).  The
+# blob lookup is written three times (k1_entry, sjdi_kv_rows, sjdi_params_of); the SJDBatchEngine tests are teacher-forced and cannot
+# see a slot that read its neighbour's blob.  These compare every slot with fp64 attention over its own operands and, bit for bit, with
+# a launch of that slot alone that takes kv_len / n_rows from the host.
+def _blob_array(ops, L, dev, kv, rows, nb):
+    arr = ops.BlobArray(L.IterParams, len(kv), dev)
+    for j, (a, r) in enumerate(zip(kv, rows)):
+        view = arr.blobs[j].view
+        view.kv_len, view.n_rows, view.batch_rows = int(a), int(r), int(nb)
+    arr.upload()
+    return arr
+
+
+_BLOB_REFS = {}
+
+
+def _blob_inputs(case, dtype, fp8):
+    """CPU inputs of a case, the caches K3 must leave behind and the per-slot references (cached: the forms of a case share them)"""
+    key = (case["name"], dtype, fp8)
+    if key in _BLOB_REFS:
+        return _BLOB_REFS[key]
+    nb, W = case["nb"], case["window"]
+    sk, sv = case["fp8_scales"] if fp8 else (1.0, 1.0)
+    q, k, v, kc, vc = BA.make_inputs(case, dtype)
+    k, v = torch.nan_to_num(k, nan=0.0), torch.nan_to_num(v, nan=0.0)
+    pad = BA.padding_rows(case)
+    g = torch.Generator().manual_seed(77)
+    # rows past a slot's n_rows: large finite values -- a kernel that attends over one of them (or over another slot's length) is far off
+    k[pad] = (torch.randn(k[pad].shape, generator=g) * 30.0).to(dtype)
+    v[pad] = (torch.randn(v[pad].shape, generator=g) * 30.0).to(dtype)
+    if fp8:
+        kc, vc = (kc.float() * 1.2).to(BA.FP8), (vc.float() * 1.2).to(BA.FP8)                      # stored byte = fp8(value / scale)
+        k, v = (k.float() * sk * 1.2).to(dtype), (v.float() * sv * 1.2).to(dtype)
+        new_k, new_v = (k.float() / sk).to(BA.FP8), (v.float() / sv).to(BA.FP8)                    # torch's round-to-nearest-even e4m3 cast
+    else:
+        new_k, new_v = k, v
+    want_k, want_v = kc.clone(), vc.clone()
+    refs = []
+    for j, (kv, n) in enumerate(zip(case["kv"], case["rows"])):
+        lo, hi = j * nb, (j + 1) * nb
+        want_k[0, lo:hi, :, kv:kv + n] = new_k[lo:hi, :n].transpose(1, 2)
+        want_v[0, lo:hi, :, kv:kv + n] = new_v[lo:hi, :n].transpose(1, 2)
+        ks = case["key_start"][lo:hi]
+        if fp8:
+            refs.append(BA.attention_fp8_refs(q[lo:hi], want_k[0, lo:hi].float() * sk, want_v[0, lo:hi].float() * sv, kv, n, ks))
+        else:
+            refs.append(BA.attention_fp64(q[lo:hi], want_k[0, lo:hi], want_v[0, lo:hi], kv, n, ks, dtype))
+    _BLOB_REFS[key] = (q, k, v, kc, vc, want_k, want_v, refs)
+    return _BLOB_REFS[key]
+
+
+def _bits(t):
+    return t.view(torch.uint8) if t.dtype == BA.FP8 else t.view(torch.int16)
+
+
+def _k1_form_launch(ops, form, q, k, v, cache, ks, params, kv_len, scales):
+    """K3 + K1 of one form on a NaN-filled workspace -> the output(s): [__call__, attend] or the 30 + 3 launches of the merged form"""
+    B, n, H, D = q.shape
+    fp8 = cache.k.dtype == BA.FP8
+    kv_host = 0 if params is not None else int(kv_len)
+    if isinstance(form, tuple):                       # ("merged", s): the splits merged by their last workgroup, 30 launches in a row + a hipGraph
+        s = form[1]
+        if fp8:
+            ops.kv_append_fp8(k, v, cache.k[0], cache.v[0], scales[0], scales[1], params, kv_host)
+        else:
+            ops.kv_append(k, v, cache.k[0], cache.v[0], params, kv_host)
+        ws = ops.attention_workspace(B, H, n, D, s, q.device).fill_(float("nan"))
+
+        def run(out):
+            if fp8:
+                ops.draft_window_attention_fp8(q, cache.k[0], cache.v[0], out, scales[0], scales[1], ks, params, kv_host, s, ws, merged=True)
+            else:
+                ops.draft_window_attention(q, cache.k[0], cache.v[0], out, ks, params, kv_host, s, ws, merged=True)
+        outs = [torch.full_like(q, 7.0) for _ in range(33)]
+        for o in outs[:30]:
+            run(o)
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            run(outs[30])
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for o in outs[30:]:
+                run(o)
+        for _ in range(10):
+            graph.replay()
+        torch.cuda.synchronize()
+        assert int(ops.k1_tickets(B, cache.k.shape[2], n, q.device).abs().sum()) == 0          # every ticket re-armed
+        return outs
+    attn = ops.HipWindowAttention(n_split=4 if form == "colsplit" else form)
+    attn.regime = "colsplit" if form == "colsplit" else "keysplit"
+    if form == "colsplit":
+        assert ops.colsplit_ok(B, n, H, cache.k.shape[2], D, cache.k.dtype)
+    attn.params, attn.kv_scale = params, scales
+    attn._workspace(B, H, n, D, q.device).fill_(float("nan"))
+    out = attn(0, q, k, v, cache, kv_len, ks)
+    torch.cuda.synchronize()
+    attn._workspace(B, H, n, D, q.device).fill_(float("nan"))
+    out2 = attn.attend(0, q, cache, kv_len, ks)
+    torch.cuda.synchronize()
+    return [out, out2]
+
+
+def _run_blob_case(dev, case, dtype, form, fp8=False):
+    """-> worst error / bound over the compared elements (16-bit caches) or worst error / tolerance (fp8)"""
+    ops, L = _ops()
+    nb, W, D = case["nb"], case["window"], case["D"]
+    sk, sv = scales = case["fp8_scales"] if fp8 else (1.0, 1.0)
+    q, k, v, kc, vc, want_k, want_v, refs = _blob_inputs(case, dtype, fp8)
+    assert max(case["kv"]) + W <= kc.shape[3], "a slot's window would leave the cache"
+    params = _blob_array(ops, L, dev, case["kv"], case["rows"], nb)
+    ks = torch.tensor(case["key_start"], dtype=torch.int32, device=dev)
+    qd, kd, vd = q.to(dev), k.to(dev), v.to(dev)
+    cache = _Cache(kc.clone().to(dev), vc.clone().to(dev))
+    outs = _k1_form_launch(ops, form, qd, kd, vd, cache, ks, params, -1, scales)
+    got_k, got_v = cache.k.cpu(), cache.v.cpu()
+    got = outs[0].float().cpu()
+    for o in outs[1:]:
+        assert torch.equal(_bits(o), _bits(outs[0])), f"{case['name']} {form}: a repeated launch gave other bytes"
+    assert torch.isfinite(got).all()
+    worst = 0.0
+    for j, (kv, n) in enumerate(zip(case["kv"], case["rows"])):
+        lo, hi = j * nb, (j + 1) * nb
+        tag = f"{case['name']} {form} slot {j} (kv_len {kv}, n_rows {n})"
+        # K3: older rows untouched, the slot's rows at ITS offset, nothing behind the window
+        for g_, w_, pre in ((got_k, want_k, kc), (got_v, want_v, vc)):
+            assert torch.equal(_bits(g_[0, lo:hi, :, :kv]), _bits(pre[0, lo:hi, :, :kv])), f"{tag}: K3 touched rows in front of kv_len"
+            assert torch.equal(_bits(g_[0, lo:hi, :, kv:kv + n]), _bits(w_[0, lo:hi, :, kv:kv + n])), f"{tag}: K3 rows are not the new rows"
+            assert torch.equal(_bits(g_[0, lo:hi, :, kv + W:]), _bits(pre[0, lo:hi, :, kv + W:])), f"{tag}: K3 wrote behind the window"
+        assert (got[lo:hi, n:] == 0).all(), f"{tag}: padding rows are not zero"
+        o = got[lo:hi, :n]
+        if fp8:
+            emu, want, conc, vis = refs[j]
+            for ref_, cm, am, cn, an in ((emu, 0.1, 5e-3, 0.02, 1e-3), (want, 0.2, 1e-2, 0.05, 2e-3)):      # test_k1_k3_fp8_kv_cache's two tolerances
+                err = (o - ref_).abs()
+                r_max, r_mean = err.amax(-1) / (cm * sv * conc + am), err.mean(-1) / (cn * sv * conc + an)
+                r = float(torch.maximum(r_max, r_mean)[vis].max()) if vis.any() else 0.0
+                worst = max(worst, r)
+                assert r < 1.0, f"{tag}: fp8 error {r:.3f} x the tolerance"
+        else:
+            exact, bound, vis = refs[j]
+            e = (o.double() - exact).abs()
+            ratio = (e / bound)[vis]
+            r = float(ratio.max()) if ratio.numel() else 0.0
+            worst = max(worst, r)
+            assert r <= 1.0, f"{tag}: error {r:.3f} x the rounding bound"
+        assert (o[~vis] == 0).all(), f"{tag}: rows without a visible key are not zero"
+        # bit for bit the launch of this slot alone, kv_len / n_rows from the host, same form and split count, fresh NaN workspace
+        solo = _Cache(kc[:, lo:hi].clone().to(dev), vc[:, lo:hi].clone().to(dev))
+        so = _k1_form_launch(ops, form, qd[lo:hi, :n].contiguous(), kd[lo:hi, :n].contiguous(), vd[lo:hi, :n].contiguous(), solo, ks[lo:hi].contiguous(),
+                             None, kv, scales)
+        same = torch.equal(_bits(so[0]), _bits(outs[0][lo:hi, :n].contiguous()))
+        if not same:
+            print(f"{tag}: max |blob array - solo| = {float((so[0].float() - outs[0][lo:hi, :n].float()).abs().max()):.3e}")
+        assert same, f"{tag}: the output differs from the launch of the slot alone"
+        assert torch.equal(_bits(solo.k[0, :, :, :kv + n]), _bits(cache.k[0, lo:hi, :, :kv + n])) and \
+            torch.equal(_bits(solo.v[0, :, :, :kv + n]), _bits(cache.v[0, lo:hi, :, :kv + n])), f"{tag}: cache rows differ from the launch of the slot alone"
+    print(f"blob-array K1 {case['name']} {str(dtype).replace('torch.', '')}{' fp8' if fp8 else ''} {form}: worst error / bound {worst:.3f}")
+    return worst
+
+
+def _blob_params():
+    out = []
+    for c in BA.BLOB_CASES:
+        for rev in ((False, True) if c["reverse"] else (False,)):
+            cc = BA.ordered(c, rev)
+            for dt in c["dtypes"]:
+                for form in c["forms"]:
+                    fid = form if not isinstance(form, tuple) else f"merged{form[1]}"
+                    out.append(pytest.param(cc, dt, form, id=f"{cc['name']}-{str(dt).replace('torch.', '')}-{fid}"))
+    return out
+
+
+@pytest.mark.parametrize("case,dtype,form", _blob_params())
+def test_k1_k3_blob_array(dev, case, dtype, form):
+    """K3 + K1 (__call__) and K1 alone (attend) of P slots in one launch, every slot's kv_len / n_rows from its own blob: K3 rows at the
+    slot's own offset, output within the rounding bound of fp64 attention over the slot's own operands, hidden and padding rows zero, and
+    the bytes of a launch of that slot alone with host kv_len / n_rows (a workgroup's arithmetic depends only on its own batch row's
+    kv_len, n_rows and key_start).  The merged form: 30 launches in a row and a hipGraph replay, tickets re-armed."""
+    _run_blob_case(dev, case, dtype, form)
+
+
+def _blob_params_fp8():
+    out = []
+    for c in BA.BLOB_CASES:
+        for form in c["fp8_forms"]:
+            out.append(pytest.param(c, c["dtypes"][0], form, id=f"{c['name']}-fp8-{form}"))
+    return out
+
+
+@pytest.mark.parametrize("case,dtype,form", _blob_params_fp8())
+def test_k1_k3_fp8_blob_array(dev, case, dtype, form):
+    """the same over fp8 caches (k1_partial_fp8 / k1_dsplit_fp8, K3-fp8): appended rows are torch's e4m3 cast of x / scale at the slot's
+    own offset, the two tolerances of test_k1_k3_fp8_kv_cache per slot, the bytes of the slot's own launch"""
+    _run_blob_case(dev, case, dtype, form, fp8=True)
+
+
+_NO_RING_SCRIPT = r"""
+import sys, torch
+sys.path.insert(0, ".")
+from tests import blob_array_cases as BA
+from tests.test_gpu_kernels import _run_blob_case
+dev = torch.device("cuda:0")
+for name, dt, form in (("gqa4_window32", torch.float16, 8), ("gqa4_window32", torch.bfloat16, 1), ("gqa2_window32", torch.bfloat16, 8)):
+    case = next(c for c in BA.BLOB_CASES if c["name"] == name)
+    _run_blob_case(dev, case, dt, form)
+print("NO_RING_OK")
+"""
+
+
+def test_k1_shared_tile_kernel_blob_array(dev):
+    """SJD_K1_RING=0 (read once per process -> a subprocess): the grouped-query cases on k1_partial_shared instead of the ring kernel"""
+    import subprocess
+    import sys
+    env = dict(os.environ, SJD_K1_RING="0", SJD_TEST_POISON="0")
+    r = subprocess.run([sys.executable, "-c", _NO_RING_SCRIPT], capture_output=True, text=True, env=env,
+                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), timeout=600)
+    print(r.stdout[-2000:])
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    assert r.stdout.strip().splitlines()[-1] == "NO_RING_OK"
+
+
+@pytest.mark.parametrize("reverse", [False, True])
+def test_k1_f32_blob_array(dev, reverse):
+    """k1_f32 (sjdi_kv_rows): every slot's output is the launch of that slot alone, bit for bit; padding rows zero"""
+    ops, L = _ops()
+    nb, W, H, D, S = 2, 16, 2, 64, 256
+    kvs, rows, kss = [200, 0, 40], [16, 7, 1], [0, 9, 0, 3, 0, 33]
+    if reverse:
+        kvs, rows, kss = kvs[::-1], rows[::-1], [0, 33, 0, 3, 0, 9]
+    B = nb * len(kvs)
+    g = torch.Generator().manual_seed(3)
+    kc, vc = torch.randn(1, B, H, S, D, generator=g).to(dev), torch.randn(1, B, H, S, D, generator=g).to(dev)
+    q, k, v = (torch.randn(B, W, H, D, generator=g).to(dev) for _ in range(3))
+    ks = torch.tensor(kss, dtype=torch.int32, device=dev)
+    attn = ops.HipWindowAttention(n_split=1)
+    attn.params = _blob_array(ops, L, dev, kvs, rows, nb)
+    cache = _Cache(kc.clone(), vc.clone())
+    out = attn(0, q, k, v, cache, -1, ks)
+    torch.cuda.synchronize()
+    assert torch.isfinite(out).all()
+    for j, (kv, n) in enumerate(zip(kvs, rows)):
+        lo, hi = j * nb, (j + 1) * nb
+        solo = _Cache(kc[:, lo:hi].clone(), vc[:, lo:hi].clone())
+        so = ops.HipWindowAttention(n_split=1)(0, q[lo:hi, :n].contiguous(), k[lo:hi, :n].contiguous(), v[lo:hi, :n].contiguous(), solo, kv, ks[lo:hi].contiguous())
+        torch.cuda.synchronize()
+        assert torch.equal(so.view(torch.int32), out[lo:hi, :n].contiguous().view(torch.int32)), f"slot {j}"
+        assert (out[lo:hi, n:] == 0).all() and so.abs().sum() > 0
+        assert torch.equal(solo.k[0, :, :, :kv + n], cache.k[0, lo:hi, :, :kv + n]) and torch.equal(cache.k[0, lo:hi, :, :kv], kc[0, lo:hi, :, :kv])
+
+
+@pytest.mark.parametrize("reverse", [False, True])
+@pytest.mark.parametrize("n_split", [1, 4])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_k1f_blob_array(dev, dtype, n_split, reverse):
+    """K1F / K1Fs (F2 + K1 in one launch; sjdi_kv_rows) with two slots of one batch row each (the kernel serves <= 32 rows): output rows and
+    appended cache rows of every slot are those of the launch of that slot alone with host kv_len / n_rows, bit for bit"""
+    ops, L = _ops()
+    n, H, D, S, nc, hid = 16, 6, 128, 512, 3, 512
+    kvs, rows, kss = ([448, 37], [16, 9], [17, 36]) if not reverse else ([37, 448], [9, 16], [36, 17])
+    B, N = 2, 3 * H * D
+    g = torch.Generator().manual_seed(5 + n_split)
+    planes = torch.zeros(nc, 32, N)
+    planes[:, :B * n] = torch.randn(nc, B * n, N, generator=g)
+    sumsq = torch.rand(2, 32, generator=g).add(0.5).mul(hid / 2.0)
+    mk = lambda a, b_: (a + b_ * torch.randn(1, D, generator=g)).to(dtype).to(dev)
+    qn = (mk(1.0, 0.2), mk(0.0, 0.1), mk(1.0, 0.2), mk(0.0, 0.1))
+    inv = (1.0 / (10000.0 ** (torch.arange(0, D, 2).float() / D))).to(dev)
+    pos = torch.stack([kvs[b] + torch.arange(n) - kss[b] for b in range(B)])
+    base_k, base_v = torch.randn(B, H, S, D, generator=g).to(dtype).to(dev), torch.randn(B, H, S, D, generator=g).to(dtype).to(dev)
+    ks = torch.tensor(kss, dtype=torch.int32, device=dev)
+    params = _blob_array(ops, L, dev, kvs, rows, 1)
+
+    def launch(pl, ss, kc, vc, p, b_, n_, prm, kv, ks_):
+        ws = ops.attention_workspace(b_, H, n_, D, n_split, dev).fill_(float("nan")) if n_split > 1 else None
+        return ops.qkv_attention_fused(ops.Partials(pl.to(dev), nc, N), kc, vc, *qn, inv, p.reshape(-1).contiguous().to(dev), b_, n_, H, D, prm, kv, ks_,
+                                       row_norm=(ss.to(dev), hid, 1e-5), dtype=dtype, n_split=n_split, workspace=ws)
+    kc, vc = base_k.clone(), base_v.clone()
+    out = launch(planes, sumsq, kc, vc, pos, B, n, params, 0, ks)
+    torch.cuda.synchronize()
+    assert torch.isfinite(out.float()).all()
+    for j, (kv, nj) in enumerate(zip(kvs, rows)):
+        pl, ss = torch.zeros(nc, 32, N), torch.ones(2, 32)
+        pl[:, :nj], ss[:, :nj] = planes[:, j * n:j * n + nj], sumsq[:, j * n:j * n + nj]
+        skc, svc = base_k[j:j + 1].clone(), base_v[j:j + 1].clone()
+        so = launch(pl, ss, skc, svc, pos[j:j + 1, :nj], 1, nj, None, kv, ks[j:j + 1].contiguous())
+        torch.cuda.synchronize()
+        assert torch.equal(so.view(torch.int16), out[j:j + 1, :nj].contiguous().view(torch.int16)), \
+            f"slot {j}: max diff {float((so.float() - out[j:j + 1, :nj].float()).abs().max()):.3e}"
+        assert (out[j, nj:] == 0).all() and so.float().abs().sum() > 0
+        for a, b_, base in ((skc, kc, base_k), (svc, vc, base_v)):
+            assert torch.equal(a[0, :, kv:kv + nj], b_[j, :, kv:kv + nj]) and torch.equal(b_[j, :, :kv], base[j, :, :kv])
+            assert not torch.equal(b_[j, :, kv:kv + nj], base[j, :, kv:kv + nj])
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("mode", ["16bit", "fp8", "fp8_head_major"])
+def test_k3_blob_array(dev, dtype, mode):
+    """kv_append / kv_append_fp8 (both layouts of the new rows) on their own: slot j's rows land at [kv_j, kv_j + n), every other cache row
+    keeps its content -- the caches of the batch rows all differ, so a row written at another slot's offset is seen"""
+    ops, L = _ops()
+    nb, n, Hkv, D, S = 2, 16, 4, 128, 1152
+    kvs = [21, 0, 300, 63, 64, 1000, 5, 511]
+    for order in (kvs, kvs[::-1]):
+        B = nb * len(order)
+        g = torch.Generator().manual_seed(9)
+        kc, vc = torch.randn(B, Hkv, S, D, generator=g).to(dtype), torch.randn(B, Hkv, S, D, generator=g).to(dtype)
+        k, v = torch.randn(B, n, Hkv, D, generator=g).to(dtype), torch.randn(B, n, Hkv, D, generator=g).to(dtype)
+        params = _blob_array(ops, L, dev, order, [n] * len(order), nb)
+        sk, sv = 0.5, 2.0
+        if mode == "16bit":
+            dk, dv = kc.clone().to(dev), vc.clone().to(dev)
+            ops.kv_append(k.to(dev), v.to(dev), dk, dv, params, 0)
+            pre_k, pre_v, new_k, new_v = kc, vc, k.transpose(1, 2), v.transpose(1, 2)
+        else:
+            pre_k, pre_v = kc.float().to(ops.FP8), vc.float().to(ops.FP8)
+            dk, dv = pre_k.clone().to(dev), pre_v.clone().to(dev)
+            hm = mode == "fp8_head_major"
+            src_k, src_v = (k.transpose(1, 2).contiguous(), v.transpose(1, 2).contiguous()) if hm else (k, v)
+            ops.kv_append_fp8(src_k.to(dev), src_v.to(dev), dk, dv, sk, sv, params, 0, head_major=hm)
+            new_k, new_v = (k.float() / sk).to(ops.FP8).transpose(1, 2), (v.float() / sv).to(ops.FP8).transpose(1, 2)
+        torch.cuda.synchronize()
+        for got, pre, new in ((dk.cpu(), pre_k, new_k), (dv.cpu(), pre_v, new_v)):
+            for j, kv in enumerate(order):
+                lo, hi = j * nb, (j + 1) * nb
+                assert torch.equal(_bits(got[lo:hi, :, kv:kv + n]), _bits(new[lo:hi].contiguous())), f"{mode} slot {j}: appended rows"
+                assert torch.equal(_bits(got[lo:hi, :, :kv]), _bits(pre[lo:hi, :, :kv])) and torch.equal(_bits(got[lo:hi, :, kv + n:]), _bits(pre[lo:hi, :, kv + n:])), \
+                    f"{mode} slot {j}: rows outside [kv_len, kv_len + n) changed"

@@ -271,3 +271,139 @@ def test_window_forward_at_production_shapes_against_independent_forwards(family
         with open(os.path.join(out_dir, f"r5_real_shape_forward_{tag_name}.json"), "w") as fh:
             json.dump(rep, fh, indent=1)
     assert rep["windows"]["argmax_agree"] >= 0.8, rep["windows"]
+
+
+# ------------------------------------------------------------------------------------------------ several prompts per forward (blob array)
+def _logits_from_head_partials(ho):
+    """the logits K2 derives from an ops.HeadOut: planes summed in chunk order, the folded final norm as a row scale, the 16-bit rounding
+    of the lm_head output (as tests/test_gpu_llamagen_batch.py::_head_logits_from_partials)"""
+    p = ho.part
+    acc = p.data[0].clone()
+    for c in range(1, p.n_chunks):
+        acc = acc + p.data[c]
+    ss, hid, eps = ho.row_norm
+    s = ss[0].clone()
+    for i in range(1, ss.shape[0]):
+        s = s + ss[i]
+    return (acc * torch.rsqrt(s / hid + eps)[:, None]).to(ho.dtype).float()
+
+
+BLOB_FORWARD_LAYERS = 3          # real widths, three layers: every kernel of the layer runs at its production launch shape; time and memory stay small
+
+# family, compress (the 12-bit weight stream), slots: kv_len / n_rows per slot.  kv_len lies on both sides of HipWindowAttention.COLSPLIT_MAX_KEYS (736);
+# a one-row slot is a finished prompt's dummy window, nine rows a ragged one
+BLOB_FORWARD_CASES = [
+    ("lumina7b", True, [300, 1216, 700, 2300], [16, 1, 9, 16]),
+    ("lumina7b", False, [2300, 700, 1216, 300], [16, 9, 1, 16]),
+    ("emu3_8b", False, [2000, 300], [32, 9]),
+]
+
+
+@pytest.mark.parametrize("family,compress,kvs,n_rows", BLOB_FORWARD_CASES, ids=["lumina7b_12bit", "lumina7b_raw", "emu3_8b"])
+@torch.no_grad()
+def test_blob_array_window_forward_against_independent_forwards(family, compress, kvs, n_rows):
+    """The Chameleon-family window forward with several prompts per launch -- every slot's kv_len / n_rows from its own sjd_iter_params blob
+    (batch_rows = 2), production G1_CFG_128ROW, K1 in the regime and split count the engine would choose -- against this file's
+    _IndependentForward (aten16 and fp32) run per slot on its own torch.cat cache.  The SJDBatchEngine tests are teacher-forced: a slot
+    that attended over its neighbour's kv_len, or appended its K/V rows at the neighbour's offset, gives self-consistent logits there.
+    Here the logits K2 would read (head partials summed) are held, PER SLOT and on the slot's valid rows only, to the bound of the
+    single-prompt test: |hip - fp32| <= 1.5 x |aten16 - fp32| (max and mean) and its argmax rule.  A pooled maximum would let one wrong
+    slot hide behind another slot's large but honest error.  Lumina-7B width (MHA 32 x 128, QK-norm, bf16, window 16, four slots, 12-bit
+    stream and uncompressed) and Emu3-8B width (GQA 32 / 8, fp16, window 32, two slots: the ring kernel)."""
+    import dataclasses
+    import sjd_amd.ops as ops
+    import sjd_amd._lib as L
+    import sjd_amd.backbones as BB
+    import sjd_amd.synthetic as synthetic
+    from sjd_amd.engine_batch import _CacheView
+    dev = torch.device("cuda:0")
+    if family == "lumina7b":
+        margs, dt, W = dataclasses.replace(BB.LUMINA_7B, num_hidden_layers=BLOB_FORWARD_LAYERS), torch.bfloat16, 16
+    else:
+        margs, dt, W = dataclasses.replace(BB.EMU3_8B, num_hidden_layers=BLOB_FORWARD_LAYERS), torch.float16, 32
+    nb, P = 2, len(kvs)
+    B, V = nb * P, margs.vocab_size
+    with torch.device(dev):
+        model = BB.ChameleonBackbone(margs, attn=ops.HipWindowAttention()).to(dt).eval()
+    synthetic.fill_state_dict_device(model, seed=0, embed_token_scale=0.7)
+    model.G1_CFG = dict(model.G1_CFG_128ROW)
+    model.enable_fused(ops, gemm="sjd", compress=compress)
+    if compress:
+        assert model.compress_stats["compressed"] >= model.compress_stats["matrices"] - 1, model.compress_stats
+    else:
+        assert model.compress_stats["compressed"] == 0
+    s_max = ((max(kvs) + W + 127) // 128) * 128
+    model.setup_cache(batch=B, s_max=s_max)
+    g = torch.Generator().manual_seed(23)
+    u0 = [20 + 7 * j for j in range(P)]                       # the uncond row of slot j hides the first u0[j] context tokens
+    ks = torch.tensor([x for j in range(P) for x in (0, u0[j])], dtype=torch.int32, device=dev)
+    po = -ks.long()
+    ctx = [torch.randint(4, 8196, (1, kv), generator=g).repeat(nb, 1).to(dev) for kv in kvs]
+    win = torch.randint(4, 8196, (P, 1, W), generator=g).repeat(1, nb, 1).view(B, W).to(dev)
+    # every slot's context through the backbone's prefill path (library GEMMs + F2 + K1 with host kv_len), two batch rows at a time
+    model.attn.params = None
+    full = model.cache
+    for j, kv in enumerate(kvs):
+        lo, hi = j * nb, (j + 1) * nb
+        rows = torch.arange(kv, device=dev)
+        pos = torch.where(rows[None] < ks[lo:hi, None], torch.ones(1, dtype=torch.long, device=dev), rows[None] + po[lo:hi, None])
+        model.cache = _CacheView(full, lo, hi)
+        model.attn.choose_regime(kv, dt, shape=(nb, kv, model.n_heads, model.n_kv_heads, model.head_dim))
+        model.forward_window(ctx[j], pos, 0, ks[lo:hi].contiguous())
+    model.cache = full
+    # the window forward: every slot's kv_len / n_rows from its blob
+    params = ops.BlobArray(L.IterParams, P, dev)
+    for j, (kv, n) in enumerate(zip(kvs, n_rows)):
+        view = params.blobs[j].view
+        view.kv_len, view.n_rows, view.batch_rows = kv, n, nb
+    params.upload()
+    kv_rows = torch.tensor(kvs, device=dev).repeat_interleave(nb)
+    pos = kv_rows[:, None] + torch.arange(W, device=dev)[None] + po[:, None]
+    shape = (B, W, model.n_heads, model.n_kv_heads, model.head_dim)
+    regime = model.attn.choose_regime(max(kvs) + W, dt, shape=shape)          # as SJDBatchEngine does per iteration
+    assert regime == "keysplit", "several prompts per forward are not a shape the column split serves"
+    seen, real = [], ops.skinny_gemm
+    ops.skinny_gemm = lambda x, *a_, **k_: (seen.append(int(x.shape[0])), real(x, *a_, **k_))[1]
+    try:
+        model.attn.params = params
+        ho = model.forward_window(win, pos, -1, ks, head_partials=True)
+    finally:
+        ops.skinny_gemm = real
+        model.attn.params = None
+    torch.cuda.synchronize()
+    assert isinstance(ho, ops.HeadOut) and ho.col0 == 0 and ho.urow_off == W
+    assert seen and set(seen) == {B * W}, "the projections ran on G1 at the full row count"
+    hip = _logits_from_head_partials(ho)[:B * W].view(B, W, -1)[..., :V]
+    assert torch.isfinite(hip).all()
+    rep = dict(family=family, dtype=str(dt), compress=bool(compress), layers=BLOB_FORWARD_LAYERS, window=W, k1_regime=regime,
+               n_split=int(model.attn.n_split or 0), slots=[])
+    failures = []
+    for j, (kv, n) in enumerate(zip(kvs, n_rows)):
+        lo, hi = j * nb, (j + 1) * nb
+        ref = {}
+        for tag, fdt in (("aten16", dt), ("fp32", torch.float32)):
+            f = _IndependentForward(model, fdt)
+            f.forward(ctx[j], 0, ks[lo:hi], po[lo:hi], (0, 32))
+            ref[tag] = f.forward(win[lo:hi, :n], kv, ks[lo:hi], po[lo:hi], (0, V))
+            del f
+        h, a16, f32 = hip[lo:hi, :n], ref["aten16"], ref["fp32"]
+        e_hip, e_aten = (h - f32).abs(), (a16 - f32).abs()
+        ia, ib = h.argmax(-1), a16.argmax(-1)
+        gap = (f32.gather(-1, ib[..., None]) - f32.gather(-1, ia[..., None])).abs()[..., 0]
+        agree = ia == ib
+        ok = agree | (gap <= 2.0 * e_aten.max())
+        rec = dict(slot=j, kv_len=kv, n_rows=n, key_start=[0, u0[j]], logit_std=round(float(f32.std()), 3),
+                   hip16_max=round(float(e_hip.max()), 5), hip16_mean=round(float(e_hip.mean()), 6),
+                   aten16_max=round(float(e_aten.max()), 5), aten16_mean=round(float(e_aten.mean()), 6),
+                   hip_over_aten_max=round(float(e_hip.max() / e_aten.max()), 3), hip_over_aten_mean=round(float(e_hip.mean() / e_aten.mean()), 3),
+                   argmax_agree=round(float(agree.float().mean()), 4), argmax_agree_or_tie=round(float(ok.float().mean()), 4))
+        rep["slots"].append(rec)
+        if not (ok.all() and e_hip.max() <= 1.5 * e_aten.max() + 1e-3 and e_hip.mean() <= 1.5 * e_aten.mean() + 1e-4):
+            failures.append(rec)
+        torch.cuda.empty_cache()
+    print("blob-array forward:", json.dumps(rep))
+    out_dir = os.environ.get("SJD_TEST_RECORD_DIR", "")          # where a run keeps its records (committed under profiles/)
+    if out_dir and os.path.isdir(out_dir):
+        with open(os.path.join(out_dir, f"blob_array_forward_{family}{'' if compress or family != 'lumina7b' else '_raw'}.json"), "w") as fh:
+            json.dump(rep, fh, indent=1)
+    assert not failures, failures
