@@ -42,6 +42,11 @@ class RowNorm(ctypes.Structure):
     _fields_ = [("sumsq", ctypes.c_void_p), ("slices", ctypes.c_int32), ("hidden", ctypes.c_int32), ("eps", ctypes.c_float)]
 
 
+class RawUnits(ctypes.Structure):
+    """sjd_raw_units: the units of a 12-bit weight stream that travel verbatim (ops.PackedZ.raw_data and its index table)"""
+    _fields_ = [("records", ctypes.c_void_p), ("index", ctypes.c_void_p), ("n", ctypes.c_int32)]
+
+
 class Slots(ctypes.Structure):
     """sjd_slots: the strides between the slots of a continuous batch (K5 / K2 / K4 of every slot in one launch each)"""
     _fields_ = [("n_slots", ctypes.c_int32), ("head_rows", ctypes.c_int32), ("params_stride", ctypes.c_int64), ("state_stride", ctypes.c_int64),
@@ -75,7 +80,7 @@ EXPORTS = ["sjd_version", "sjd_error_string", "sjd_reguess", "sjd_logits_to_prob
            "sjd_verify_accept_ex", "sjd_upload_async", "sjd_stream_synchronize", "sjd_gateup_silu", "sjd_host_wait_u64",
            "sjd_philox_fill", "sjd_philox_offset_increment", "sjd_skinny_gemm_z", "sjd_gateup_silu_z",
            "sjd_draft_window_attention_colsplit", "sjd_draft_window_attention_fp8_colsplit",
-           "sjd_head_combine", "sjd_raw_units_fixup", "sjd_raw_gateup_fixup",
+           "sjd_head_combine",
            "sjd_reguess_slots", "sjd_logits_to_probs_sample_part_slots", "sjd_verify_accept_slots"]
 # what include/sjd_hip_experimental.h adds: libsjd_hip_exp.so only (the measured no-go structures of rounds 2-5 and the G1w tuning entry)
 EXP_EXPORTS = ["sjd_weight_prefetch", "sjd_qkv_attention_fused", "sjd_qkv_attention_fused_split", "sjd_skinny_gemm_reduce", "sjd_reduce_timeouts",
@@ -147,10 +152,8 @@ def _bind_product(lib):
     lib.sjd_logits_to_probs_sample_part_slots.argtypes = [ctypes.POINTER(HeadPartials), f32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(Slots), vp]
     lib.sjd_verify_accept_slots.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, ctypes.POINTER(Slots), vp]
     lib.sjd_logits_to_probs_sample_ex.argtypes = [vp, vp, i64, f32, i32, i32, vp, vp, vp, vp, vp, vp]
-    lib.sjd_skinny_gemm_z.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-    lib.sjd_gateup_silu_z.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, ctypes.POINTER(RowNorm), vp]
-    lib.sjd_raw_units_fixup.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.sjd_raw_gateup_fixup.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, ctypes.POINTER(RowNorm), vp]
+    lib.sjd_skinny_gemm_z.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(RawUnits), vp]
+    lib.sjd_gateup_silu_z.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, ctypes.POINTER(RowNorm), ctypes.POINTER(RawUnits), vp]
     lib.sjd_philox_fill.argtypes = [vp, i64, ctypes.c_uint64, ctypes.c_uint64, i32, i32, vp]
     lib.sjd_philox_offset_increment.restype = ctypes.c_uint64
     lib.sjd_philox_offset_increment.argtypes = [i64, i32]
@@ -178,7 +181,7 @@ def load_exp():
     lib.sjd_draft_window_attention_merged.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.sjd_draft_window_attention_fp8_merged.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, i32, i32, vp, vp, vp]
     lib.sjd_o_merge_prologue_probe.argtypes = [vp, vp, i32, i32, i32, vp]
-    lib.sjd_skinny_gemm_z_wide.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.sjd_skinny_gemm_z_wide.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(RawUnits), vp]
     lib.sjd_mlp_pair_z.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, ctypes.POINTER(RowNorm), vp, i32, vp]
     lib.sjd_weight_prefetch.argtypes = [vp, i64, i32, vp, vp]
     lib.sjd_qkv_attention_fused.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, ctypes.POINTER(RowNorm),

@@ -1098,12 +1098,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t g1z_unit_rsrc(const unsigned c
 // records (sjd_skinny_gemm's order), which sjd_amd.ops.pack_weight_z appends to the header array.  The wave that owns such a unit runs the
 // PLAIN loop over those records (eight in flight, no decode) instead of the 12-bit one: one wave-uniform branch per kernel, the same MFMA
 // sequence, and a matrix without raw units never leaves the old path.  (A fix-up launch behind the kernel was built first, csrc/sjd_gemm_raw.h:
-// +5-7 us per projection with 1 % raw units -- a unit's MFMA chain is serial -- it now serves only the sub-tiled kernel.)
-// Row tiles up to which a raw unit's plain records are multiplied INSIDE the 12-bit kernels; kernels with more row tiles leave raw units to the
-// fix-up launch (csrc/sjd_gemm_raw.h; sjd_amd.ops decides with the same number, sjd_g1z_raw_inline_rows()).
-#ifndef G1Z_RAW_INLINE_MAX_MT
-#define G1Z_RAW_INLINE_MAX_MT 8
-#endif
+// +5-7 us per projection with 1 % raw units -- a unit's MFMA chain is serial -- it now serves only the kernels without this path: the
+// dispatchers sjd_skinny_gemm_z and g1sz_launch launch it behind them.)
 __device__ __forceinline__ bool g1z_unit_is_raw(const g1z_hraw &h) { return __builtin_amdgcn_readfirstlane((int)h.a.y) < 0; }
 __device__ __forceinline__ const u32x4 *g1z_raw_records(const u32x2 *__restrict__ exc, const g1z_hraw &h, int lane)
 {
@@ -1212,7 +1208,7 @@ __global__ __launch_bounds__(512) void g1z_gateup_silu(const unsigned short *__r
         }
     };
     // a unit that travels verbatim (see g1z_raw_records): the plain trip over its 1-KiB records, eight in flight
-    const bool z_raw = (1 <= G1Z_RAW_INLINE_MAX_MT) && g1z_unit_is_raw(hraw);
+    const bool z_raw = g1z_unit_is_raw(hraw);
     const u32x4 *rr = z_raw ? g1z_raw_records(exc, hraw, lane) : reinterpret_cast<const u32x4 *>(x);
     u32x4 rc[8];
     if (z_raw) {
@@ -1276,6 +1272,11 @@ __global__ __launch_bounds__(512) void g1z_gateup_silu(const unsigned short *__r
     }
     SJD_TR(6);
 }
+
+// Does the G1sz instantiation (SP k-steps per phase, MT row tiles) multiply raw units in the kernel?  SP = 32 with two row tiles -- hidden 4096 at
+// 64 rows -- sits at its 256 registers: there g1sz_launch runs the fix-up launch behind the kernel (csrc/sjd_gemm_raw.h).  The kernel body and the
+// launcher both read this.
+constexpr bool g1sz_raw_inline(int SP, int MT) { return !(SP == 32 && MT == 2); }
 
 // ---- G1sz for a 64-row window (see g1_gateup_silu_tall)
 template <int SP, int MT, bool DB, bool WIDE>
@@ -1382,9 +1383,7 @@ __global__ __launch_bounds__(512) void g1z_gateup_silu_tall(const unsigned short
         }
     };
     // a unit that travels verbatim (see g1z_raw_records): the plain trip over its 1-KiB records, eight in flight
-    // (SP = 32 with two row tiles -- hidden 4096 at 64 rows -- sits at its 256 registers: there the raw units are left to the fix-up launch,
-    //  sjd_raw_gateup_fixup; sjd_amd.ops.gateup_silu knows)
-    constexpr bool RAW_HERE = !(SP == 32 && MT == 2) && MT <= G1Z_RAW_INLINE_MAX_MT;
+    constexpr bool RAW_HERE = g1sz_raw_inline(SP, MT);
     const bool z_raw = RAW_HERE && g1z_unit_is_raw(hraw);
     const u32x4 *rr = z_raw ? g1z_raw_records(exc, hraw, lane) : reinterpret_cast<const u32x4 *>(x);
     constexpr int RD = 4;                     // records in flight
@@ -1455,8 +1454,10 @@ __global__ __launch_bounds__(512) void g1z_gateup_silu_tall(const unsigned short
     SJD_TR(6);
 }
 
+#include "sjd_gemm_raw.h"          // (the fix-up launch for raw units behind the stream kernels that have no in-kernel path for them)
+
 static int g1sz_launch(const void *x, const void *wz, const void *exc, int exc_cap, void *y, int M, int I, int K, int step_major, const sjd_row_norm *rn,
-                       hipStream_t s)
+                       const sjd_raw_units *raw, hipStream_t s)
 {
     const int MT = M <= 32 ? 1 : 2;
     const int SP = K / (64 * MT);                                  // one arena, 2 MT phases (double-buffered half phases measured slower: g1_gateup_silu)
@@ -1473,7 +1474,8 @@ static int g1sz_launch(const void *x, const void *wz, const void *exc, int exc_c
         if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1z_gateup_silu_tall<SP_, MT_, false, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL((g1z_gateup_silu_tall<SP_, MT_, false, W_>), grid, block, lds, s, (const unsigned short *)x, (const unsigned char *)wz, (const u32x2 *)exc, \
                            (unsigned short *)y, M, I, K, rec_stride | (exc_cap << 16), ss, sl, ih, eps); \
-        return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH; \
+        if (hipGetLastError() != hipSuccess) return SJD_ERR_LAUNCH; \
+        return g1sz_raw_inline(SP_, MT_) ? SJD_OK : g1_raw_gateup_launch(x, raw, y, M, I, K, rn, s); \
     }
 #define SJD_G1SZ_CASE32(SP_) SJD_G1SZ_CASE32_W(SP_, false) SJD_G1SZ_CASE32_W(SP_, true)
 #define SJD_G1SZ_CASE32_W(SP_, W_) \
@@ -1494,14 +1496,15 @@ static int g1sz_launch(const void *x, const void *wz, const void *exc, int exc_c
 
 // sjd_gateup_silu over ops.pack_weight_z([Wg; Wu], K / 2, step_major): same result, bit for bit; bf16 only.
 extern "C" int sjd_gateup_silu_z(const void *x, const void *wz, const void *exc, int exc_cap, void *y, int M, int I, int K, int step_major, int dtype,
-                                 const sjd_row_norm *row_norm, void *stream)
+                                 const sjd_row_norm *row_norm, const sjd_raw_units *raw, void *stream)
 {
     if (!x || !wz || !exc || !y || M < 1 || I < 64 || K < 512 || !(exc_cap == 32 || exc_cap == 64 || exc_cap == 128)) return SJD_ERR_BAD_ARG;
+    if (!g1_raw_desc_ok(raw)) return SJD_ERR_BAD_ARG;
     if (row_norm && (!row_norm->sumsq || row_norm->slices < 1 || row_norm->hidden < 1)) return SJD_ERR_BAD_ARG;
     if (row_norm && row_norm->slices > 8) return SJD_ERR_UNSUPPORTED;
     if (M > 64 || (I % 64) != 0 || !(K == 512 || K == 1024 || K == 2048 || K == 4096) || (M > 32 && K == 512) || dtype != SJD_DTYPE_BF16)
         return SJD_ERR_UNSUPPORTED;
-    return g1sz_launch(x, wz, exc, exc_cap, y, M, I, K, step_major, row_norm, (hipStream_t)stream);
+    return g1sz_launch(x, wz, exc, exc_cap, y, M, I, K, step_major, row_norm, raw, (hipStream_t)stream);
 }
 
 template <int DT>
@@ -1732,7 +1735,7 @@ __global__ __launch_bounds__(MAXT) void g1z_skinny_gemm(const unsigned short *__
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) a[mt] = xl[mt * xs + min(s, steps - 1) * 64 + g1_slot(lane >> 5, lane & 31, u)];
     };
-    if (MT <= G1Z_RAW_INLINE_MAX_MT && g1z_unit_is_raw(hraw)) {          // this wave's unit travels verbatim: the plain loop (see g1z_raw_records)
+    if (g1z_unit_is_raw(hraw)) {          // this wave's unit travels verbatim: the plain loop (see g1z_raw_records)
         const u32x4 *rr = g1z_raw_records(exc, hraw, lane);
         constexpr int RD = (MT == 2 && MAXT == 1024) ? 2 : 8;      // records in flight (the 128-register budget of 16-wave workgroups with two row tiles: 2)
         u32x4 rc[RD];
@@ -1916,12 +1919,13 @@ __global__ __launch_bounds__(512) void g1z_skinny_gemm_tiled(const unsigned shor
         }
 }
 
-// x [M <= 64, K] bf16, wz / exc = ops.pack_weight_z(W [N_packed, K], KC, step_major) -> out fp32 [n_chunks, 32 * ceil(M / 32), N] for the N
-// columns from 32 * tile0: what sjd_skinny_gemm_cols writes from the uncompressed packing of the same weight, bit for bit.
+// x [M <= 128, K] bf16, wz / exc = ops.pack_weight_z(W [N_packed, K], KC, step_major) -> out fp32 [n_chunks, 32 * ceil(M / 32), N] for the N
+// columns from 32 * tile0: what sjd_skinny_gemm_cols writes from the uncompressed packing of the same weight, bit for bit.  raw: the packing's
+// raw units (include/sjd_hip.h); every branch below knows whether its kernel multiplies them itself or needs the fix-up launch behind it.
 extern "C" int sjd_skinny_gemm_z(const void *x, const void *wz, const void *exc, int exc_cap, float *out, int M, int N, int K, int KC, int waves,
-                                 int step_major, int dtype, int N_packed, int tile0, void *stream)
+                                 int step_major, int dtype, int N_packed, int tile0, const sjd_raw_units *raw, void *stream)
 {
-    if (!(exc_cap == 32 || exc_cap == 64 || exc_cap == 128)) return SJD_ERR_BAD_ARG;
+    if (!(exc_cap == 32 || exc_cap == 64 || exc_cap == 128) || !g1_raw_desc_ok(raw)) return SJD_ERR_BAD_ARG;
     if (!x || !wz || !exc || !out || M < 1 || N < 32 || (N % 32) != 0 || (N_packed % 32) != 0 || (K % 16) != 0 || KC < 16 || (KC % 16) != 0)
         return SJD_ERR_BAD_ARG;
     if (waves < 1 || waves > 16) return SJD_ERR_BAD_ARG;
@@ -1933,13 +1937,15 @@ extern "C" int sjd_skinny_gemm_z(const void *x, const void *wz, const void *exc,
     const dim3 grid((n_out + waves - 1) / waves, n_chunks), block(waves * 64);
     hipStream_t s = (hipStream_t)stream;
     const int rs = step_major ? n_tiles : 1;
+    auto then_raw_fixup = [&](int rc) { return rc != SJD_OK ? rc : g1_raw_units_launch(x, raw, out, M, N, K, KC, tile0, s); };
     {   // 33..64 rows with FOUR column tiles per workgroup: kernel G1w's 12-bit form (csrc/sjd_gemm_wide.h, template parameter Z).  The one shape where it beats
         // the kernels below -- the o projection of a 64-row window, 9.3 against 10.7 us (profiles/r6_g1wz_sweep_64rows_emu3.jsonl); everywhere else it measured
-        // slower and lives in the experimental library only.  Raw units are left to sjd_raw_units_fixup (sjd_amd.ops.skinny_gemm_cols knows).  SJD_G1WZ=0: off.
+        // slower and lives in the experimental library only.  It has no in-kernel path for raw units.  SJD_G1WZ=0: off.
         static const bool wz_on = [] { const char *e = getenv("SJD_G1WZ"); return !(e && e[0] == '0'); }();
-        if (wz_on && MT == 2 && waves == 4) return g1_wide_launch_z<2, 1, 4, 4, 3, 2, 2>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+        if (wz_on && MT == 2 && waves == 4)
+            return then_raw_fixup(g1_wide_launch_z<2, 1, 4, 4, 3, 2, 2>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s));
     }
-    if (MT > 2 || lds > 160 * 1024) {             // sub-tiled activation (65..128 rows, or a 64-row window with a tall K chunk): <= 8 waves
+    if (MT > 2 || lds > 160 * 1024) {             // sub-tiled activation (65..128 rows, or a 64-row window with a tall K chunk): <= 8 waves, no raw path
         if (waves > 8) return SJD_ERR_BAD_ARG;
         const size_t lds_t = (size_t)2 * MT * G1_SUB * 1024;
 #define SJD_G1ZT(MT_, W_) do { \
@@ -1949,8 +1955,9 @@ extern "C" int sjd_skinny_gemm_z(const void *x, const void *wz, const void *exc,
         if (exc_cap > 64) { if (MT == 2) SJD_G1ZT(2, true); else if (MT == 3) SJD_G1ZT(3, true); else if (MT == 4) SJD_G1ZT(4, true); else return SJD_ERR_UNSUPPORTED; }
         else { if (MT == 2) SJD_G1ZT(2, false); else if (MT == 3) SJD_G1ZT(3, false); else if (MT == 4) SJD_G1ZT(4, false); else return SJD_ERR_UNSUPPORTED; }
 #undef SJD_G1ZT
-        return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+        return then_raw_fixup(hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH);
     }
+    // g1z_skinny_gemm multiplies raw units in the kernel
 #define SJD_G1Z_LAUNCH_W(MT_, MAXT_, W_) do { \
         if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1z_skinny_gemm<MT_, MAXT_, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL((g1z_skinny_gemm<MT_, MAXT_, W_>), grid, block, lds, s, (const unsigned short *)x, (const unsigned char *)wz, \
@@ -1968,13 +1975,21 @@ extern "C" int sjd_gemm_num_chunks(int K, int KC) { return (K + KC - 1) / KC; }
 // out: fp32 [n_chunks, 32, N] partial products; the consumer sums the chunks.
 template <int DT, int MT>
 static int g1_launch(const void *x, const void *w_packed, float *out, int M, int N, int K, int KC, int waves, int step_major, hipStream_t s,
-                     int n_tiles_packed = 0, int tile0 = 0)
+                     int n_tiles_packed, int tile0)
 {
     const int n_out = N / 32, n_tiles = n_tiles_packed > 0 ? n_tiles_packed : n_out, n_chunks = (K + KC - 1) / KC;
     if (tile0 < 0 || tile0 + n_out > n_tiles) return SJD_ERR_BAD_ARG;
     const dim3 grid((n_out + waves - 1) / waves, n_chunks), block(waves * 64);
     const size_t lds_whole = (size_t)MT * ((KC < K ? KC : K) / 16) * 64 * 16;       // the whole activation chunk staged at once
     static const bool force_tiled = [] { const char *e = getenv("SJD_G1_TILED"); return e && e[0] == '1'; }();      // tuning aid (64-row windows)
+    auto tiled8 = [&](auto nw) {                  // g1_skinny_gemm_tiled8 with nw = 4 or 8 waves per workgroup (MT > 2 only)
+        constexpr int NW = decltype(nw)::value;
+        const size_t lds_8 = (size_t)2 * MT * 8 * 1024;
+        (void)hipFuncSetAttribute((const void *)g1_skinny_gemm_tiled8<DT, MT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_8);
+        hipLaunchKernelGGL((g1_skinny_gemm_tiled8<DT, MT, NW>), grid, block, lds_8, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K,
+                           KC, n_tiles, step_major ? n_tiles : 1, tile0);
+        return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+    };
     if constexpr (MT == 2) {
         // 33..64-row windows (Emu3's draft window of 32 with CFG; two prompts per forward) on the uncompressed stream, both 16-bit types: G1w with two
         // row tiles and the register budget of two workgroups per CU (late round 6) -- per launch at Emu3's shapes q|k|v 12.6 / 13.6 us, o 9.4 / 11.2,
@@ -2008,11 +2023,7 @@ static int g1_launch(const void *x, const void *w_packed, float *out, int M, int
             }
         }
         if (waves != 4) return SJD_ERR_BAD_ARG;
-        const size_t lds_8 = (size_t)2 * MT * 8 * 1024;
-        (void)hipFuncSetAttribute((const void *)g1_skinny_gemm_tiled8<DT, MT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_8);
-        hipLaunchKernelGGL((g1_skinny_gemm_tiled8<DT, MT, 4>), grid, block, lds_8, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K,
-                           KC, n_tiles, step_major ? n_tiles : 1, tile0);
-        return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+        return tiled8(std::integral_constant<int, 4>{});
     } else
     if constexpr (MT >= 2) if (MT > 2 || lds_whole > 160 * 1024 || (force_tiled && waves <= 8)) {     // sub-tiled activation: no limit on KC
         if (waves > 8) return SJD_ERR_BAD_ARG;
@@ -2035,19 +2046,9 @@ static int g1_launch(const void *x, const void *w_packed, float *out, int M, int
         }
         static const bool sub8 = [] { const char *e = getenv("SJD_G1_SUB8"); return !(e && e[0] == '0'); }();      // (A/B aid: 0 = the 16-step kernel for every wave count)
         static const bool sub8w8 = [] { const char *e = getenv("SJD_G1_SUB8_W8"); return !(e && e[0] == '0'); }();   // (A/B aid: 0 = eight-wave workgroups on the 16-step kernel)
-        if constexpr (MT > 2) if (waves == 4 && sub8) {        // 4-wave workgroups: 8-step sub-tiles, two workgroups per CU
-            const size_t lds_8 = (size_t)2 * MT * 8 * 1024;
-            (void)hipFuncSetAttribute((const void *)g1_skinny_gemm_tiled8<DT, MT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_8);
-            hipLaunchKernelGGL((g1_skinny_gemm_tiled8<DT, MT, 4>), grid, block, lds_8, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K,
-                               KC, n_tiles, step_major ? n_tiles : 1, tile0);
-            return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
-        }
-        if constexpr (MT > 2) if (waves == 8 && sub8 && sub8w8) {
-            const size_t lds_8 = (size_t)2 * MT * 8 * 1024;
-            (void)hipFuncSetAttribute((const void *)g1_skinny_gemm_tiled8<DT, MT, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_8);
-            hipLaunchKernelGGL((g1_skinny_gemm_tiled8<DT, MT, 8>), grid, block, lds_8, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K,
-                               KC, n_tiles, step_major ? n_tiles : 1, tile0);
-            return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+        if constexpr (MT > 2) {
+            if (waves == 4 && sub8) return tiled8(std::integral_constant<int, 4>{});        // 4-wave workgroups: 8-step sub-tiles, two workgroups per CU
+            if (waves == 8 && sub8 && sub8w8) return tiled8(std::integral_constant<int, 8>{});
         }
         const size_t lds_t = (size_t)2 * MT * G1_SUB * 1024;
         (void)hipFuncSetAttribute((const void *)g1_skinny_gemm_tiled<DT, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
@@ -2072,15 +2073,10 @@ static int g1_launch(const void *x, const void *w_packed, float *out, int M, int
     return SJD_ERR_UNSUPPORTED;
 }
 
-// Column window of a packed weight: out[c, m, j] for the N = 32 * n columns [32 * tile0, 32 * tile0 + N) of a weight packed with N_packed columns.
-extern "C" int sjd_skinny_gemm_cols(const void *x, const void *w_packed, float *out, int M, int N, int K, int KC, int waves, int step_major,
-                                    int dtype, int N_packed, int tile0, void *stream)
+// the (dtype, row tiles) ladder of the two entry points below, which have checked their arguments
+static int g1_dispatch(const void *x, const void *w_packed, float *out, int M, int N, int K, int KC, int waves, int step_major, int dtype, int np, int tile0,
+                       hipStream_t s)
 {
-    if (!x || !w_packed || !out || M < 1 || M > 256 || N < 32 || (N % 32) != 0 || (N_packed % 32) != 0 || (K % 16) != 0 || KC < 16 || (KC % 16) != 0)
-        return SJD_ERR_BAD_ARG;
-    if (waves < 1 || waves > 16) return SJD_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int np = N_packed / 32;
     if (dtype == SJD_DTYPE_BF16 && M <= 32) return g1_launch<SJD_DTYPE_BF16, 1>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
     if (dtype == SJD_DTYPE_F16 && M <= 32) return g1_launch<SJD_DTYPE_F16, 1>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
     if (dtype == SJD_DTYPE_BF16 && M <= 64) return g1_launch<SJD_DTYPE_BF16, 2>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
@@ -2096,25 +2092,23 @@ extern "C" int sjd_skinny_gemm_cols(const void *x, const void *w_packed, float *
     return SJD_ERR_UNSUPPORTED;
 }
 
+// Column window of a packed weight: out[c, m, j] for the N = 32 * n columns [32 * tile0, 32 * tile0 + N) of a weight packed with N_packed columns.
+extern "C" int sjd_skinny_gemm_cols(const void *x, const void *w_packed, float *out, int M, int N, int K, int KC, int waves, int step_major,
+                                    int dtype, int N_packed, int tile0, void *stream)
+{
+    if (!x || !w_packed || !out || M < 1 || M > 256 || N < 32 || (N % 32) != 0 || (N_packed % 32) != 0 || (K % 16) != 0 || KC < 16 || (KC % 16) != 0)
+        return SJD_ERR_BAD_ARG;
+    if (waves < 1 || waves > 16) return SJD_ERR_BAD_ARG;
+    return g1_dispatch(x, w_packed, out, M, N, K, KC, waves, step_major, dtype, N_packed / 32, tile0, (hipStream_t)stream);
+}
+
+// the whole weight: the column window [0, N) of a weight packed with N columns
 extern "C" int sjd_skinny_gemm(const void *x, const void *w_packed, float *out, int M, int N, int K, int KC, int waves, int step_major,
                                int dtype, void *stream)
 {
     if (!x || !w_packed || !out || M < 1 || M > 256 || (N % 32) != 0 || (K % 16) != 0 || KC < 16 || (KC % 16) != 0) return SJD_ERR_BAD_ARG;
     if (waves < 1 || waves > 16) return SJD_ERR_BAD_ARG;       // (the staged activation chunk must fit in LDS: min(KC, K) <= 2560 / 1280)
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == SJD_DTYPE_BF16 && M <= 32) return g1_launch<SJD_DTYPE_BF16, 1>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    if (dtype == SJD_DTYPE_F16 && M <= 32) return g1_launch<SJD_DTYPE_F16, 1>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    if (dtype == SJD_DTYPE_BF16 && M <= 64) return g1_launch<SJD_DTYPE_BF16, 2>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    if (dtype == SJD_DTYPE_F16 && M <= 64) return g1_launch<SJD_DTYPE_F16, 2>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    if (dtype == SJD_DTYPE_BF16 && M <= 96) return g1_launch<SJD_DTYPE_BF16, 3>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    if (dtype == SJD_DTYPE_F16 && M <= 96) return g1_launch<SJD_DTYPE_F16, 3>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    if (dtype == SJD_DTYPE_BF16 && M <= 128) return g1_launch<SJD_DTYPE_BF16, 4>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    if (dtype == SJD_DTYPE_F16 && M <= 128) return g1_launch<SJD_DTYPE_F16, 4>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    if (dtype == SJD_DTYPE_BF16 && M <= 160) return g1_launch<SJD_DTYPE_BF16, 5>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    if (dtype == SJD_DTYPE_BF16 && M <= 192) return g1_launch<SJD_DTYPE_BF16, 6>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    if (dtype == SJD_DTYPE_BF16 && M <= 224) return g1_launch<SJD_DTYPE_BF16, 7>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    if (dtype == SJD_DTYPE_BF16) return g1_launch<SJD_DTYPE_BF16, 8>(x, w_packed, out, M, N, K, KC, waves, step_major, s);
-    return SJD_ERR_UNSUPPORTED;
+    return g1_dispatch(x, w_packed, out, M, N, K, KC, waves, step_major, dtype, N / 32, 0, (hipStream_t)stream);
 }
 
 #ifdef SJD_EXPERIMENTAL        // G1 + F1r in one launch, the MLP pair, the loader / consumer engine, the G1w tuning entry
@@ -2157,23 +2151,24 @@ extern "C" int sjd_skinny_gemm_reduce(const void *x, const void *w_packed, float
 // Kernel G1w over the 12-bit stream (late round 6 experiment, csrc/sjd_gemm_wide.h `Z`): bit-identical planes, measured SLOWER than what the product runs
 // (the decode costs a one-wave-per-SIMD kernel more issue slots than the 25 % of weight bytes buy: 256 rows q|k|v 44.2 against 35.3 us on the uncompressed
 // stream, gate|up 71.3 / 56.8; 64 rows: level with G1z except the o projection, 9.3 / 10.7 us; profiles/r6_g1wz_sweep_*.jsonl).  tiles: 2, 3, 4, 6, 8 column
-// tiles per workgroup; 33..256 rows; raw units are left to sjd_raw_units_fixup.
+// tiles per workgroup; 33..256 rows; raw units always through the fix-up launch behind the kernel.
 extern "C" int sjd_skinny_gemm_z_wide(const void *x, const void *wz, const void *exc, int exc_cap, float *out, int M, int N, int K, int KC, int tiles,
-                                      int step_major, int N_packed, int tile0, void *stream)
+                                      int step_major, int N_packed, int tile0, const sjd_raw_units *raw, void *stream)
 {
-    if (!(exc_cap == 32 || exc_cap == 64 || exc_cap == 128)) return SJD_ERR_BAD_ARG;
+    if (!(exc_cap == 32 || exc_cap == 64 || exc_cap == 128) || !g1_raw_desc_ok(raw)) return SJD_ERR_BAD_ARG;
     if (!x || !wz || !exc || !out || M < 33 || M > 256 || N < 32 || (N % 32) != 0 || (N_packed % 32) != 0 || (K % 16) != 0 || KC < 16 || (KC % 16) != 0 || KC > 4096)
         return SJD_ERR_BAD_ARG;
     const int waves = tiles, n_out = N / 32, n_tiles = N_packed / 32, MT = (M + 31) / 32;
     if (tile0 < 0 || tile0 + n_out > n_tiles) return SJD_ERR_BAD_ARG;
     if (!(waves == 2 || waves == 3 || waves == 4 || waves == 6 || waves == 8) || (MT == 3 && waves == 2)) return SJD_ERR_BAD_ARG;
     hipStream_t s_ = (hipStream_t)stream;
+    auto then_raw_fixup = [&](int rc) { return rc != SJD_OK ? rc : g1_raw_units_launch(x, raw, out, M, N, K, KC, tile0, s_); };
 #define SJD_G1WZ_T(MT_, WPS_) do { switch (waves) { \
-        case 2: if constexpr (MT_ != 3) return g1_wide_launch_z<MT_, 1, 2, 4, 3, 2, WPS_>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s_); else return SJD_ERR_BAD_ARG; \
-        case 3: return g1_wide_launch_z<MT_, 1, 3, 4, 3, 2, WPS_>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s_); \
-        case 4: return g1_wide_launch_z<MT_, 1, 4, 4, 3, 2, WPS_>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s_); \
-        case 6: return g1_wide_launch_z<MT_, 2, 3, 4, 3, 2, WPS_>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s_); \
-        default: return g1_wide_launch_z<MT_, 2, 4, 4, 3, 2, WPS_>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s_); } } while (0)
+        case 2: if constexpr (MT_ != 3) return then_raw_fixup(g1_wide_launch_z<MT_, 1, 2, 4, 3, 2, WPS_>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s_)); else return SJD_ERR_BAD_ARG; \
+        case 3: return then_raw_fixup(g1_wide_launch_z<MT_, 1, 3, 4, 3, 2, WPS_>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s_)); \
+        case 4: return then_raw_fixup(g1_wide_launch_z<MT_, 1, 4, 4, 3, 2, WPS_>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s_)); \
+        case 6: return then_raw_fixup(g1_wide_launch_z<MT_, 2, 3, 4, 3, 2, WPS_>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s_)); \
+        default: return then_raw_fixup(g1_wide_launch_z<MT_, 2, 4, 4, 3, 2, WPS_>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s_)); } } while (0)
     switch (MT) {
     case 2: SJD_G1WZ_T(2, 2);
     case 3: SJD_G1WZ_T(3, 1);
@@ -2237,8 +2232,6 @@ extern "C" int sjd_reduce_timeouts(void)
 }
 
 #endif  // SJD_EXPERIMENTAL
-
-#include "sjd_gemm_raw.h"
 
 #ifdef SJD_TRACE
 extern "C" int sjd_debug_trace_g1(unsigned long long *host_out, int n_wg)

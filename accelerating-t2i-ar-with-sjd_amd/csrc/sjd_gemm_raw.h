@@ -7,9 +7,10 @@
 // WHERE the verbatim records are multiplied:
 //   * g1z_skinny_gemm, g1z_gateup_silu and g1z_gateup_silu_tall (all but SP = 32 x two row tiles) run them IN the kernel: the wave that owns a
 //     raw unit takes a plain loop over its records (csrc/sjd_gemm.hip: g1z_raw_records) -- 1 % raw units cost 0-3 % of a launch;
-//   * the sub-tiled kernel (65..128 rows, or a 64-row window whose chunk does not fit LDS) and the one G1sz instantiation that sits at its
-//     register limit run over the zeros and a FIX-UP launch behind them (this file) recomputes exactly the tiles the raw units feed -- the
-//     same MFMA sequence per (tile, chunk, row tile) as g1_skinny_gemm.  (The fix-up was built first, for every kernel: +5-7 us per projection,
+//   * the sub-tiled kernel (65..128 rows, or a 64-row window whose chunk does not fit LDS), kernel G1w's 12-bit form and the one G1sz
+//     instantiation that sits at its register limit run over the zeros and a FIX-UP launch behind them (this file) recomputes exactly the
+//     tiles the raw units feed -- the same MFMA sequence per (tile, chunk, row tile) as g1_skinny_gemm.  The dispatchers that pick the stream
+//     kernel (sjd_skinny_gemm_z, g1sz_launch) launch it: no caller decides.  (The fix-up was built first, for every kernel: +5-7 us per projection,
 //     a unit's MFMAs are one dependent chain -- hence the in-kernel path for the 32 / 64-row kernels that carry the headline configurations.)
 // Either way the planes / activations are bit-identical to the uncompressed kernels' (tests/test_gpu_glue.py::test_g1z_raw_units_*,
 // test_g1sz_raw_pairs_*), and a matrix without raw units never leaves the old path.
@@ -121,32 +122,33 @@ __global__ __launch_bounds__(256) void g1_raw_gateup(const unsigned short *__res
     }
 }
 
-// index: int32 [n_raw, 2] = (k chunk, tile of the PACKED weight); raw: n_raw x (KC / 16) records of 1 KiB (a short last chunk is padded).
-// out: the planes sjd_skinny_gemm_z(x, ..., N, K, KC, ..., N_packed, tile0) has just written on the same stream.
-extern "C" int sjd_raw_units_fixup(const void *x, const void *raw, const int32_t *index, int n_raw, float *out, int M, int N, int K, int KC,
-                                   int tile0, int dtype, void *stream)
+// Is `raw` a descriptor the entry points accept?  (NULL or n == 0: no raw units.)
+static bool g1_raw_desc_ok(const sjd_raw_units *raw) { return !raw || raw->n == 0 || (raw->n > 0 && raw->records && raw->index); }
+
+// raw->index: int32 [n, 2] = (k chunk, tile of the PACKED weight); raw->records: n x (KC / 16) records of 1 KiB (a short last chunk is padded).
+// out: the planes a stream kernel WITHOUT the in-kernel raw path has just written on `s` for (x, ..., N, K, KC, ..., N_packed, tile0).
+static int g1_raw_units_launch(const void *x, const sjd_raw_units *raw, float *out, int M, int N, int K, int KC, int tile0, hipStream_t s)
 {
-    if (n_raw == 0) return SJD_OK;
-    if (!x || !raw || !index || !out || n_raw < 0 || M < 1 || M > 256 || N < 32 || (N % 32) || (K % 16) || KC < 16 || (KC % 16) || tile0 < 0) return SJD_ERR_BAD_ARG;
-    if (dtype != SJD_DTYPE_BF16) return SJD_ERR_UNSUPPORTED;
+    if (!raw || raw->n == 0) return SJD_OK;
+    if (!x || !raw->records || !raw->index || !out || raw->n < 0 || M < 1 || M > 256 || N < 32 || (N % 32) || (K % 16) || KC < 16 || (KC % 16) || tile0 < 0)
+        return SJD_ERR_BAD_ARG;
     const int mt = (M + 31) / 32;
-    hipLaunchKernelGGL((g1_raw_units<SJD_DTYPE_BF16>), dim3(n_raw, mt), dim3(64), 0, (hipStream_t)stream, (const unsigned short *)x, (const u32x4 *)raw,
-                       (const int *)index, out, M, N, K, KC, tile0, 32 * mt);
+    hipLaunchKernelGGL((g1_raw_units<SJD_DTYPE_BF16>), dim3(raw->n, mt), dim3(64), 0, s, (const unsigned short *)x, (const u32x4 *)raw->records,
+                       (const int *)raw->index, out, M, N, K, KC, tile0, 32 * mt);
     return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
 }
 
-// tiles: int32 [n_pairs] gate tiles t (columns [32 t, 32 t + 32) of y); raw: per pair [K half][gate | up][K / 32 records].  y: what
-// sjd_gateup_silu_z(x, ..., M, I, K, ...) has just written on the same stream.
-extern "C" int sjd_raw_gateup_fixup(const void *x, const void *raw, const int32_t *tiles, int n_pairs, void *y, int M, int I, int K, int dtype,
-                                    const sjd_row_norm *row_norm, void *stream)
+// raw->index: int32 [n] gate tiles t (columns [32 t, 32 t + 32) of y); raw->records: per pair [K half][gate | up][K / 32 records].  y: what a
+// G1sz instantiation WITHOUT the in-kernel raw path (g1sz_raw_inline) has just written on `s` for (x, ..., M, I, K, ...).
+static int g1_raw_gateup_launch(const void *x, const sjd_raw_units *raw, void *y, int M, int I, int K, const sjd_row_norm *row_norm, hipStream_t s)
 {
-    if (n_pairs == 0) return SJD_OK;
-    if (!x || !raw || !tiles || !y || n_pairs < 0 || M < 1 || M > 64 || I < 64 || (I % 64) || K < 64 || (K % 64)) return SJD_ERR_BAD_ARG;
+    if (!raw || raw->n == 0) return SJD_OK;
+    if (!x || !raw->records || !raw->index || !y || raw->n < 0 || M < 1 || M > 64 || I < 64 || (I % 64) || K < 64 || (K % 64)) return SJD_ERR_BAD_ARG;
     if (row_norm && (!row_norm->sumsq || row_norm->slices < 1 || row_norm->hidden < 1)) return SJD_ERR_BAD_ARG;
-    if (dtype != SJD_DTYPE_BF16 || (row_norm && row_norm->slices > 8)) return SJD_ERR_UNSUPPORTED;
+    if (row_norm && row_norm->slices > 8) return SJD_ERR_UNSUPPORTED;
     const int mt = (M + 31) / 32;
-    hipLaunchKernelGGL((g1_raw_gateup<SJD_DTYPE_BF16>), dim3(n_pairs, mt), dim3(256), 0, (hipStream_t)stream, (const unsigned short *)x, (const u32x4 *)raw,
-                       (const int *)tiles, (unsigned short *)y, M, I, K, 32 * mt, row_norm ? row_norm->sumsq : nullptr, row_norm ? row_norm->slices : 0,
+    hipLaunchKernelGGL((g1_raw_gateup<SJD_DTYPE_BF16>), dim3(raw->n, mt), dim3(256), 0, s, (const unsigned short *)x, (const u32x4 *)raw->records,
+                       (const int *)raw->index, (unsigned short *)y, M, I, K, 32 * mt, row_norm ? row_norm->sumsq : nullptr, row_norm ? row_norm->slices : 0,
                        row_norm ? 1.0f / (float)row_norm->hidden : 0.f, row_norm ? row_norm->eps : 0.f);
     return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
 }

@@ -101,7 +101,7 @@ template <int DT> __device__ __forceinline__ f32x16 gw_fake_mma(u32x4 a, u32x4 b
 // low bytes of the pair R k-steps ahead behind an even k-step's last MFMA, its codes behind the odd one's -- so the hand counts stand; an even k-step
 // decodes BOTH operands of its pair (its registers are then free for the refill) and waits one group less deep (the codes are one k-step younger than the
 // low bytes); an odd k-step waits for nothing.  The unit headers are requested in front of the prologue and waited for behind it without draining it.
-// WIDE: headers of 128 entries.  Raw units (a header count of -1) decode to garbage here: the caller runs sjd_raw_units_fixup behind the launch.
+// WIDE: headers of 128 entries.  Raw units (a header count of -1) decode to garbage here: the entry points run the fix-up launch (sjd_gemm_raw.h) behind this one.
 template <int DT, int MT, int CT, int NW, int SUB, int NS, int RW, int WPS, bool Z = false, bool WIDE = false>
 __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__restrict__ x, const u32x4 *__restrict__ wp, float *__restrict__ out,
                                                         int M, int N, int K, int KC, int n_tiles, int rec_stride, int tile0, int ldx, int xmap,

@@ -643,6 +643,17 @@ def xcc_map(gx, gy=1, device="cuda:0"):
     return out
 
 
+def _raw_units(w_packed, gateup=False):
+    """PackedZ -> ctypes pointer to the sjd_raw_units of its verbatim units (or None): the (chunk, tile) table of the plane kernels, or with
+    gateup=True the gate-tile table of the raw (gate, up) pairs.  Where they are multiplied is the C entry point's business."""
+    index, n = (w_packed.raw_tiles, w_packed.n_raw_pairs) if gateup else (w_packed.raw_index, w_packed.n_raw)
+    if not n:
+        return None
+    ru = L.RawUnits()
+    ru.records, ru.index, ru.n = w_packed.raw_data.data_ptr(), index.data_ptr(), n
+    return ctypes.pointer(ru)
+
+
 def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_major=True):
     """G1 over the vocabulary columns [col0, col0 + n_cols) (32-aligned) of a weight packed with N_packed columns -> Partials [n_chunks, R, n_cols]."""
     M = x.shape[0]
@@ -651,16 +662,8 @@ def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_m
     out = torch.empty(nc, _prows(M), n_cols, dtype=torch.float32, device=x.device)
     if isinstance(w_packed, PackedZ):
         assert (w_packed.KC, w_packed.step_major) == (KC, bool(step_major)) and x.dtype == torch.bfloat16
-        if M > 128 or ((M > 64 or (M > 32 and min(KC, K) > 1280)) and waves > 8):
-            raise ValueError(f"G1z: a {M}-row window with K chunks of {KC} runs on the sub-tiled kernel (up to 128 rows, at most 8 waves), got waves={waves}")
         L.check(L.load().sjd_skinny_gemm_z(_ptr(x), _ptr(w_packed.data), _ptr(w_packed.exc), w_packed.cap, _ptr(out), M, n_cols, K, KC, waves, int(step_major),
-                                          _dtype_code(x.dtype), N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_z")
-        if w_packed.n_raw and (M > 64 or (M > 32 and (min(KC, K) > 1280 or waves == 4))):
-            # g1z_skinny_gemm runs a raw unit's plain records in the kernel; the SUB-TILED kernel (65..128 rows, or 33..64 with a chunk that does not
-            # fit LDS) and the 12-bit form of kernel G1w (33..64 rows with four column tiles per workgroup, late round 6) do not: there the tiles fed by
-            # raw units are recomputed by a launch behind it (csrc/sjd_gemm_raw.h)
-            L.check(L.load().sjd_raw_units_fixup(_ptr(x), _ptr(w_packed.raw_data), _ptr(w_packed.raw_index), w_packed.n_raw, _ptr(out), M, n_cols, K, KC,
-                                                col0 // 32, _dtype_code(x.dtype), _stream()), "sjd_raw_units_fixup")
+                                          _dtype_code(x.dtype), N_packed, col0 // 32, _raw_units(w_packed), _stream()), "sjd_skinny_gemm_z")
         return Partials(out, nc, n_cols)
     L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed), _ptr(out), M, n_cols, K, KC, waves, int(step_major), _dtype_code(x.dtype),
                                          N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols")
@@ -669,7 +672,7 @@ def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_m
 
 def skinny_gemm_z_wide(x, w_packed, tiles, col0=0, n_cols=None):
     """EXPERIMENTAL (libsjd_hip_exp.so; late round 6): kernel G1w over the 12-bit stream -- x [33..256, K] bf16, w_packed a PackedZ, `tiles` = 2, 3, 4, 6 or 8
-    column tiles per workgroup -> Partials bit-identical to skinny_gemm_cols on the same packing (raw units through the fix-up launch).  Measured slower
+    column tiles per workgroup -> Partials bit-identical to skinny_gemm_cols on the same packing (raw units included).  Measured slower
     than the product's kernels: kept for its test and tools/g1wz_sweep.py."""
     assert isinstance(w_packed, PackedZ) and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[1] == w_packed.K
     M, K, KC = x.shape[0], w_packed.K, w_packed.KC
@@ -677,10 +680,7 @@ def skinny_gemm_z_wide(x, w_packed, tiles, col0=0, n_cols=None):
     nc = (K + KC - 1) // KC
     out = torch.empty(nc, _prows(M), n, dtype=torch.float32, device=x.device)
     L.check(L.load_exp().sjd_skinny_gemm_z_wide(_ptr(x), _ptr(w_packed.data), _ptr(w_packed.exc), w_packed.cap, _ptr(out), M, n, K, KC, int(tiles),
-                                               int(w_packed.step_major), w_packed.N, col0 // 32, _stream()), "sjd_skinny_gemm_z_wide")
-    if w_packed.n_raw:
-        L.check(L.load().sjd_raw_units_fixup(_ptr(x), _ptr(w_packed.raw_data), _ptr(w_packed.raw_index), w_packed.n_raw, _ptr(out), M, n, K, KC,
-                                            col0 // 32, _dtype_code(x.dtype), _stream()), "sjd_raw_units_fixup")
+                                               int(w_packed.step_major), w_packed.N, col0 // 32, _raw_units(w_packed), _stream()), "sjd_skinny_gemm_z_wide")
     return Partials(out, nc, n)
 
 
@@ -942,10 +942,7 @@ def gateup_silu(x, w_packed, inter, hidden, step_major=False, row_norm=None):
         assert (w_packed.KC, w_packed.step_major) == (hidden // 2, bool(step_major)) and x.dtype == torch.bfloat16
         assert w_packed.n_raw == 0 or w_packed.raw_tiles is not None, "a gate|up weight with raw units must be packed with gateup=True"
         L.check(L.load().sjd_gateup_silu_z(_ptr(x), _ptr(w_packed.data), _ptr(w_packed.exc), w_packed.cap, _ptr(y), T, inter, hidden, int(step_major),
-                                          _dtype_code(x.dtype), _row_norm(row_norm), _stream()), "sjd_gateup_silu_z")
-        if w_packed.n_raw_pairs and T > 32 and hidden == 4096:      # (the one G1sz instantiation without the in-kernel raw path: see g1z_gateup_silu_tall)
-            L.check(L.load().sjd_raw_gateup_fixup(_ptr(x), _ptr(w_packed.raw_data), _ptr(w_packed.raw_tiles), w_packed.n_raw_pairs, _ptr(y), T, inter, hidden,
-                                                 _dtype_code(x.dtype), _row_norm(row_norm), _stream()), "sjd_raw_gateup_fixup")
+                                          _dtype_code(x.dtype), _row_norm(row_norm), _raw_units(w_packed, gateup=True), _stream()), "sjd_gateup_silu_z")
         return y
     L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype),
                                     _row_norm(row_norm), _stream()), "sjd_gateup_silu")

@@ -361,27 +361,28 @@ int sjd_skinny_gemm(const void *x, const void *w_packed, float *out, int M, int 
  * per matrix by the packer, which declines a matrix that needs more than 127 in some unit: {base, count}, then {k-step << 9 | lane << 3 | element,
  * 16 bits}) and are patched into the MFMA operand registers.  The operands, the accumulation order and the
  * result are BIT-IDENTICAL to the uncompressed kernels on the same weight: no change of precision, 25 % fewer bytes through the fabric that
- * bounds the window forward.  bf16 only (SJD_ERR_UNSUPPORTED otherwise), M <= 64, KC <= 4096.
+ * bounds the window forward.  bf16 only (SJD_ERR_UNSUPPORTED otherwise), M <= 128 (sjd_gateup_silu_z: M <= 64), KC <= 4096.
+ * Round 6 -- the per-unit escape of the stream (csrc/sjd_gemm_raw.h).  A (k-chunk, 32-column tile) unit with more out-of-window weights than a
+ * header holds (zero rows, pruned blocks, more than sixteen binades in one unit: a real checkpoint, reference IS:287-289, ML:83-140) no longer
+ * makes the packer decline the matrix: the unit is zero-filled in the stream and travels verbatim in `raw->records` (1-KiB records in
+ * sjd_skinny_gemm's order, KC / 16 per unit).  The entry points multiply those records themselves -- inside the stream kernel, or where that
+ * kernel has no such path by ONE small launch behind it on the same stream (the same MFMA sequence per (tile, chunk, row tile)): either way the
+ * result is bit-identical to the uncompressed kernels', and the caller only passes what the packer produced.  raw NULL or n == 0: no raw units;
+ * n > 0 with a null records / index, or n < 0: SJD_ERR_BAD_ARG.
+ *   sjd_skinny_gemm_z: index int32 [n, 2] = (chunk, packed tile) of unit i of `records`
+ *   sjd_gateup_silu_z: index int32 [n] = the gate tiles of the raw (gate, up) PAIRS; records per pair [K half][gate | up][K / 32 records] (the
+ *                      packer lists the whole pair when any of its four units is raw)
  * replaces, like G1 / G1s: the nn.Linear calls of the decoder layer (reference modeling_chameleon.py:527-529, 579, 193-195) and lm_head
  * (modeling_chameleon.py:1560-1561) for the window forward. */
+typedef struct sjd_raw_units {
+    const void *records;
+    const int32_t *index;
+    int32_t n;
+} sjd_raw_units;
 int sjd_skinny_gemm_z(const void *x, const void *wz, const void *exc, int exc_cap, float *out, int M, int N, int K, int KC, int waves, int step_major,
-                      int dtype, int N_packed, int tile0, void *stream);
+                      int dtype, int N_packed, int tile0, const sjd_raw_units *raw, void *stream);
 int sjd_gateup_silu_z(const void *x, const void *wz, const void *exc, int exc_cap, void *y, int M, int I, int K, int step_major, int dtype,
-                      const sjd_row_norm *row_norm, void *stream);
-
-/* Round 6 -- the per-unit escape of the 12-bit stream (csrc/sjd_gemm_raw.h).  A (k-chunk, 32-column tile) unit with more out-of-window weights
- * than a header holds (zero rows, pruned blocks, more than sixteen binades in one unit: a real checkpoint, reference IS:287-289, ML:83-140) no
- * longer makes sjd_amd.ops.pack_weight_z decline the matrix: the unit is zero-filled in the stream, travels verbatim in `raw` (1-KiB records in
- * sjd_skinny_gemm's order, KC / 16 per unit) and ONE small launch behind the stream kernel, on the same stream, recomputes the tiles it feeds --
- * the same MFMA sequence per (tile, chunk, row tile), bit-identical to the uncompressed kernels.  n_raw == 0: no launch.
- *   sjd_raw_units_fixup : behind sjd_skinny_gemm_z(x, ..., out, M, N, K, KC, ..., N_packed, tile0); index int32 [n_raw, 2] = (chunk, packed tile)
- *   sjd_raw_gateup_fixup: behind sjd_gateup_silu_z(x, ..., y, M, I, K, ..., row_norm); tiles int32 [n_pairs] gate tiles, raw per pair
- *                         [K half][gate | up][K / 32 records] (the packer lists the whole pair when any of its four units is raw)
- * replaces, like G1z / G1sz: the nn.Linear calls of the decoder layer (reference modeling_chameleon.py:527-529, 579, 193-195) and lm_head. */
-int sjd_raw_units_fixup(const void *x, const void *raw, const int32_t *index, int n_raw, float *out, int M, int N, int K, int KC, int tile0,
-                        int dtype, void *stream);
-int sjd_raw_gateup_fixup(const void *x, const void *raw, const int32_t *tiles, int n_pairs, void *y, int M, int I, int K, int dtype,
-                         const sjd_row_norm *row_norm, void *stream);
+                      const sjd_row_norm *row_norm, const sjd_raw_units *raw, void *stream);
 
 
 /* K1 / K3 over an fp8 KV cache (BASELINE config 5; there is no fp8 in the reference -- the parity target is the bf16 result

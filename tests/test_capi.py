@@ -81,6 +81,7 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(L.HeadPartials) == 96 and L.HeadPartials.row_sumsq.offset == 48          # static_assert'ed in sjd_sampling.hip
     assert L.HeadPartials.zero_state.offset == 88                                                 # (round 4: the rows' zero state, last member)
     assert ctypes.sizeof(L.RowNorm) == 24
+    assert ctypes.sizeof(L.RawUnits) == 24 and L.RawUnits.n.offset == 16                          # sjd_raw_units
 
 
 def test_bad_arguments_are_rejected_without_a_gpu():
@@ -93,6 +94,12 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     # round 4 entry points: argument checks run before any launch
     assert lib.sjd_draft_window_attention_colsplit(None, None, None, None, 2, 16, 32, 32, 128, 1024, 0, None, None, 0, None) == -1
     assert lib.sjd_draft_window_attention_fp8_colsplit(None, None, None, None, 2, 16, 32, 32, 128, 1024, 0, 1.0, 1.0, None, None, 0, None) == -1
+    # a malformed raw-unit descriptor (n > 0 without records / index, n < 0) is a bad argument of both 12-bit entry points, whatever else is passed
+    buf = ctypes.create_string_buffer(64)
+    b = ctypes.c_void_p(ctypes.addressof(buf))
+    for ru in (L.RawUnits(None, b, 1), L.RawUnits(b, None, 1), L.RawUnits(b, b, -1)):
+        assert lib.sjd_skinny_gemm_z(b, b, b, 32, b, 8, 64, 256, 128, 2, 0, 0, 64, 0, ctypes.byref(ru), None) == -1
+        assert lib.sjd_gateup_silu_z(b, b, b, 32, b, 8, 64, 512, 0, 0, None, ctypes.byref(ru), None) == -1
 
 
 def test_host_wait_on_the_mirror_sequence_word():

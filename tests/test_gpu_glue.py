@@ -683,7 +683,8 @@ def _hostile_weights(kind, N, K, g):
 
 @pytest.mark.parametrize("kind", ["zero_rows", "zero_blocks", "student_t3", "scale_spread"])
 @pytest.mark.parametrize("M,N,K,KC,waves,step_major", [(32, 512, 1024, 512, 6, True), (17, 256, 880, 256, 4, False), (64, 512, 2048, 1024, 8, True),
-                                                       (128, 256, 1024, 512, 8, True), (64, 512, 2048, 512, 4, True), (40, 256, 880, 256, 4, False)])
+                                                       (128, 256, 1024, 512, 8, True), (64, 512, 2048, 512, 4, True), (40, 256, 880, 256, 4, False),
+                                                       (48, 256, 2816, 1408, 8, True)])        # (the last: two row tiles on the sub-tiled kernel)
 def test_g1z_raw_units_match_g1_bit_for_bit(dev, kind, M, N, K, KC, waves, step_major):
     """round 6: the matrix ALWAYS packs -- units the 12-bit format cannot hold travel verbatim and the fix-up launch (csrc/sjd_gemm_raw.h) recomputes
     their tiles: the planes are those of G1 on the uncompressed stream, bit for bit, for every weight statistic above; also through a column
@@ -706,7 +707,8 @@ def test_g1z_raw_units_match_g1_bit_for_bit(dev, kind, M, N, K, KC, waves, step_
 
 
 @pytest.mark.parametrize("kind", ["zero_rows", "zero_blocks", "student_t3", "scale_spread"])
-@pytest.mark.parametrize("T,inter,hidden,step_major", [(32, 512, 1024, True), (9, 256, 512, False), (64, 512, 2048, True), (32, 11008, 4096, True)])
+@pytest.mark.parametrize("T,inter,hidden,step_major", [(32, 512, 1024, True), (9, 256, 512, False), (64, 512, 2048, True), (32, 11008, 4096, True),
+                                                       (64, 512, 4096, True), (40, 256, 4096, False)])       # (the last two: the G1sz instantiation without an in-kernel raw path)
 def test_g1sz_raw_pairs_match_g1s_bit_for_bit(dev, kind, T, inter, hidden, step_major):
     """the same for the fused gate|up kernel: a raw unit lists its (gate tile, up tile) pair, the fix-up redoes both accumulations and the SiLU
     epilogue of the pair -- the activations are G1s's on the uncompressed stream, bit for bit, with and without the folded RMSNorm's row scale"""
@@ -768,12 +770,16 @@ def test_g1z_refuses_what_it_does_not_serve(dev):
     lib = L.load()
     p = lambda t: ctypes.c_void_p(t.data_ptr())
     s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    assert lib.sjd_skinny_gemm_z(p(x16), p(wz.data), p(wz.exc), 32, p(out), 8, 64, 256, 128, 2, 0, 1, 64, 0, s) != 0      # fp16
-    assert lib.sjd_skinny_gemm_z(p(x16), p(wz.data), p(wz.exc), 32, p(out), 129, 64, 256, 128, 2, 0, 0, 64, 0, s) != 0    # > 128 rows
-    assert lib.sjd_skinny_gemm_z(p(x16), p(wz.data), p(wz.exc), 32, p(out), 96, 64, 256, 128, 12, 0, 0, 64, 0, s) != 0    # sub-tiled kernel: <= 8 waves
-    assert lib.sjd_skinny_gemm_z(p(x16), p(wz.data), None, 32, p(out), 8, 64, 256, 128, 2, 0, 0, 64, 0, s) != 0           # no header table
-    assert lib.sjd_skinny_gemm_z(p(x16), p(wz.data), p(wz.exc), 48, p(out), 8, 64, 256, 128, 2, 0, 0, 64, 0, s) != 0      # header capacity
-    assert lib.sjd_gateup_silu_z(p(x16), p(wz.data), p(wz.exc), 32, p(out), 8, 64, 512, 0, 1, None, s) != 0               # fp16
+    assert lib.sjd_skinny_gemm_z(p(x16), p(wz.data), p(wz.exc), 32, p(out), 8, 64, 256, 128, 2, 0, 1, 64, 0, None, s) != 0      # fp16
+    assert lib.sjd_skinny_gemm_z(p(x16), p(wz.data), p(wz.exc), 32, p(out), 129, 64, 256, 128, 2, 0, 0, 64, 0, None, s) != 0    # > 128 rows
+    assert lib.sjd_skinny_gemm_z(p(x16), p(wz.data), p(wz.exc), 32, p(out), 96, 64, 256, 128, 12, 0, 0, 64, 0, None, s) != 0    # sub-tiled kernel: <= 8 waves
+    assert lib.sjd_skinny_gemm_z(p(x16), p(wz.data), None, 32, p(out), 8, 64, 256, 128, 2, 0, 0, 64, 0, None, s) != 0           # no header table
+    assert lib.sjd_skinny_gemm_z(p(x16), p(wz.data), p(wz.exc), 48, p(out), 8, 64, 256, 128, 2, 0, 0, 64, 0, None, s) != 0      # header capacity
+    assert lib.sjd_gateup_silu_z(p(x16), p(wz.data), p(wz.exc), 32, p(out), 8, 64, 512, 0, 1, None, None, s) != 0         # fp16
+    xb = x16.to(torch.bfloat16)                  # otherwise valid arguments with a malformed raw-unit descriptor: refused before any launch
+    assert lib.sjd_skinny_gemm_z(p(xb), p(wz.data), p(wz.exc), wz.cap, p(out), 8, 64, 256, 128, 2, 0, 0, 64, 0, None, s) == 0
+    for ru in (L.RawUnits(None, None, 1), L.RawUnits(wz.exc.data_ptr(), wz.exc.data_ptr(), -1)):      # n = 1 without records; n = -1
+        assert lib.sjd_skinny_gemm_z(p(xb), p(wz.data), p(wz.exc), wz.cap, p(out), 8, 64, 256, 128, 2, 0, 0, 64, 0, ctypes.byref(ru), s) != 0
 
 
 @pytest.mark.parametrize("M,N,K,KC,waves,step_major", [(32, 4096, 4096, 1024, 6, True), (64, 2048, 2752, 1024, 8, False), (32, 1024, 4096, 2048, 8, True)])
