@@ -288,9 +288,9 @@ class LlamaGenBackbone(nn.Module):
     HEAD_CFG_256ROW = (640, 4, True)
     G1_WIDE_TILES = (2, 3, 4, 6, 8)
 
-    def enable_fused(self, ops, gemm="sjd", max_rows=64):
-        """Switch draft windows of <= max_rows rows (64, 128 or 256: rows = prompts per forward x CFG batch x window; 256 needs bf16, what
-        kernel G1 serves) to the hand-written HIP path: per layer F1r, G1 q|k|v, F2 (the interleaved rotary from a
+    def enable_fused(self, ops, gemm="sjd", max_rows=64, untuned_fp16=False):
+        """Switch draft windows of <= max_rows rows (64, 128 or 256: rows = prompts per forward x CFG batch x window; fp16 weights take 256
+        with untuned_fp16=True only: kernel G1w serves them on the launch shapes swept in bf16) to the hand-written HIP path: per layer F1r, G1 q|k|v, F2 (the interleaved rotary from a
         table, SJD_F2_ROPE_TABLE), K1, G1 o, F1r, G1 gate|up (+ F3, or G1s where ops.gateup_silu_ok allows), G1 down; then the output head
         on G1, whose split-K partials K2 reads (head_partials).  The RMSNorm gains are folded into packed copies of the weights (the
         norm becomes a row scale applied by F2 / F3 / K2, as ChameleonBackbone's folded path does).  w1 / w3 are concatenated once into
@@ -305,8 +305,10 @@ class LlamaGenBackbone(nn.Module):
             raise ValueError(f"LlamaGenBackbone.enable_fused: head_dim {self.head_dim} is not served (F2's table rotary takes head_dim 64 or 128)")
         if max_rows not in (64, 128, 256):
             raise ValueError(f"LlamaGenBackbone.enable_fused: max_rows is 64, 128 or 256 (the three sets of G1 launch shapes), got {max_rows!r}")
-        if max_rows > 128 and dt != torch.bfloat16:
-            raise ValueError("LlamaGenBackbone.enable_fused: kernel G1 serves fp16 windows of at most 128 rows; max_rows=256 needs bf16 weights")
+        if max_rows > 128 and dt != torch.bfloat16 and not untuned_fp16:
+            # (the plain call keeps what it did before fp16 was served at 129..256 rows: nobody gets launch shapes that were never swept for fp16 unasked)
+            raise ValueError("LlamaGenBackbone.enable_fused: max_rows=256 packs bf16 weights; it keeps fp16 windows of at most 128 rows unless "
+                             "untuned_fp16=True (kernel G1 serves fp16 at 129..256 rows on the launch shapes swept in bf16)")
         if max_rows > 64:            # (the default keeps packing exactly what it packed before: a G1_CFG / HEAD_CFG set by the caller still wins)
             sfx = f"_{max_rows}ROW"
             if "G1_CFG" not in self.__dict__:

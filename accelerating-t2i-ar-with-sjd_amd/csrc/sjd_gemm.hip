@@ -2007,7 +2007,7 @@ static int g1_launch(const void *x, const void *w_packed, float *out, int M, int
             }
         }
     }
-    if constexpr (MT > 4) {      // 129..256-row windows (five to eight prompts per forward): G1w (sjd_gemm_wide.h, round 6).  `waves` = column tiles per
+    if constexpr (MT > 4) {      // 129..256-row windows (five to eight prompts per forward), both 16-bit types: G1w (sjd_gemm_wide.h, round 6).  `waves` = column tiles per
         // workgroup: 2, 3, 4 (one per wave) or 6, 8 (two per wave: every activation fragment read from LDS feeds two MFMAs); stages of four k-steps,
         // three ring slots (96 KiB + 1), weight ring of eight k-steps.  SJD_G1_WIDE=0 (A/B aid): round 5's g1_skinny_gemm_tiled8 with four waves,
         // one workgroup per CU (a wave holds MT x 16 accumulators + 2 MT staging pieces + the weight ring: > 256 registers), 2 x MT x 8 KiB of LDS.
@@ -2086,9 +2086,13 @@ static int g1_dispatch(const void *x, const void *w_packed, float *out, int M, i
     if (dtype == SJD_DTYPE_BF16 && M <= 128) return g1_launch<SJD_DTYPE_BF16, 4>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
     if (dtype == SJD_DTYPE_F16 && M <= 128) return g1_launch<SJD_DTYPE_F16, 4>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
     if (dtype == SJD_DTYPE_BF16 && M <= 160) return g1_launch<SJD_DTYPE_BF16, 5>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
+    if (dtype == SJD_DTYPE_F16 && M <= 160) return g1_launch<SJD_DTYPE_F16, 5>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
     if (dtype == SJD_DTYPE_BF16 && M <= 192) return g1_launch<SJD_DTYPE_BF16, 6>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
+    if (dtype == SJD_DTYPE_F16 && M <= 192) return g1_launch<SJD_DTYPE_F16, 6>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
     if (dtype == SJD_DTYPE_BF16 && M <= 224) return g1_launch<SJD_DTYPE_BF16, 7>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
+    if (dtype == SJD_DTYPE_F16 && M <= 224) return g1_launch<SJD_DTYPE_F16, 7>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
     if (dtype == SJD_DTYPE_BF16) return g1_launch<SJD_DTYPE_BF16, 8>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
+    if (dtype == SJD_DTYPE_F16) return g1_launch<SJD_DTYPE_F16, 8>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);       // (both entries have checked M <= 256)
     return SJD_ERR_UNSUPPORTED;
 }
 

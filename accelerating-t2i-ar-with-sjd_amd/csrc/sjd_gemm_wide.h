@@ -338,15 +338,22 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
 #ifdef GW_NO_STORE
     if (acc[0][0][0] != 12345.0f) return;
 #endif
+    // The fp16 forms with five to eight row tiles take the lane index for the plane stores from the hardware again here, behind the last wait (a volatile
+    // statement stays behind gw_wait<0>, so nothing of it is live in the loop): carried from the top of the kernel, `lane & 31` is live across the whole main loop, and with eight row tiles x two column
+    // tiles (256 accumulators + both rings) it was the one register too many -- stored to scratch in front of the loop and reloaded here.  (The bf16 forms
+    // keep the carried index: their code objects are unchanged; the two with eight row tiles x two column tiles have that same store / reload pair outside
+    // the loop)
+    int el = lane;
+    if constexpr (DT == SJD_DTYPE_F16 && MT > 4) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(el));
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
         if (t_out[c] >= N / 32) continue;
-        float *o = out + ((size_t)chunk * (32 * MT)) * N + (size_t)t_out[c] * 32 + (lane & 31);
+        float *o = out + ((size_t)chunk * (32 * MT)) * N + (size_t)t_out[c] * 32 + (el & 31);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int m = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (el >> 5);
                 o[(size_t)m * N] = acc[c][mt][r];
             }
     }

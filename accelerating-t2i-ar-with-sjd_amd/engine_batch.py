@@ -58,9 +58,9 @@ class SJDBatchEngine:
             if getattr(backbone, "_ops", None) is None:
                 raise ValueError("SJDBatchEngine serves a LlamaGen backbone on the fused HIP path only: call "
                                  f"model.enable_fused(ops, gemm='sjd', max_rows=...) first ({rows} window rows per forward here)")
-            if backbone.output.weight.dtype == torch.float16 and rows > 128:
-                raise ValueError(f"kernel G1 serves fp16 windows of at most 128 rows: n_prompts * n_batch * max_window = {rows} > 128 "
-                                 "(use bf16 weights, or fewer prompts per forward)")
+            if backbone.output.weight.dtype == torch.float16 and rows > 128 and getattr(backbone, "max_rows", 64) < rows:
+                raise ValueError(f"the backbone was packed for fp16 windows of at most {getattr(backbone, 'max_rows', 64)} rows, but n_prompts * n_batch * max_window = {rows}: "
+                                 "call enable_fused(ops, gemm='sjd', max_rows=256, untuned_fp16=True), or use fewer prompts per forward")
             if getattr(backbone, "max_rows", 64) < rows:
                 raise ValueError(f"the backbone was packed for windows of at most max_rows={getattr(backbone, 'max_rows', 64)} rows, but "
                                  f"n_prompts * n_batch * max_window = {rows}: call enable_fused(ops, gemm='sjd', max_rows={128 if rows <= 128 else 256})")

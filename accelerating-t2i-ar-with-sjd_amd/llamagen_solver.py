@@ -217,10 +217,11 @@ class LlamaGenSolver:
         return generated
 
     def slots_for(self, n_prompts, n_batch):
-        """prompts per window forward: prompts_per_forward, or what the kernels' row limit allows (256 rows in bf16, 128 in fp16)"""
+        """prompts per window forward: prompts_per_forward, or what the row limit allows: 256 rows; an fp16 backbone that was not packed for them
+        (enable_fused(max_rows=256, untuned_fp16=True)) keeps its 128"""
         model = self.model
-        rows_limit = 256 if model.output.weight.dtype == torch.bfloat16 else 128
-        slots = self.prompts_per_forward or max(1, rows_limit // (n_batch * model.max_num_new_tokens))
+        wide = model.output.weight.dtype == torch.bfloat16 or getattr(model, "max_rows", 64) >= 256
+        slots = self.prompts_per_forward or max(1, (256 if wide else 128) // (n_batch * model.max_num_new_tokens))
         return max(1, min(int(slots), n_prompts))
 
     def _generate_many(self, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, **sampling_kwargs):

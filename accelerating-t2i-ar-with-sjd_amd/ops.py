@@ -496,6 +496,13 @@ def pack_weight_z(weight, KC, step_major=False, gateup=False):
     return PackedZ(data, exc, N, K, KC, step_major, total, raw_index, raw_tiles, raw_view, stats)
 
 
+def _same_16bit_type(x, w_packed, what):
+    """the kernels read the packed records as the activation's type: bf16 rows against fp16 records (or the reverse) would multiply garbage"""
+    wd = getattr(w_packed, "dtype", None)
+    if {x.dtype, wd} == {torch.bfloat16, torch.float16}:
+        raise L.SjdLibraryError(f"{what}: activation {x.dtype} against a weight packed from {wd}: pack the weight in the activation's type")
+
+
 def _prows(M):
     """row padding of the G1 partial planes: whole 32-row MFMA tiles (M <= 256: up to eight prompts per forward)"""
     return ((int(M) + 31) // 32) * 32
@@ -503,9 +510,10 @@ def _prows(M):
 
 def skinny_gemm(x, w_packed, N, K, KC, waves=4, step_major=False):
     """x [M <= 256, K] bf16/fp16 -> Partials([n_chunks, 32 * ceil(M / 32), N] fp32).  waves = column tiles per workgroup: 1..16 up to 64 rows, <= 8 up to
-    128 rows; 129..256 rows (bf16, uncompressed packing) run on kernel G1w: 2, 3, 4, 6 or 8."""
+    128 rows; 129..256 rows (bf16 or fp16, uncompressed packing) run on kernel G1w: 2, 3, 4, 6 or 8."""
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N * K
+    _same_16bit_type(x, w_packed, "skinny_gemm")
     if isinstance(w_packed, PackedZ):
         return skinny_gemm_cols(x, w_packed, N, K, KC, 0, N, waves, step_major)
     nc = (K + KC - 1) // KC
@@ -665,6 +673,7 @@ def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_m
         L.check(L.load().sjd_skinny_gemm_z(_ptr(x), _ptr(w_packed.data), _ptr(w_packed.exc), w_packed.cap, _ptr(out), M, n_cols, K, KC, waves, int(step_major),
                                           _dtype_code(x.dtype), N_packed, col0 // 32, _raw_units(w_packed), _stream()), "sjd_skinny_gemm_z")
         return Partials(out, nc, n_cols)
+    _same_16bit_type(x, w_packed, "skinny_gemm_cols")
     L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed), _ptr(out), M, n_cols, K, KC, waves, int(step_major), _dtype_code(x.dtype),
                                          N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols")
     return Partials(out, nc, n_cols)

@@ -342,7 +342,8 @@ int sjd_gateup_silu(const void *x, const void *w_packed, void *y, int M, int I, 
  * order (0: one contiguous run per tile, 1: the records of all tiles interleaved per k-step).
  * Round 6 -- kernel G1w (csrc/sjd_gemm_wide.h: activation stages by LDS-DMA into a ring shared by the workgroup, hand-counted waits, two to eight row
  * tiles of accumulators per wave) runs when `waves` is 2, 3, 4, 6 or 8 (then = column tiles per workgroup: one per wave up to 4, two per wave for 6 / 8)
- * and 32 < M <= 64 (bf16 or fp16), 64 < M <= 128 (bf16; M <= 96: not 2) or 128 < M <= 256 (bf16 only, these tile counts only): no limit on KC.  Same
+ * and 32 < M <= 64 (bf16 or fp16), 64 < M <= 128 (bf16; M <= 96: not 2) or 128 < M <= 256 (bf16 or fp16; these tile counts only:
+ * SJD_ERR_BAD_ARG otherwise): no limit on KC.  fp16 at 64 < M <= 128 stays on the sub-tiled kernels.  Same
  * chunking and accumulation order as the kernels above: the planes do not depend on which kernel ran (tests/test_gpu_glue.py::test_g1w_*,
  * test_g1_skinny_gemm_*_row_tiles).  SJD_G1_WIDE_64 / _128 / SJD_G1_WIDE = 0 in the environment keep the older kernels (A/B aids). */
 int sjd_gemm_num_chunks(int K, int KC);

@@ -104,11 +104,14 @@ def sweep(args):
         print(json.dumps(dict(best=name, preset=args.preset, cfg=[r["kc"], r["waves"], r["step_major"]], us=r["us"], tbps=r["tbps"])), flush=True)
 
 
-def _make(preset, model_type, image_size, dev):
+DTYPES = dict(bf16=torch.bfloat16, fp16=torch.float16)
+
+
+def _make(preset, model_type, image_size, dev, dtype=torch.bfloat16):
     import sjd_amd.synthetic as synthetic
     a = _args(preset, model_type, image_size)
     with torch.device(dev):
-        m = BB.LlamaGenBackbone(a, attn=ops.HipWindowAttention()).to(torch.bfloat16).eval()
+        m = BB.LlamaGenBackbone(a, attn=ops.HipWindowAttention()).to(dtype).eval()
     synthetic.fill_state_dict_device(m, seed=0, embed_token_scale=0.5)
     return m
 
@@ -126,7 +129,7 @@ class _Leg:
             self.cond = torch.tensor([207, a.num_classes], device=dev)
             self.ks = torch.zeros(2, dtype=torch.int32, device=dev)
         else:
-            cap = (torch.randn(1, self.T, a.caption_dim, generator=g, device=dev) * 0.5).to(torch.bfloat16)
+            cap = (torch.randn(1, self.T, a.caption_dim, generator=g, device=dev) * 0.5).to(model.output.weight.dtype)
             self.cond = torch.cat([cap, torch.zeros_like(cap) + model.cls_embedding.uncond_embedding.to(cap.dtype)])
             self.ks = torch.full((2,), CAP_PAD, dtype=torch.int32, device=dev)          # left-padded caption: the first rows are hidden
         self.s_max = ((self.T + self.N + window + 32 + 31) // 32) * 32
@@ -219,7 +222,7 @@ class _BatchLeg:
             if a.model_type == "c2i":
                 cond, ks = torch.tensor([(207 + 101 * j) % 1000, a.num_classes], device=dev), torch.zeros(2, dtype=torch.int32)
             else:
-                cap = (torch.randn(1, T, a.caption_dim, generator=torch.Generator().manual_seed(3 + j)) * 0.5).to(dev, torch.bfloat16)
+                cap = (torch.randn(1, T, a.caption_dim, generator=torch.Generator().manual_seed(3 + j)) * 0.5).to(dev, m.output.weight.dtype)
                 cond = torch.cat([cap, torch.zeros_like(cap) + m.cls_embedding.uncond_embedding.to(cap.dtype)])
                 ks = torch.full((2,), CAP_PAD, dtype=torch.int32)
             specs.append(WindowSpec(first_tokens=None, first_positions=None, key_start=ks, pos_offset=torch.zeros(2, dtype=torch.long), kv_base=T,
@@ -257,48 +260,59 @@ def _f2_ab(dev, rows=256, H=20, D=64, hid=1280):
 
 
 def batch(args):
+    """--dtype bf16 / fp16: one type; both: the legs of both types in every round, alternated (fp16 beside its bf16 twin from one session).
+    --counts: prompts per forward to measure (1 = SJDEngine, more = SJDBatchEngine)."""
     dev = torch.device("cuda:0")
-    out = dict(configs=[], window=args.window, cfg=True, dtype="bf16", rounds=args.rounds, steps=args.steps, warmup=args.warmup)
+    names = ["bf16", "fp16"] if args.dtype == "both" else [args.dtype]
+    counts = [int(c) for c in args.counts.split(",")]
+    out = dict(configs=[], window=args.window, cfg=True, dtype=args.dtype, rounds=args.rounds, steps=args.steps, warmup=args.warmup)
     for preset, mt, size in CONFIGS:
         if args.only and preset not in args.only.split(","):
             continue
-        base = _make(preset, mt, size, dev)
-        models = {1: base}
-        for P in (2, 4, 8):
-            models[P] = _make(preset, mt, size, dev)
-            models[P].load_state_dict(base.state_dict())
-        for P, m in models.items():
-            rows = P * 2 * args.window
-            m.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256))
-        legs = {1: _Leg(base, args.window, dev)}
-        legs.update({P: _BatchLeg(models[P], P, args.window, dev) for P in (2, 4, 8)})
-        ms, tps = {P: [] for P in legs}, {P: [] for P in legs}
+        models, legs = {}, {}
+        for dn in names:
+            base = _make(preset, mt, size, dev, DTYPES[dn])
+            for P in counts:
+                m = models[dn, P] = base if P == counts[0] else _make(preset, mt, size, dev, DTYPES[dn])
+                if m is not base:
+                    m.load_state_dict(base.state_dict())
+            for P in counts:
+                rows = P * 2 * args.window
+                models[dn, P].enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), untuned_fp16=True)
+                legs[dn, P] = _Leg(models[dn, P], args.window, dev) if P == 1 else _BatchLeg(models[dn, P], P, args.window, dev)
+        ms, tps = {k: [] for k in legs}, {k: [] for k in legs}
         for _ in range(args.rounds):
-            for P, leg in legs.items():
-                if P == 1:
-                    _, st, _ = leg.decode(args.warmup, args.steps)
-                    ms[P].append(1e3 * st.seconds / max(1, st.timed_nfe))
-                    tps[P].append(st.tokens / st.seconds)
-                else:
-                    a_, b_ = leg.decode(args.warmup, args.steps)
-                    ms[P].append(a_)
-                    tps[P].append(b_)
-        med_ms = {P: statistics.median(v) for P, v in ms.items()}
-        med_tps = {P: statistics.median(v) for P, v in tps.items()}
-        rec = dict(preset=preset, model_type=mt, image_size=size, layers=base.n_layers,
-                   ms_per_step={str(P): round(v, 3) for P, v in med_ms.items()},
-                   tokens_per_s={str(P): round(v, 1) for P, v in med_tps.items()},
-                   ms_per_step_rounds={str(P): [round(x, 3) for x in v] for P, v in ms.items()},
-                   tokens_per_s_rounds={str(P): [round(x, 1) for x in v] for P, v in tps.items()},
-                   tokens_per_s_vs_one_prompt={str(P): round(med_tps[P] / med_tps[1], 2) for P in legs},
-                   fraction_of_8tbps={str(P): round(models[P].packed_bytes() / (med_ms[P] * 1e-3) / (PEAK_TBPS * 1e12), 3) for P in legs},
-                   g1_cfg={str(P): [models[P].G1_CFG, list(models[P].HEAD_CFG)] for P in legs})
-        print(json.dumps(rec), flush=True)
-        out["configs"].append(rec)
+            for P in counts:
+                for dn in names:
+                    leg = legs[dn, P]
+                    if P == 1:
+                        _, st, _ = leg.decode(args.warmup, args.steps)
+                        ms[dn, P].append(1e3 * st.seconds / max(1, st.timed_nfe))
+                        tps[dn, P].append(st.tokens / st.seconds)
+                    else:
+                        a_, b_ = leg.decode(args.warmup, args.steps)
+                        ms[dn, P].append(a_)
+                        tps[dn, P].append(b_)
+        for dn in names:
+            med_ms = {P: statistics.median(ms[dn, P]) for P in counts}
+            med_tps = {P: statistics.median(tps[dn, P]) for P in counts}
+            rec = dict(preset=preset, model_type=mt, image_size=size, layers=models[dn, counts[0]].n_layers,
+                       ms_per_step={str(P): round(v, 3) for P, v in med_ms.items()},
+                       tokens_per_s={str(P): round(v, 1) for P, v in med_tps.items()},
+                       ms_per_step_rounds={str(P): [round(x, 3) for x in ms[dn, P]] for P in counts},
+                       tokens_per_s_rounds={str(P): [round(x, 1) for x in tps[dn, P]] for P in counts},
+                       tokens_per_s_vs_one_prompt={str(P): round(med_tps[P] / med_tps[counts[0]], 2) for P in counts},
+                       fraction_of_8tbps={str(P): round(models[dn, P].packed_bytes() / (med_ms[P] * 1e-3) / (PEAK_TBPS * 1e12), 3) for P in counts},
+                       g1_cfg={str(P): [models[dn, P].G1_CFG, list(models[dn, P].HEAD_CFG)] for P in counts})
+            if args.dtype == "both":
+                rec["dtype"] = dn
+            print(json.dumps(rec), flush=True)
+            out["configs"].append(rec)
         del legs, models, base
         torch.cuda.empty_cache()
-    out["f2_table_256rows"] = _f2_ab(dev)
-    print(json.dumps(out["f2_table_256rows"]), flush=True)
+    if args.dtype == "bf16":
+        out["f2_table_256rows"] = _f2_ab(dev)
+        print(json.dumps(out["f2_table_256rows"]), flush=True)
     if args.out:
         with open(args.out, "w") as f:
             json.dump(out, f, indent=1)
@@ -307,10 +321,10 @@ def batch(args):
 def step(args):
     dev = torch.device("cuda:0")
     preset, mt, size = next(c for c in CONFIGS if c[0] == args.preset)
-    m = _make(preset, mt, size, dev)
+    m = _make(preset, mt, size, dev, DTYPES[args.dtype])
     if args.prompts > 1:
         rows = args.prompts * 2 * args.window
-        m.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256))
+        m.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), untuned_fp16=True)
         ms, tps = _BatchLeg(m, args.prompts, args.window, dev).decode(args.warmup, args.steps)
         print(json.dumps(dict(preset=preset, prompts=args.prompts, ms_per_step=round(ms, 3), tokens_per_s=round(tps, 1))), flush=True)
         return
@@ -335,6 +349,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default="")
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "both"], help="--batch / --step: weight type (both: --batch only, legs alternated)")
+    ap.add_argument("--counts", default="1,2,4,8", help="--batch: prompts per forward to measure")
     args = ap.parse_args()
     if args.sweep:
         sweep(args)
