@@ -12,6 +12,8 @@ DTYPE_BF16, DTYPE_F16, DTYPE_F32 = 0, 1, 2
 # mode bits in the high bits of the glue kernels' dtype argument (include/sjd_hip.h)
 F1_POST_NORM = 0x100
 F2_ROPE_TABLE = 0x200
+F2_HEAD_PAD128 = 0x400         # with F2_ROPE_TABLE and D = 100: 100-wide source heads, 128-wide q / cache rows, pad columns written as zeros
+K1_HEAD_DIM_100 = 0x800        # the 16-bit K1 entry points: D = 128 storage with zero pad columns, softmax scale 1/sqrt(100)
 QKN_SHARDS_SHIFT = 16
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -234,9 +234,11 @@ class LlamaGenBackbone(nn.Module):
         self.n_layers = args.n_layer
 
     def setup_cache(self, batch, s_max, dtype=None, device=None):
+        """the cache rows are head_dim wide -- or 128 wide with zero pad columns once enable_fused(pad_head_dim=True) has switched a
+        head_dim-100 model (GPT-3B) to padded storage; the rotary table keeps its true width ([., head_dim / 2, 2])"""
         p = self.tok_embeddings.weight
-        self.cache = StaticKVCache(self.n_layers, batch, self.n_kv_heads, s_max, self.head_dim, dtype or p.dtype,
-                                   device or p.device)
+        self.cache = StaticKVCache(self.n_layers, batch, self.n_kv_heads, s_max, getattr(self, "_head_pad", None) or self.head_dim,
+                                   dtype or p.dtype, device or p.device)
         self.buffers_version = getattr(self, "buffers_version", 0) + 1
         self.freqs = self.freqs.to(p.device)
         self._rope_ext = _rope_table_extended(self.freqs, s_max)
@@ -287,12 +289,32 @@ class LlamaGenBackbone(nn.Module):
     G1_CFG_LLAMAGEN_256ROW = dict(qkv=(256, 4, False), o=(256, 2, False), gate_up=(320, 4, True), down=(512, 4, False))
     HEAD_CFG_256ROW = (640, 4, True)
     G1_WIDE_TILES = (2, 3, 4, 6, 8)
+    # GPT-3B (dim 3200, 32 heads of 100 stored 128 wide: pad_head_dim=True; inter 8704; the o projection's K is 32 * 128 = 4096): the KC 256 / 320 / 512
+    # of the sets above would leave 13 / 10 / 17 planes, so the chunks are the smallest multiples of 16 that give eight -- 400 for hidden 3200, 512 for
+    # the o projection, 1088 for the down projection.  `tools/llamagen_bench.py --sweep --preset GPT-3B` at 32 rows (profiles/llamagen_g1_sweep_3b.jsonl):
+    # per projection the fastest shape with at most eight planes, us per launch q|k|v 12.83 (five planes), o 8.28, gate|up 20.81 (three planes),
+    # down 13.69, head 19.51; against the smallest-chunk set (400, 2) / (512, 2) / (400, 2) / (1088, 2) + head (640, 4) the fused step goes
+    # 2.19 -> 1.89 ms (profiles/llamagen_3b.json)
+    G1_CFG_LLAMAGEN_3B = dict(qkv=(640, 8, True), o=(512, 4, False), gate_up=(1088, 8, True), down=(1088, 4, True))
+    HEAD_CFG_3B = (1088, 8, True)
+    HEAD_PAD = 128                # storage head dim of a padded model (the K1 / F2 shape of Lumina-7B: 32 heads, D 128, H == H_kv)
 
-    def enable_fused(self, ops, gemm="sjd", max_rows=64, untuned_fp16=False):
+    @staticmethod
+    def _pad_o_weight(wo, n_heads, head_dim, head_pad):
+        """wo [dim, H * head_dim] -> [dim, H * head_pad]: zero columns at each head's pad positions, so K1's [T, H * head_pad] output feeds the o
+        projection as it stands (its pad columns are zero and meet zero weights)"""
+        w = wo.new_zeros(wo.shape[0], n_heads, head_pad)
+        w[:, :, :head_dim] = wo.view(wo.shape[0], n_heads, head_dim)
+        return w.view(wo.shape[0], n_heads * head_pad)
+
+    def enable_fused(self, ops, gemm="sjd", max_rows=64, untuned_fp16=False, pad_head_dim=False):
         """Switch draft windows of <= max_rows rows (64, 128 or 256: rows = prompts per forward x CFG batch x window; fp16 weights take 256
         with untuned_fp16=True only: kernel G1w serves them on the launch shapes swept in bf16) to the hand-written HIP path: per layer F1r, G1 q|k|v, F2 (the interleaved rotary from a
         table, SJD_F2_ROPE_TABLE), K1, G1 o, F1r, G1 gate|up (+ F3, or G1s where ops.gateup_silu_ok allows), G1 down; then the output head
-        on G1, whose split-K partials K2 reads (head_partials).  The RMSNorm gains are folded into packed copies of the weights (the
+        on G1, whose split-K partials K2 reads (head_partials).  pad_head_dim=True serves head_dim 100 (GPT-3B) stored 128 wide: q|k|v is
+        packed at its true size and F2 (SJD_F2_HEAD_PAD128) writes 128-wide q / cache rows with zero pad columns, K1 runs at D = 128 with the
+        softmax scale of 100 (SJD_K1_HEAD_DIM_100), wo is packed with zero columns at the pad positions; the cache becomes 128 wide (an existing
+        one is re-allocated: prefill again); windows of at most 64 rows; no effect at head_dim 64 / 128.  The RMSNorm gains are folded into packed copies of the weights (the
         norm becomes a row scale applied by F2 / F3 / K2, as ChameleonBackbone's folded path does).  w1 / w3 are concatenated once into
         [w1; w3] (gate | up) and re-pointed at its halves (state dict unchanged).  The prefill and longer inputs stay on forward_embeds.
         `ops` is sjd_amd.ops.  Raises ValueError for what the kernels do not serve."""
@@ -301,8 +323,23 @@ class LlamaGenBackbone(nn.Module):
         dt = self.output.weight.dtype
         if dt not in (torch.bfloat16, torch.float16):
             raise ValueError(f"LlamaGenBackbone.enable_fused needs 16-bit weights (bf16 or fp16), got {dt}")
-        if self.head_dim not in (64, 128):
-            raise ValueError(f"LlamaGenBackbone.enable_fused: head_dim {self.head_dim} is not served (F2's table rotary takes head_dim 64 or 128)")
+        pad100 = bool(pad_head_dim) and self.head_dim == 100
+        if self.head_dim not in (64, 128) and not pad100:
+            raise ValueError(f"LlamaGenBackbone.enable_fused: head_dim {self.head_dim} is not served (F2's table rotary takes head_dim 64 or 128; "
+                             "head_dim 100 runs stored 128 wide with pad_head_dim=True)")
+        if pad100:
+            if self.n_heads != self.n_kv_heads:
+                raise ValueError("LlamaGenBackbone.enable_fused: pad_head_dim=True serves multi-head attention (n_kv_head == n_head) only")
+            if max_rows > 64:
+                raise ValueError("LlamaGenBackbone.enable_fused: pad_head_dim=True serves windows of at most 64 rows (one prompt per forward); "
+                                 f"max_rows={max_rows!r} has no swept G1 launch shapes at head_dim 100 yet")
+            if self.args.dim % 32 != 0 or (3 * self.args.dim) % 32 != 0:
+                raise ValueError(f"LlamaGenBackbone.enable_fused: dim {self.args.dim} -- kernel G1 takes whole 32-column tiles and 16-wide k-steps "
+                                 "(dim a multiple of 32: at head_dim 100 a head count that is a multiple of 8)")
+            if "G1_CFG" not in self.__dict__:
+                self.G1_CFG = dict(self.G1_CFG_LLAMAGEN_3B)
+            if "HEAD_CFG" not in self.__dict__:
+                self.HEAD_CFG = tuple(self.HEAD_CFG_3B)
         if max_rows not in (64, 128, 256):
             raise ValueError(f"LlamaGenBackbone.enable_fused: max_rows is 64, 128 or 256 (the three sets of G1 launch shapes), got {max_rows!r}")
         if max_rows > 128 and dt != torch.bfloat16 and not untuned_fp16:
@@ -322,6 +359,7 @@ class LlamaGenBackbone(nn.Module):
             self.G1_CFG = dict(self.G1_CFG_LLAMAGEN)
         c = self.G1_CFG
         fold = lambda w, g: (w.float() * g.float()[None, :]).to(w.dtype)      # W' = W diag(gamma)
+        wo_of = (lambda w: self._pad_o_weight(w, self.n_heads, self.head_dim, self.HEAD_PAD)) if pad100 else (lambda w: w)
         self._packed, self._fused = [], []
         with torch.no_grad():
             for layer in self.layers:
@@ -331,7 +369,7 @@ class LlamaGenBackbone(nn.Module):
                 f.w1.weight.data, f.w3.weight.data = gu[:ni], gu[ni:]
                 self._fused.append(gu)
                 self._packed.append(dict(qkv=ops.pack_weight(fold(a.wqkv.weight, layer.attention_norm.weight), c["qkv"][0], c["qkv"][2]),
-                                         o=ops.pack_weight(a.wo.weight, c["o"][0], c["o"][2]),
+                                         o=ops.pack_weight(wo_of(a.wo.weight), c["o"][0], c["o"][2]),
                                          gate_up=ops.pack_weight(fold(gu, layer.ffn_norm.weight), c["gate_up"][0], c["gate_up"][2]),
                                          down=ops.pack_weight(f.w2.weight, c["down"][0], c["down"][2])))
             wf = fold(self.output.weight, self.norm.weight)
@@ -344,6 +382,11 @@ class LlamaGenBackbone(nn.Module):
         self._ops = ops
         self._fused_rows = self.max_rows = int(max_rows)
         self.supports_head_partials = True
+        self._head_pad = self.HEAD_PAD if pad100 else None
+        if pad100 and self.cache is not None and self.cache.k.shape[-1] != self.HEAD_PAD:
+            # (a cache set up before this call is head_dim wide: the same cache at the storage width, empty -- either order of the two calls ends 128 wide)
+            ck = self.cache.k
+            self.setup_cache(ck.shape[1], ck.shape[3], ck.dtype, ck.device)
         self.buffers_version = getattr(self, "buffers_version", 0) + 1          # captured hipGraphs hold the packed weights' addresses
         return self
 
@@ -356,6 +399,8 @@ class LlamaGenBackbone(nn.Module):
         ops, B, n = self._ops, tokens.shape[0], tokens.shape[1]
         T, eps, cfg = B * n, self.args.norm_eps, self.G1_CFG
         H, Hkv, D, hid = self.n_heads, self.n_kv_heads, self.head_dim, self.args.dim
+        DS = self._head_pad or D                # storage head dim of q, the cache rows and K1's output (128 for a padded head_dim 100)
+        akw = dict(head_dim=D) if DS != D else {}
         inter = self._fused[0].shape[0] // 2
         params = getattr(self.attn, "params", None)
         kv_arg = kv_len if params is None else 0
@@ -369,9 +414,9 @@ class LlamaGenBackbone(nn.Module):
             rn = (ops.residual_sumsq(h, delta), hid, eps)
             qkv = g1(h, li, "qkv", (H + 2 * Hkv) * D, hid)
             q = ops.qknorm_rope_append(qkv, kc, vc, None, None, None, None, None, pos, B, n, H, Hkv, D, params, kv_arg, dtype=h.dtype,
-                                       row_norm=rn, rope_table=self._rope_ext)
-            o = self.attn.attend(li, q, self.cache, kv_len, key_start)
-            rn = (ops.residual_sumsq(h, g1(o.view(T, H * D), li, "o", hid, H * D)), hid, eps)
+                                       row_norm=rn, rope_table=self._rope_ext, head_pad=self._head_pad)
+            o = self.attn.attend(li, q, self.cache, kv_len, key_start, **akw)
+            rn = (ops.residual_sumsq(h, g1(o.view(T, H * DS), li, "o", hid, H * DS)), hid, eps)
             if fuse_mlp:
                 act = ops.gateup_silu(h, self._packed[li]["gate_up"], inter, hid, cfg["gate_up"][2], row_norm=rn)
             else:

@@ -291,7 +291,8 @@ __device__ __forceinline__ void k1_merge_publish(float (*red_o)[K1_ROWS][D + K1_
 }
 
 // NW wave64 per workgroup (4, or 8 for two waves per SIMD: twice the key tiles in flight per CU; the key-parts are merged in LDS)
-template <int DT, int D, int NW>
+// DL: the LOGICAL head dim of the softmax scale (SJD_K1_HEAD_DIM_100: heads stored D = 128 wide with zero pad columns, scale 1/sqrt(100))
+template <int DT, int D, int NW, int DL = D>
 __global__ __launch_bounds__(64 * NW) void k1_partial(
     const unsigned short *__restrict__ q, const unsigned short *__restrict__ kc, const unsigned short *__restrict__ vc,
     const sjd_iter_params *__restrict__ params, const int *__restrict__ key_start,        // (among the first 16 dwords: preloaded into SGPRs)
@@ -328,7 +329,7 @@ __global__ __launch_bounds__(64 * NW) void k1_partial(
     const int n_c = min(K1_ROWS, n_total - row0);                 // may be <= 0 for padding chunks
     const int kv_len = kv_base + row0;                            // keys < kv_len are visible to every row of the chunk
     const int total = kv_len + max(n_c, 0);                       // keys >= total are not visible to any row
-    const float scale = rsqrtf((float)D);
+    const float scale = rsqrtf((float)DL);
 
     // tile range of this workgroup / wave
     int t_lo, t_hi, eff_split, tps;
@@ -1622,7 +1623,10 @@ static int k1_waves()
     return w;
 }
 
-template <int DT, int D>
+// DL: the logical head dim of the softmax scale (SJD_K1_HEAD_DIM_100: D = 128 storage, DL = 100).  Only the forms the product dispatch picks
+// carry it -- k1_dsplit, k1_partial (+ k1_combine, which has no scale of its own) and the four-slot ring kernel; every A/B form selected by an
+// environment switch declines with SJD_ERR_UNSUPPORTED, so no launch ever runs with 1/sqrt(128) under the bit.
+template <int DT, int D, int DL = D>
 static int launch_attention(const void *q, const void *kc, const void *vc, void *out, int B, int n_rows, int H, int H_kv, int S_max,
                             const int32_t *key_start, const sjd_iter_params *params, int kv_len, int n_split, void *workspace,
                             hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, unsigned *ticket = nullptr, bool colsplit = false)
@@ -1650,9 +1654,19 @@ static int launch_attention(const void *q, const void *kc, const void *vc, void 
     // launch, no workspace, no combine.  SJD_K1_DSPLIT=0|1 (A/B aid).
     static const int dsplit = [] { const char *e = getenv("SJD_K1_DSPLIT"); return e ? atoi(e) : SJD_K1_DSPLIT_DEFAULT; }();
     if (colsplit && !(D == 128 && H == H_kv)) return SJD_ERR_UNSUPPORTED;
+    if constexpr (DL != D) {
+        static_assert(D == 128, "a logical head dim is served at storage D = 128 only");
+        if (H != H_kv) return SJD_ERR_UNSUPPORTED;
+    }
     if ((colsplit || (!shared && dsplit)) && D == 128 && H == H_kv) {
         if constexpr (D == 128) {
             static const int pf = [] { const char *e = getenv("SJD_K1_DSPLIT_PF"); return e ? atoi(e) : 0; }();      // (0: one tile ahead; 3 / 4: tiles in flight per wave)
+            if constexpr (DL != D) {
+                if (pf == 9 || pf == 4 || pf == 3) return SJD_ERR_UNSUPPORTED;
+                hipLaunchKernelGGL((k1_dsplit<DT, D, 8, 4, DL>), dim3(4 * n_chunks * H * B), dim3(512), 0, stream, (const unsigned short *)q,
+                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, (unsigned short *)out, n_rows, H, H_kv,
+                                   S_max, kv_len, n_chunks, B);
+            } else
             if (pf == 9) {        // (9: the column split over an LDS-DMA ring of full key rows)
                 const size_t lds = (size_t)16 * (K1_KT * D * 2 + K1_KT * (D / 4) * 2);
                 (void)hipFuncSetAttribute((const void *)k1_dsplit_ring<DT, D, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1676,6 +1690,30 @@ static int launch_attention(const void *q, const void *kc, const void *vc, void 
             return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
         }
     }
+    if constexpr (DL != D) {
+        if (shared) {
+            if (!ring || ring_slots != 4 || getenv("SJD_K1_RING_HALVES")) return SJD_ERR_UNSUPPORTED;
+            constexpr size_t lds4 = (size_t)4 * 2 * K1_KT * D * 2 + (size_t)4 * K1_ROWS * D * 2, lds8 = (size_t)4 * 2 * K1_KT * D * 2 + (size_t)8 * K1_ROWS * D * 2;
+            if (pairs == 8) {
+                (void)hipFuncSetAttribute((const void *)k1_partial_ring<DT, D, 8, 4, DL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
+                hipLaunchKernelGGL((k1_partial_ring<DT, D, 8, 4, DL>), dim3(n_split, H_kv, B), dim3(512), lds8, stream, (const unsigned short *)q,
+                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, n_rows, H, H_kv, S_max,
+                                   kv_len, n_split, n_chunks, B);
+            } else {
+                (void)hipFuncSetAttribute((const void *)k1_partial_ring<DT, D, 4, 4, DL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
+                hipLaunchKernelGGL((k1_partial_ring<DT, D, 4, 4, DL>), dim3(n_split, H_kv, B), dim3(256), lds4, stream, (const unsigned short *)q,
+                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, n_rows, H, H_kv, S_max,
+                                   kv_len, n_split, n_chunks, B);
+            }
+        } else if (k1_waves() == 8)
+            hipLaunchKernelGGL((k1_partial<DT, D, 8, DL>), dim3(n_chunks * n_split, H_kv, B), dim3(512), 0, stream, (const unsigned short *)q,
+                               (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, direct, n_rows, H, H_kv, S_max,
+                               kv_len, n_split, n_chunks, merge_out, ticket);
+        else
+            hipLaunchKernelGGL((k1_partial<DT, D, 4, DL>), dim3(n_chunks * n_split, H_kv, B), dim3(256), 0, stream, (const unsigned short *)q,
+                               (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, direct, n_rows, H, H_kv, S_max,
+                               kv_len, n_split, n_chunks, merge_out, ticket);
+    } else
     if (shared && ring) {
         if constexpr (D == 128) {
 #define SJD_K1R_LAUNCH(NWV_, R_) do {                                                                                                        \
@@ -1747,6 +1785,11 @@ static int k1_dispatch(const void *q, const void *k_cache, const void *v_cache, 
                        const sjd_iter_params *params, int kv_len, int n_split, void *workspace, void *stream,
                        void *ev_start, void *ev_stop, unsigned *ticket, bool colsplit = false)
 {
+    // the mode bit of `dtype`: SJD_K1_HEAD_DIM_100 -- heads stored 128 wide with zero pad columns 100..127, softmax scale 1/sqrt(100)
+    if (dtype & ~(SJD_DTYPE_MASK | SJD_K1_HEAD_DIM_100)) return SJD_ERR_UNSUPPORTED;
+    const bool dl100 = (dtype & SJD_K1_HEAD_DIM_100) != 0;
+    dtype &= SJD_DTYPE_MASK;
+    if (dl100 && (D != 128 || H != H_kv || (dtype != SJD_DTYPE_BF16 && dtype != SJD_DTYPE_F16))) return SJD_ERR_UNSUPPORTED;
     if (!q || !k_cache || !v_cache || !out || (!workspace && !colsplit) || B < 1 || n_rows < 1 || H < 1 || H_kv < 1 || n_split < 1) return SJD_ERR_BAD_ARG;
     if (H % H_kv != 0 || (S_max % K1_KT) != 0) return SJD_ERR_BAD_ARG;
     if (dtype == SJD_DTYPE_F32) {
@@ -1763,6 +1806,10 @@ static int k1_dispatch(const void *q, const void *k_cache, const void *v_cache, 
     if (!(G == 1 || G == 2 || G == 4 || G == 8)) return SJD_ERR_UNSUPPORTED;
     if (G == 8 && k1_waves() != 8 && !(D == 128 && n_rows <= K1_ROWS && !getenv("SJD_K1_NO_SHARED"))) return SJD_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
+    if (dl100) {
+        if (dtype == SJD_DTYPE_BF16) return launch_attention<SJD_DTYPE_BF16, 128, 100>(q, k_cache, v_cache, out, B, n_rows, H, H_kv, S_max, key_start, params, kv_len, n_split, workspace, s, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, ticket, colsplit);
+        return launch_attention<SJD_DTYPE_F16, 128, 100>(q, k_cache, v_cache, out, B, n_rows, H, H_kv, S_max, key_start, params, kv_len, n_split, workspace, s, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, ticket, colsplit);
+    }
 #define SJD_K1_CASE(DT_, D_) \
     if (dtype == DT_ && D == D_) return launch_attention<DT_, D_>(q, k_cache, v_cache, out, B, n_rows, H, H_kv, S_max, key_start, params, kv_len, n_split, workspace, s, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, ticket, colsplit);
     SJD_K1_CASE(SJD_DTYPE_BF16, 128)
@@ -1889,6 +1936,7 @@ static int k1_dispatch_fp8(const void *q, const void *k_cache, const void *v_cac
                            const sjd_iter_params *params, int kv_len, int n_split, void *workspace, void *stream, unsigned *ticket,
                            bool colsplit = false)
 {
+    if (dtype & ~SJD_DTYPE_MASK) return SJD_ERR_UNSUPPORTED;      // (SJD_K1_HEAD_DIM_100 is served over 16-bit caches only)
     if (!q || !k_cache || !v_cache || !out || (!workspace && !colsplit) || B < 1 || n_rows < 1 || H < 1 || H_kv < 1 || n_split < 1) return SJD_ERR_BAD_ARG;
     if (H % H_kv != 0 || (S_max % K1_KT) != 0 || !(k_scale > 0.f) || !(v_scale > 0.f)) return SJD_ERR_BAD_ARG;
     const int G = H / H_kv;

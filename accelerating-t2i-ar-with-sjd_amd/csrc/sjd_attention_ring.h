@@ -78,7 +78,7 @@ __device__ __forceinline__ float k1r_sum_across_groups(float v)
 }
 
 // NWV = waves per workgroup = (q head of the group, 16-row chunk) pairs: 4 or 8.  R = ring slots.
-template <int DT, int D, int NWV, int R>
+template <int DT, int D, int NWV, int R, int DL = D>      // DL: logical head dim of the softmax scale (see k1_partial)
 __global__ __launch_bounds__(64 * NWV) void k1_partial_ring(
     const unsigned short *__restrict__ q, const unsigned short *__restrict__ kc, const unsigned short *__restrict__ vc,
     const sjd_iter_params *__restrict__ params, const int *__restrict__ key_start,        // (among the first 16 dwords: preloaded into SGPRs)
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(64 * NWV) void k1_partial_ring(
     const int head = hkv * G + head_in_group;
     int kv_base, n_total, kstart;
     k1_entry(params, key_start, b, kv_len_arg, n_rows, kv_base, n_total, kstart);
-    const float scale = rsqrtf((float)D);
+    const float scale = rsqrtf((float)DL);
 
     // this wave's rows and tile range (identical to what k1_partial / k1_combine derive for its chunk)
     const int row0 = chunk * K1_ROWS;
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(64 * NWV) void k1_partial_ring(
 // merge their eight (m, l, O) through LDS and write the NORMALISED 16-bit output: one launch, no workspace, no exchange between
 // workgroups.  Cost: QK^T and the softmax run four times (16-row windows: the MFMA pipe idles anyway) and every CU pulls K + V / 4
 // (2.5 x the bytes through its L1, 1 x from HBM).
-template <int DT, int D, int NW, int DS>
+template <int DT, int D, int NW, int DS, int DL = D>     // DL: logical head dim of the softmax scale (see k1_partial)
 __global__ __launch_bounds__(64 * NW) void k1_dsplit(
     const unsigned short *__restrict__ q, const unsigned short *__restrict__ kc, const unsigned short *__restrict__ vc,
     const sjd_iter_params *__restrict__ params, const int *__restrict__ key_start, unsigned short *__restrict__ out,
@@ -364,7 +364,7 @@ __global__ __launch_bounds__(64 * NW) void k1_dsplit(
     const int n_c = min(K1_ROWS, n_total - row0);
     const int kv_len = kv_base + row0;
     const int total = kv_len + max(n_c, 0);
-    const float scale = rsqrtf((float)D);
+    const float scale = rsqrtf((float)DL);
     const int t_lo = kstart / K1_KT, t_hi = (total + K1_KT - 1) / K1_KT;
 
     vec qf[KS];

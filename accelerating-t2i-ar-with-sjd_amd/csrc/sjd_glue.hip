@@ -361,9 +361,12 @@ __device__ __forceinline__ float row_sumsq_total(const float *__restrict__ row_s
 // KV8: the cache holds OCP fp8 e4m3 bytes (value = fp8 * scale); k/v rows are quantised on the way in (q stays 16-bit)
 // TBL (SJD_F2_ROPE_TABLE, LlamaGen): the interleaved 2-D rotary of reference llamagen.py:457-467 -- lane l owns the pair (2l, 2l + 1), and
 // `inv_freq` is an fp32 table [S_rows >= S_max, D/2, 2] of (cos, sin), row p serving position p (positions clamp to [0, S_max - 1]).  No QK-norm.
+// DS (SJD_F2_HEAD_PAD128, LlamaGen GPT-3B): the STORAGE head dim of q_out and the caches where it differs from the source's D -- D = 100, DS = 128,
+// table mode only.  Lanes 0..49 own the pairs of the 100-wide source head and of the [., 50, 2] table row exactly as above; lanes 50..63 store
+// zeros into columns 100..127 of every row the kernel writes (q, k and v), so the pad columns never depend on what the buffers held.
 __device__ __forceinline__ unsigned char f2_to_fp8(float x) { return (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(x, x, 0, false) & 0xff); }
 
-template <int DT, int D, bool KV8, bool TBL = false>
+template <int DT, int D, bool KV8, bool TBL = false, int DS = D>
 __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
     const unsigned short *__restrict__ qkv, unsigned short *__restrict__ q_out, unsigned short *__restrict__ k_cache,
     unsigned short *__restrict__ v_cache, const unsigned short *__restrict__ qn_w, const unsigned short *__restrict__ qn_b,
@@ -373,6 +376,7 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
     const float *__restrict__ row_sumsq, int rs_slices, float rs_inv_hidden, float rs_eps, int hps_q, int hps_k)
 {
     SJD_TRG(1, 0);
+    static_assert(DS == D || (TBL && !KV8 && DS == 128 && D < DS && (D % 2) == 0), "a padded head: table mode, 16-bit cache, 64 lanes cover the 128 stored columns");
     constexpr int HALF = D / 2;
     constexpr int PPL = HALF / 64 > 0 ? HALF / 64 : 1;       // pairs per lane (D=128: 1, D=64: lanes 32..63 idle)
     constexpr int EST = TBL ? 2 : 1, E1 = TBL ? 1 : HALF;    // the lane's pair: elements (EST * lane, EST * lane + E1)
@@ -505,15 +509,20 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
     // which therefore could not be issued before kv_len had arrived.
     unsigned short *dst = nullptr;
     unsigned char *dst8 = nullptr;                            // KV8: byte rows of the fp8 cache
-    if (is_q) dst = q_out + ((size_t)tok * H + hl) * D;
+    if (is_q) dst = q_out + ((size_t)tok * H + hl) * DS;
     else {
         const int r = kv_len + i;
         if (r >= S_max) return;
-        const size_t off = (((size_t)b * H_kv + hl) * S_max + r) * D;
+        const size_t off = (((size_t)b * H_kv + hl) * S_max + r) * DS;
         if (KV8) dst8 = reinterpret_cast<unsigned char *>(is_k ? k_cache : v_cache) + off;
         else dst = (is_k ? k_cache : v_cache) + off;
     }
     if (!is_q && !is_k) {                                     // V: plain copy into the cache
+        if constexpr (DS != D) {                              // (every lane stores: the pad lanes hold x0 = x1 = 0, written as zero bits)
+            dst[2 * lane] = active ? Cvt<DT>::from_f(x0) : (unsigned short)0;
+            dst[2 * lane + 1] = active ? Cvt<DT>::from_f(x1) : (unsigned short)0;
+            return;
+        }
         if (active) {
             if (KV8) { dst8[EST * lane] = f2_to_fp8(x0 * q8); dst8[EST * lane + E1] = f2_to_fp8(x1 * q8); }
             else { dst[EST * lane] = Cvt<DT>::from_f(x0); dst[EST * lane + E1] = Cvt<DT>::from_f(x1); }
@@ -544,6 +553,9 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
             const float o1 = x1 * ifr + x0 * tsn;
             dst[2 * lane] = Cvt<DT>::from_f(o0);
             dst[2 * lane + 1] = Cvt<DT>::from_f(o1);
+        }
+        if constexpr (DS != D) {
+            if (!active) { dst[2 * lane] = 0; dst[2 * lane + 1] = 0; }      // pad columns D..DS-1 of the q / k row
         }
     } else if (active) {
         const float ang = (float)posv * ifr;
@@ -580,7 +592,9 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
 // `inv_freq`, read ONCE per wave.  The table row's address hangs on the position, so the order of requests is: position (scalar), the first
 // four planes of all HPW heads (they do not need it), then the table row -- one vector round trip with the planes, not one in front of them.
 // No QK-norm, no fp8 cache; the arithmetic of the one-head kernel's TBL branch element for element (no FMA contraction).
-template <int DT, int D, bool KV8, int HPW, bool SHARD = false, bool TBL = false>
+// DS (SJD_F2_HEAD_PAD128): see the one-head kernel -- 100-wide heads in the planes (400-byte head strides keep the 8-byte loads aligned), 128-wide
+// rows out; lanes 50..63 store the zero pad columns of each of the wave's HPW heads.
+template <int DT, int D, bool KV8, int HPW, bool SHARD = false, bool TBL = false, int DS = D>
 __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
     unsigned short *__restrict__ q_out, unsigned short *__restrict__ k_cache, unsigned short *__restrict__ v_cache,
     const unsigned short *__restrict__ qn_w, const unsigned short *__restrict__ qn_b, const unsigned short *__restrict__ kn_w,
@@ -588,6 +602,7 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
     int S_max, const sjd_iter_params *__restrict__ params, int kv_len_arg, const float *__restrict__ part, int n_chunks, int prows, float k_inv,
     float v_inv, const float *__restrict__ row_sumsq, int rs_slices, float rs_inv_hidden, float rs_eps, int hps_q, int hps_k)
 {
+    static_assert(DS == D || (TBL && !KV8 && DS == 128 && D < DS && (D % 4) == 0), "a padded head: table mode, 16-bit cache, 8-byte aligned head strides in the planes");
     constexpr int HALF = D / 2;
     constexpr int NG = SHARD ? HPW : 1;                       // gain / bias rows held per lane
     const int lane = threadIdx.x & 63;
@@ -683,11 +698,14 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
     const int rrow = kv_len + i;
     if (!is_q && rrow >= S_max) return;
     if (!is_q && !is_k) {                                     // V: plain copy into the cache
-        if (active) {
+        if (active || DS != D) {                              // (a padded head: every lane stores, the pad lanes zero bits)
 #pragma unroll
             for (int j = 0; j < HPW; ++j) {
-                const size_t off = (((size_t)b * H_kv + hl0 + j) * S_max + rrow) * D;
-                if constexpr (TBL) {
+                const size_t off = (((size_t)b * H_kv + hl0 + j) * S_max + rrow) * DS;
+                if constexpr (DS != D) {
+                    *reinterpret_cast<unsigned *>(v_cache + off + 2 * lane) =
+                        active ? (unsigned)Cvt<DT>::from_f(x0[j]) | ((unsigned)Cvt<DT>::from_f(x1[j]) << 16) : 0u;
+                } else if constexpr (TBL) {
                     *reinterpret_cast<unsigned *>(v_cache + off + 2 * lane) =
                         (unsigned)Cvt<DT>::from_f(x0[j]) | ((unsigned)Cvt<DT>::from_f(x1[j]) << 16);
                 } else if (KV8) {
@@ -726,9 +744,19 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
                 const float o0 = x0[j] * ifr - x1[j] * tsn;
                 const float o1 = x1[j] * ifr + x0[j] * tsn;
                 const unsigned pk = (unsigned)Cvt<DT>::from_f(o0) | ((unsigned)Cvt<DT>::from_f(o1) << 16);
-                unsigned short *dst = is_q ? q_out + ((size_t)tok * H + hl0 + j) * D
-                                           : k_cache + (((size_t)b * H_kv + hl0 + j) * S_max + rrow) * D;
+                unsigned short *dst = is_q ? q_out + ((size_t)tok * H + hl0 + j) * DS
+                                           : k_cache + (((size_t)b * H_kv + hl0 + j) * S_max + rrow) * DS;
                 *reinterpret_cast<unsigned *>(dst + 2 * lane) = pk;
+            }
+        }
+        if constexpr (DS != D) {
+            if (!active) {                                    // pad columns D..DS-1 of the wave's q / k rows
+#pragma unroll
+                for (int j = 0; j < HPW; ++j) {
+                    unsigned short *dst = is_q ? q_out + ((size_t)tok * H + hl0 + j) * DS
+                                               : k_cache + (((size_t)b * H_kv + hl0 + j) * S_max + rrow) * DS;
+                    *reinterpret_cast<unsigned *>(dst + 2 * lane) = 0u;
+                }
             }
         }
     } else if (active) {
@@ -854,13 +882,15 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
 {
     // the mode bits of `dtype`: SJD_QKN_SHARDS(mp) -- QK-norm gain / bias stored [mp, D], head h of q uses row h / (H / mp), of k h / (H_kv / mp);
     // SJD_F2_ROPE_TABLE -- LlamaGen's interleaved rotary from a (cos, sin) table in `inv_freq`
-    if (dtype & ~(SJD_DTYPE_MASK | SJD_QKN_SHARDS_MASK | SJD_F2_ROPE_TABLE)) return SJD_ERR_UNSUPPORTED;
+    // SJD_F2_HEAD_PAD128 -- with the table mode and D = 100: 100-wide source heads, 128-wide q_out / cache rows whose pad columns are written as zeros
+    if (dtype & ~(SJD_DTYPE_MASK | SJD_QKN_SHARDS_MASK | SJD_F2_ROPE_TABLE | SJD_F2_HEAD_PAD128)) return SJD_ERR_UNSUPPORTED;
     const int shards = (dtype & SJD_QKN_SHARDS_MASK) >> SJD_QKN_SHARDS_SHIFT;
-    const bool table = (dtype & SJD_F2_ROPE_TABLE) != 0;
+    const bool table = (dtype & SJD_F2_ROPE_TABLE) != 0, pad128 = (dtype & SJD_F2_HEAD_PAD128) != 0;
     dtype &= SJD_DTYPE_MASK;
+    if (pad128 && (!table || D != 100)) return SJD_ERR_UNSUPPORTED;
     if (table && (qn_w || qn_b || kn_w || kn_b)) return SJD_ERR_BAD_ARG;      // (LlamaGen has no QK-norm)
     // (table mode above 64 rows reads split-K planes only: the many-row windows come from G1; a dense source stays refused)
-    if (table && (kv8 || (B * n > 64 && !part) || (D != 64 && D != 128))) return SJD_ERR_UNSUPPORTED;
+    if (table && (kv8 || (B * n > 64 && !part) || (D != 64 && D != 128 && !pad128))) return SJD_ERR_UNSUPPORTED;
     if (shards > 1 && (H % shards != 0 || H_kv % shards != 0)) return SJD_ERR_BAD_ARG;
     const int hps_q = shards > 1 ? H / shards : 0, hps_k = shards > 1 ? H_kv / shards : 0;     // heads per shard (0: one shared row)
     if (part && (B * n > 256 || n_chunks < 1)) return SJD_ERR_BAD_ARG;
@@ -876,19 +906,21 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
     const bool rows_ok = !(f2r_env && f2r_env[0] == '0');
     if (rows_ok && table && part && B * n > 64 && (H % 4) == 0 && (H_kv % 4) == 0) {      // (other head counts: the one-head table kernel below)
         const dim3 g2((B * n * ((H + 2 * H_kv) / 4) + 3) / 4);
-#define SJD_F2RT_CASE(DT_, D_)                                                                                                             \
+#define SJD_F2RT_CASE(DT_, D_, DS_)                                                                                                        \
         if (dtype == DT_ && D == D_) {                                                                                                     \
-            hipLaunchKernelGGL((f2_qknorm_rope_append_rows<DT_, D_, false, 4, false, true>), g2, block, 0, s, (unsigned short *)q_out,     \
+            hipLaunchKernelGGL((f2_qknorm_rope_append_rows<DT_, D_, false, 4, false, true, DS_>), g2, block, 0, s, (unsigned short *)q_out,     \
                                (unsigned short *)k_cache, (unsigned short *)v_cache, nullptr, nullptr, nullptr, nullptr, inv_freq,         \
                                (const long *)positions, B, n, H, H_kv, S_max, params, kv_len, part, n_chunks, prows, 1.0f, 1.0f,           \
                                rn ? rn->sumsq : nullptr, rn ? rn->slices : 0, rn ? 1.0f / (float)rn->hidden : 0.f, rn ? rn->eps : 0.f, 0,  \
                                0);                                                                                                         \
             return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;                                                              \
         }
-        SJD_F2RT_CASE(SJD_DTYPE_BF16, 128)
-        SJD_F2RT_CASE(SJD_DTYPE_F16, 128)
-        SJD_F2RT_CASE(SJD_DTYPE_BF16, 64)
-        SJD_F2RT_CASE(SJD_DTYPE_F16, 64)
+        SJD_F2RT_CASE(SJD_DTYPE_BF16, 128, 128)
+        SJD_F2RT_CASE(SJD_DTYPE_F16, 128, 128)
+        SJD_F2RT_CASE(SJD_DTYPE_BF16, 64, 64)
+        SJD_F2RT_CASE(SJD_DTYPE_F16, 64, 64)
+        SJD_F2RT_CASE(SJD_DTYPE_BF16, 100, 128)
+        SJD_F2RT_CASE(SJD_DTYPE_F16, 100, 128)
 #undef SJD_F2RT_CASE
         return SJD_ERR_UNSUPPORTED;
     }
@@ -916,19 +948,21 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
         return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;                                                                   \
     }
     if (table) {
-#define SJD_F2T_CASE(DT_, D_)                                                                                                              \
+#define SJD_F2T_CASE(DT_, D_, DS_)                                                                                                         \
         if (dtype == DT_ && D == D_) {                                                                                                     \
-            hipLaunchKernelGGL((f2_qknorm_rope_append<DT_, D_, false, true>), grid, block, 0, s, (const unsigned short *)qkv,              \
+            hipLaunchKernelGGL((f2_qknorm_rope_append<DT_, D_, false, true, DS_>), grid, block, 0, s, (const unsigned short *)qkv,              \
                                (unsigned short *)q_out, (unsigned short *)k_cache, (unsigned short *)v_cache, nullptr, nullptr, nullptr,   \
                                nullptr, inv_freq, (const long *)positions, B, n, H, H_kv, S_max, params, kv_len, part, n_chunks, prows,    \
                                1.0f, 1.0f, rn ? rn->sumsq : nullptr, rn ? rn->slices : 0, rn ? 1.0f / (float)rn->hidden : 0.f,             \
                                rn ? rn->eps : 0.f, 0, 0);                                                                                  \
             return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;                                                              \
         }
-        SJD_F2T_CASE(SJD_DTYPE_BF16, 128)
-        SJD_F2T_CASE(SJD_DTYPE_F16, 128)
-        SJD_F2T_CASE(SJD_DTYPE_BF16, 64)
-        SJD_F2T_CASE(SJD_DTYPE_F16, 64)
+        SJD_F2T_CASE(SJD_DTYPE_BF16, 128, 128)
+        SJD_F2T_CASE(SJD_DTYPE_F16, 128, 128)
+        SJD_F2T_CASE(SJD_DTYPE_BF16, 64, 64)
+        SJD_F2T_CASE(SJD_DTYPE_F16, 64, 64)
+        SJD_F2T_CASE(SJD_DTYPE_BF16, 100, 128)
+        SJD_F2T_CASE(SJD_DTYPE_F16, 100, 128)
 #undef SJD_F2T_CASE
         return SJD_ERR_UNSUPPORTED;
     }

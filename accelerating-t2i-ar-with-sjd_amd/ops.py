@@ -278,19 +278,29 @@ def colsplit_ok(B, n, H, H_kv, D, cache_dtype):
     return H == H_kv and D == 128 and n <= 16 and B * H <= 64 and cache_dtype in (torch.bfloat16, torch.float16, FP8)
 
 
-def draft_window_attention_colsplit(q, k_cache, v_cache, out, key_start, params, kv_len, kv_scale=(1.0, 1.0)):
-    """K1 without key splits: four workgroups per (batch, head) split the output columns, one launch, no workspace (see include/sjd_hip.h)."""
+def _k1_mode(head_dim, D):
+    """the K1 mode bit of a logical head dim: None or D = none; 100 at D = 128 = SJD_K1_HEAD_DIM_100 (16-bit caches)"""
+    if head_dim is None or head_dim == D:
+        return 0
+    if (head_dim, D) != (100, 128):
+        raise L.SjdLibraryError(f"K1 serves a logical head_dim of 100 stored 128 wide only, got {head_dim} at D = {D}")
+    return L.K1_HEAD_DIM_100
+
+
+def draft_window_attention_colsplit(q, k_cache, v_cache, out, key_start, params, kv_len, kv_scale=(1.0, 1.0), head_dim=None):
+    """K1 without key splits: four workgroups per (batch, head) split the output columns, one launch, no workspace (see include/sjd_hip.h).
+    head_dim: the logical head dim where it differs from the stored D (100 at D = 128: zero pad columns, softmax scale 1/sqrt(100))."""
     B, n, H, D = q.shape
     assert q.is_contiguous() and out.is_contiguous() and k_cache.is_contiguous() and v_cache.is_contiguous()
     assert key_start is None or (key_start.dtype == torch.int32 and key_start.is_cuda)
     if k_cache.dtype == FP8:
         L.check(L.load().sjd_draft_window_attention_fp8_colsplit(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), B, n, H, k_cache.shape[1], D,
-                                                                k_cache.shape[2], _dtype_code(q.dtype), float(kv_scale[0]), float(kv_scale[1]),
-                                                                _ptr(key_start), params.ptr if params is not None else None, int(kv_len),
-                                                                _stream()), "sjd_draft_window_attention_fp8_colsplit")
+                                                                k_cache.shape[2], _dtype_code(q.dtype) | _k1_mode(head_dim, D), float(kv_scale[0]),
+                                                                float(kv_scale[1]), _ptr(key_start), params.ptr if params is not None else None,
+                                                                int(kv_len), _stream()), "sjd_draft_window_attention_fp8_colsplit")
     else:
         L.check(L.load().sjd_draft_window_attention_colsplit(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), B, n, H, k_cache.shape[1], D,
-                                                            k_cache.shape[2], _dtype_code(q.dtype), _ptr(key_start),
+                                                            k_cache.shape[2], _dtype_code(q.dtype) | _k1_mode(head_dim, D), _ptr(key_start),
                                                             params.ptr if params is not None else None, int(kv_len), _stream()),
                 "sjd_draft_window_attention_colsplit")
 
@@ -300,24 +310,26 @@ def attention_workspace(B, H, n_rows, D, n_split, device):
     return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
 
 
-def draft_window_attention(q, k_cache, v_cache, out, key_start, params, kv_len, n_split, workspace, ev0=None, ev1=None, merged=None):
+def draft_window_attention(q, k_cache, v_cache, out, key_start, params, kv_len, n_split, workspace, ev0=None, ev1=None, merged=None, head_dim=None):
     """q/out [B,n,H,D]; caches [B,Hkv,S,D] already holding the window rows; key_start int32 [B] (device).
     ev0/ev1: optional raw hipEvent_t handles recorded around the k1_partial launch.  merged: one launch -- the key splits are merged by
-    the last of their workgroups to finish (same output bits); False: k1_partial + k1_combine, two launches."""
+    the last of their workgroups to finish (same output bits); False: k1_partial + k1_combine, two launches.
+    head_dim: the logical head dim where it differs from the stored D (see draft_window_attention_colsplit)."""
     B, n, H, D = q.shape
+    dcode = _dtype_code(q.dtype) | _k1_mode(head_dim, D)
     assert q.is_contiguous() and out.is_contiguous() and k_cache.is_contiguous() and v_cache.is_contiguous()
     assert key_start is None or (key_start.dtype == torch.int32 and key_start.is_cuda)
     need = L.load().sjd_attention_workspace_bytes(B, H, n, D, n_split)
     assert workspace.numel() * 4 >= need, "attention workspace too small"
     if (K1_MERGED_DEFAULT if merged is None else merged) and q.dtype != torch.float32:
         L.check(L.load_exp().sjd_draft_window_attention_merged(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), B, n, H,
-                                                          k_cache.shape[1], D, k_cache.shape[2], _dtype_code(q.dtype),
+                                                          k_cache.shape[1], D, k_cache.shape[2], dcode,
                                                           _ptr(key_start), params.ptr if params is not None else None,
                                                           int(kv_len), int(n_split), _ptr(workspace), _ptr(k1_tickets(B, k_cache.shape[1], n, q.device)),
                                                           _stream(), ev0, ev1), "sjd_draft_window_attention_merged")
         return
     L.check(L.load().sjd_draft_window_attention_ex(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), B, n, H,
-                                                  k_cache.shape[1], D, k_cache.shape[2], _dtype_code(q.dtype),
+                                                  k_cache.shape[1], D, k_cache.shape[2], dcode,
                                                   _ptr(key_start), params.ptr if params is not None else None,
                                                   int(kv_len), int(n_split), _ptr(workspace), _stream(), ev0, ev1),
             "sjd_draft_window_attention")
@@ -857,14 +869,16 @@ def _row_norm(row_norm):
 
 
 def qknorm_rope_append(qkv, k_cache, v_cache, qn_w, qn_b, kn_w, kn_b, inv_freq, positions, B, n, H, H_kv, D, params, kv_len,
-                       kv_scale=(1.0, 1.0), dtype=None, row_norm=None, qk_shards=1, rope_table=None):
+                       kv_scale=(1.0, 1.0), dtype=None, row_norm=None, qk_shards=1, rope_table=None, head_pad=None):
     """qkv [B*n, (H+2Hkv)*D] (tensor or G1 Partials) -> q [B,n,H,D]; k/v rows are written into k_cache/v_cache [B,Hkv,S,D].
     An fp8 cache (dtype FP8) receives fp8(x / scale) with kv_scale = (k, v); `dtype` = the activation dtype (needed with Partials
     into an fp8 cache, where no 16-bit tensor is around to tell).  row_norm = (sumsq, hidden, eps): the projection ran on the
     un-normalised residual stream with the norm gain folded into its weight; the row scale is applied here (folded-norm path).
     qk_shards = mp > 1: the QK-norm gains / biases are [mp, D] (model_parallel_size mp), head h of q uses row h // (H // mp), of k h // (Hkv // mp).
     rope_table: LlamaGen's interleaved 2-D rotary (SJD_F2_ROPE_TABLE) from an fp32 (cos, sin) table [S_rows >= S_max, D/2, 2], row p serving
-    position p; inv_freq is ignored then and the QK-norm arguments must be None."""
+    position p; inv_freq is ignored then and the QK-norm arguments must be None.
+    head_pad = 128 (SJD_F2_HEAD_PAD128; with rope_table and D = 100 only): the source heads are D = 100 wide, q comes back [B,n,H,128] and the
+    caches are [B,Hkv,S,128]; the pad columns of every written row are written as zeros."""
     t, part, nc = _part_args(qkv)
     assert (t is None or t.is_contiguous()) and positions.is_contiguous() and positions.dtype == torch.int64
     mode = 0
@@ -872,11 +886,16 @@ def qknorm_rope_append(qkv, k_cache, v_cache, qn_w, qn_b, kn_w, kn_b, inv_freq, 
         assert rope_table.dtype == torch.float32 and rope_table.is_contiguous() and rope_table.shape[1:] == (D // 2, 2)
         assert rope_table.shape[0] >= k_cache.shape[2], "the rotary table needs a row per cache position"
         inv_freq, mode = rope_table, L.F2_ROPE_TABLE
+    DS = D
+    if head_pad is not None and head_pad != D:
+        assert rope_table is not None and (D, head_pad) == (100, 128), "head_pad: head_dim 100 stored 128 wide, table rotary only"
+        assert k_cache.shape[3] == head_pad and v_cache.shape[3] == head_pad, "head_pad: the caches are [B, Hkv, S, 128]"
+        DS, mode = head_pad, mode | L.F2_HEAD_PAD128
     assert inv_freq.dtype == torch.float32 and inv_freq.is_contiguous()
     fp8 = k_cache.dtype == FP8
     act = dtype or (t.dtype if t is not None else k_cache.dtype)
     assert act in (torch.bfloat16, torch.float16)
-    q = torch.empty(B, n, H, D, dtype=act, device=k_cache.device)
+    q = torch.empty(B, n, H, DS, dtype=act, device=k_cache.device)
     L.check(L.load().sjd_qknorm_rope_append_ex(_ptr(t), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(qn_w), _ptr(qn_b), _ptr(kn_w),
                                               _ptr(kn_b), _ptr(inv_freq), _ptr(positions), B, n, H, H_kv, D, k_cache.shape[2],
                                               _dtype_code(act) | (int(qk_shards) << L.QKN_SHARDS_SHIFT if qk_shards > 1 else 0) | mode, int(fp8),
@@ -1096,9 +1115,19 @@ class HipWindowAttention:
         return self._ws
 
     def __call__(self, layer, q, k, v, cache, kv_len, key_start):
+        kc, vc = cache.k[layer], cache.v[layer]
+        if q.shape[3] == 100 and kc.shape[3] == 128:
+            # a head_dim-100 model on a cache stored 128 wide (LlamaGenBackbone.enable_fused(pad_head_dim=True)): zero pad columns in, K1 at
+            # D = 128 with the softmax scale of 100, the pad columns of the output (zeros) sliced off
+            if kc.dtype == FP8:
+                raise L.SjdLibraryError("HipWindowAttention: a padded head_dim 100 needs a 16-bit cache")
+            zp = lambda t: torch.nn.functional.pad(t, (0, 28))
+            return self._call(layer, zp(q), zp(k), zp(v), kc, vc, kv_len, key_start, 100)[..., :100]
+        return self._call(layer, q, k, v, kc, vc, kv_len, key_start, None)
+
+    def _call(self, layer, q, k, v, kc, vc, kv_len, key_start, head_dim):
         B, n, H, D = q.shape
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        kc, vc = cache.k[layer], cache.v[layer]
         self._resolve_split(B, kc.shape[1], n, H, kc.shape[2] * kc.shape[3] * kc.element_size() if kc.dtype == FP8 else None)
         if isinstance(key_start, torch.Tensor) and key_start.is_cuda and key_start.dtype == torch.int32:
             ks = key_start
@@ -1118,7 +1147,7 @@ class HipWindowAttention:
             return out
         kv_append(k, v, kc, vc, self.params, kv_host)
         if colsplit:
-            draft_window_attention_colsplit(q, kc, vc, out, ks, self.params, kv_host)
+            draft_window_attention_colsplit(q, kc, vc, out, ks, self.params, kv_host, head_dim=head_dim)
             return out
         ev0 = ev1 = None
         if self.profile_layer is not None and layer == self.profile_layer and n <= 32:
@@ -1135,13 +1164,16 @@ class HipWindowAttention:
                 kv_rows = int(kv_len) + n
             alg = 2 * B * Hkv * kv_rows * D * esz + B * n * H * D * esz
             self.profile_records.append((ev0, ev1, alg, kv_rows))
-        draft_window_attention(q, kc, vc, out, ks, self.params, kv_host, self.n_split, ws, ev0, ev1)
+        draft_window_attention(q, kc, vc, out, ks, self.params, kv_host, self.n_split, ws, ev0, ev1, head_dim=head_dim)
         return out
 
-    def attend(self, layer, q, cache, kv_len, key_start):
-        """K1 only: the window's K/V rows were already written into the cache (fused F2 path)."""
+    def attend(self, layer, q, cache, kv_len, key_start, head_dim=None):
+        """K1 only: the window's K/V rows were already written into the cache (fused F2 path).  head_dim: the model's head dim where q and
+        the cache are stored wider (100 in 128-wide rows with zero pad columns: SJD_K1_HEAD_DIM_100)."""
         B, n, H, D = q.shape
         kc, vc = cache.k[layer], cache.v[layer]
+        if head_dim is not None and head_dim != D and kc.dtype == FP8:
+            raise L.SjdLibraryError("HipWindowAttention: a padded head_dim 100 needs a 16-bit cache")
         kv_host = 0 if self.params is not None else int(kv_len)
         # (the split workspace is allocated whatever the regime: its first allocation bumps ws_version, which makes the engines drop every
         #  captured graph -- that must happen before the first capture, not at the crossover in the middle of an image; ADVICE r4)
@@ -1149,14 +1181,14 @@ class HipWindowAttention:
         ws = self._workspace(B, H, n, D, q.device)
         if self.regime == "colsplit" and colsplit_ok(B, n, H, kc.shape[1], D, kc.dtype):
             out = torch.empty_like(q)
-            draft_window_attention_colsplit(q, kc, vc, out, key_start, self.params, kv_host, self.scale_of(layer))
+            draft_window_attention_colsplit(q, kc, vc, out, key_start, self.params, kv_host, self.scale_of(layer), head_dim=head_dim)
             return out
         out = torch.empty_like(q)
         if kc.dtype == FP8:
             sk, sv = self.scale_of(layer)
             draft_window_attention_fp8(q, kc, vc, out, sk, sv, key_start, self.params, kv_host, self.n_split, ws)
         else:
-            draft_window_attention(q, kc, vc, out, key_start, self.params, kv_host, self.n_split, ws)
+            draft_window_attention(q, kc, vc, out, key_start, self.params, kv_host, self.n_split, ws, head_dim=head_dim)
         return out
 
     def profile_summary(self):

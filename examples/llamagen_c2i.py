@@ -74,7 +74,8 @@ def main():
         synthetic.fill_state_dict_device(gpt, seed=0, embed_token_scale=0.5)
     if a.fused:
         rows = (a.prompts_per_forward or len(a.class_id)) * 2 * a.window          # prompts x CFG pair x window rows per forward
-        gpt.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256))
+        # (GPT-3B's 32 heads are 100 wide: the kernels store them 128 wide with zero pad columns, which the backbone does on request only)
+        gpt.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), pad_head_dim=gpt.head_dim == 100)
     jac = dict(jacobi_loop_interval_l=1, jacobi_loop_interval_r=latent ** 2 - a.window - 2, max_num_new_tokens=a.window,
                guidance_scale=a.cfg_scale, seed=a.seed, multi_token_init_scheme="random", do_cfg=True, image_top_k=a.top_k,
                text_top_k=10, prefix_token_sampler_scheme="speculative_jacobi")

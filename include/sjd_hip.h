@@ -54,10 +54,23 @@ extern "C" {
  *                         from split-K planes; 64 < B*n <= 256 (version 103) from split-K planes only (`part` != NULL) -- a dense source
  *                         with more than 64 rows stays SJD_ERR_UNSUPPORTED.  Above 64 rows a wave serves four consecutive heads of one
  *                         kind when H and H_kv are multiples of 4 (one head per wave otherwise, or with SJD_F2_ROWS=0 in the
- *                         environment); both forms write the same bits. */
+ *                         environment); both forms write the same bits.
+ *   SJD_F2_HEAD_PAD128    sjd_qknorm_rope_append / _ex, only together with SJD_F2_ROPE_TABLE and D = 100 (LlamaGen GPT-3B: 32 heads of 100;
+ *                         SJD_ERR_UNSUPPORTED otherwise): the SOURCE heads are 100 wide -- a dense qkv [T, (H + 2 H_kv) * 100] or split-K
+ *                         planes with (H + 2 H_kv) * 100 columns -- and the table is [S_rows, 50, 2]; the DESTINATIONS are 128 wide:
+ *                         q_out [B, n, H, 128], the caches [B, H_kv, S_max, 128].  Columns 0..99 of every written row are the bits the
+ *                         table mode writes at a native D; columns 100..127 of every written row (q, k and v) are written as zeros, so
+ *                         nothing depends on what the buffers held.  Row limits and sources as for SJD_F2_ROPE_TABLE.
+ * A mode bit of the 16-bit draft-window attention entry points (sjd_draft_window_attention / _ex / _colsplit):
+ *   SJD_K1_HEAD_DIM_100   heads STORED 128 wide (D = 128) whose columns 100..127 are zero in q, K and V: the softmax scale is 1/sqrt(100),
+ *                         the logical head dim, in place of 1/sqrt(D); the pad columns add nothing to q k^T and the output's pad columns
+ *                         are zero.  Valid with D = 128, H == H_kv and dtype bf16 / fp16 only -- SJD_ERR_UNSUPPORTED otherwise, from the
+ *                         fp32 variant, from the fp8-cache entry points, and from the A/B kernel forms chosen by environment switches. */
 #define SJD_DTYPE_MASK 0xff
 #define SJD_F1_POST_NORM 0x100
 #define SJD_F2_ROPE_TABLE 0x200
+#define SJD_F2_HEAD_PAD128 0x400
+#define SJD_K1_HEAD_DIM_100 0x800
 #define SJD_QKN_SHARDS_SHIFT 16
 #define SJD_QKN_SHARDS_MASK (0xff << SJD_QKN_SHARDS_SHIFT)
 #define SJD_QKN_SHARDS(mp) ((int)(mp) << SJD_QKN_SHARDS_SHIFT)

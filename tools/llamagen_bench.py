@@ -14,6 +14,9 @@
             the fraction of 8 TB/s each step streams; then F2's table rotary at 256 rows, GPT-XL shape: four heads per wave against one
             (SJD_F2_ROWS=0), us per launch from a hipGraph of back-to-back launches.
   --step    the fused step alone (one preset, --steps timed iterations): what the rocprofv3 by-shape table is taken from.
+  --fused3b GPT-3B c2i 384px (24 layers, 32 heads of 100 stored 128 wide: enable_fused(pad_head_dim=True)), window 16, CFG, bf16: fused ms per SJD
+            step over --rounds rounds (median), the packed bytes a step streams and their fraction of 8 TB/s.  No ATen leg: un-fused GPT-3B does
+            not run on K1 (no head_dim-100 instantiation), so there is nothing to alternate with.
 """
 import argparse
 import json
@@ -28,8 +31,9 @@ import torch  # noqa: E402
 import sjd_amd.backbones as BB  # noqa: E402
 import sjd_amd.ops as ops  # noqa: E402
 
-PRESETS = {"GPT-B": (12, 12, 768), "GPT-L": (24, 16, 1024), "GPT-XL": (36, 20, 1280), "GPT-XXL": (48, 24, 1536)}
+PRESETS = {"GPT-B": (12, 12, 768), "GPT-L": (24, 16, 1024), "GPT-XL": (36, 20, 1280), "GPT-XXL": (48, 24, 1536), "GPT-3B": (24, 32, 3200)}
 CONFIGS = [("GPT-B", "c2i", 256), ("GPT-XL", "t2i", 512), ("GPT-XXL", "t2i", 512)]
+CONFIG_3B = ("GPT-3B", "c2i", 384)        # head_dim 100: fused only, with pad_head_dim=True (--fused3b)
 PEAK_TBPS = 8.0
 CAP_PAD = 7            # left-padded caption rows of the t2i runs (key_start)
 
@@ -68,17 +72,23 @@ def sweep(args):
     D = a.dim // a.n_head
     ff = int(2 * (4 * a.dim) / 3)
     inter = ff if ff % a.multiple_of == 0 else ff + a.multiple_of - (ff % a.multiple_of)
-    shapes = dict(qkv=(3 * a.n_head * D, a.dim), o=(a.dim, a.dim), gate_up=(2 * inter, a.dim), down=(a.dim, inter), head=(a.vocab_size, a.dim))
+    DS = 128 if D == 100 else D           # (a head_dim of 100 is stored 128 wide: the o projection's K is H * 128, zero columns at the pad positions)
+    shapes = dict(qkv=(3 * a.n_head * D, a.dim), o=(a.dim, a.n_head * DS), gate_up=(2 * inter, a.dim), down=(a.dim, inter), head=(a.vocab_size, a.dim))
+    # split-K chunks: the sets' 128..1280, and for GPT-3B the multiples of 16 that leave at most eight planes of K = 3200 / 4096 / 8704
+    kcs = (128, 256, 320, 512, 640, 1280) if D != 100 else (400, 512, 640, 800, 1088, 1280, 1600, 2176)
     dev = torch.device("cuda:0")
     M = args.rows
+    max_planes = 8 if (M > 64 or D == 100) else None
     g = torch.Generator(device=dev).manual_seed(1)
     best = {}
     for name, (N, K) in shapes.items():
         copies = max(2, -(-768 * 2**20 // (N * K * 2)))        # > 0.75 GB in flight: past the 256 MB Infinity Cache
         ws = [(torch.randn(N, K, generator=g, device=dev) / K ** 0.5).to(torch.bfloat16) for _ in range(copies)]
         x = torch.randn(M, K, generator=g, device=dev).to(torch.bfloat16)
-        for kc in (128, 256, 320, 512, 640, 1280):
-            if kc > K or (M > 64 and -(-K // kc) > 8):       # (the wider sets: at most eight split-K planes, the limit the 32-row set observes)
+        for kc in kcs:
+            if kc > K or (max_planes and name != "head" and -(-K // kc) > max_planes):       # (the wider sets and GPT-3B: at most eight split-K planes, the limit the 32-row set observes)
+                continue
+            if kc > (2560 if M <= 32 else 1280) and M <= 64:       # (the staged activation chunk must fit in LDS)
                 continue
             for sm in (True, False):
                 packed = [ops.pack_weight(w, kc, sm) for w in ws]
@@ -320,8 +330,14 @@ def batch(args):
 
 def step(args):
     dev = torch.device("cuda:0")
-    preset, mt, size = next(c for c in CONFIGS if c[0] == args.preset)
+    preset, mt, size = next(c for c in CONFIGS + [CONFIG_3B] if c[0] == args.preset)
     m = _make(preset, mt, size, dev, DTYPES[args.dtype])
+    if preset == "GPT-3B":
+        assert args.prompts == 1, "GPT-3B (head_dim 100 stored 128 wide) is served at one prompt per forward"
+        m.enable_fused(ops, gemm="sjd", pad_head_dim=True)
+        _, st, _ = _Leg(m, args.window, dev).decode(args.warmup, args.steps)
+        print(json.dumps(dict(preset=preset, ms_per_step=round(1e3 * st.seconds / max(1, st.timed_nfe), 3), timed_steps=st.timed_nfe)), flush=True)
+        return
     if args.prompts > 1:
         rows = args.prompts * 2 * args.window
         m.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), untuned_fp16=True)
@@ -334,12 +350,43 @@ def step(args):
     print(json.dumps(dict(preset=preset, ms_per_step=round(1e3 * st.seconds / max(1, st.timed_nfe), 3), timed_steps=st.timed_nfe)), flush=True)
 
 
+def fused3b(args):
+    dev = torch.device("cuda:0")
+    preset, mt, size = CONFIG_3B
+    m = _make(preset, mt, size, dev)
+    if args.cfg_from:            # launch shapes from the `best` lines of a --sweep output instead of LlamaGenBackbone.G1_CFG_LLAMAGEN_3B (a caller's set wins)
+        best = {r["best"]: tuple(r["cfg"]) for r in map(json.loads, open(args.cfg_from)) if "best" in r}
+        m.G1_CFG = {k: best[k] for k in ("qkv", "o", "gate_up", "down")}
+        m.HEAD_CFG = best["head"]
+    m.enable_fused(ops, gemm="sjd", pad_head_dim=True)
+    leg = _Leg(m, args.window, dev)
+    ms = []
+    for _ in range(args.rounds):
+        _, st, _ = leg.decode(args.warmup, args.steps)
+        ms.append(1e3 * st.seconds / max(1, st.timed_nfe))
+    seq, st, wall = leg.decode()
+    med, nbytes = statistics.median(ms), m.packed_bytes()
+    rec = dict(preset=preset, model_type=mt, image_size=size, window=args.window, cfg=True, dtype="bf16", layers=m.n_layers, head_dim=m.head_dim,
+               head_dim_stored=m.cache.k.shape[-1], prompts_per_forward=1, ms_per_step=dict(fused=round(med, 3)),
+               ms_per_step_rounds=dict(fused=[round(x, 3) for x in ms]), aten=None,
+               aten_note="no ATen leg: un-fused GPT-3B does not run on K1 (head_dim 100 has no instantiation)",
+               whole_image=dict(tokens=len(seq) - 1, nfe=st.nfe, seconds=round(wall, 3), tokens_per_s=round((len(seq) - 1) / wall, 1)),
+               packed_gb_per_step=round(nbytes / 1e9, 3), fused_fraction_of_8tbps=round(nbytes / (med * 1e-3) / (PEAK_TBPS * 1e12), 3),
+               g1_cfg=m.G1_CFG, head_cfg=list(m.HEAD_CFG))
+    print(json.dumps(rec), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump([rec], f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--ab", action="store_true")
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--batch", action="store_true")
+    ap.add_argument("--fused3b", action="store_true")
+    ap.add_argument("--cfg-from", default="", help="--fused3b: a --sweep output whose `best` lines give the G1 launch shapes")
     ap.add_argument("--prompts", type=int, default=1, help="--step: prompts per forward (SJDBatchEngine above 1)")
     ap.add_argument("--preset", default="GPT-XL", choices=list(PRESETS))
     ap.add_argument("--only", default="")
@@ -360,6 +407,8 @@ def main():
         batch(args)
     if args.step:
         step(args)
+    if args.fused3b:
+        fused3b(args)
 
 
 if __name__ == "__main__":
