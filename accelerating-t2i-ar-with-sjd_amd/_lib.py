@@ -14,10 +14,11 @@ F1_POST_NORM = 0x100
 F2_ROPE_TABLE = 0x200
 F2_HEAD_PAD128 = 0x400         # with F2_ROPE_TABLE and D = 100: 100-wide source heads, 128-wide q / cache rows, pad columns written as zeros
 K1_HEAD_DIM_100 = 0x800        # the 16-bit K1 entry points: D = 128 storage with zero pad columns, softmax scale 1/sqrt(100)
+F2_ONE_HEAD = 0x1000           # F2 above 64 rows of split-K planes: one head per wave in place of four (same bits; the parity tests compare them)
 QKN_SHARDS_SHIFT = 16
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SO_PATH = os.environ.get("SJD_HIP_LIB") or os.path.join(_HERE, "libsjd_hip.so")      # SJD_HIP_LIB: an instrumented build (tools/phase_trace.py)
+SO_PATH = os.environ.get("SJD_HIP_LIB") or os.path.join(_HERE, "libsjd_hip.so")      # SJD_HIP_LIB: an instrumented build (tools/phase_trace.py), or EXP_SO_PATH where a test compares against an alternative form
 
 
 class RowRule(ctypes.Structure):

@@ -22,10 +22,10 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include <math.h>
-#include <stdlib.h>
 
 #include "../../include/sjd_hip.h"
 #include "sjd_coherent.h"
+#include "sjd_switches.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -498,6 +498,7 @@ __global__ __launch_bounds__(64 * NW) void k1_partial(
 #endif
 }
 
+#ifdef SJD_EXPERIMENTAL        // the round-3 shared-tile kernel (replaced by the ring kernel; SJD_K1_RING=0, sjd_switches.h): libsjd_hip_exp.so only
 // ------------------------------------------------------------------------------------------------ K1 (shared tiles)
 // Grouped-query attention and/or several 16-row chunks (Emu3: H/H_kv = 4, draft window 32): in k1_partial every (head, chunk) pair
 // streams the same K/V tiles by itself, 8 times the bytes through L2/L1.  Here ONE workgroup owns a (batch, kv head, key split) and
@@ -506,7 +507,7 @@ __global__ __launch_bounds__(64 * NW) void k1_partial(
 // read back transposed).  The next tile's loads are in flight while the current one is consumed; one barrier per tile.
 // Same split / workspace layout as k1_partial (the waves of a pair cover all tiles of the split, so no LDS merge), k1_combine
 // is unchanged.
-// NSET key tiles travel at a time: 3.  Six (SJD_K1_SHARED_SETS=6; a register set is only 2 * MAXP 16-byte pieces) measured EQUAL in round 3
+// NSET key tiles travel at a time: 3.  Six (a register set is only 2 * MAXP 16-byte pieces) measured EQUAL in round 3
 // -- 17.2 / 26.4 / 36.7 us per layer at kv 1024 / 4096 / 8192 against 16.9 / 25.5 / 36.3 (Emu3 shape, 16 splits, with k1_combine) -- so
 // the bytes in flight are not what bounds this kernel: a tile costs 1.4-1.9 us whatever travels behind it (LDS fragment reads of eight
 // waves, the dependent QK^T -> softmax -> PV chain of each, one workgroup barrier), profiles/r3_k1_microbench.jsonl.
@@ -710,14 +711,13 @@ __global__ __launch_bounds__(64 * NWV) void k1_partial_shared(
 #endif
     (void)nw;
 }
+#endif  // SJD_EXPERIMENTAL
 
-#ifndef SJD_K1_DSPLIT_DEFAULT
-#define SJD_K1_DSPLIT_DEFAULT 0
-#endif
 #include "sjd_attention_ring.h"
 
 // RS (round 4 experiment): row blocks per 16-row chunk = workgroups per (batch, head, chunk).  RS = 2 gives Emu3's shape 256 workgroups instead
-// of 128 (8 rows x 128 d each, one float4 per thread and split; the arithmetic per element is unchanged) -- and measured slower, see the launcher.
+// of 128 (8 rows x 128 d each, one float4 per thread and split; the arithmetic per element is unchanged) -- and measured SLOWER (Emu3 pair 22.2 -> 24.8 us, Lumina 14.1 -> 14.8 us, profiles/r4_k1_combine_rs.txt: the launch is bound by its cold
+// start and its one round trip, not by the CUs it covers), so RS = 1 is the only instantiation.
 template <int DT, int D, int RS = 1>
 __global__ __launch_bounds__(256) void k1_combine(const float *__restrict__ ws_o, const float *__restrict__ ws_ml,
                                                  unsigned short *__restrict__ out, int n_rows, int H, int n_split, int n_chunks,
@@ -1614,86 +1614,75 @@ extern "C" int64_t sjd_attention_workspace_bytes(int B, int H, int n_rows, int D
     return (int64_t)B * H * n_chunks * n_split * K1_ROWS * (D + 2) * (int64_t)sizeof(float);
 }
 
-// waves per k1_partial workgroup (SJD_K1_WAVES=4|8, read once).  8 = two waves per SIMD, twice the key tiles in flight per CU, the eight
-// key-parts merged in LDS: k1_partial + k1_combine per layer 12.5 / 16.0 / 19.7 / 26.2 us at kv_len 64 / 448 / 1216 / 2368 against
-// 13.2 / 16.4 / 21.7 / 28.4 us with 4 waves (profiles/r2_k1_waves_splits.jsonl; more splits lose either way).
-static int k1_waves()
+// what follows K1's partial launch, over 16-bit and fp8 caches alike: nothing when the partial kernel wrote the output itself (one key split,
+// or the splits merged by their last workgroup), else k1_combine.  ev1 closes the partial kernel's interval (sjd_draft_window_attention_ex).
+template <int DT, int D>
+static int k1_finish(bool out_written, const float *ws_o, const float *ws_ml, void *out, int B, int n_rows, int H, int n_chunks, int n_split,
+                     const int32_t *key_start, const sjd_iter_params *params, int kv_len, hipStream_t stream, hipEvent_t ev1 = nullptr)
 {
-    static const int w = [] { const char *e = getenv("SJD_K1_WAVES"); return (e && atoi(e) == 4) ? 4 : 8; }();
-    return w;
+    if (ev1) (void)hipEventRecord(ev1, stream);
+    if (hipGetLastError() != hipSuccess) return SJD_ERR_LAUNCH;
+    if (out_written) return SJD_OK;
+    hipLaunchKernelGGL((k1_combine<DT, D>), dim3(n_chunks, H, B), dim3(256), 0, stream, ws_o, ws_ml, (unsigned short *)out, n_rows, H,
+                       n_split, n_chunks, params, key_start, kv_len);
+    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
 }
 
-// DL: the logical head dim of the softmax scale (SJD_K1_HEAD_DIM_100: D = 128 storage, DL = 100).  Only the forms the product dispatch picks
-// carry it -- k1_dsplit, k1_partial (+ k1_combine, which has no scale of its own) and the four-slot ring kernel; every A/B form selected by an
-// environment switch declines with SJD_ERR_UNSUPPORTED, so no launch ever runs with 1/sqrt(128) under the bit.
+// One ladder: the column split (k1_dsplit, chosen by the colsplit entry points) -> the LDS-DMA ring kernel for the shapes whose rows share
+// key tiles (8 or 4 (head, chunk) pairs; four slots = three tiles of 16 KiB in flight per workgroup, profiles/r4_k1_ring_halves.txt) ->
+// k1_partial with eight waves (two per SIMD, the eight key-parts merged in LDS: profiles/r2_k1_waves_splits.jsonl), then k1_finish.
+// DL: the logical head dim of the softmax scale (SJD_K1_HEAD_DIM_100: D = 128 storage, DL = 100), passed through to every kernel.
+// The experimental library keeps two alternative forms that tests compare against (sjd_switches.h).
 template <int DT, int D, int DL = D>
 static int launch_attention(const void *q, const void *kc, const void *vc, void *out, int B, int n_rows, int H, int H_kv, int S_max,
                             const int32_t *key_start, const sjd_iter_params *params, int kv_len, int n_split, void *workspace,
                             hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, unsigned *ticket = nullptr, bool colsplit = false)
 {
+    static_assert(DL == D || D == 128, "a logical head dim is served at storage D = 128 only");
     const int n_chunks = (n_rows + K1_ROWS - 1) / K1_ROWS;
     float *ws_o = (float *)workspace;
     float *ws_ml = ws_o + (size_t)B * H * n_chunks * n_split * K1_ROWS * D;
     if (ev0) (void)hipEventRecord(ev0, stream);
     const int pairs = (H / H_kv) * n_chunks;           // (q head of a group, row chunk) pairs that read the same K/V tiles
-    const bool shared = D == 128 && (pairs == 4 || pairs == 8) && (H / H_kv > 1 || n_chunks > 1) && !getenv("SJD_K1_NO_SHARED");
-    // a single key split needs no combine: k1_partial normalises and writes the 16-bit output directly (SJD_K1_NO_DIRECT=1: tuning aid)
-    static const bool no_direct = getenv("SJD_K1_NO_DIRECT") != nullptr;
-    unsigned short *direct = (!shared && n_split == 1 && !no_direct) ? (unsigned short *)out : nullptr;
-    // round 3: the splits are merged by the last of their workgroups to finish (k1_merge_publish): no k1_combine launch (SJD_K1_NO_MERGE=1:
-    // the two-kernel form, A/B).  `ticket`: one zero-initialised uint32 per (batch, kv head, chunk), handed over by the caller
-    // (sjd_draft_window_attention_merged); they re-arm themselves.
-    static const bool no_merge = getenv("SJD_K1_NO_MERGE") != nullptr;
-    unsigned short *merge_out = (ticket && !shared && !direct && !no_merge) ? (unsigned short *)out : nullptr;
-    // round 4: the shared-tile shapes run on the LDS-DMA ring kernel (sjd_attention_ring.h); SJD_K1_RING=0: k1_partial_shared (A/B),
-    // SJD_K1_RING_SLOTS=4|6|8: ring depth (default 4 = three tiles of 16 KiB in flight per workgroup: measured best, profiles/r4_k1_ring_halves.txt --
-    // the DMA pipeline alone runs at the HBM rate with any depth, a deeper ring only delays the first tile)
-    static const bool ring = [] { const char *e = getenv("SJD_K1_RING"); return !(e && e[0] == '0'); }();
-    static const int ring_slots = [] { const char *e = getenv("SJD_K1_RING_SLOTS"); const int v = e ? atoi(e) : 4; return (v == 6 || v == 8) ? v : 4; }();
-    // round 4: the multi-head window without key splits -- four workgroups per (batch, head) split the OUTPUT COLUMNS (k1_dsplit): one
-    // launch, no workspace, no combine.  SJD_K1_DSPLIT=0|1 (A/B aid).
-    static const int dsplit = [] { const char *e = getenv("SJD_K1_DSPLIT"); return e ? atoi(e) : SJD_K1_DSPLIT_DEFAULT; }();
+    const bool shared = D == 128 && (pairs == 4 || pairs == 8) && (H / H_kv > 1 || n_chunks > 1);
+    // a single key split needs no combine: k1_partial normalises and writes the 16-bit output directly
+    bool one_split_direct = n_split == 1;
+#ifdef SJD_EXPERIMENTAL
+    if (sjd_switches::get().k1_no_direct) one_split_direct = false;
+#endif
+    unsigned short *direct = (!shared && one_split_direct) ? (unsigned short *)out : nullptr;
+    // round 3: the splits are merged by the last of their workgroups to finish (k1_merge_publish): no k1_combine launch.  `ticket`: one
+    // zero-initialised uint32 per (batch, kv head, chunk), handed over by the caller (sjd_draft_window_attention_merged); they re-arm themselves.
+    unsigned short *merge_out = (ticket && !shared && !direct) ? (unsigned short *)out : nullptr;
     if (colsplit && !(D == 128 && H == H_kv)) return SJD_ERR_UNSUPPORTED;
-    if constexpr (DL != D) {
-        static_assert(D == 128, "a logical head dim is served at storage D = 128 only");
-        if (H != H_kv) return SJD_ERR_UNSUPPORTED;
-    }
-    if ((colsplit || (!shared && dsplit)) && D == 128 && H == H_kv) {
-        if constexpr (D == 128) {
-            static const int pf = [] { const char *e = getenv("SJD_K1_DSPLIT_PF"); return e ? atoi(e) : 0; }();      // (0: one tile ahead; 3 / 4: tiles in flight per wave)
-            if constexpr (DL != D) {
-                if (pf == 9 || pf == 4 || pf == 3) return SJD_ERR_UNSUPPORTED;
-                hipLaunchKernelGGL((k1_dsplit<DT, D, 8, 4, DL>), dim3(4 * n_chunks * H * B), dim3(512), 0, stream, (const unsigned short *)q,
-                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, (unsigned short *)out, n_rows, H, H_kv,
-                                   S_max, kv_len, n_chunks, B);
-            } else
-            if (pf == 9) {        // (9: the column split over an LDS-DMA ring of full key rows)
-                const size_t lds = (size_t)16 * (K1_KT * D * 2 + K1_KT * (D / 4) * 2);
-                (void)hipFuncSetAttribute((const void *)k1_dsplit_ring<DT, D, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                hipLaunchKernelGGL((k1_dsplit_ring<DT, D, 4>), dim3(4 * n_chunks * H * B), dim3(512), lds, stream, (const unsigned short *)q,
-                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, (unsigned short *)out, n_rows, H, H_kv,
-                                   S_max, kv_len, n_chunks, B);
-            } else
-            if (pf == 4)
-                hipLaunchKernelGGL((k1_dsplit_pf<DT, D, 8, 4, 4>), dim3(4 * n_chunks * H * B), dim3(512), 0, stream, (const unsigned short *)q,
-                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, (unsigned short *)out, n_rows, H, H_kv,
-                                   S_max, kv_len, n_chunks, B);
-            else if (pf == 3)
-                hipLaunchKernelGGL((k1_dsplit_pf<DT, D, 8, 4, 3>), dim3(4 * n_chunks * H * B), dim3(512), 0, stream, (const unsigned short *)q,
-                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, (unsigned short *)out, n_rows, H, H_kv,
-                                   S_max, kv_len, n_chunks, B);
-            else
-            hipLaunchKernelGGL((k1_dsplit<DT, D, 8, 4>), dim3(4 * n_chunks * H * B), dim3(512), 0, stream, (const unsigned short *)q,
+    if (DL != D && H != H_kv) return SJD_ERR_UNSUPPORTED;
+    if constexpr (D == 128) {
+        // round 4: the multi-head window without key splits -- four workgroups per (batch, head) split the OUTPUT COLUMNS (k1_dsplit): one
+        // launch, no workspace, no combine
+        if (colsplit) {
+            hipLaunchKernelGGL((k1_dsplit<DT, D, 8, 4, DL>), dim3(4 * n_chunks * H * B), dim3(512), 0, stream, (const unsigned short *)q,
                                (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, (unsigned short *)out, n_rows, H, H_kv,
                                S_max, kv_len, n_chunks, B);
             if (ev1) (void)hipEventRecord(ev1, stream);
             return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
         }
-    }
-    if constexpr (DL != D) {
         if (shared) {
-            if (!ring || ring_slots != 4 || getenv("SJD_K1_RING_HALVES")) return SJD_ERR_UNSUPPORTED;
-            constexpr size_t lds4 = (size_t)4 * 2 * K1_KT * D * 2 + (size_t)4 * K1_ROWS * D * 2, lds8 = (size_t)4 * 2 * K1_KT * D * 2 + (size_t)8 * K1_ROWS * D * 2;
+#ifdef SJD_EXPERIMENTAL        // SJD_K1_RING=0: the round-3 shared-tile kernel the ring kernel replaced (its blob-array test runs it)
+            if (!sjd_switches::get().k1_ring) {
+                if constexpr (DL != D) return SJD_ERR_UNSUPPORTED;
+                else if (pairs == 8)
+                    hipLaunchKernelGGL((k1_partial_shared<DT, D, 8, 3>), dim3(n_split, H_kv, B), dim3(512), 0, stream, (const unsigned short *)q,
+                                       (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, n_rows, H, H_kv, S_max,
+                                       kv_len, n_split, n_chunks);
+                else
+                    hipLaunchKernelGGL((k1_partial_shared<DT, D, 4, 3>), dim3(n_split, H_kv, B), dim3(256), 0, stream, (const unsigned short *)q,
+                                       (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, n_rows, H, H_kv, S_max,
+                                       kv_len, n_split, n_chunks);
+                return k1_finish<DT, D>(false, ws_o, ws_ml, out, B, n_rows, H, n_chunks, n_split, key_start, params, kv_len, stream, ev1);
+            }
+#endif
+            // round 4: the LDS-DMA ring kernel (sjd_attention_ring.h); its LDS is the ring of four slots, then the waves' Q rows
+            constexpr size_t ring = (size_t)4 * 2 * K1_KT * D * 2, lds8 = ring + (size_t)8 * K1_ROWS * D * 2, lds4 = ring + (size_t)4 * K1_ROWS * D * 2;
             if (pairs == 8) {
                 (void)hipFuncSetAttribute((const void *)k1_partial_ring<DT, D, 8, 4, DL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
                 hipLaunchKernelGGL((k1_partial_ring<DT, D, 8, 4, DL>), dim3(n_split, H_kv, B), dim3(512), lds8, stream, (const unsigned short *)q,
@@ -1705,79 +1694,13 @@ static int launch_attention(const void *q, const void *kc, const void *vc, void 
                                    (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, n_rows, H, H_kv, S_max,
                                    kv_len, n_split, n_chunks, B);
             }
-        } else if (k1_waves() == 8)
-            hipLaunchKernelGGL((k1_partial<DT, D, 8, DL>), dim3(n_chunks * n_split, H_kv, B), dim3(512), 0, stream, (const unsigned short *)q,
-                               (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, direct, n_rows, H, H_kv, S_max,
-                               kv_len, n_split, n_chunks, merge_out, ticket);
-        else
-            hipLaunchKernelGGL((k1_partial<DT, D, 4, DL>), dim3(n_chunks * n_split, H_kv, B), dim3(256), 0, stream, (const unsigned short *)q,
-                               (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, direct, n_rows, H, H_kv, S_max,
-                               kv_len, n_split, n_chunks, merge_out, ticket);
-    } else
-    if (shared && ring) {
-        if constexpr (D == 128) {
-#define SJD_K1R_LAUNCH(NWV_, R_) do {                                                                                                        \
-            const size_t lds = (size_t)(R_) * 2 * K1_KT * D * 2 + (size_t)(NWV_) * K1_ROWS * D * 2;                                          \
-            (void)hipFuncSetAttribute((const void *)k1_partial_ring<DT, D, NWV_, R_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k1_partial_ring<DT, D, NWV_, R_>), dim3(n_split, H_kv, B), dim3(64 * NWV_), lds, stream, (const unsigned short *)q, \
-                               (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, n_rows, H, H_kv, S_max,  \
-                               kv_len, n_split, n_chunks, B); } while (0)
-            static const bool halves = getenv("SJD_K1_RING_HALVES") != nullptr;       // (experiment: two 4-wave workgroups per (batch, kv head, split))
-            if (pairs == 8 && halves) {
-                const size_t lds = (size_t)4 * 2 * K1_KT * D * 2 + (size_t)4 * K1_ROWS * D * 2;
-                (void)hipFuncSetAttribute((const void *)k1_partial_ring<DT, D, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                hipLaunchKernelGGL((k1_partial_ring<DT, D, 4, 4>), dim3(2 * n_split, H_kv, B), dim3(256), lds, stream, (const unsigned short *)q,
-                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, n_rows, H, H_kv, S_max,
-                                   kv_len, n_split, n_chunks, B, 2);
-            } else
-            if (pairs == 8) { if (ring_slots == 4) SJD_K1R_LAUNCH(8, 4); else if (ring_slots == 8) SJD_K1R_LAUNCH(8, 8); else SJD_K1R_LAUNCH(8, 6); }
-            else { if (ring_slots == 4) SJD_K1R_LAUNCH(4, 4); else if (ring_slots == 8) SJD_K1R_LAUNCH(4, 8); else SJD_K1R_LAUNCH(4, 6); }
-#undef SJD_K1R_LAUNCH
-        }
-    } else if (shared) {
-        if constexpr (D == 128) {
-            static const bool three = [] { const char *e = getenv("SJD_K1_SHARED_SETS"); return !(e && atoi(e) == 6); }();      // 6: the deeper pipeline (A/B, measured equal)
-            if (pairs == 8 && three)
-                hipLaunchKernelGGL((k1_partial_shared<DT, D, 8, 3>), dim3(n_split, H_kv, B), dim3(512), 0, stream, (const unsigned short *)q,
-                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, n_rows, H, H_kv, S_max,
-                                   kv_len, n_split, n_chunks);
-            else if (pairs == 8)
-                hipLaunchKernelGGL((k1_partial_shared<DT, D, 8, 6>), dim3(n_split, H_kv, B), dim3(512), 0, stream, (const unsigned short *)q,
-                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, n_rows, H, H_kv, S_max,
-                                   kv_len, n_split, n_chunks);
-            else if (three)
-                hipLaunchKernelGGL((k1_partial_shared<DT, D, 4, 3>), dim3(n_split, H_kv, B), dim3(256), 0, stream, (const unsigned short *)q,
-                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, n_rows, H, H_kv, S_max,
-                                   kv_len, n_split, n_chunks);
-            else
-                hipLaunchKernelGGL((k1_partial_shared<DT, D, 4, 6>), dim3(n_split, H_kv, B), dim3(256), 0, stream, (const unsigned short *)q,
-                                   (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, n_rows, H, H_kv, S_max,
-                                   kv_len, n_split, n_chunks);
-        }
-    } else if (k1_waves() == 8)
-        hipLaunchKernelGGL((k1_partial<DT, D, 8>), dim3(n_chunks * n_split, H_kv, B), dim3(512), 0, stream, (const unsigned short *)q,
-                           (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, direct, n_rows, H, H_kv, S_max,
-                           kv_len, n_split, n_chunks, merge_out, ticket);
-    else
-        hipLaunchKernelGGL((k1_partial<DT, D, 4>), dim3(n_chunks * n_split, H_kv, B), dim3(256), 0, stream, (const unsigned short *)q,
-                           (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, direct, n_rows, H, H_kv, S_max,
-                           kv_len, n_split, n_chunks, merge_out, ticket);
-    if (ev1) (void)hipEventRecord(ev1, stream);
-    if (hipGetLastError() != hipSuccess) return SJD_ERR_LAUNCH;
-    if (direct || merge_out) return SJD_OK;             // one key split, or the splits merged in the kernel: the output is written
-    if constexpr (D == 128) {      // two workgroups per (batch, head, chunk) while that still leaves at most ~2 per CU (window shapes; a prefill keeps one)
-        // (measured, round 4: SLOWER -- Emu3 pair 22.2 -> 24.8 us, Lumina 14.1 -> 14.8 us, profiles/r4_k1_combine_rs.txt -- the launch is bound by
-        //  its cold start and its one round trip, not by the CUs it covers; off unless SJD_K1_COMBINE_RS=2)
-        static const bool rs2 = [] { const char *e = getenv("SJD_K1_COMBINE_RS"); return e && e[0] == '2'; }();
-        if (rs2 && (long)n_chunks * H * B <= 256) {
-            hipLaunchKernelGGL((k1_combine<DT, D, 2>), dim3(2 * n_chunks, H, B), dim3(256), 0, stream, ws_o, ws_ml, (unsigned short *)out, n_rows, H,
-                               n_split, n_chunks, params, key_start, kv_len);
-            return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+            return k1_finish<DT, D>(false, ws_o, ws_ml, out, B, n_rows, H, n_chunks, n_split, key_start, params, kv_len, stream, ev1);
         }
     }
-    hipLaunchKernelGGL((k1_combine<DT, D>), dim3(n_chunks, H, B), dim3(256), 0, stream, ws_o, ws_ml, (unsigned short *)out, n_rows, H,
-                       n_split, n_chunks, params, key_start, kv_len);
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+    hipLaunchKernelGGL((k1_partial<DT, D, 8, DL>), dim3(n_chunks * n_split, H_kv, B), dim3(512), 0, stream, (const unsigned short *)q,
+                       (const unsigned short *)kc, (const unsigned short *)vc, params, key_start, ws_o, ws_ml, direct, n_rows, H, H_kv, S_max,
+                       kv_len, n_split, n_chunks, merge_out, ticket);
+    return k1_finish<DT, D>(direct || merge_out, ws_o, ws_ml, out, B, n_rows, H, n_chunks, n_split, key_start, params, kv_len, stream, ev1);
 }
 
 static int k1_dispatch(const void *q, const void *k_cache, const void *v_cache, void *out, int B, int n_rows,
@@ -1801,10 +1724,8 @@ static int k1_dispatch(const void *q, const void *k_cache, const void *v_cache, 
     }
     const int G = H / H_kv;
     // group 8 (the 30B-class Chameleon, 64 / 8 heads): one draft window of <= 16 rows is 8 (head, chunk) pairs -- the LDS-DMA ring kernel with
-    // eight waves; 17..32 rows (two chunks) run on k1_partial with eight waves, one per head of the group (key parts 1); four-wave k1_partial
-    // (SJD_K1_WAVES=4) has no wave per head there and declines
+    // eight waves; 17..32 rows (two chunks) run on k1_partial with eight waves, one per head of the group (key parts 1)
     if (!(G == 1 || G == 2 || G == 4 || G == 8)) return SJD_ERR_UNSUPPORTED;
-    if (G == 8 && k1_waves() != 8 && !(D == 128 && n_rows <= K1_ROWS && !getenv("SJD_K1_NO_SHARED"))) return SJD_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     if (dl100) {
         if (dtype == SJD_DTYPE_BF16) return launch_attention<SJD_DTYPE_BF16, 128, 100>(q, k_cache, v_cache, out, B, n_rows, H, H_kv, S_max, key_start, params, kv_len, n_split, workspace, s, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, ticket, colsplit);
@@ -1902,33 +1823,16 @@ static int launch_attention_fp8(const void *q, const void *kc, const void *vc, v
     }
     float *ws_o = (float *)workspace;
     float *ws_ml = ws_o + (size_t)B * H * n_chunks * n_split * K1_ROWS * D;
-    static const bool no_direct = getenv("SJD_K1_NO_DIRECT") != nullptr;
-    unsigned short *direct = (n_split == 1 && !no_direct) ? (unsigned short *)out : nullptr;      // one key split: no combine launch
-    static const bool no_merge = getenv("SJD_K1_NO_MERGE") != nullptr;
-    unsigned short *merge_out = (ticket && !direct && !no_merge) ? (unsigned short *)out : nullptr;      // splits merged by their last workgroup
-    if (k1_waves() == 8)
-        hipLaunchKernelGGL((k1_partial_fp8<DT, D, 8>), dim3(n_chunks * n_split, H_kv, B), dim3(512), 0, stream, (const unsigned short *)q,
-                           (const unsigned char *)kc, (const unsigned char *)vc, params, key_start, ws_o, ws_ml, direct, n_rows, H, H_kv, S_max,
-                           kv_len, n_split, n_chunks, k_scale, v_scale, merge_out, ticket);
-    else
-        hipLaunchKernelGGL((k1_partial_fp8<DT, D, 4>), dim3(n_chunks * n_split, H_kv, B), dim3(256), 0, stream, (const unsigned short *)q,
-                           (const unsigned char *)kc, (const unsigned char *)vc, params, key_start, ws_o, ws_ml, direct, n_rows, H, H_kv, S_max,
-                           kv_len, n_split, n_chunks, k_scale, v_scale, merge_out, ticket);
-    if (hipGetLastError() != hipSuccess) return SJD_ERR_LAUNCH;
-    if (direct || merge_out) return SJD_OK;
-    if constexpr (D == 128) {      // two workgroups per (batch, head, chunk) while that still leaves at most ~2 per CU (window shapes; a prefill keeps one)
-        // (measured, round 4: SLOWER -- Emu3 pair 22.2 -> 24.8 us, Lumina 14.1 -> 14.8 us, profiles/r4_k1_combine_rs.txt -- the launch is bound by
-        //  its cold start and its one round trip, not by the CUs it covers; off unless SJD_K1_COMBINE_RS=2)
-        static const bool rs2 = [] { const char *e = getenv("SJD_K1_COMBINE_RS"); return e && e[0] == '2'; }();
-        if (rs2 && (long)n_chunks * H * B <= 256) {
-            hipLaunchKernelGGL((k1_combine<DT, D, 2>), dim3(2 * n_chunks, H, B), dim3(256), 0, stream, ws_o, ws_ml, (unsigned short *)out, n_rows, H,
-                               n_split, n_chunks, params, key_start, kv_len);
-            return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
-        }
-    }
-    hipLaunchKernelGGL((k1_combine<DT, D>), dim3(n_chunks, H, B), dim3(256), 0, stream, ws_o, ws_ml, (unsigned short *)out, n_rows, H,
-                       n_split, n_chunks, params, key_start, kv_len);
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+    bool one_split_direct = n_split == 1;      // one key split: no combine launch
+#ifdef SJD_EXPERIMENTAL
+    if (sjd_switches::get().k1_no_direct) one_split_direct = false;
+#endif
+    unsigned short *direct = one_split_direct ? (unsigned short *)out : nullptr;
+    unsigned short *merge_out = (ticket && !direct) ? (unsigned short *)out : nullptr;      // splits merged by their last workgroup
+    hipLaunchKernelGGL((k1_partial_fp8<DT, D, 8>), dim3(n_chunks * n_split, H_kv, B), dim3(512), 0, stream, (const unsigned short *)q,
+                       (const unsigned char *)kc, (const unsigned char *)vc, params, key_start, ws_o, ws_ml, direct, n_rows, H, H_kv, S_max,
+                       kv_len, n_split, n_chunks, k_scale, v_scale, merge_out, ticket);
+    return k1_finish<DT, D>(direct || merge_out, ws_o, ws_ml, out, B, n_rows, H, n_chunks, n_split, key_start, params, kv_len, stream);
 }
 
 static int k1_dispatch_fp8(const void *q, const void *k_cache, const void *v_cache, void *out, int B, int n_rows, int H,

@@ -16,7 +16,6 @@
 //     kernel (F1 / F2 / F3 take n_chunks), so no reduction pass and no atomics;
 //   * loads are issued 8 k-steps ahead of their MFMA (register double buffer) and marked non-temporal (read once).
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include <type_traits>
 
 #include "../../include/sjd_hip.h"
@@ -1938,13 +1937,11 @@ extern "C" int sjd_skinny_gemm_z(const void *x, const void *wz, const void *exc,
     hipStream_t s = (hipStream_t)stream;
     const int rs = step_major ? n_tiles : 1;
     auto then_raw_fixup = [&](int rc) { return rc != SJD_OK ? rc : g1_raw_units_launch(x, raw, out, M, N, K, KC, tile0, s); };
-    {   // 33..64 rows with FOUR column tiles per workgroup: kernel G1w's 12-bit form (csrc/sjd_gemm_wide.h, template parameter Z).  The one shape where it beats
-        // the kernels below -- the o projection of a 64-row window, 9.3 against 10.7 us (profiles/r6_g1wz_sweep_64rows_emu3.jsonl); everywhere else it measured
-        // slower and lives in the experimental library only.  It has no in-kernel path for raw units.  SJD_G1WZ=0: off.
-        static const bool wz_on = [] { const char *e = getenv("SJD_G1WZ"); return !(e && e[0] == '0'); }();
-        if (wz_on && MT == 2 && waves == 4)
-            return then_raw_fixup(g1_wide_launch_z<2, 1, 4, 4, 3, 2, 2>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s));
-    }
+    // 33..64 rows with FOUR column tiles per workgroup: kernel G1w's 12-bit form (csrc/sjd_gemm_wide.h, template parameter Z).  The one shape where it beats
+    // the kernels below -- the o projection of a 64-row window, 9.3 against 10.7 us (profiles/r6_g1wz_sweep_64rows_emu3.jsonl); everywhere else it measured
+    // slower and lives in the experimental library only.  It has no in-kernel path for raw units.
+    if (MT == 2 && waves == 4)
+        return then_raw_fixup(g1_wide_launch_z<2, 1, 4, 4, 3, 2, 2>(x, wz, exc, exc_cap, out, M, N, K, KC, n_tiles, step_major, tile0, s));
     if (MT > 2 || lds > 160 * 1024) {             // sub-tiled activation (65..128 rows, or a 64-row window with a tall K chunk): <= 8 waves, no raw path
         if (waves > 8) return SJD_ERR_BAD_ARG;
         const size_t lds_t = (size_t)2 * MT * G1_SUB * 1024;
@@ -1981,22 +1978,12 @@ static int g1_launch(const void *x, const void *w_packed, float *out, int M, int
     if (tile0 < 0 || tile0 + n_out > n_tiles) return SJD_ERR_BAD_ARG;
     const dim3 grid((n_out + waves - 1) / waves, n_chunks), block(waves * 64);
     const size_t lds_whole = (size_t)MT * ((KC < K ? KC : K) / 16) * 64 * 16;       // the whole activation chunk staged at once
-    static const bool force_tiled = [] { const char *e = getenv("SJD_G1_TILED"); return e && e[0] == '1'; }();      // tuning aid (64-row windows)
-    auto tiled8 = [&](auto nw) {                  // g1_skinny_gemm_tiled8 with nw = 4 or 8 waves per workgroup (MT > 2 only)
-        constexpr int NW = decltype(nw)::value;
-        const size_t lds_8 = (size_t)2 * MT * 8 * 1024;
-        (void)hipFuncSetAttribute((const void *)g1_skinny_gemm_tiled8<DT, MT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_8);
-        hipLaunchKernelGGL((g1_skinny_gemm_tiled8<DT, MT, NW>), grid, block, lds_8, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K,
-                           KC, n_tiles, step_major ? n_tiles : 1, tile0);
-        return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
-    };
     if constexpr (MT == 2) {
         // 33..64-row windows (Emu3's draft window of 32 with CFG; two prompts per forward) on the uncompressed stream, both 16-bit types: G1w with two
         // row tiles and the register budget of two workgroups per CU (late round 6) -- per launch at Emu3's shapes q|k|v 12.6 / 13.6 us, o 9.4 / 11.2,
         // gate|up 39.0 / 43.1, down 22.5 / 25.2 against the kernels below (profiles/r6_g1w_sweep_64rows_emu3.jsonl); `waves` = column tiles per
-        // workgroup: 2, 3, 4, 6, 8.  Same chunking and accumulation order: bit-identical planes.  SJD_G1_WIDE_64=0: the kernels below (A/B aid).
-        static const bool wide64 = [] { const char *e = getenv("SJD_G1_WIDE_64"); return !(e && e[0] == '0'); }();
-        if (wide64 && M > 32) {
+        // workgroup: 2, 3, 4, 6, 8.  Same chunking and accumulation order: bit-identical planes.
+        if (M > 32) {
             switch (waves) {
             case 2: return g1_wide_launch<DT, MT, 1, 2, 4, 3, 2, 2>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
             case 3: return g1_wide_launch<DT, MT, 1, 3, 4, 3, 2, 2>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
@@ -2009,31 +1996,24 @@ static int g1_launch(const void *x, const void *w_packed, float *out, int M, int
     }
     if constexpr (MT > 4) {      // 129..256-row windows (five to eight prompts per forward), both 16-bit types: G1w (sjd_gemm_wide.h, round 6).  `waves` = column tiles per
         // workgroup: 2, 3, 4 (one per wave) or 6, 8 (two per wave: every activation fragment read from LDS feeds two MFMAs); stages of four k-steps,
-        // three ring slots (96 KiB + 1), weight ring of eight k-steps.  SJD_G1_WIDE=0 (A/B aid): round 5's g1_skinny_gemm_tiled8 with four waves,
-        // one workgroup per CU (a wave holds MT x 16 accumulators + 2 MT staging pieces + the weight ring: > 256 registers), 2 x MT x 8 KiB of LDS.
-        static const bool wide = [] { const char *e = getenv("SJD_G1_WIDE"); return !(e && e[0] == '0'); }();
-        if (wide) {
-            switch (waves) {
-            case 2: return g1_wide_launch<DT, MT, 1, 2, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-            case 3: return g1_wide_launch<DT, MT, 1, 3, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-            case 4: return g1_wide_launch<DT, MT, 1, 4, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-            case 6: return g1_wide_launch<DT, MT, 2, 3, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-            case 8: return g1_wide_launch<DT, MT, 2, 4, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-            default: return SJD_ERR_BAD_ARG;
-            }
+        // three ring slots (96 KiB + 1), weight ring of eight k-steps.
+        switch (waves) {
+        case 2: return g1_wide_launch<DT, MT, 1, 2, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+        case 3: return g1_wide_launch<DT, MT, 1, 3, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+        case 4: return g1_wide_launch<DT, MT, 1, 4, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+        case 6: return g1_wide_launch<DT, MT, 2, 3, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+        case 8: return g1_wide_launch<DT, MT, 2, 4, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+        default: return SJD_ERR_BAD_ARG;
         }
-        if (waves != 4) return SJD_ERR_BAD_ARG;
-        return tiled8(std::integral_constant<int, 4>{});
     } else
-    if constexpr (MT >= 2) if (MT > 2 || lds_whole > 160 * 1024 || (force_tiled && waves <= 8)) {     // sub-tiled activation: no limit on KC
+    if constexpr (MT >= 2) if (MT > 2 || lds_whole > 160 * 1024) {     // sub-tiled activation: no limit on KC
         if (waves > 8) return SJD_ERR_BAD_ARG;
         if constexpr ((MT == 3 || MT == 4) && DT == SJD_DTYPE_BF16) {
             // 65..128-row windows (three / four prompts per forward) in bf16: G1w too (late round 6) -- with its own launch shapes it is 5-10 % faster per
             // launch than the sub-tiled kernels (profiles/r6_g1w_sweep_128rows.jsonl: q|k|v 23.1 / 24.5, o 11.6 / 12.4, gate|up 37.2 / 40.4, down 21.9 / 24.2 us);
-            // `waves` = column tiles per workgroup: 2, 3, 4, 6, 8; any other count, fp16, or SJD_G1_WIDE_128=0 (A/B aid) keep the sub-tiled kernels below.
+            // `waves` = column tiles per workgroup: 2, 3, 4, 6, 8; any other count, or fp16, keeps the sub-tiled kernels below.
             // Same chunking and accumulation order: the planes are the sub-tiled kernels', bit for bit.
-            static const bool wide128 = [] { const char *e = getenv("SJD_G1_WIDE_128"); return !(e && e[0] == '0'); }();
-            if (wide128 && M > 64) {
+            if (M > 64) {
                 if constexpr (MT == 4) if (waves == 2) return g1_wide_launch<DT, MT, 1, 2, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
                 switch (waves) {          // (three row tiles x two waves: a k-step has too few MFMAs to carry its DMA pieces -- the sub-tiled kernel keeps that shape)
                 case 3: return g1_wide_launch<DT, MT, 1, 3, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
@@ -2044,11 +2024,17 @@ static int g1_launch(const void *x, const void *w_packed, float *out, int M, int
                 }
             }
         }
-        static const bool sub8 = [] { const char *e = getenv("SJD_G1_SUB8"); return !(e && e[0] == '0'); }();      // (A/B aid: 0 = the 16-step kernel for every wave count)
-        static const bool sub8w8 = [] { const char *e = getenv("SJD_G1_SUB8_W8"); return !(e && e[0] == '0'); }();   // (A/B aid: 0 = eight-wave workgroups on the 16-step kernel)
         if constexpr (MT > 2) {
-            if (waves == 4 && sub8) return tiled8(std::integral_constant<int, 4>{});        // 4-wave workgroups: 8-step sub-tiles, two workgroups per CU
-            if (waves == 8 && sub8 && sub8w8) return tiled8(std::integral_constant<int, 8>{});
+            auto tiled8 = [&](auto nw) {              // g1_skinny_gemm_tiled8 with nw = 4 or 8 waves per workgroup: 8-step sub-tiles (4 waves: two workgroups per CU)
+                constexpr int NW = decltype(nw)::value;
+                const size_t lds_8 = (size_t)2 * MT * 8 * 1024;
+                (void)hipFuncSetAttribute((const void *)g1_skinny_gemm_tiled8<DT, MT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_8);
+                hipLaunchKernelGGL((g1_skinny_gemm_tiled8<DT, MT, NW>), grid, block, lds_8, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K,
+                                   KC, n_tiles, step_major ? n_tiles : 1, tile0);
+                return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+            };
+            if (waves == 4) return tiled8(std::integral_constant<int, 4>{});
+            if (waves == 8) return tiled8(std::integral_constant<int, 8>{});
         }
         const size_t lds_t = (size_t)2 * MT * G1_SUB * 1024;
         (void)hipFuncSetAttribute((const void *)g1_skinny_gemm_tiled<DT, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);

@@ -145,7 +145,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
     // columns of EVERY chunk -- 5.6 MB for the down projection at 256 rows against 4 MB of L2: PMC showed 45 MB of activation re-reads going to HBM
     // (profiles/g1w_traffic.json).  With a power-of-two chunk count the chunk follows the XCD instead (chunk = XCD mod n_chunks; sixteen and more
     // chunks: XCD + 8 * ...), an XCD then re-reads 1 / min(8, n_chunks) of the activation.  Which workgroup computes which (tile, chunk) does not
-    // change any result.  xmap = 0: the plain map (A/B aid, SJD_G1W_XMAP=0).
+    // change any result.  xmap = 0: the plain map (four row tiles and below).
     int bx = blockIdx.x, chunk = blockIdx.y;
     {
         const int gx = gridDim.x, nc = gridDim.y;
@@ -377,9 +377,8 @@ static int g1_wide_launch(const void *x, const void *w_packed, float *out, int M
     auto kern = g1_wide<DT, MT, CT, NW, SUB, NS, RW, WPS>;
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     // (the XCD-aware map pays where the activation outgrows an XCD's L2 share: eight prompts 6.75 -> 6.58 ms per step, two alternations on one box; at 128
-    //  rows and below it is neutral end to end and costs the gate|up launch 3 us alone: plain map there.  profiles/r6_g1w_xmap_ab.txt; SJD_G1W_XMAP=0 / 1 forces)
-    static const int xenv = [] { const char *e = getenv("SJD_G1W_XMAP"); return !e ? -1 : (e[0] == '0' ? 0 : 1); }();
-    const int xmap = xenv >= 0 ? xenv : (MT > 4 ? 1 : 0);
+    //  rows and below it is neutral end to end and costs the gate|up launch 3 us alone: plain map there.  profiles/r6_g1w_xmap_ab.txt)
+    constexpr int xmap = MT > 4;
     hipLaunchKernelGGL(kern, grid, block, lds, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K, KC, n_tiles, step_major ? n_tiles : 1, tile0, ldx > 0 ? ldx : K, xmap,
                        (const u32x2 *)nullptr, 0);
     return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
@@ -394,8 +393,7 @@ static int g1_wide_launch_z(const void *x, const void *wz, const void *exc, int 
     const dim3 grid((n_out + NW * CT - 1) / (NW * CT), n_chunks), block(64 * NW);
     constexpr size_t lds = g1_wide_lds<MT, SUB, NS>();
     static_assert(lds <= 160 * 1024, "the activation ring must fit in LDS");
-    static const int xenv = [] { const char *e = getenv("SJD_G1W_XMAP"); return !e ? -1 : (e[0] == '0' ? 0 : 1); }();
-    const int xmap = xenv >= 0 ? xenv : (MT > 4 ? 1 : 0);
+    constexpr int xmap = MT > 4;
 #define SJD_G1WZ(WIDE_) do { \
         auto kern = g1_wide<SJD_DTYPE_BF16, MT, CT, NW, SUB, NS, RW, WPS, true, WIDE_>; \
         (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \

@@ -883,9 +883,10 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
     // the mode bits of `dtype`: SJD_QKN_SHARDS(mp) -- QK-norm gain / bias stored [mp, D], head h of q uses row h / (H / mp), of k h / (H_kv / mp);
     // SJD_F2_ROPE_TABLE -- LlamaGen's interleaved rotary from a (cos, sin) table in `inv_freq`
     // SJD_F2_HEAD_PAD128 -- with the table mode and D = 100: 100-wide source heads, 128-wide q_out / cache rows whose pad columns are written as zeros
-    if (dtype & ~(SJD_DTYPE_MASK | SJD_QKN_SHARDS_MASK | SJD_F2_ROPE_TABLE | SJD_F2_HEAD_PAD128)) return SJD_ERR_UNSUPPORTED;
+    // SJD_F2_ONE_HEAD -- one head per wave even above 64 rows of split-K planes (the parity tests compare the two forms)
+    if (dtype & ~(SJD_DTYPE_MASK | SJD_QKN_SHARDS_MASK | SJD_F2_ROPE_TABLE | SJD_F2_HEAD_PAD128 | SJD_F2_ONE_HEAD)) return SJD_ERR_UNSUPPORTED;
     const int shards = (dtype & SJD_QKN_SHARDS_MASK) >> SJD_QKN_SHARDS_SHIFT;
-    const bool table = (dtype & SJD_F2_ROPE_TABLE) != 0, pad128 = (dtype & SJD_F2_HEAD_PAD128) != 0;
+    const bool table = (dtype & SJD_F2_ROPE_TABLE) != 0, pad128 = (dtype & SJD_F2_HEAD_PAD128) != 0, one_head = (dtype & SJD_F2_ONE_HEAD) != 0;
     dtype &= SJD_DTYPE_MASK;
     if (pad128 && (!table || D != 100)) return SJD_ERR_UNSUPPORTED;
     if (table && (qn_w || qn_b || kn_w || kn_b)) return SJD_ERR_BAD_ARG;      // (LlamaGen has no QK-norm)
@@ -901,10 +902,8 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
     const int waves = B * n * (H + 2 * H_kv);
     const dim3 grid((waves + 3) / 4), block(256);
     hipStream_t s = (hipStream_t)stream;
-    // more than 64 rows of split-K partials: HPW heads per wave (f2_qknorm_rope_append_rows); SJD_F2_ROWS=0 keeps the one-head kernel (A/B aid)
-    const char *f2r_env = getenv("SJD_F2_ROWS");              // (read per launch: the parity test flips it inside one process)
-    const bool rows_ok = !(f2r_env && f2r_env[0] == '0');
-    if (rows_ok && table && part && B * n > 64 && (H % 4) == 0 && (H_kv % 4) == 0) {      // (other head counts: the one-head table kernel below)
+    // more than 64 rows of split-K partials: HPW heads per wave (f2_qknorm_rope_append_rows) unless the caller asks for the one-head kernel
+    if (!one_head && table && part && B * n > 64 && (H % 4) == 0 && (H_kv % 4) == 0) {      // (other head counts: the one-head table kernel below)
         const dim3 g2((B * n * ((H + 2 * H_kv) / 4) + 3) / 4);
 #define SJD_F2RT_CASE(DT_, D_, DS_)                                                                                                        \
         if (dtype == DT_ && D == D_) {                                                                                                     \
@@ -924,7 +923,7 @@ static int f2_launch(const void *qkv, void *q_out, void *k_cache, void *v_cache,
 #undef SJD_F2RT_CASE
         return SJD_ERR_UNSUPPORTED;
     }
-    if (rows_ok && !table && part && B * n > 64 && (H % 4) == 0 && (H_kv % 4) == 0 && D == 128 && dtype == SJD_DTYPE_BF16) {
+    if (!one_head && !table && part && B * n > 64 && (H % 4) == 0 && (H_kv % 4) == 0 && D == 128 && dtype == SJD_DTYPE_BF16) {
         const dim3 g2((B * n * ((H + 2 * H_kv) / 4) + 3) / 4);
 #define SJD_F2R(KV8_, SH_)                                                                                                                 \
         hipLaunchKernelGGL((f2_qknorm_rope_append_rows<SJD_DTYPE_BF16, 128, KV8_, 4, SH_>), g2, block, 0, s, (unsigned short *)q_out,      \

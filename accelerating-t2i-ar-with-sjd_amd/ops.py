@@ -869,7 +869,7 @@ def _row_norm(row_norm):
 
 
 def qknorm_rope_append(qkv, k_cache, v_cache, qn_w, qn_b, kn_w, kn_b, inv_freq, positions, B, n, H, H_kv, D, params, kv_len,
-                       kv_scale=(1.0, 1.0), dtype=None, row_norm=None, qk_shards=1, rope_table=None, head_pad=None):
+                       kv_scale=(1.0, 1.0), dtype=None, row_norm=None, qk_shards=1, rope_table=None, head_pad=None, one_head=False):
     """qkv [B*n, (H+2Hkv)*D] (tensor or G1 Partials) -> q [B,n,H,D]; k/v rows are written into k_cache/v_cache [B,Hkv,S,D].
     An fp8 cache (dtype FP8) receives fp8(x / scale) with kv_scale = (k, v); `dtype` = the activation dtype (needed with Partials
     into an fp8 cache, where no 16-bit tensor is around to tell).  row_norm = (sumsq, hidden, eps): the projection ran on the
@@ -878,14 +878,15 @@ def qknorm_rope_append(qkv, k_cache, v_cache, qn_w, qn_b, kn_w, kn_b, inv_freq, 
     rope_table: LlamaGen's interleaved 2-D rotary (SJD_F2_ROPE_TABLE) from an fp32 (cos, sin) table [S_rows >= S_max, D/2, 2], row p serving
     position p; inv_freq is ignored then and the QK-norm arguments must be None.
     head_pad = 128 (SJD_F2_HEAD_PAD128; with rope_table and D = 100 only): the source heads are D = 100 wide, q comes back [B,n,H,128] and the
-    caches are [B,Hkv,S,128]; the pad columns of every written row are written as zeros."""
+    caches are [B,Hkv,S,128]; the pad columns of every written row are written as zeros.
+    one_head (SJD_F2_ONE_HEAD): above 64 rows of Partials, one head per wave in place of four -- the same bits (parity tests and A/B timing)."""
     t, part, nc = _part_args(qkv)
     assert (t is None or t.is_contiguous()) and positions.is_contiguous() and positions.dtype == torch.int64
-    mode = 0
+    mode = L.F2_ONE_HEAD if one_head else 0
     if rope_table is not None:
         assert rope_table.dtype == torch.float32 and rope_table.is_contiguous() and rope_table.shape[1:] == (D // 2, 2)
         assert rope_table.shape[0] >= k_cache.shape[2], "the rotary table needs a row per cache position"
-        inv_freq, mode = rope_table, L.F2_ROPE_TABLE
+        inv_freq, mode = rope_table, mode | L.F2_ROPE_TABLE
     DS = D
     if head_pad is not None and head_pad != D:
         assert rope_table is not None and (D, head_pad) == (100, 128), "head_pad: head_dim 100 stored 128 wide, table rotary only"

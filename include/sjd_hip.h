@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define SJD_VERSION 103
+#define SJD_VERSION 104
 #define SJD_MAX_WINDOW 64      /* max draft-window length L (reference max_num_new_tokens: 16 / 32 by default, a free CLI argument of eval_model.py:76;
                                   64 = one wavefront of accept tests in K4, 128 forward rows with CFG) */
 #define SJD_MAX_RANGES 4
@@ -34,7 +34,7 @@ extern "C" {
 #define SJD_DTYPE_F16 1
 #define SJD_DTYPE_F32 2        /* K1/K3 only: exact-fp32 VALU variant for small parity runs (not a performance path) */
 
-/* Mode bits in the high bits of the `dtype` argument of the glue entry points (version 101; SJD_F2_ROPE_TABLE: 102, its 65..256 rows: 103).  dtype & SJD_DTYPE_MASK is the dtype code
+/* Mode bits in the high bits of the `dtype` argument of the glue entry points (version 101; SJD_F2_ROPE_TABLE: 102, its 65..256 rows: 103; SJD_F2_ONE_HEAD: 104).  dtype & SJD_DTYPE_MASK is the dtype code
  * above; a value without mode bits selects the plain kernels, bit for bit as before.  An entry point given a bit it does not know returns
  * SJD_ERR_UNSUPPORTED.
  *   SJD_F1_POST_NORM      sjd_add_rmsnorm: the swin-norm order of ChameleonSwinDecoderLayer (reference modeling_chameleon.py:670-735),
@@ -53,24 +53,29 @@ extern "C" {
  *                         SJD_ERR_BAD_ARG; an fp8 cache or D not 64 / 128: SJD_ERR_UNSUPPORTED.  Rows: B*n <= 64 from a dense `qkv` or
  *                         from split-K planes; 64 < B*n <= 256 (version 103) from split-K planes only (`part` != NULL) -- a dense source
  *                         with more than 64 rows stays SJD_ERR_UNSUPPORTED.  Above 64 rows a wave serves four consecutive heads of one
- *                         kind when H and H_kv are multiples of 4 (one head per wave otherwise, or with SJD_F2_ROWS=0 in the
- *                         environment); both forms write the same bits.
+ *                         kind when H and H_kv are multiples of 4 (one head per wave otherwise, or with SJD_F2_ONE_HEAD); both forms
+ *                         write the same bits.
  *   SJD_F2_HEAD_PAD128    sjd_qknorm_rope_append / _ex, only together with SJD_F2_ROPE_TABLE and D = 100 (LlamaGen GPT-3B: 32 heads of 100;
  *                         SJD_ERR_UNSUPPORTED otherwise): the SOURCE heads are 100 wide -- a dense qkv [T, (H + 2 H_kv) * 100] or split-K
  *                         planes with (H + 2 H_kv) * 100 columns -- and the table is [S_rows, 50, 2]; the DESTINATIONS are 128 wide:
  *                         q_out [B, n, H, 128], the caches [B, H_kv, S_max, 128].  Columns 0..99 of every written row are the bits the
  *                         table mode writes at a native D; columns 100..127 of every written row (q, k and v) are written as zeros, so
  *                         nothing depends on what the buffers held.  Row limits and sources as for SJD_F2_ROPE_TABLE.
+ *   SJD_F2_ONE_HEAD       sjd_qknorm_rope_append / _ex / _fp8 (version 104): one head per wave even above 64 rows of split-K planes, where
+ *                         a wave otherwise serves four consecutive heads when H and H_kv are multiples of 4.  It selects the kernel that
+ *                         other head counts run anyway; both forms write the same bits (the parity tests compare them).  No effect at
+ *                         64 rows and below or on a dense source.
  * A mode bit of the 16-bit draft-window attention entry points (sjd_draft_window_attention / _ex / _colsplit):
  *   SJD_K1_HEAD_DIM_100   heads STORED 128 wide (D = 128) whose columns 100..127 are zero in q, K and V: the softmax scale is 1/sqrt(100),
  *                         the logical head dim, in place of 1/sqrt(D); the pad columns add nothing to q k^T and the output's pad columns
  *                         are zero.  Valid with D = 128, H == H_kv and dtype bf16 / fp16 only -- SJD_ERR_UNSUPPORTED otherwise, from the
- *                         fp32 variant, from the fp8-cache entry points, and from the A/B kernel forms chosen by environment switches. */
+ *                         fp32 variant and from the fp8-cache entry points. */
 #define SJD_DTYPE_MASK 0xff
 #define SJD_F1_POST_NORM 0x100
 #define SJD_F2_ROPE_TABLE 0x200
 #define SJD_F2_HEAD_PAD128 0x400
 #define SJD_K1_HEAD_DIM_100 0x800
+#define SJD_F2_ONE_HEAD 0x1000
 #define SJD_QKN_SHARDS_SHIFT 16
 #define SJD_QKN_SHARDS_MASK (0xff << SJD_QKN_SHARDS_SHIFT)
 #define SJD_QKN_SHARDS(mp) ((int)(mp) << SJD_QKN_SHARDS_SHIFT)
@@ -358,7 +363,7 @@ int sjd_gateup_silu(const void *x, const void *w_packed, void *y, int M, int I, 
  * and 32 < M <= 64 (bf16 or fp16), 64 < M <= 128 (bf16; M <= 96: not 2) or 128 < M <= 256 (bf16 or fp16; these tile counts only:
  * SJD_ERR_BAD_ARG otherwise): no limit on KC.  fp16 at 64 < M <= 128 stays on the sub-tiled kernels.  Same
  * chunking and accumulation order as the kernels above: the planes do not depend on which kernel ran (tests/test_gpu_glue.py::test_g1w_*,
- * test_g1_skinny_gemm_*_row_tiles).  SJD_G1_WIDE_64 / _128 / SJD_G1_WIDE = 0 in the environment keep the older kernels (A/B aids). */
+ * test_g1_skinny_gemm_*_row_tiles). */
 int sjd_gemm_num_chunks(int K, int KC);
 
 /* the same over the N = 32 n columns [32 * tile0, 32 * tile0 + N) of a weight packed with N_packed columns (the output head evaluated on

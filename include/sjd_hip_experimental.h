@@ -7,6 +7,9 @@
  * G1w.  The product library is compiled WITHOUT their kernels and without their run-time switches inside the hot kernels (the reducing tail of
  * g1_skinny_gemm, the in-kernel split merge of k1_partial): engine.py / engine_batch.py / backbones.py reach none of them with default
  * switches; the opt-in switches of backbones.py (SJD_K1_FUSED, SJD_REDUCE_FUSED, SJD_MLP_PAIR, SJD_PREFETCH, ...) load this library.
+ * Only this library reads the environment (csrc/sjd_switches.h, once per process): SJD_K1_NO_DIRECT (one key split still runs k1_partial +
+ * k1_combine) and SJD_K1_RING=0 (the shared-tile shapes on k1_partial_shared) select the two alternative K1 forms that tests compare the
+ * product's against through the ordinary attention entry points.  The product library has no environment switch.
  * Conventions as in sjd_hip.h.
  */
 #ifndef SJD_HIP_EXPERIMENTAL_H

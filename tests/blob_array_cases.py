@@ -162,7 +162,7 @@ def attention_fp8_refs(q, kd, vd, kv_len, n_rows, key_start):
 # ---- F2 (QK-norm + RoPE + KV append) under a blob array: tests/test_gpu_glue.py
 F2_SLOT_KV = [21, 0, 300, 63, 64, 1000, 5, 511]
 
-# name, nb, n, slots, H, Hkv, n_chunks (0: a dense qkv source), qk_norm, folded row_norm, QK-norm shards, fp8 cache, dtypes, SJD_F2_ROWS values
+# name, nb, n, slots, H, Hkv, n_chunks (0: a dense qkv source), qk_norm, folded row_norm, QK-norm shards, fp8 cache, dtypes, rows ("0": ops one_head=True, "1": the four-heads-per-wave kernel)
 F2_BLOB_CASES = [
     ("qknorm_partials_64rows", 2, 16, 2, 8, 8, 3, True, False, 1, False, ("bf16", "fp16"), (None,)),
     ("plain_folded_64rows", 2, 16, 2, 8, 2, 4, False, True, 1, False, ("bf16", "fp16"), (None,)),

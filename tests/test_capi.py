@@ -40,6 +40,16 @@ def test_exports_match_header():
     assert lib.sjd_error_string(-2) == b"unsupported configuration"
 
 
+def test_only_the_experimental_library_reads_the_environment():
+    """the product library's dispatch has no environment switch: it does not even import getenv; the experimental one (csrc/sjd_switches.h) does"""
+    import subprocess
+    L = _ensure_built()
+    undefined = lambda path: {ln.split()[-1].split("@")[0] for ln in
+                              subprocess.run(["nm", "-D", "--undefined-only", path], capture_output=True, text=True, check=True).stdout.splitlines()}
+    assert "getenv" not in undefined(L.SO_PATH) and "secure_getenv" not in undefined(L.SO_PATH)
+    assert "getenv" in undefined(L.EXP_SO_PATH)
+
+
 def test_experimental_library_is_a_superset_with_its_own_header():
     """libsjd_hip_exp.so (same sources, -DSJD_EXPERIMENTAL): everything the product exports plus exactly what include/sjd_hip_experimental.h declares"""
     L = _ensure_built()

@@ -267,10 +267,10 @@ def test_partials_feed_glue_kernels(dev):
 @pytest.mark.parametrize("fp8", [False, True])
 @pytest.mark.parametrize("B,n,H,Hkv,n_chunks,qk_norm,folded", [(16, 16, 32, 32, 2, True, True), (8, 16, 32, 8, 4, False, True), (6, 16, 8, 4, 5, True, False),
                                                          (5, 16, 8, 8, 9, True, True), (16, 13, 4, 4, 1, False, False)])
-def test_f2_many_row_kernel_is_the_one_head_kernel_bit_for_bit(dev, monkeypatch, fp8, B, n, H, Hkv, n_chunks, qk_norm, folded):
+def test_f2_many_row_kernel_is_the_one_head_kernel_bit_for_bit(dev, fp8, B, n, H, Hkv, n_chunks, qk_norm, folded):
     """round 6: windows of more than 64 rows run F2 with four heads of a token per wave (f2_qknorm_rope_append_rows: the planes of four heads in
     flight together, the rotary angle computed once instead of once per head) -- q and the cache rows must be those of the one-head kernel
-    (SJD_F2_ROWS=0), bit for bit: 256 rows of Lumina's 96 heads, Emu3's GQA shape, ragged chunk counts, with and without the folded RMSNorm"""
+    (one_head=True: SJD_F2_ONE_HEAD), bit for bit: 256 rows of Lumina's 96 heads, Emu3's GQA shape, ragged chunk counts, with and without the folded RMSNorm"""
     import sjd_amd.ops as ops
     D, S, kv_len, T = 128, 64, 21, B * n
     g = torch.Generator().manual_seed(B * 100 + n_chunks)
@@ -286,13 +286,13 @@ def test_f2_many_row_kernel_is_the_one_head_kernel_bit_for_bit(dev, monkeypatch,
     if folded:
         rn = (torch.rand(3, ops._prows(T), generator=g).add(0.5).mul(1000.0).to(dev), 4096, 1e-5)
     outs = []
-    for flag in ("0", "1"):
-        monkeypatch.setenv("SJD_F2_ROWS", flag)
+    for one_head in (True, False):
         if fp8:
             kc, vc = torch.zeros(B, Hkv, S, D, dtype=torch.uint8, device=dev).view(ops.FP8), torch.zeros(B, Hkv, S, D, dtype=torch.uint8, device=dev).view(ops.FP8)
         else:
             kc, vc = torch.zeros(B, Hkv, S, D, dtype=torch.bfloat16, device=dev), torch.zeros(B, Hkv, S, D, dtype=torch.bfloat16, device=dev)
-        q = ops.qknorm_rope_append(part, kc, vc, *args, inv, pos, B, n, H, Hkv, D, None, kv_len, kv_scale=(0.05, 0.03), dtype=torch.bfloat16, row_norm=rn)
+        q = ops.qknorm_rope_append(part, kc, vc, *args, inv, pos, B, n, H, Hkv, D, None, kv_len, kv_scale=(0.05, 0.03), dtype=torch.bfloat16, row_norm=rn,
+                                   one_head=one_head)
         torch.cuda.synchronize()
         outs.append((q, kc.view(torch.uint8) if fp8 else kc, vc.view(torch.uint8) if fp8 else vc))
     for a, b_ in zip(*outs):
@@ -861,12 +861,12 @@ def _f2_blob_ids():
 
 
 @pytest.mark.parametrize("case,dt,rows_flag", _f2_blob_ids())
-def test_f2_blob_array(dev, monkeypatch, case, dt, rows_flag):
+def test_f2_blob_array(dev, case, dt, rows_flag):
     """F2 with several prompts per launch: batch row b appends its K/V rows at the kv_len of blob b // nb (sjdi_kv_rows in the two split-K
     kernels, sjdi_params_of for a dense source).  q is bit-identical to the same call with a host kv_len (q does not depend on it); slot
     j's K/V rows sit at [kv_j, kv_j + n) and are the bytes of a launch of that slot alone with host kv_len; every other cache row still
     holds the sentinel the caches were filled with.  Rotate-half with and without per-head QK-norm, folded row_norm, SJD_QKN_SHARDS, dense
-    and split-K sources, the one-head and the four-heads-per-wave kernel (SJD_F2_ROWS), 16-bit and fp8 caches, slots in both orders.
+    and split-K sources, the one-head and the four-heads-per-wave kernel (SJD_F2_ONE_HEAD), 16-bit and fp8 caches, slots in both orders.
     The dense QK-norm variant is also held against the ATen sequence test_f2_qknorm_rope_append uses, at its tolerance."""
     import sjd_amd.ops as ops
     import sjd_amd._lib as L
@@ -874,8 +874,6 @@ def test_f2_blob_array(dev, monkeypatch, case, dt, rows_flag):
     from tests.blob_array_cases import F2_SLOT_KV
     name, nb, n, slots, H, Hkv, n_chunks, qk_norm, folded, shards, fp8, _, _ = case
     dtype = torch.bfloat16 if dt == "bf16" else torch.float16
-    if rows_flag is not None:
-        monkeypatch.setenv("SJD_F2_ROWS", rows_flag)
     D, S, hid = 128, 1152, 4096
     B, ncol = nb * slots, (H + 2 * Hkv) * D
     T = B * n
@@ -915,7 +913,7 @@ def test_f2_blob_array(dev, monkeypatch, case, dt, rows_flag):
                 ss[:, :t1 - t0] = sumsq[:, t0:t1]
                 rn = (ss.to(dev), hid, 1e-5)
         return ops.qknorm_rope_append(src, kc, vc, *args, inv, pos[r0:r0 + rows].reshape(-1).contiguous().to(dev), rows, n, H, Hkv, D, params, kv_len,
-                                      kv_scale=scale, dtype=dtype, row_norm=rn, qk_shards=shards)
+                                      kv_scale=scale, dtype=dtype, row_norm=rn, qk_shards=shards, one_head=rows_flag == "0")
 
     for kvs in (F2_SLOT_KV[:slots], F2_SLOT_KV[:slots][::-1]):
         kv_rows = torch.tensor(kvs).repeat_interleave(nb)

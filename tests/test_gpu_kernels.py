@@ -369,13 +369,16 @@ print(h.hexdigest())
 
 def test_k1_single_split_direct_output_is_what_combine_would_write(dev):
     """n_split == 1: k1_partial normalises and writes the 16-bit output itself (no workspace round trip, no k1_combine launch); the bytes
-    are those of partial + combine (SJD_K1_NO_DIRECT=1, read once per process -> two subprocesses), 16-bit and fp8 caches."""
+    are those of partial + combine, 16-bit and fp8 caches.  The product library has only the direct form; the two-kernel form is the
+    experimental library's under SJD_K1_NO_DIRECT=1 (read once per process -> two subprocesses)."""
     import subprocess
     import sys
+    _, L = _ops()
     outs = []
-    for env_extra in ({}, {"SJD_K1_NO_DIRECT": "1"}):
+    for env_extra in ({}, {"SJD_K1_NO_DIRECT": "1", "SJD_HIP_LIB": L.EXP_SO_PATH}):
         env = dict(os.environ, **env_extra)
-        env.pop("SJD_K1_NO_DIRECT", None) if not env_extra else None
+        if not env_extra:
+            env.pop("SJD_K1_NO_DIRECT", None)
         r = subprocess.run([sys.executable, "-c", _DIRECT_SCRIPT], capture_output=True, text=True, env=env,
                            cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -1144,10 +1147,12 @@ print("NO_RING_OK")
 
 
 def test_k1_shared_tile_kernel_blob_array(dev):
-    """SJD_K1_RING=0 (read once per process -> a subprocess): the grouped-query cases on k1_partial_shared instead of the ring kernel"""
+    """the grouped-query cases on k1_partial_shared instead of the ring kernel: the experimental library under SJD_K1_RING=0 (read once per
+    process -> a subprocess)"""
     import subprocess
     import sys
-    env = dict(os.environ, SJD_K1_RING="0", SJD_TEST_POISON="0")
+    _, L = _ops()
+    env = dict(os.environ, SJD_K1_RING="0", SJD_HIP_LIB=L.EXP_SO_PATH, SJD_TEST_POISON="0")
     r = subprocess.run([sys.executable, "-c", _NO_RING_SCRIPT], capture_output=True, text=True, env=env,
                        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), timeout=600)
     print(r.stdout[-2000:])

@@ -1,7 +1,7 @@
 """Several LlamaGen images per forward on the hand-written HIP path.
 
   * F2's table rotary (SJD_F2_ROPE_TABLE) for 65..256 rows read from split-K planes, bit for bit against the ATen rotary
-    (_apply_rope_interleaved) and a plain copy of v: the four-heads-per-wave kernel, the one-head kernel, SJD_F2_ROWS=0, one blob and an
+    (_apply_rope_interleaved) and a plain copy of v: the four-heads-per-wave kernel, the one-head kernel, SJD_F2_ONE_HEAD, one blob and an
     array of blobs with batch_rows = 2; the refusals that stay;
   * the fused window forward at GPT-XL width with 128 and 256 rows (eight slots, every slot its own KV length) against an fp32 forward, in
     the envelope of the ATen bf16 forward;
@@ -29,7 +29,7 @@ def _bits(t):
 
 
 # ------------------------------------------------------------------------------------------------ a. F2, table mode, many rows
-def _f2_many(D, dtype, rows, H, slots=None, cls=120, grid=4, S=512, kv_len=150):
+def _f2_many(D, dtype, rows, H, slots=None, cls=120, grid=4, S=512, kv_len=150, one_head=False):
     """B batch rows x n window rows = `rows`, three planes of ceil32(rows) rows.  slots None: two batch rows, one kv_len by value.
     slots = [kv, kv']: two slots of two batch rows each (batch_rows = 2), every slot its own kv_len from its blob."""
     B = 2 if slots is None else 2 * len(slots)
@@ -54,7 +54,8 @@ def _f2_many(D, dtype, rows, H, slots=None, cls=120, grid=4, S=512, kv_len=150):
             v.n_rows, v.kv_len, v.batch_rows = n, kv, 2
             params.blobs[j].upload()
     q = ops.qknorm_rope_append(ops.Partials(part, 3, N), kc, vc, None, None, None, None, None, pos.reshape(-1).contiguous(), B, n, H, H, D,
-                               params.blobs[0] if params is not None else None, kv_len if params is None else 0, dtype=dtype, rope_table=table)
+                               params.blobs[0] if params is not None else None, kv_len if params is None else 0, dtype=dtype, rope_table=table,
+                               one_head=one_head)
     torch.cuda.synchronize()
     fr = freqs[pos.clamp(max=freqs.shape[0] - 1)]
     xq, xk, xv = x.view(B, n, 3 * H, D).split([H, H, H], dim=2)
@@ -88,13 +89,11 @@ def test_f2_rope_table_many_rows_slot_blobs(D, dtype, rows, H):
 
 
 @pytest.mark.parametrize("D", [64, 128])
-def test_f2_rope_table_many_rows_forms_agree(D, monkeypatch):
-    """the four-heads-per-wave kernel and the one-head kernel (SJD_F2_ROWS=0, read per launch) write the same bits"""
+def test_f2_rope_table_many_rows_forms_agree(D):
+    """the four-heads-per-wave kernel and the one-head kernel (one_head=True: SJD_F2_ONE_HEAD) write the same bits"""
     a = _f2_many(D, torch.bfloat16, 256, 4, slots=[150, 171])
-    monkeypatch.setenv("SJD_F2_ROWS", "0")
-    b = _f2_many(D, torch.bfloat16, 256, 4, slots=[150, 171])
-    c = _f2_many(D, torch.float16, 96, 4)
-    monkeypatch.delenv("SJD_F2_ROWS")
+    b = _f2_many(D, torch.bfloat16, 256, 4, slots=[150, 171], one_head=True)
+    c = _f2_many(D, torch.float16, 96, 4, one_head=True)
     d = _f2_many(D, torch.float16, 96, 4)
     for u, v in zip(a + c, b + d):
         assert torch.equal(_bits(u), _bits(v))

@@ -114,8 +114,8 @@ def test_solver_refusals_for_several_prompts():
 
 def test_lib_version_and_mode_constants():
     hdr = open(os.path.join(ROOT, "include", "sjd_hip.h")).read()
-    assert int(re.search(r"#define SJD_VERSION (\d+)", hdr).group(1)) == 103
-    assert L.load().sjd_version() == 103
+    assert int(re.search(r"#define SJD_VERSION (\d+)", hdr).group(1)) == 104
+    assert L.load().sjd_version() == 104
     assert L.F2_ROPE_TABLE == int(re.search(r"#define SJD_F2_ROPE_TABLE (0x[0-9a-f]+)", hdr).group(1), 16) == 0x200
     assert "64 < B*n <= 256" in hdr
 

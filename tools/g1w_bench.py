@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""G1w (csrc/sjd_gemm_wide.h: the 65..256-row weight-streaming projection, round 6) against g1_skinny_gemm_tiled8 and hipBLASLt at the
-Lumina-7B layer shapes: hipGraph replays over several weight copies (every launch streams from HBM).  --check compares the planes bit for
+"""G1w (csrc/sjd_gemm_wide.h: the 65..256-row weight-streaming projection, round 6) against hipBLASLt at the Lumina-7B layer shapes (the
+g1_skinny_gemm_tiled8 leg went with the SJD_G1_WIDE switch; its figures are in profiles/r6_g1w_sweep_*.jsonl): hipGraph replays over several weight copies (every launch streams from HBM).  --check compares the planes bit for
 bit with the 32-row kernel first.  One JSON line per (shape, configuration)."""
 import argparse
 import ctypes
@@ -21,8 +21,6 @@ CAND = dict(qkv=[(2048, 3, 1), (2048, 4, 1), (2048, 8, 1), (1024, 8, 1), (832, 8
             o=[(1024, 2, 1), (896, 4, 1), (512, 4, 1), (1024, 4, 1), (2048, 2, 1), (1024, 3, 1)],
             gate_up=[(2048, 4, 1), (2048, 8, 1), (1376, 8, 1), (2048, 6, 1), (1376, 4, 1), (1024, 8, 1)],
             down=[(2752, 2, 1), (1408, 4, 1), (2752, 4, 1), (1376, 4, 1), (2752, 3, 1), (1408, 8, 1), (2752, 8, 1)])
-OLD = dict(qkv=(2048, 4, 1), o=(896, 4, 1), gate_up=(2048, 4, 1), down=(1376, 4, 1))          # backbones.G1_CFG_256ROW (round 5)
-OLD128 = dict(qkv=(2048, 4, 1), o=(896, 4, 1), gate_up=(2048, 8, 1), down=(1376, 4, 1))       # backbones.G1_CFG_128ROW
 VP = ctypes.c_void_p
 
 
@@ -56,7 +54,7 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("--variants", default="0", help="comma list of variants of sjd_skinny_gemm_wide (csrc/sjd_gemm.hip): 0 = the product's (stage 4 k-steps, 3 slots), 1 (4, 4), 10 eight waves, 20 two workgroups per CU (128 rows)")
     ap.add_argument("--check", action="store_true")
-    ap.add_argument("--no-old", action="store_true")
+    ap.add_argument("--no-old", action="store_true", help="accepted and ignored: the older kernels' leg is gone")
     ap.add_argument("--no-blas", action="store_true")
     ap.add_argument("--pad", type=int, default=0, help="row stride of x = K + pad elements (L2 channel spread experiment)")
     ap.add_argument("--trace", action="store_true", help="SJD_HIP_EXP_LIB is a -DSJD_TRACE build: per-workgroup wall / shader-clock stamps of the last launch")
@@ -69,7 +67,6 @@ def main():
                     o=[(512, 8, 0), (512, 4, 1), (1024, 2, 1), (1024, 4, 1), (512, 2, 1)],
                     gate_up=[(2048, 8, 1), (2048, 6, 1), (2048, 4, 1), (1024, 8, 1), (4096, 4, 1)],
                     down=[(896, 8, 0), (896, 8, 1), (1792, 4, 1), (1024, 4, 1), (2048, 4, 1), (1792, 8, 1)])
-        OLD128.update(qkv=(512, 8, 0), o=(512, 8, 0), gate_up=(2048, 8, 1), down=(896, 8, 0))      # backbones.G1_CFG_EMU3 (64-row windows)
     dev = torch.device("cuda:0")
     lib = L.load_exp()          # (the tuning entry sjd_skinny_gemm_wide lives in libsjd_hip_exp.so; SJD_HIP_EXP_LIB: a probe build of it)
     M = a.rows
@@ -88,18 +85,6 @@ def main():
         if not a.no_blas:
             us = timed_graph(lambda i: F.linear(xc, ws[i % a.copies]), a.launches)
             print(json.dumps(dict(shape=name, rows=M, kernel="hipblaslt", us=round(us, 2), TBps=round(bytes_w / us / 1e6, 3))), flush=True)
-        if not a.no_old:
-            KC, waves, sm = (OLD if M > 128 else OLD128)[name]
-            wps = [ops.pack_weight(w, KC, bool(sm)) for w in ws]
-            nc = (K + KC - 1) // KC
-            out = torch.empty(nc, ((M + 31) // 32) * 32, N, dtype=torch.float32, device=dev)
-            os.environ["SJD_G1_WIDE"] = "0"
-
-            def old(i):
-                L.check(lib.sjd_skinny_gemm(VP(xc.data_ptr()), VP(wps[i % a.copies].data_ptr()), VP(out.data_ptr()), M, N, K, KC, waves, sm, 0, stream()), "g1")
-            us = timed_graph(old, a.launches)
-            print(json.dumps(dict(shape=name, rows=M, kernel="tiled8", KC=KC, tiles=waves, planes=nc, us=round(us, 2), TBps=round(bytes_w / us / 1e6, 3))), flush=True)
-            del wps, out
         rows = []
         for (KC, tiles, sm) in cands:
             wps = [ops.pack_weight(w, KC, bool(sm)) for w in ws]

@@ -12,7 +12,7 @@
             at 1 (SJDEngine on the default packing: the one-prompt path), 2, 4 and 8 prompts per forward (packed with max_rows 64 / 128 / 256),
             all legs in one process on the same weights, timed in alternation over --rounds rounds (median and the per-round values reported),
             the fraction of 8 TB/s each step streams; then F2's table rotary at 256 rows, GPT-XL shape: four heads per wave against one
-            (SJD_F2_ROWS=0), us per launch from a hipGraph of back-to-back launches.
+            (SJD_F2_ONE_HEAD), us per launch from a hipGraph of back-to-back launches.
   --step    the fused step alone (one preset, --steps timed iterations): what the rocprofv3 by-shape table is taken from.
   --fused3b GPT-3B c2i 384px (24 layers, 32 heads of 100 stored 128 wide: enable_fused(pad_head_dim=True)), window 16, CFG, bf16: fused ms per SJD
             step over --rounds rounds (median), the packed bytes a step streams and their fraction of 8 TB/s.  No ATen leg: un-fused GPT-3B does
@@ -245,7 +245,7 @@ class _BatchLeg:
 
 
 def _f2_ab(dev, rows=256, H=20, D=64, hid=1280):
-    """F2's table rotary at `rows` rows, GPT-XL shape, planes source: us per launch, four heads per wave against one (SJD_F2_ROWS=0)"""
+    """F2's table rotary at `rows` rows, GPT-XL shape, planes source: us per launch, four heads per wave against one (SJD_F2_ONE_HEAD)"""
     g = torch.Generator(device=dev).manual_seed(2)
     S, N, n = 1216, 3 * H * D, 16
     B = rows // n
@@ -257,15 +257,10 @@ def _f2_ab(dev, rows=256, H=20, D=64, hid=1280):
     pos = (400 + torch.arange(n, device=dev))[None].repeat(B, 1).reshape(-1).contiguous()
     ss = torch.rand(3, rows, device=dev) * hid
     out = {}
-    for name, env in (("rows_kernel", None), ("one_head_kernel", "0"), ("rows_kernel_again", None)):
-        if env is None:
-            os.environ.pop("SJD_F2_ROWS", None)
-        else:
-            os.environ["SJD_F2_ROWS"] = env
+    for name, one_head in (("rows_kernel", False), ("one_head_kernel", True), ("rows_kernel_again", False)):
         fn = lambda i: ops.qknorm_rope_append(parts[i % copies], kc, vc, None, None, None, None, None, pos, B, n, H, H, D, None, 400,
-                                              dtype=torch.bfloat16, row_norm=(ss, hid, 1e-5), rope_table=table)
+                                              dtype=torch.bfloat16, row_norm=(ss, hid, 1e-5), rope_table=table, one_head=one_head)
         out[name] = round(_graph_us(fn, 4 * copies), 2)
-    os.environ.pop("SJD_F2_ROWS", None)
     return dict(shape=dict(rows=rows, H=H, D=D, planes=5), us_per_launch=out)
 
 

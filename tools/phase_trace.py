@@ -105,7 +105,7 @@ def trace_k1_shared(lib, torch, ops, np):
         t0 = t[:, 0].min()
         d = lambda a, b: us((t[:, b] - t[:, a]).mean())
         tiles = (kv + n + 31) // 32 / ns
-        print(json.dumps(dict(kernel=("k1_partial_shared<f16,128,8 waves>" if os.environ.get("SJD_K1_RING") == "0" else "k1_partial_ring<f16,128,8 waves>"), kv_len=kv, n_split=ns, workgroups=int(len(t)), tiles_per_workgroup=round(tiles, 1),
+        print(json.dumps(dict(kernel="k1_partial_ring<f16,128,8 waves>", kv_len=kv, n_split=ns, workgroups=int(len(t)), tiles_per_workgroup=round(tiles, 1),
                               phase_us=dict(tile_ranges=d(0, 1), first_tile=d(1, 2), key_loop=d(2, 3), publish=d(3, 5)),
                               key_loop_us_per_tile=round(d(2, 3) / max(tiles - 1, 1), 2),
                               end_us=dict(mean=us((t[:, 5] - t0).mean()), max=us((t[:, 5] - t0).max())))), flush=True)
@@ -355,7 +355,7 @@ def main():
         return
     if "--k2-emu3" in sys.argv:
         return trace_k2_emu3(lib, torch, ops, np)
-    if "--k1s" in sys.argv:          # the shared-tile K1 shapes only (round 4: the LDS-DMA ring kernel; SJD_K1_RING=0 the round-3 kernel)
+    if "--k1s" in sys.argv:          # the shared-tile K1 shapes only (round 4: the LDS-DMA ring kernel, the only one this product-source build has)
         trace_k1_shared(lib, torch, ops, np)
         return
     if "--g1s" in sys.argv:
