@@ -84,7 +84,8 @@ EXPORTS = ["sjd_version", "sjd_error_string", "sjd_reguess", "sjd_logits_to_prob
            "sjd_philox_fill", "sjd_philox_offset_increment", "sjd_skinny_gemm_z", "sjd_gateup_silu_z",
            "sjd_draft_window_attention_colsplit", "sjd_draft_window_attention_fp8_colsplit",
            "sjd_head_combine",
-           "sjd_reguess_slots", "sjd_logits_to_probs_sample_part_slots", "sjd_verify_accept_slots"]
+           "sjd_reguess_slots", "sjd_logits_to_probs_sample_part_slots", "sjd_verify_accept_slots",
+           "sjd_logits_to_probs_sample_part_slots_g", "sjd_head_combine_g"]
 # what include/sjd_hip_experimental.h adds: libsjd_hip_exp.so only (the measured no-go structures of rounds 2-5 and the G1w tuning entry)
 EXP_EXPORTS = ["sjd_weight_prefetch", "sjd_qkv_attention_fused", "sjd_qkv_attention_fused_split", "sjd_skinny_gemm_reduce", "sjd_reduce_timeouts",
                "sjd_draft_window_attention_merged", "sjd_draft_window_attention_fp8_merged", "sjd_mlp_pair_z", "sjd_mlp_pair_timeouts",
@@ -151,8 +152,10 @@ def _bind_product(lib):
     lib.sjd_skinny_gemm_cols.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.sjd_logits_to_probs_sample_part.argtypes = [ctypes.POINTER(HeadPartials), f32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.sjd_head_combine.argtypes = [ctypes.POINTER(HeadPartials), f32, i32, i32, vp, vp, vp]
+    lib.sjd_head_combine_g.argtypes = [ctypes.POINTER(HeadPartials), vp, i32, i32, vp, vp, vp]
     lib.sjd_reguess_slots.argtypes = [vp, vp, vp, i32, i32, vp, vp, ctypes.POINTER(Slots), vp]
     lib.sjd_logits_to_probs_sample_part_slots.argtypes = [ctypes.POINTER(HeadPartials), f32, i32, i32, vp, vp, vp, vp, ctypes.POINTER(Slots), vp]
+    lib.sjd_logits_to_probs_sample_part_slots_g.argtypes = [ctypes.POINTER(HeadPartials), vp, i32, i32, vp, vp, vp, vp, ctypes.POINTER(Slots), vp]
     lib.sjd_verify_accept_slots.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, ctypes.POINTER(Slots), vp]
     lib.sjd_logits_to_probs_sample_ex.argtypes = [vp, vp, i64, f32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.sjd_skinny_gemm_z.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(RawUnits), vp]

@@ -106,12 +106,15 @@ __device__ __forceinline__ void k2_row_scales(const sjd_head_partials &hp, int t
 // rounding (the grammar mask stays in K2).  Same operations in the same order as K2's own pass 1: bit-identical scores.  Used when the head's
 // window is wide (ops.logits_to_probs_sample_part): Emu3 K2 89.9 -> 71.7 + 7.2 us.
 __global__ __launch_bounds__(256) void k2a_head_combine(const sjd_head_partials hp, float guidance, int V, const sjd_iter_params *__restrict__ params,
-                                                        float *__restrict__ zbuf)
+                                                        float *__restrict__ zbuf, const float *__restrict__ guidance_dev)
 {
     const int row = blockIdx.y;
     const int c4 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;           // column offset inside the head's window (n_cols % 4 == 0)
     if (c4 >= hp.n_cols) return;
     const int n_rows_dev = params->n_rows, use_cfg_dev = params->use_cfg;
+    // the scale from device memory (guidance_dev: ONE value; NULL: the scalar argument) -- one uniform load, with the row count's, from a valid address either way
+    const float gd = *(guidance_dev ? guidance_dev : reinterpret_cast<const float *>(params));
+    guidance = guidance_dev ? gd : guidance;
     const bool two = hp.urow_off > 0;
     const float *c = hp.part + (size_t)row * hp.row_stride + c4;
     const float *u = hp.part + (size_t)(hp.urow_off + row) * hp.row_stride + c4;
@@ -164,7 +167,8 @@ template <bool PART, bool SLOTS = false>
 __global__ __launch_bounds__(SJD_TPB) void k2_logits_to_probs_sample(
     const float *__restrict__ logits_c, const float *__restrict__ logits_u, long row_stride, float guidance, int V,
     const sjd_iter_params *__restrict__ params, const float *__restrict__ noise, float *__restrict__ probs_out,
-    int64_t *__restrict__ tokens_out, const sjd_head_partials hp_arg, int64_t *__restrict__ amax_out, int lds_floats, const sjd_slots sb)
+    int64_t *__restrict__ tokens_out, const sjd_head_partials hp_arg, int64_t *__restrict__ amax_out, int lds_floats, const sjd_slots sb,
+    const float *__restrict__ guidance_slots)
 {
     __shared__ SjdShared sh;
     extern __shared__ __attribute__((aligned(16))) float sjd_dyn_lds[];      // round 4: the staged scores of a row too wide for registers
@@ -181,6 +185,10 @@ __global__ __launch_bounds__(SJD_TPB) void k2_logits_to_probs_sample(
         probs_out += s * (size_t)sb.probs_stride;
         tokens_out = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(tokens_out) + s * (size_t)sb.state_stride);
         if (amax_out) amax_out = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(amax_out) + s * (size_t)sb.state_stride);
+        // the slot's own guidance scale (guidance_slots[n_slots], device; NULL: the scalar argument serves every slot): ONE load, uniform for
+        // the workgroup, from a valid address either way (no branch: it rides with the first batch of loads below) -- never in the column loops
+        const float gs = *(guidance_slots ? guidance_slots + s : reinterpret_cast<const float *>(params));
+        guidance = guidance_slots ? gs : guidance;
     }
     const sjd_head_partials &hp = SLOTS ? hp_slot : hp_arg;
     const int row = blockIdx.x;
@@ -215,6 +223,7 @@ __global__ __launch_bounds__(SJD_TPB) void k2_logits_to_probs_sample(
     asm volatile("" :: "s"(zl), "s"(zh), "s"(use_cfg_dev), "s"(ph_blocks), "s"(ph_seed), "s"(ph_off), "s"(n_rows_dev),
                  "s"(rule.n_ranges), "s"(rule.forced), "s"(rule.temperature), "s"(sv[0]), "s"(sv[1]), "s"(sv[2]), "s"(sv[3]), "s"(sv[4]),
                  "s"(sv[5]), "s"(sv[6]), "s"(sv[7]), "s"(sw[0]), "s"(sw[1]), "s"(sw[2]), "s"(sw[3]), "s"(sw[4]), "s"(sw[5]), "s"(sw[6]), "s"(sw[7]));
+    if constexpr (SLOTS) asm volatile("" :: "s"(guidance));                 // (the slot's scale: wanted here too, with the same wait)
     if (row >= n_rows_dev) return;
     SJD_TRS(row, 1);              // first batch (row count, rule, statistics, zero state) arrived
     const int zlo = zst ? zl : -1, zhi = zst ? zh : -1;
@@ -944,7 +953,7 @@ extern "C" int sjd_logits_to_probs_sample_ex(const float *logits_c, const float 
     const int lds_floats = sjd_stage_lds_floats((long)V + 2 * SJD_DRAW_LIST);
     (void)hipFuncSetAttribute((const void *)k2_logits_to_probs_sample<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_floats * 4);
     hipLaunchKernelGGL(k2_logits_to_probs_sample<false>, dim3(max_rows), dim3(SJD_TPB), (size_t)lds_floats * 4, (hipStream_t)stream, logits_c, logits_u,
-                       (long)row_stride, guidance, V, params, noise, probs_out, tokens_out, none, amax_out, lds_floats, sjd_slots{});
+                       (long)row_stride, guidance, V, params, noise, probs_out, tokens_out, none, amax_out, lds_floats, sjd_slots{}, (const float *)nullptr);
     return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
 }
 
@@ -958,20 +967,34 @@ extern "C" int sjd_logits_to_probs_sample_part(const sjd_head_partials *head, fl
     const int lds_floats = sjd_stage_lds_floats((long)head->n_cols + 8 + 2 * SJD_DRAW_LIST);     // (the rows' windows lie inside the head's column window; + the draw list)
     (void)hipFuncSetAttribute((const void *)k2_logits_to_probs_sample<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_floats * 4);
     hipLaunchKernelGGL(k2_logits_to_probs_sample<true>, dim3(max_rows), dim3(SJD_TPB), (size_t)lds_floats * 4, (hipStream_t)stream, (const float *)nullptr,
-                       (const float *)nullptr, (long)0, guidance, V, params, noise, probs_out, tokens_out, *head, amax_out, lds_floats, sjd_slots{});
+                       (const float *)nullptr, (long)0, guidance, V, params, noise, probs_out, tokens_out, *head, amax_out, lds_floats, sjd_slots{}, (const float *)nullptr);
     return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
 }
 
-extern "C" int sjd_head_combine(const sjd_head_partials *head, float guidance, int max_rows, int V, const sjd_iter_params *params, float *z_out,
-                                void *stream)
+static int sjd_head_combine_launch(const sjd_head_partials *head, float guidance, const float *guidance_dev, int max_rows, int V,
+                                   const sjd_iter_params *params, float *z_out, void *stream)
 {
     if (!head || !head->part || head->n_chunks < 1 || head->n_cols < 4 || (head->n_cols & 3) || head->col0 < 0 || head->row_stride < head->n_cols) return SJD_ERR_BAD_ARG;
     if ((head->row_stride & 3) || (head->chunk_stride & 3) || ((uintptr_t)head->part & 15) || ((uintptr_t)z_out & 15)) return SJD_ERR_BAD_ARG;
     if (!params || !z_out || max_rows < 1 || max_rows > SJD_MAX_WINDOW || V < 1) return SJD_ERR_BAD_ARG;
     if (head->row_sumsq && (head->slices < 1 || head->prows < 1)) return SJD_ERR_BAD_ARG;
     const dim3 grid((head->n_cols / 4 + 255) / 256, max_rows);
-    hipLaunchKernelGGL(k2a_head_combine, grid, dim3(256), 0, (hipStream_t)stream, *head, guidance, V, params, z_out);
+    hipLaunchKernelGGL(k2a_head_combine, grid, dim3(256), 0, (hipStream_t)stream, *head, guidance, V, params, z_out, guidance_dev);
     return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+}
+
+extern "C" int sjd_head_combine(const sjd_head_partials *head, float guidance, int max_rows, int V, const sjd_iter_params *params, float *z_out,
+                                void *stream)
+{
+    return sjd_head_combine_launch(head, guidance, nullptr, max_rows, V, params, z_out, stream);
+}
+
+// the scale read from device memory (ONE float32, 4-byte aligned): a captured launch follows its contents
+extern "C" int sjd_head_combine_g(const sjd_head_partials *head, const float *guidance, int max_rows, int V, const sjd_iter_params *params,
+                                  float *z_out, void *stream)
+{
+    if (!guidance || ((uintptr_t)guidance & 3)) return SJD_ERR_BAD_ARG;
+    return sjd_head_combine_launch(head, 0.0f, guidance, max_rows, V, params, z_out, stream);
 }
 
 extern "C" int sjd_verify_accept_ex(const sjd_iter_params *params, sjd_state *state, const float *probs, const float *prev_probs,
@@ -1009,8 +1032,9 @@ extern "C" int sjd_reguess_slots(const sjd_iter_params *params0, sjd_state *stat
     return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
 }
 
-extern "C" int sjd_logits_to_probs_sample_part_slots(const sjd_head_partials *head, float guidance, int max_rows, int V, const sjd_iter_params *params0,
-                                                     float *probs_out0, int64_t *tokens_out0, int64_t *amax_out0, const sjd_slots *slots, void *stream)
+static int sjd_k2_slots_launch(const sjd_head_partials *head, float guidance, const float *guidance_slots, int max_rows, int V,
+                               const sjd_iter_params *params0, float *probs_out0, int64_t *tokens_out0, int64_t *amax_out0, const sjd_slots *slots,
+                               void *stream)
 {
     if (!head || !head->part || head->n_chunks < 1 || head->n_cols < 1 || head->col0 < 0 || head->row_stride < head->n_cols) return SJD_ERR_BAD_ARG;
     if (!params0 || !probs_out0 || !tokens_out0 || max_rows < 1 || max_rows > SJD_MAX_WINDOW || V < 1) return SJD_ERR_BAD_ARG;
@@ -1022,8 +1046,23 @@ extern "C" int sjd_logits_to_probs_sample_part_slots(const sjd_head_partials *he
     (void)hipFuncSetAttribute((const void *)k2_logits_to_probs_sample<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_floats * 4);
     hipLaunchKernelGGL((k2_logits_to_probs_sample<true, true>), dim3(max_rows, slots->n_slots), dim3(SJD_TPB), (size_t)lds_floats * 4, (hipStream_t)stream,
                        (const float *)nullptr, (const float *)nullptr, (long)0, guidance, V, params0, (const float *)nullptr, probs_out0, tokens_out0, *head,
-                       amax_out0, lds_floats, *slots);
+                       amax_out0, lds_floats, *slots, guidance_slots);
     return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+}
+
+extern "C" int sjd_logits_to_probs_sample_part_slots(const sjd_head_partials *head, float guidance, int max_rows, int V, const sjd_iter_params *params0,
+                                                     float *probs_out0, int64_t *tokens_out0, int64_t *amax_out0, const sjd_slots *slots, void *stream)
+{
+    return sjd_k2_slots_launch(head, guidance, nullptr, max_rows, V, params0, probs_out0, tokens_out0, amax_out0, slots, stream);
+}
+
+// slot s combines with guidance[s] (device float32 [slots->n_slots], 4-byte aligned), otherwise the launch above
+extern "C" int sjd_logits_to_probs_sample_part_slots_g(const sjd_head_partials *head, const float *guidance, int max_rows, int V,
+                                                       const sjd_iter_params *params0, float *probs_out0, int64_t *tokens_out0, int64_t *amax_out0,
+                                                       const sjd_slots *slots, void *stream)
+{
+    if (!guidance || ((uintptr_t)guidance & 3)) return SJD_ERR_BAD_ARG;
+    return sjd_k2_slots_launch(head, 0.0f, guidance, max_rows, V, params0, probs_out0, tokens_out0, amax_out0, slots, stream);
 }
 
 extern "C" int sjd_verify_accept_slots(const sjd_iter_params *params0, sjd_state *state0, const float *probs0, const float *prev_probs0, float *scratch0,

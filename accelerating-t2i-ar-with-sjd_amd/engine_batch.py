@@ -17,6 +17,7 @@ transformer forward is shared:
 
 A slot that reaches its end token keeps riding along with a one-row dummy window (its tokens are ignored) until every slot is done.
 """
+import dataclasses
 import time
 from typing import List
 
@@ -38,6 +39,42 @@ class _CacheView:
 
 class _Slot:
     pass
+
+
+# what the prompts of one decode_many may NOT differ in: the window iterations run in lock-step through one set of launches, one scheme, one noise
+# source.  guidance_scale and seed are per prompt (temperature / top-p / top-k already are: they live in each prompt's grammar); do_cfg may differ
+# as long as "CFG on" (below) does not.
+_PER_PROMPT_FIELDS = ("guidance_scale", "seed", "do_cfg")
+_CFG_ON = "do_cfg and guidance_scale != 1"
+
+
+def _cfg_on(c):
+    return bool(c.do_cfg and (c.guidance_scale != 1))
+
+
+def per_prompt_configs(cfg, n_prompts):
+    """decode_many's `cfg` -> (the config every shared field is read from, None | the N per-prompt configs).  A sequence must hold one SJDConfig
+    per prompt; every field except guidance_scale / seed / do_cfg must agree, and so must "CFG on" (it fixes the batch rows per slot)."""
+    if isinstance(cfg, SJDConfig):
+        return cfg, None
+    cfgs = list(cfg)
+    if len(cfgs) != n_prompts:
+        raise ValueError(f"decode_many got {len(cfgs)} configs for {n_prompts} prompts: pass one SJDConfig, or one per prompt")
+    for j, c in enumerate(cfgs):
+        if not isinstance(c, SJDConfig):
+            raise ValueError(f"config of prompt {j} is {type(c).__name__}, not an SJDConfig")
+    for f in dataclasses.fields(SJDConfig):
+        if f.name in _PER_PROMPT_FIELDS:
+            continue
+        for j, c in enumerate(cfgs[1:], 1):
+            if getattr(c, f.name) != getattr(cfgs[0], f.name):
+                raise ValueError(f"SJDConfig.{f.name} must agree across the prompts of one decode_many, but prompt 0 has "
+                                 f"{getattr(cfgs[0], f.name)!r} and prompt {j} has {getattr(c, f.name)!r}")
+    for j, c in enumerate(cfgs[1:], 1):
+        if _cfg_on(c) != _cfg_on(cfgs[0]):
+            raise ValueError(f"'{_CFG_ON}' (CFG on / off: the batch rows of a slot) must agree across the prompts of one decode_many, but it is "
+                             f"{_cfg_on(cfgs[0])} for prompt 0 and {_cfg_on(c)} for prompt {j}: mixing CFG-on and CFG-off prompts is not served")
+    return cfgs[0], cfgs
 
 
 class SJDBatchEngine:
@@ -115,6 +152,11 @@ class SJDBatchEngine:
         self.kv_len_dev = self.params.dev.view(torch.int32)[off // 4::nb_params // 4]
         self.row_slot = torch.arange(self.B, device=dev) // n_batch
         self._guidance = 3.0
+        # one guidance scale per SLOT, for a decode_many whose prompts differ in it: K2's slot launch reads the device array (captured graphs point
+        # at it, so it exists before the first capture), an admission writes the slot's element of the pinned twin and uploads it behind the blob
+        self._guid_host = torch.zeros(self.P, dtype=torch.float32, pin_memory=True)
+        self._guid_dev = torch.zeros(self.P, dtype=torch.float32, device=dev)
+        self._mixed_guidance = False
         # K2 reads the output head's split-K partials (no fp32 logits tensor) when the backbone can produce them
         self.head_partials = bool(head_partials) and getattr(backbone, "supports_head_partials", False)
         self._dbg = None                       # [B, L, V] logits as K2 derived them; allocated only for observers (hook)
@@ -227,10 +269,12 @@ class SJDBatchEngine:
                 self._dbg = torch.zeros(self.B, self.Lmax, self.V, dtype=torch.float32, device=self.device)
             dbg = self._dbg
             dbg.zero_()
+        wide = part and not ops.head_slots_ok(logits)          # a head wide enough for K2a: it runs in front of every slot's own K2
         def k2_k4(i, s):
             tok_out, amax_out = (s.amax_ptr, s.tokens_ptr) if getattr(self, "_greedy", False) else (s.tokens_ptr, s.amax_ptr)
-            if part:
-                ops.logits_to_probs_sample_part(logits, self._guidance, s.params, None, s.probs[cur], tok_out, amax_out_ptr=amax_out,
+            if part:               # (different scales: K2a reads the slot's element of the engine's array -- a wide head, see below)
+                g = self._guid_dev[i:i + 1] if self._mixed_guidance else self._guidance
+                ops.logits_to_probs_sample_part(logits, g, s.params, None, s.probs[cur], tok_out, amax_out_ptr=amax_out,
                                                 dbg=None if dbg is None else dbg[i * self.nb:(i + 1) * self.nb], row0=i * self.nb * self.Lmax,
                                                 urow_off=self.Lmax if self.nb > 1 else 0, zero_state=s.zero_state[cur])
             else:
@@ -240,17 +284,35 @@ class SJDBatchEngine:
                                            amax_out_ptr=amax_out)
                 s.zero_state[cur].fill_(-1)
             ops.verify_accept(s.params, s.state, s.probs[cur], s.probs[1 - cur], None, None, s.scratch, mirror=True)
-        if self.slot_launches and part and ops.head_slots_ok(logits):
+        if self.slot_launches and part and not wide:
             # one K2 and one K4 launch for all slots (a workgroup per (row, slot) / per slot): eight prompts 8 x (28 + 24) us -> one of each
             greedy = getattr(self, "_greedy", False)
             sl = self._slots_desc
             if dbg is not None:
                 sl = ops.slots_of(self.params, self.state, self.probs_all, self.zero_state_all, self.scratch_all, self.nb, dbg=dbg)
-            ops.logits_to_probs_sample_part_slots(sl, logits, self._guidance, self.params, self.probs_all, cur, "amax" if greedy else "tokens",
+            g = self._guid_dev if self._mixed_guidance else self._guidance
+            ops.logits_to_probs_sample_part_slots(sl, logits, g, self.params, self.probs_all, cur, "amax" if greedy else "tokens",
                                                   "tokens" if greedy else "amax", self.state, self.zero_state_all, self.nb, dbg=dbg)
             ops.verify_accept_slots(sl, self.params, self.state, self.probs_all, cur, self.scratch_all)
             return
+        if not wide:                                               # (a wide head: K2a takes the scale by pointer)
+            self._refuse_mixed_guidance_per_slot()
         self._per_slot(k2_k4)
+
+    def _guidance_key(self):
+        """the guidance part of a graph key: the scale itself (baked into the captured launches), or -- prompts with different scales -- a constant:
+        the captured K2 reads the engine's array, whatever it holds"""
+        return "per-slot array" if self._mixed_guidance else self._guidance
+
+    def _refuse_mixed_guidance_per_slot(self, why=None):
+        """Different guidance scales in one batch are served by the ONE K2 launch over all slots (sjd_logits_to_probs_sample_part_slots_g) and,
+        for a head window wide enough for K2a (LlamaGen's 16384 columns, Emu3), by K2a in front of every slot's K2 (sjd_head_combine_g): both read
+        the engine's array.  The one-slot K2 over a NARROW head (SJD_SLOT_LAUNCHES=0) or over dense logits bakes one scalar into its graphs:
+        refused, never decoded with the first prompt's value (cut line)."""
+        if self._mixed_guidance:
+            raise ValueError("prompts with different guidance scales need K2 as one launch over all slots or K2a in front of it, but this engine "
+                             "launches K2 per slot over " + (why or "a narrow head window (SJD_SLOT_LAUNCHES=0)") + ": decode prompts of one "
+                             "guidance scale per decode_many on this configuration")
 
     def _launch_forward(self, cols):
         if not self.use_graph:
@@ -269,7 +331,7 @@ class SJDBatchEngine:
         return self._graph_logits[fkey]
 
     def _launch_sample(self, cur, logits, cols):
-        key = (cur, self._guidance, cols, self.hook is not None, getattr(self, "_greedy", False))
+        key = (cur, self._guidance_key(), cols, self.hook is not None, getattr(self, "_greedy", False))
         if not self.use_graph or ("fwd", cols) not in self._graphs:
             self._sample_body(cur, logits, cols)
             return
@@ -289,7 +351,7 @@ class SJDBatchEngine:
             self._sample_body(cur, logits, cols)
             return logits
         self._check_graph_buffers()
-        key = ("win", cols, cur, self._guidance, self.hook is not None, getattr(self, "_greedy", False))
+        key = ("win", cols, cur, self._guidance_key(), self.hook is not None, getattr(self, "_greedy", False))
         if key not in self._graphs:
             if self._eager_runs.get(key, 0) < 1:
                 self._eager_runs[key] = 1
@@ -329,10 +391,12 @@ class SJDBatchEngine:
 
     # ------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def decode_many(self, prompts: List[List[int]], specs: List[WindowSpec], grammars, cfg: SJDConfig, seeds=None,
+    def decode_many(self, prompts: List[List[int]], specs: List[WindowSpec], grammars, cfg, seeds=None,
                     warmup_iters=0, timed_iters=None, on_timed_start=None, on_timed_end=None):
-        """One SJDConfig for all prompts (seed = cfg.seed + prompt index unless `seeds` is given).  Returns [(sequence, DecodeStats)] in
-        prompt order; with timed_iters the stats cover window iterations [warmup_iters, warmup_iters + timed_iters).
+        """cfg: one SJDConfig for all prompts (seed = cfg.seed + prompt index unless `seeds` is given), or a sequence of N, one per prompt: prompt
+        j then decodes with cfg[j].guidance_scale and cfg[j].seed (as given: no index is added) -- exactly what it would decode alone with that
+        config; the other fields must agree (per_prompt_configs).  Temperature, top-p and top-k are per prompt through `grammars`.  Returns
+        [(sequence, DecodeStats)] in prompt order; with timed_iters the stats cover window iterations [warmup_iters, warmup_iters + timed_iters).
 
         len(prompts) may exceed the number of slots (continuous batching): a slot whose prompt reached its end token is handed the next
         prompt of the list -- state machine, grammar and generators re-created, its KV rows reused from 0, its prompt prefilled eagerly
@@ -340,9 +404,14 @@ class SJDBatchEngine:
         list is exhausted does a finished slot ride along with a one-row dummy window."""
         # GenerationConfig(do_sample=False): K2's MODE of p goes where its draw would (state.tokens; the draw lands in state.amax and is ignored),
         # nothing is consumed from a slot's generator for it, the verify step's draws follow at once (SJDEngine.decode, JL:124-129)
+        N = len(prompts)
+        cfg, cfgs = per_prompt_configs(cfg, N)
+        # prompts that all share one scale (a list of equal configs included) take the scalar launches and graph keys of a single config
+        self._mixed_guidance = cfgs is not None and len({float(c.guidance_scale) for c in cfgs}) > 1
+        if not self.head_partials:
+            self._refuse_mixed_guidance_per_slot("dense logits (the backbone hands out no head partials)")
         self._greedy = greedy = not getattr(cfg, "do_sample", True)
         k2_draws = 0 if greedy else 1
-        N = len(prompts)
         assert len(specs) == len(grammars) == N and N >= self.P
         if cfg.multi_token_init_scheme not in ("random", "repeat_horizon", "sample_horizon"):
             raise ValueError(f"multi_token_init_scheme should be 'random', 'repeat_horizon' or 'sample_horizon', but got {cfg.multi_token_init_scheme}")
@@ -360,11 +429,12 @@ class SJDBatchEngine:
         do_cfg = cfg.do_cfg and (cfg.guidance_scale != 1)
         W = cfg.max_num_new_tokens
         self._guidance = float(cfg.guidance_scale)
+        prompt_seed = lambda j: cfgs[j].seed if cfgs is not None else (None if cfg.seed is None else cfg.seed + j)
         attn = getattr(self.backbone, "attn", None)
         full_cache = self.backbone.cache
         results = [None] * N
         pre_seeds = None
-        if seeds is None and cfg.seed is None and any(getattr(sp, "cond_embeds", None) is not None for sp in specs):
+        if seeds is None and any(prompt_seed(j) is None for j in range(N)) and any(getattr(sp, "cond_embeds", None) is not None for sp in specs):
             # no seed: the N per-prompt seeds are drawn from the default generator UP FRONT, in prompt order -- a prompt's first token (drawn at
             # its admission) then depends neither on the number of slots nor on which slot finished first
             pre_seeds = [int(t) for t in torch.randint(0, 2 ** 62, (N,), device=dev, generator=default_gen).tolist()]
@@ -379,7 +449,12 @@ class SJDBatchEngine:
             j, s = next_prompt, self.slots[i]
             next_prompt += 1
             s.prompt_index = j
-            seed = (seeds[j] if seeds is not None else (None if cfg.seed is None else cfg.seed + j))
+            seed = seeds[j] if seeds is not None else prompt_seed(j)
+            guidance = float(cfgs[j].guidance_scale) if cfgs is not None else self._guidance
+            if self._mixed_guidance:            # the slot's scale goes up stream-ordered, like its blob below: no synchronisation of its own
+                self._guid_host[i] = guidance
+                L.check(L.load().sjd_upload_async(self._guid_dev.data_ptr() + 4 * i, self._guid_host.data_ptr() + 4 * i, 4, ops._stream()),
+                        "sjd_upload_async")
             cond = getattr(specs[j], "cond_embeds", None)
             self.key_start[i * nb:(i + 1) * nb].copy_(specs[j].key_start.to(device=dev, dtype=torch.int32))
             first_tok = None
@@ -388,7 +463,7 @@ class SJDBatchEngine:
                 # first image token comes from the last row's logits, drawn from the PROMPT's generator (seed + j, or its up-front seed)
                 from .llamagen_solver import sample as _lg_sample
                 sk = dict(specs[j].cond_sampling or {})
-                scale = float(sk.pop("cfg_scale", self._guidance))
+                scale = float(sk.pop("cfg_scale", guidance))
                 T = cond.shape[1]
                 if specs[j].kv_base != T:
                     raise ValueError(f"WindowSpec.cond_embeds has {T} rows but kv_base = {specs[j].kv_base}: the window starts behind the conditioning")
@@ -448,7 +523,7 @@ class SJDBatchEngine:
             lc = logits[0, -1:, :]
             lu = logits[1, -1:, :] if nb > 1 else None
             tok_out, amax_out = (s.amax_ptr, s.tokens_ptr) if greedy else (s.tokens_ptr, s.amax_ptr)
-            ops.logits_to_probs_sample(lc, lu, self._guidance, s.params, None, s.probs[buf], tok_out, amax_out_ptr=amax_out)
+            ops.logits_to_probs_sample(lc, lu, guidance, s.params, None, s.probs[buf], tok_out, amax_out_ptr=amax_out)
             s.zero_state[buf].fill_(-1)
             ops.verify_accept(s.params, s.state, s.probs[buf], s.probs[1 - buf], None, None, s.scratch, mirror=True)
             s.ph_off += s.ph_step * k2_draws                       # the [1, V] multinomial of iteration 0 (greedy: none)

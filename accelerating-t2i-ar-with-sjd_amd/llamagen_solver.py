@@ -118,6 +118,28 @@ def generate(model, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cfg_int
     return seq
 
 
+_PER_PROMPT_ARGS = ("cfg_scale", "temperature", "top_k", "top_p")
+
+
+def per_prompt_values(name, value, n_prompts):
+    """generate()'s cfg_scale / temperature / top_k / top_p: a number -> None (one value for every prompt, as ever); a sequence or 1-d tensor ->
+    its n_prompts Python numbers, one per prompt.  Raises ValueError for a wrong length and for a sequence with one prompt per call."""
+    if isinstance(value, torch.Tensor):
+        if value.ndim == 0:
+            return None
+        value = value.flatten().tolist()
+    elif hasattr(value, "tolist") and getattr(value, "ndim", 0) >= 1:          # numpy
+        value = value.tolist()
+    if not isinstance(value, (list, tuple)):
+        return None
+    if n_prompts <= 1:
+        raise ValueError(f"{name} was given as a sequence of {len(value)} values, but generate() got one prompt: a value per prompt needs "
+                         "several prompts per call (pass a number)")
+    if len(value) != n_prompts:
+        raise ValueError(f"{name} has {len(value)} values for {n_prompts} prompts: pass one number, or one per prompt")
+    return list(value)
+
+
 class MaxlenCriteria:
     """reference LS:341-347"""
 
@@ -157,9 +179,14 @@ class LlamaGenSolver:
         # from CPU generators (the golden fixtures were produced by CPU runs of the reference)
         self.noise_device = noise_device
 
-    def create_logits_processor(self):
-        from transformers.generation.logits_process import LogitsProcessorList
-        return LogitsProcessorList([TopKLogitsWarper(top_k=self.image_top_k), TopPLogitsWarper3d(top_p=self.image_top_p)])
+    def create_logits_processor(self, top_k=None, top_p=None, temperature=None):
+        """top_k / top_p / temperature: one prompt's own values (generate() with a value per prompt); None: the solver's, temperature 1"""
+        from transformers.generation.logits_process import LogitsProcessorList, TemperatureLogitsWarper
+        procs = [TopKLogitsWarper(top_k=self.image_top_k if top_k is None else int(top_k)),
+                 TopPLogitsWarper3d(top_p=self.image_top_p if top_p is None else float(top_p))]
+        if temperature is not None and float(temperature) != 1.0:          # ahead of top-p: the order of `sample` (and of the kernels)
+            procs.insert(0, TemperatureLogitsWarper(float(temperature)))
+        return LogitsProcessorList(procs)
 
     @torch.no_grad()
     def prefill(self, cond_combined, cfg_scale, **sampling_kwargs):
@@ -180,9 +207,13 @@ class LlamaGenSolver:
 
     @torch.no_grad()
     def generate(self, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cfg_interval=-1, **sampling_kwargs):
+        """cond with N > 1 prompts: cfg_scale, temperature, top_k and top_p each take a number (as ever) or N values, one per prompt
+        (_generate_many)."""
         model = self.model
         if cond.shape[0] > 1:
             return self._generate_many(cond, max_new_tokens, emb_masks, cfg_scale, **sampling_kwargs)
+        for name in _PER_PROMPT_ARGS:
+            per_prompt_values(name, cfg_scale if name == "cfg_scale" else sampling_kwargs.get(name), 1)
         if model.model_type == 'c2i':
             cond_combined = torch.cat([cond, torch.ones_like(cond) * model.num_classes]) if cfg_scale > 1.0 else cond
             T = 1
@@ -226,10 +257,18 @@ class LlamaGenSolver:
 
     def _generate_many(self, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, **sampling_kwargs):
         """N > 1 prompts (class ids [N], or caption embeddings [N, T, C] with emb_masks [N, T]): slots_for(N) of them share every window
-        forward (SJDBatchEngine), the rest enter as slots finish.  Returns LongTensor [N, max_new_tokens] in prompt order."""
+        forward (SJDBatchEngine), the rest enter as slots finish.  Returns LongTensor [N, max_new_tokens] in prompt order.
+
+        cfg_scale / temperature / top_k / top_p as numbers mean what they mean for one prompt: the settings of the FIRST image token's draw (the
+        windows use the sampler's guidance_scale and the solver's image_top_k / image_top_p).  Given as N values, value j is prompt j's setting
+        for its whole decode: its first draw AND its windows (guidance scale in K2, temperature / top-k / top-p in its rules), so a batch may
+        mix them; prompt j then equals what it gives decoded alone with those settings and seed + j."""
         from .engine import WindowSpec
         model = self.model
         N, dev = cond.shape[0], cond.device
+        scales = per_prompt_values("cfg_scale", cfg_scale, N)
+        per = {k: per_prompt_values(k, sampling_kwargs[k], N) for k in _PER_PROMPT_ARGS[1:] if k in sampling_kwargs}
+        per = {k: v for k, v in per.items() if v is not None}
         if getattr(model, "_ops", None) is None:
             raise ValueError(f"generate() with {N} prompts runs on the fused HIP path only: call model.enable_fused(ops, gemm='sjd', "
                              "max_rows=128 or 256) first, or generate one prompt per call")
@@ -237,8 +276,10 @@ class LlamaGenSolver:
             raise ValueError(f"generate() with {N} prompts draws its noise in the kernels: noise_device={self.noise_device!r} is served for "
                              "one prompt per call only (use noise_device=None)")
         do_cfg = bool(model.do_cfg) and (model.guidance_scale != 1)
-        if do_cfg != (cfg_scale > 1.0):
-            raise ValueError(f"cfg_scale {cfg_scale} at prefill must match do_cfg / guidance_scale of the sampler (do_cfg={do_cfg})")
+        for j, sc in enumerate([cfg_scale] if scales is None else scales):
+            if do_cfg != (sc > 1.0):
+                raise ValueError(f"cfg_scale {sc}" + ("" if scales is None else f" of prompt {j}") + " at prefill must match do_cfg / guidance_scale "
+                                 f"of the sampler (do_cfg={do_cfg}): a batch is CFG-on or CFG-off as a whole")
         nb = 2 if do_cfg else 1
         if model.model_type == 'c2i':
             T = 1
@@ -267,12 +308,15 @@ class LlamaGenSolver:
             else:
                 ks = torch.zeros(nb, dtype=torch.int32)
             specs.append(WindowSpec(first_tokens=None, first_positions=None, key_start=ks, pos_offset=torch.zeros(nb, dtype=torch.long),
-                                    kv_base=T, cond_embeds=model.embed_condition(cc), cond_sampling=dict(cfg_scale=cfg_scale, **sampling_kwargs)))
+                                    kv_base=T, cond_embeds=model.embed_condition(cc),
+                                    cond_sampling=dict(sampling_kwargs, cfg_scale=cfg_scale if scales is None else float(scales[j]),
+                                                       **{k: v[j] for k, v in per.items()})))
         from transformers import GenerationConfig
         generation_config = GenerationConfig(max_new_tokens=T + max_new_tokens, max_length=T + max_new_tokens, temperature=1.0,
                                              top_k=None, do_sample=True, return_dict_in_generate=False)
-        outputs = model._sample_many(specs, [self.create_logits_processor() for _ in range(N)], [MaxlenCriteria(max_new_tokens)],
-                                     generation_config, slots)
+        procs = [self.create_logits_processor(**{k: v[j] for k, v in per.items()}) for j in range(N)]
+        outputs = model._sample_many(specs, procs, [MaxlenCriteria(max_new_tokens)], generation_config, slots,
+                                     guidance_scales=None if scales is None else [float(x) for x in scales])
         generated = outputs[:, -max_new_tokens:]
         model.clear_kvcache()
         return generated

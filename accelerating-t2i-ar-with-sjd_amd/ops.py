@@ -717,7 +717,8 @@ def logits_to_probs_sample_part(head: HeadOut, guidance, params: DeviceBlob, noi
                                 row0=0, urow_off=None, zero_state=None):
     """K2 reading the unmaterialised output head (see sjd_head_partials in include/sjd_hip.h).  dbg: optional fp32 [2, rows, V] that
     receives the logits K2 derived (cond, uncond) -- observers only.  row0 / urow_off: this launch's cond rows start at partial row
-    `row0` and its uncond rows `urow_off` rows further (several prompts share one head launch: SJDBatchEngine)."""
+    `row0` and its uncond rows `urow_off` rows further (several prompts share one head launch: SJDBatchEngine).  guidance: a float, or -- for a
+    head wide enough for K2a only -- ONE device float32 (a 1-element tensor) that K2a reads at run time (sjd_head_combine_g)."""
     max_rows, V = probs_out.shape
     hp = _head_partials(head, max_rows, V, probs_out.device, dbg, row0, urow_off, zero_state)
     p = head.part
@@ -727,12 +728,22 @@ def logits_to_probs_sample_part(head: HeadOut, guidance, params: DeviceBlob, noi
         # K2a (round 4): a WIDE head window (Emu3: 32768 columns x 2 planes x 2 rows = 524 KB per row) is combined into guided scores on the whole
         # chip first; K2 then reads ONE plane per row -- bit-identical scores (sjd_head_combine in include/sjd_hip.h)
         z = torch.empty(max_rows, p.N, dtype=torch.float32, device=probs_out.device)
-        L.check(L.load().sjd_head_combine(ctypes.byref(hp), float(guidance), max_rows, V, params.ptr, _ptr(z), _stream()), "sjd_head_combine")
+        if isinstance(guidance, torch.Tensor):
+            if not (guidance.dtype == torch.float32 and guidance.numel() == 1 and guidance.device == probs_out.device):
+                raise ValueError(f"guidance scale in device memory: one float32 on {probs_out.device}, got {tuple(guidance.shape)} {guidance.dtype} "
+                                 f"on {guidance.device}")
+            L.check(L.load().sjd_head_combine_g(ctypes.byref(hp), _ptr(guidance), max_rows, V, params.ptr, _ptr(z), _stream()), "sjd_head_combine_g")
+            guidance = 0.0                  # (K2 below reads ONE plane, no uncond row: it combines nothing)
+        else:
+            L.check(L.load().sjd_head_combine(ctypes.byref(hp), float(guidance), max_rows, V, params.ptr, _ptr(z), _stream()), "sjd_head_combine")
         h2 = L.HeadPartials()
         h2.part, h2.n_chunks, h2.row_stride, h2.chunk_stride = z.data_ptr(), 1, p.N, max_rows * p.N
         h2.col0, h2.n_cols, h2.urow_off, h2.round_dtype = hp.col0, hp.n_cols, 0, 2            # SJD_DTYPE_F32: no rounding, no scale, no uncond row
         h2.zero_state = hp.zero_state
         hp = h2
+    if isinstance(guidance, torch.Tensor):
+        raise ValueError("a guidance scale in device memory is served for heads wide enough for K2a (sjd_head_combine_g) and by the slot launch "
+                         "(logits_to_probs_sample_part_slots); the one-slot K2 over a narrow head takes a float")
     L.check(L.load().sjd_logits_to_probs_sample_part(ctypes.byref(hp), float(guidance), max_rows, V, params.ptr, _ptr(noise), _ptr(probs_out),
                                                     tokens_out_ptr, amax_out_ptr, _stream()), "sjd_logits_to_probs_sample_part")
 
@@ -789,15 +800,16 @@ def reguess_slots(slots, params: "BlobArray", state: "BlobArray", input_ids_out,
 
 def head_slots_ok(head: "HeadOut"):
     """the *_slots K2 launch reads the head's planes itself: a head wide enough for K2a (Emu3) keeps the per-slot launches"""
-    p = head.part
-    return not (p.N >= _HEAD_COMBINE_MIN_COLS and p.N % 4 == 0 and p.data.data_ptr() % 16 == 0)
+    return not head_combine_ok(_head_partials(head, 0, 0, None))      # (the predicate logits_to_probs_sample_part itself decides with)
 
 
 def logits_to_probs_sample_part_slots(slots, head: "HeadOut", guidance, params: "BlobArray", probs, cur, tokens_field, amax_field, state: "BlobArray",
                                       zero_state, n_batch, dbg=None):
     """K2 of every slot in one launch (see logits_to_probs_sample_part): slot s reads the cond rows [s * n_batch * L, ...) of the shared head launch
     and its uncond rows L further (n_batch 2), writes probs[s, cur] and the int64 rows `tokens_field` / `amax_field` (names of sjd_state fields,
-    amax_field may be None) of its state."""
+    amax_field may be None) of its state.  guidance: a float for every slot (sjd_logits_to_probs_sample_part_slots, as ever), or a device float32
+    tensor of n_slots values, slot s combining with guidance[s] (sjd_logits_to_probs_sample_part_slots_g: the launch reads the array, so a
+    captured graph follows a later change of its contents)."""
     P, _, max_rows, V = probs.shape
     hp = _head_partials(head, max_rows, V, probs.device, None, 0, max_rows if n_batch > 1 else 0, zero_state[0, cur])
     if dbg is not None:
@@ -805,6 +817,14 @@ def logits_to_probs_sample_part_slots(slots, head: "HeadOut", guidance, params: 
         if n_batch > 1:
             hp.dbg_u = dbg[1].data_ptr()
     s0 = state.blobs[0]
+    if isinstance(guidance, torch.Tensor):
+        if not (guidance.dtype == torch.float32 and guidance.is_contiguous() and guidance.numel() == slots.n_slots and guidance.device == probs.device):
+            raise ValueError(f"per-slot guidance scales: a contiguous float32 tensor of {slots.n_slots} values on {probs.device}, got "
+                             f"{tuple(guidance.shape)} {guidance.dtype} on {guidance.device}")
+        L.check(L.load().sjd_logits_to_probs_sample_part_slots_g(ctypes.byref(hp), _ptr(guidance), max_rows, V, params.ptr, _ptr(probs[0, cur]),
+                                                                s0.field_ptr(tokens_field), s0.field_ptr(amax_field) if amax_field else None,
+                                                                ctypes.byref(slots), _stream()), "sjd_logits_to_probs_sample_part_slots_g")
+        return
     L.check(L.load().sjd_logits_to_probs_sample_part_slots(ctypes.byref(hp), float(guidance), max_rows, V, params.ptr, _ptr(probs[0, cur]),
                                                           s0.field_ptr(tokens_field), s0.field_ptr(amax_field) if amax_field else None,
                                                           ctypes.byref(slots), _stream()), "sjd_logits_to_probs_sample_part_slots")

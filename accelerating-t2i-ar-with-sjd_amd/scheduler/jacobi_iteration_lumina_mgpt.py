@@ -15,6 +15,7 @@ The model class handed to renew_sampler must be one of this package's backbones 
 state-dict keys as the reference checkpoints) -- the transformer forward stays PyTorch-ROCm, its attention is K1.
 """
 import ctypes
+import dataclasses
 import random
 from typing import Optional
 
@@ -371,12 +372,13 @@ def renew_sampler(model_class):
             return torch.tensor([seq], dtype=torch.long, device=dev)
 
         @torch.no_grad()
-        def _sample_many(self, specs, logits_processors, stopping_criteria, generation_config, n_slots):
+        def _sample_many(self, specs, logits_processors, stopping_criteria, generation_config, n_slots, guidance_scales=None):
             """Several LlamaGen prompts through ONE window forward per iteration (SJDBatchEngine): specs[j] carries prompt j's conditioning
             (WindowSpec.cond_embeds: the engine prefills it into a slot's cache rows and draws the first image token), logits_processors[j]
             its processor list.  n_slots prompts share a forward; further prompts enter as slots finish (continuous batching).  The cache
             for n_slots x CFG rows must be allocated.  Prompt j's generators are seeded self.seed + j.  Returns LongTensor [N, tokens] in
-            prompt order; self.last_sjd_stats = the N DecodeStats."""
+            prompt order; self.last_sjd_stats = the N DecodeStats.  guidance_scales: None (self.guidance_scale for every prompt), or N values --
+            prompt j's windows then combine with guidance_scales[j] (one SJDConfig per prompt; its seed stays self.seed + j)."""
             from ..engine_batch import SJDBatchEngine
             if self.prefix_token_sampler_scheme not in ("speculative_jacobi", "jacobi"):
                 raise ValueError(f"prefix_token_sampler_scheme: {self.prefix_token_sampler_scheme}")
@@ -412,6 +414,11 @@ def renew_sampler(model_class):
             if eng is None:
                 eng = self._sjd_engines[key] = SJDBatchEngine(self, self.vocab_size, dev, n_slots, max_window=self.max_num_new_tokens, n_batch=B,
                                                               use_graph=getattr(self, "sjd_use_graph", True))
+            if guidance_scales is not None:
+                if len(guidance_scales) != N:
+                    raise ValueError(f"guidance_scales has {len(guidance_scales)} values for {N} prompts")
+                cfg = [dataclasses.replace(cfg, guidance_scale=float(g), seed=None if self.seed is None else self.seed + j)
+                       for j, g in enumerate(guidance_scales)]
             results = eng.decode_many([[] for _ in range(N)], specs, grammars, cfg)
             self.last_sjd_stats = [st for _, st in results]
             for seq, st in results:

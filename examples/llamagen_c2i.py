@@ -31,7 +31,8 @@ def parse_args(argv=None):
     ap.add_argument("--class-id", type=int, nargs="+", default=[207],
                     help="one ImageNet class, or several: they share the window forwards (needs --fused) and one PNG is written per label")
     ap.add_argument("--prompts-per-forward", type=int, default=None, help="several labels: how many share a forward (default: what 256 rows hold)")
-    ap.add_argument("--cfg-scale", type=float, default=4.0)
+    ap.add_argument("--cfg-scale", type=float, nargs="+", default=[4.0],
+                    help="classifier-free guidance scale: one value, or one per --class-id (the labels still share their window forwards)")
     ap.add_argument("--top-k", type=int, default=1000)
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--window", type=int, default=16)
@@ -41,6 +42,10 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if len(a.class_id) > 1 and not a.fused:
         ap.error("several --class-id labels are decoded together on the fused HIP path: add --fused")
+    if len(a.cfg_scale) not in (1, len(a.class_id)):
+        ap.error(f"--cfg-scale takes one value or one per --class-id ({len(a.class_id)}), got {len(a.cfg_scale)}")
+    if len(a.cfg_scale) == 1 or len(a.class_id) == 1:
+        a.cfg_scale = a.cfg_scale[0]                                                     # a number: every prompt's scale, as ever
     return a
 
 
@@ -76,8 +81,9 @@ def main():
         rows = (a.prompts_per_forward or len(a.class_id)) * 2 * a.window          # prompts x CFG pair x window rows per forward
         # (GPT-3B's 32 heads are 100 wide: the kernels store them 128 wide with zero pad columns, which the backbone does on request only)
         gpt.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), pad_head_dim=gpt.head_dim == 100)
+    one_scale = a.cfg_scale if isinstance(a.cfg_scale, float) else a.cfg_scale[0]        # (a scale per label: this one only says "CFG on")
     jac = dict(jacobi_loop_interval_l=1, jacobi_loop_interval_r=latent ** 2 - a.window - 2, max_num_new_tokens=a.window,
-               guidance_scale=a.cfg_scale, seed=a.seed, multi_token_init_scheme="random", do_cfg=True, image_top_k=a.top_k,
+               guidance_scale=one_scale, seed=a.seed, multi_token_init_scheme="random", do_cfg=True, image_top_k=a.top_k,
                text_top_k=10, prefix_token_sampler_scheme="speculative_jacobi")
     gpt.__class__ = renew_llamagen(gpt.__class__)
     gpt._init_new_params(**jac)

@@ -236,6 +236,11 @@ int sjd_logits_to_probs_sample_part(const sjd_head_partials *head /* host struct
 int sjd_head_combine(const sjd_head_partials *head /* host struct, passed by value to the kernel */, float guidance, int max_rows, int V,
                      const sjd_iter_params *params, float *z_out, void *stream);
 
+/* sjd_head_combine with the guidance scale read from device memory (guidance: ONE float32): bit for bit the call above with that value; a
+ * captured launch follows the value's later changes (SJDBatchEngine: a slot of a wide head changes its prompt's scale without a new graph). */
+int sjd_head_combine_g(const sjd_head_partials *head, const float *guidance /* device */, int max_rows, int V, const sjd_iter_params *params,
+                       float *z_out, void *stream);
+
 /* K4 -- probabilistic verify-and-accept (longest accepted prefix) + residual resample of the first reject.
  * replaces SpeculativeSampler.__call__ / find_first_misaligned_token_inds / prefix_matching_next_tokens
  * (reference jacobi_iteration_lumina_mgpt.py:203-376).
@@ -268,6 +273,12 @@ int sjd_reguess_slots(const sjd_iter_params *params0, sjd_state *state0, int64_t
 int sjd_logits_to_probs_sample_part_slots(const sjd_head_partials *head, float guidance, int max_rows, int V, const sjd_iter_params *params0,
                                           float *probs_out0, int64_t *tokens_out0, int64_t *amax_out0 /* may be NULL */, const sjd_slots *slots,
                                           void *stream);
+/* the launch above with a guidance scale PER SLOT: slot s combines z = u + guidance[s] (c - u) (guidance: device float32 [slots->n_slots], read once
+ * per workgroup).  Bit for bit what the scalar entry points give a slot called with guidance[s]; a captured launch follows the array's contents, so a
+ * slot that is handed the next prompt of a queue changes its scale with a 4-byte upload (SJDBatchEngine, one SJDConfig per prompt). */
+int sjd_logits_to_probs_sample_part_slots_g(const sjd_head_partials *head, const float *guidance, int max_rows, int V, const sjd_iter_params *params0,
+                                            float *probs_out0, int64_t *tokens_out0, int64_t *amax_out0 /* may be NULL */, const sjd_slots *slots,
+                                            void *stream);
 /* sjd_verify_accept_ex per slot (rs / noise2 generated in the kernel) */
 int sjd_verify_accept_slots(const sjd_iter_params *params0, sjd_state *state0, const float *probs0, const float *prev_probs0, float *scratch0,
                             int max_rows, int V, sjd_state *host_mirror0 /* may be NULL */, const sjd_slots *slots, void *stream);
