@@ -297,6 +297,15 @@ class LlamaGenBackbone(nn.Module):
     # 2.19 -> 1.89 ms (profiles/llamagen_3b.json)
     G1_CFG_LLAMAGEN_3B = dict(qkv=(640, 8, True), o=(512, 4, False), gate_up=(1088, 8, True), down=(1088, 4, True))
     HEAD_CFG_3B = (1088, 8, True)
+    # GPT-3B with several prompts per forward (enable_fused(pad_head_dim=True, padded_batch=True, max_rows=128 / 256)): the same rule at 128 and 256 rows --
+    # `tools/llamagen_bench.py --sweep --preset GPT-3B --rows 128 / 256` (profiles/llamagen_g1_sweep_3b_128rows.jsonl, _256rows.jsonl), per projection the
+    # fastest shape with at most eight planes (chunk >= 400 / 512 / 1088 for K = 3200 / 4096 / 8704) among kernel G1w's column-tile counts; us per launch
+    # at 128 rows q|k|v 16.80 (three planes), o 9.68, gate|up 26.54, down 16.56, head 24.82 (two planes); at 256 rows 25.45, 14.40, 37.97, 23.14, 35.56.
+    # (q|k|v's 9600 columns are 300 tiles: 75 workgroups of four; the head's 512 tiles by four; fp16 at 65..128 rows keeps the sub-tiled kernels on these shapes)
+    G1_CFG_LLAMAGEN_3B_128ROW = dict(qkv=(1088, 4, False), o=(512, 4, False), gate_up=(1088, 8, False), down=(1088, 4, True))
+    HEAD_CFG_3B_128ROW = (1600, 4, True)
+    G1_CFG_LLAMAGEN_3B_256ROW = dict(qkv=(1088, 4, False), o=(512, 4, True), gate_up=(1088, 8, True), down=(1088, 4, True))
+    HEAD_CFG_3B_256ROW = (1600, 4, True)
     HEAD_PAD = 128                # storage head dim of a padded model (the K1 / F2 shape of Lumina-7B: 32 heads, D 128, H == H_kv)
 
     @staticmethod
@@ -307,14 +316,16 @@ class LlamaGenBackbone(nn.Module):
         w[:, :, :head_dim] = wo.view(wo.shape[0], n_heads, head_dim)
         return w.view(wo.shape[0], n_heads * head_pad)
 
-    def enable_fused(self, ops, gemm="sjd", max_rows=64, untuned_fp16=False, pad_head_dim=False):
+    def enable_fused(self, ops, gemm="sjd", max_rows=64, untuned_fp16=False, pad_head_dim=False, padded_batch=False):
         """Switch draft windows of <= max_rows rows (64, 128 or 256: rows = prompts per forward x CFG batch x window; fp16 weights take 256
         with untuned_fp16=True only: kernel G1w serves them on the launch shapes swept in bf16) to the hand-written HIP path: per layer F1r, G1 q|k|v, F2 (the interleaved rotary from a
         table, SJD_F2_ROPE_TABLE), K1, G1 o, F1r, G1 gate|up (+ F3, or G1s where ops.gateup_silu_ok allows), G1 down; then the output head
         on G1, whose split-K partials K2 reads (head_partials).  pad_head_dim=True serves head_dim 100 (GPT-3B) stored 128 wide: q|k|v is
         packed at its true size and F2 (SJD_F2_HEAD_PAD128) writes 128-wide q / cache rows with zero pad columns, K1 runs at D = 128 with the
         softmax scale of 100 (SJD_K1_HEAD_DIM_100), wo is packed with zero columns at the pad positions; the cache becomes 128 wide (an existing
-        one is re-allocated: prefill again); windows of at most 64 rows; no effect at head_dim 64 / 128.  The RMSNorm gains are folded into packed copies of the weights (the
+        one is re-allocated: prefill again); windows of at most 64 rows unless padded_batch=True, which packs the padded model for max_rows 128 / 256 on
+        the sets swept at GPT-3B's shapes (G1_CFG_LLAMAGEN_3B_128ROW / _256ROW: several prompts per forward; no effect without pad_head_dim=True at
+        head_dim 100, nor at 64 rows); no effect at head_dim 64 / 128.  The RMSNorm gains are folded into packed copies of the weights (the
         norm becomes a row scale applied by F2 / F3 / K2, as ChameleonBackbone's folded path does).  w1 / w3 are concatenated once into
         [w1; w3] (gate | up) and re-pointed at its halves (state dict unchanged).  The prefill and longer inputs stay on forward_embeds.
         `ops` is sjd_amd.ops.  Raises ValueError for what the kernels do not serve."""
@@ -330,28 +341,27 @@ class LlamaGenBackbone(nn.Module):
         if pad100:
             if self.n_heads != self.n_kv_heads:
                 raise ValueError("LlamaGenBackbone.enable_fused: pad_head_dim=True serves multi-head attention (n_kv_head == n_head) only")
-            if max_rows > 64:
-                raise ValueError("LlamaGenBackbone.enable_fused: pad_head_dim=True serves windows of at most 64 rows (one prompt per forward); "
-                                 f"max_rows={max_rows!r} has no swept G1 launch shapes at head_dim 100 yet")
+            if max_rows > 64 and not padded_batch:
+                # (the plain call keeps what it did before the wider sets were swept: nobody's GPT-3B is packed for several prompts per forward unasked)
+                raise ValueError("LlamaGenBackbone.enable_fused: pad_head_dim=True serves windows of at most 64 rows (one prompt per forward) unless "
+                                 f"padded_batch=True, which packs max_rows={max_rows!r} on the launch shapes swept at head_dim 100 "
+                                 "(G1_CFG_LLAMAGEN_3B_128ROW / _256ROW)")
             if self.args.dim % 32 != 0 or (3 * self.args.dim) % 32 != 0:
                 raise ValueError(f"LlamaGenBackbone.enable_fused: dim {self.args.dim} -- kernel G1 takes whole 32-column tiles and 16-wide k-steps "
                                  "(dim a multiple of 32: at head_dim 100 a head count that is a multiple of 8)")
-            if "G1_CFG" not in self.__dict__:
-                self.G1_CFG = dict(self.G1_CFG_LLAMAGEN_3B)
-            if "HEAD_CFG" not in self.__dict__:
-                self.HEAD_CFG = tuple(self.HEAD_CFG_3B)
         if max_rows not in (64, 128, 256):
             raise ValueError(f"LlamaGenBackbone.enable_fused: max_rows is 64, 128 or 256 (the three sets of G1 launch shapes), got {max_rows!r}")
         if max_rows > 128 and dt != torch.bfloat16 and not untuned_fp16:
             # (the plain call keeps what it did before fp16 was served at 129..256 rows: nobody gets launch shapes that were never swept for fp16 unasked)
             raise ValueError("LlamaGenBackbone.enable_fused: max_rows=256 packs bf16 weights; it keeps fp16 windows of at most 128 rows unless "
                              "untuned_fp16=True (kernel G1 serves fp16 at 129..256 rows on the launch shapes swept in bf16)")
-        if max_rows > 64:            # (the default keeps packing exactly what it packed before: a G1_CFG / HEAD_CFG set by the caller still wins)
-            sfx = f"_{max_rows}ROW"
+        if max_rows > 64 or pad100:  # (the default keeps packing exactly what it packed before: a G1_CFG / HEAD_CFG set by the caller still wins)
+            sfx = ("_3B" if pad100 else "") + (f"_{max_rows}ROW" if max_rows > 64 else "")          # G1_CFG_LLAMAGEN_3B, _128ROW, _3B_128ROW, ...
             if "G1_CFG" not in self.__dict__:
                 self.G1_CFG = dict(getattr(self, "G1_CFG_LLAMAGEN" + sfx))
             if "HEAD_CFG" not in self.__dict__:
                 self.HEAD_CFG = tuple(getattr(self, "HEAD_CFG" + sfx))
+        if max_rows > 64:
             bad = [k for k, c_ in list(self.G1_CFG.items()) + [("head", self.HEAD_CFG)] if c_[1] not in self.G1_WIDE_TILES]
             if bad:
                 raise ValueError(f"windows of more than 64 rows take {self.G1_WIDE_TILES} column tiles per workgroup; offending launch shapes: {bad}")

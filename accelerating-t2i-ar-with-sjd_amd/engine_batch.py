@@ -94,13 +94,16 @@ class SJDBatchEngine:
             # would fall onto ATen silently: not bit-identical to the oracle replays, and no head partials for K2
             if getattr(backbone, "_ops", None) is None:
                 raise ValueError("SJDBatchEngine serves a LlamaGen backbone on the fused HIP path only: call "
-                                 f"model.enable_fused(ops, gemm='sjd', max_rows=...) first ({rows} window rows per forward here)")
+                                 f"model.enable_fused(ops, gemm='sjd', max_rows=...) first ({rows} window rows per forward here"
+                                 + ("; head_dim 100: with pad_head_dim=True, padded_batch=True)" if getattr(backbone, "head_dim", 0) == 100 else ")"))
+            # (a head_dim-100 backbone stored 128 wide is packed for more than 64 rows on request only: the refusals name both arguments)
+            padded = ", pad_head_dim=True, padded_batch=True" if getattr(backbone, "_head_pad", None) else ""
             if backbone.output.weight.dtype == torch.float16 and rows > 128 and getattr(backbone, "max_rows", 64) < rows:
                 raise ValueError(f"the backbone was packed for fp16 windows of at most {getattr(backbone, 'max_rows', 64)} rows, but n_prompts * n_batch * max_window = {rows}: "
-                                 "call enable_fused(ops, gemm='sjd', max_rows=256, untuned_fp16=True), or use fewer prompts per forward")
+                                 f"call enable_fused(ops, gemm='sjd', max_rows=256, untuned_fp16=True{padded}), or use fewer prompts per forward")
             if getattr(backbone, "max_rows", 64) < rows:
                 raise ValueError(f"the backbone was packed for windows of at most max_rows={getattr(backbone, 'max_rows', 64)} rows, but "
-                                 f"n_prompts * n_batch * max_window = {rows}: call enable_fused(ops, gemm='sjd', max_rows={128 if rows <= 128 else 256})")
+                                 f"n_prompts * n_batch * max_window = {rows}: call enable_fused(ops, gemm='sjd', max_rows={128 if rows <= 128 else 256}{padded})")
         if rows > 128 and getattr(backbone, "_gemm", None) == "sjd" and getattr(backbone, "_packed", None):
             # 129..256 window rows run on kernel G1w (csrc/sjd_gemm_wide.h): the uncompressed packing, 2 / 3 / 4 / 6 / 8 column tiles per
             # workgroup for every projection AND the output head.  Anything else used to fall onto the library-GEMM prefill path silently

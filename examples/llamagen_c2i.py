@@ -6,6 +6,7 @@ without them both networks get synthetic weights, which exercises every step but
 
     python examples/llamagen_c2i.py --class-id 207 --out sample.png
     python examples/llamagen_c2i.py --fused --class-id 207 1 980 417 --out grid.png      # four images per forward: grid_207.png, grid_1.png, ...
+    python examples/llamagen_c2i.py --fused --gpt-model GPT-3B --image-size 384 --class-id 207 1 980 417      # GPT-3B too (heads of 100 stored 128 wide)
 """
 import argparse
 import os
@@ -80,7 +81,9 @@ def main():
     if a.fused:
         rows = (a.prompts_per_forward or len(a.class_id)) * 2 * a.window          # prompts x CFG pair x window rows per forward
         # (GPT-3B's 32 heads are 100 wide: the kernels store them 128 wide with zero pad columns, which the backbone does on request only)
-        gpt.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), pad_head_dim=gpt.head_dim == 100)
+        # (... and several labels per forward on the padded model need its own swept launch shapes: padded_batch, no effect on the other models)
+        gpt.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), pad_head_dim=gpt.head_dim == 100,
+                         padded_batch=rows > 64)
     one_scale = a.cfg_scale if isinstance(a.cfg_scale, float) else a.cfg_scale[0]        # (a scale per label: this one only says "CFG on")
     jac = dict(jacobi_loop_interval_l=1, jacobi_loop_interval_r=latent ** 2 - a.window - 2, max_num_new_tokens=a.window,
                guidance_scale=one_scale, seed=a.seed, multi_token_init_scheme="random", do_cfg=True, image_top_k=a.top_k,

@@ -12,7 +12,8 @@
             at 1 (SJDEngine on the default packing: the one-prompt path), 2, 4 and 8 prompts per forward (packed with max_rows 64 / 128 / 256),
             all legs in one process on the same weights, timed in alternation over --rounds rounds (median and the per-round values reported),
             the fraction of 8 TB/s each step streams; then F2's table rotary at 256 rows, GPT-XL shape: four heads per wave against one
-            (SJD_F2_ONE_HEAD), us per launch from a hipGraph of back-to-back launches.
+            (SJD_F2_ONE_HEAD), us per launch from a hipGraph of back-to-back launches.  --only GPT-3B: the same legs for GPT-3B c2i 384px alone
+            (pad_head_dim=True; above one prompt padded_batch=True), without the F2 part.
   --step    the fused step alone (one preset, --steps timed iterations): what the rocprofv3 by-shape table is taken from.
   --fused3b GPT-3B c2i 384px (24 layers, 32 heads of 100 stored 128 wide: enable_fused(pad_head_dim=True)), window 16, CFG, bf16: fused ms per SJD
             step over --rounds rounds (median), the packed bytes a step streams and their fraction of 8 TB/s.  No ATen leg: un-fused GPT-3B does
@@ -271,8 +272,9 @@ def batch(args):
     names = ["bf16", "fp16"] if args.dtype == "both" else [args.dtype]
     counts = [int(c) for c in args.counts.split(",")]
     out = dict(configs=[], window=args.window, cfg=True, dtype=args.dtype, rounds=args.rounds, steps=args.steps, warmup=args.warmup)
-    for preset, mt, size in CONFIGS:
-        if args.only and preset not in args.only.split(","):
+    only = args.only.split(",") if args.only else []
+    for preset, mt, size in CONFIGS + ([CONFIG_3B] if "GPT-3B" in only else []):          # (GPT-3B on request only: the default run is what it was)
+        if only and preset not in only:
             continue
         models, legs = {}, {}
         for dn in names:
@@ -283,7 +285,8 @@ def batch(args):
                     m.load_state_dict(base.state_dict())
             for P in counts:
                 rows = P * 2 * args.window
-                models[dn, P].enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), untuned_fp16=True)
+                models[dn, P].enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), untuned_fp16=True,
+                                           pad_head_dim=preset == "GPT-3B", padded_batch=preset == "GPT-3B" and rows > 64)
                 legs[dn, P] = _Leg(models[dn, P], args.window, dev) if P == 1 else _BatchLeg(models[dn, P], P, args.window, dev)
         ms, tps = {k: [] for k in legs}, {k: [] for k in legs}
         for _ in range(args.rounds):
@@ -301,12 +304,15 @@ def batch(args):
         for dn in names:
             med_ms = {P: statistics.median(ms[dn, P]) for P in counts}
             med_tps = {P: statistics.median(tps[dn, P]) for P in counts}
-            rec = dict(preset=preset, model_type=mt, image_size=size, layers=models[dn, counts[0]].n_layers,
+            m0 = models[dn, counts[0]]
+            rec = dict(preset=preset, model_type=mt, image_size=size, layers=m0.n_layers, head_dim=m0.head_dim, head_dim_stored=m0.cache.k.shape[-1],
                        ms_per_step={str(P): round(v, 3) for P, v in med_ms.items()},
                        tokens_per_s={str(P): round(v, 1) for P, v in med_tps.items()},
                        ms_per_step_rounds={str(P): [round(x, 3) for x in ms[dn, P]] for P in counts},
                        tokens_per_s_rounds={str(P): [round(x, 1) for x in tps[dn, P]] for P in counts},
                        tokens_per_s_vs_one_prompt={str(P): round(med_tps[P] / med_tps[counts[0]], 2) for P in counts},
+                       prompt_steps_per_s_vs_one_prompt={str(P): round(P * med_ms[counts[0]] / (counts[0] * med_ms[P]), 2) for P in counts},
+                       packed_gb_per_step={str(P): round(models[dn, P].packed_bytes() / 1e9, 3) for P in counts},
                        fraction_of_8tbps={str(P): round(models[dn, P].packed_bytes() / (med_ms[P] * 1e-3) / (PEAK_TBPS * 1e12), 3) for P in counts},
                        g1_cfg={str(P): [models[dn, P].G1_CFG, list(models[dn, P].HEAD_CFG)] for P in counts})
             if args.dtype == "both":
@@ -315,7 +321,7 @@ def batch(args):
             out["configs"].append(rec)
         del legs, models, base
         torch.cuda.empty_cache()
-    if args.dtype == "bf16":
+    if args.dtype == "bf16" and only != ["GPT-3B"]:
         out["f2_table_256rows"] = _f2_ab(dev)
         print(json.dumps(out["f2_table_256rows"]), flush=True)
     if args.out:
@@ -327,19 +333,15 @@ def step(args):
     dev = torch.device("cuda:0")
     preset, mt, size = next(c for c in CONFIGS + [CONFIG_3B] if c[0] == args.preset)
     m = _make(preset, mt, size, dev, DTYPES[args.dtype])
-    if preset == "GPT-3B":
-        assert args.prompts == 1, "GPT-3B (head_dim 100 stored 128 wide) is served at one prompt per forward"
-        m.enable_fused(ops, gemm="sjd", pad_head_dim=True)
-        _, st, _ = _Leg(m, args.window, dev).decode(args.warmup, args.steps)
-        print(json.dumps(dict(preset=preset, ms_per_step=round(1e3 * st.seconds / max(1, st.timed_nfe), 3), timed_steps=st.timed_nfe)), flush=True)
-        return
+    pad = preset == "GPT-3B"             # (head_dim 100 stored 128 wide; several prompts per forward: its own swept sets, padded_batch=True)
     if args.prompts > 1:
         rows = args.prompts * 2 * args.window
-        m.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), untuned_fp16=True)
+        m.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), untuned_fp16=True, pad_head_dim=pad,
+                       padded_batch=pad and rows > 64)
         ms, tps = _BatchLeg(m, args.prompts, args.window, dev).decode(args.warmup, args.steps)
         print(json.dumps(dict(preset=preset, prompts=args.prompts, ms_per_step=round(ms, 3), tokens_per_s=round(tps, 1))), flush=True)
         return
-    m.enable_fused(ops, gemm="sjd")
+    m.enable_fused(ops, gemm="sjd", pad_head_dim=pad)
     leg = _Leg(m, args.window, dev)
     _, st, _ = leg.decode(args.warmup, args.steps)
     print(json.dumps(dict(preset=preset, ms_per_step=round(1e3 * st.seconds / max(1, st.timed_nfe), 3), timed_steps=st.timed_nfe)), flush=True)
