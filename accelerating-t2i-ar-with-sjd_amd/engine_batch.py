@@ -395,7 +395,7 @@ class SJDBatchEngine:
     # ------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def decode_many(self, prompts: List[List[int]], specs: List[WindowSpec], grammars, cfg, seeds=None,
-                    warmup_iters=0, timed_iters=None, on_timed_start=None, on_timed_end=None):
+                    warmup_iters=0, timed_iters=None, on_timed_start=None, on_timed_end=None, detokenize=None):
         """cfg: one SJDConfig for all prompts (seed = cfg.seed + prompt index unless `seeds` is given), or a sequence of N, one per prompt: prompt
         j then decodes with cfg[j].guidance_scale and cfg[j].seed (as given: no index is added) -- exactly what it would decode alone with that
         config; the other fields must agree (per_prompt_configs).  Temperature, top-p and top-k are per prompt through `grammars`.  Returns
@@ -404,7 +404,17 @@ class SJDBatchEngine:
         len(prompts) may exceed the number of slots (continuous batching): a slot whose prompt reached its end token is handed the next
         prompt of the list -- state machine, grammar and generators re-created, its KV rows reused from 0, its prompt prefilled eagerly
         over its own batch rows -- while the other slots keep their windows; the captured window graphs are unaffected.  Only when the
-        list is exhausted does a finished slot ride along with a one-row dummy window."""
+        list is exhausted does a finished slot ride along with a one-row dummy window.
+
+        detokenize: None, or a callable (the finished prompt's sequence, a 1-d LongTensor on the device) -> image tensor.  It is called when a
+        prompt reaches its end, before the slot is handed the next prompt, eagerly on ONE side stream the engine owns (detok_stream): an event
+        recorded on the decode stream, the side stream waits for it, the callable runs under torch.cuda.stream(side).  The decode stream never
+        waits for the side stream, so the convolutions run under the window forwards of the other slots; the captured graphs hold none of the
+        callable's buffers (it allocates under the side stream, from the allocator's pool of that stream, and the ids it reads are a tensor of
+        their own per prompt, marked record_stream -- a refilled slot writes nowhere near them).  The side stream is synchronised once, at the
+        end.  The return value is then (results, images): images[j] is prompt j's (None for a prompt a timed run never finished), and
+        detok_events[j] the event recorded behind its callable.  A callable whose library searches its kernels on the first call of a shape
+        (MIOpen convolutions: seconds) is best called once before decode_many (LlamaGenSolver.generate does)."""
         # GenerationConfig(do_sample=False): K2's MODE of p goes where its draw would (state.tokens; the draw lands in state.amax and is ignored),
         # nothing is consumed from a slot's generator for it, the verify step's draws follow at once (SJDEngine.decode, JL:124-129)
         N = len(prompts)
@@ -553,6 +563,24 @@ class SJDBatchEngine:
             s.finished = s.X[-1] in cfg.eos_token_ids or len(s.X) >= cfg.max_length
             s.cur_len = len(s.X)
 
+        images, self.detok_events = [None] * N, [None] * N
+        if detokenize is not None and getattr(self, "detok_stream", None) is None:
+            self.detok_stream = torch.cuda.Stream(device=dev)      # one extra stream: the process uses two of its hardware queues
+
+        def detok(s):
+            """the finished prompt of slot s -> its image, on the side stream, ordered behind everything the decode stream has been given"""
+            side, main = self.detok_stream, torch.cuda.current_stream(dev)
+            ids = torch.tensor(s.X, dtype=torch.long, device=dev)
+            ready = torch.cuda.Event()
+            ready.record(main)
+            side.wait_event(ready)
+            ids.record_stream(side)
+            with torch.cuda.stream(side):
+                images[s.prompt_index] = detokenize(ids)
+                done = torch.cuda.Event()
+                done.record(side)
+            self.detok_events[s.prompt_index] = done
+
         def harvest(s):
             s.harvested = True
             s.stats.wall_seconds = time.perf_counter() - s.t_admit
@@ -585,6 +613,8 @@ class SJDBatchEngine:
             for i, s in enumerate(self.slots):
                 if s.finished and not s.harvested:
                     harvest(s)
+                    if detokenize is not None:
+                        detok(s)
                     if next_prompt < N:
                         if attn is not None and hasattr(attn, "params"):
                             attn.params = None
@@ -701,6 +731,8 @@ class SJDBatchEngine:
             if timed_iters is not None and it == warmup_iters + timed_iters:
                 break
         ev1.record()
+        if detokenize is not None:
+            self.detok_stream.synchronize()                    # the one wait for the side stream
         torch.cuda.synchronize()
         from .engine import check_reduce_timeouts
         check_reduce_timeouts()                    # (a reducing projection that gave up a wait: wrong numbers must not become tokens -- ADVICE r3)
@@ -722,4 +754,6 @@ class SJDBatchEngine:
             X, st = r
             st.seconds, st.host_seconds, st.sync_seconds = seconds, host_s, sync_s
             out.append((X, st))
+        if detokenize is not None:
+            return out, images
         return out

@@ -16,6 +16,10 @@ from . import backbones as BB
 from . import ops
 
 
+IMAGE_START, IMAGE_END, IMAGE_NEW_LINE, GRID_BASE = 8197, 8196, 8803, 8804       # <racm3:break>, <eoss>, <reserved08799>, <reserved08800> + 4
+IMAGE_ID_LO, IMAGE_ID_HI = 4, 8196                                                # image BPE ids 4..8195
+
+
 class _EosCriteria:
     def __init__(self, eos_token_id):
         self.eos_token_id = list(eos_token_id)
@@ -39,8 +43,15 @@ class FlexARInferenceSolver:
     """reference IS:273-450.  `model_path` may be a directory with `config.json` + `*.safetensors` / `pytorch_model.bin`
     holding reference (HF Chameleon) weights, or `model=` may pass a ready `sjd_amd.backbones.ChameleonBackbone`."""
 
+    vq_model = None         # (class defaults: no decoder, the default id table)
+    bpe_to_vq = None
+
     def __init__(self, model_path=None, precision="bf16", target_size=512, cache_dir=None, device="cpu", tokenizer=None,
-                 model: Optional[BB.ChameleonBackbone] = None, item_processor=None, fused=True, gemm="sjd"):
+                 model: Optional[BB.ChameleonBackbone] = None, item_processor=None, fused=True, gemm="sjd", vq_model=None, bpe_to_vq=None):
+        """vq_model: a detokenizers.ChameleonVQ, or a state dict in `vqgan.ckpt` keys (loaded into a full-size ChameleonVQ; the encoder side is
+        dropped) -- with it decode_image / decode_ids / generate_ids(decode=True) return PIL images without the reference's item processor.
+        bpe_to_vq: the BPE id -> VQ code mapping of the image span, a length-V int64 table or a callable on an int64 tensor; default
+        default_bpe_to_vq (id - 4 over 4..8195)."""
         self.dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[precision]
         self.device = torch.device(device)
         self.target_size = target_size
@@ -66,6 +77,32 @@ class FlexARInferenceSolver:
                                                                    type(e).__name__, e)
                 item_processor = None
         self.item_processor = item_processor
+        self.vq_model = self._vq_decoder(vq_model)
+        if bpe_to_vq is not None and not callable(bpe_to_vq):
+            bpe_to_vq = torch.as_tensor(bpe_to_vq, dtype=torch.int64)
+            if bpe_to_vq.dim() != 1:
+                raise ValueError(f"bpe_to_vq: a 1-d table indexed by BPE id (or a callable), got shape {tuple(bpe_to_vq.shape)}")
+        self.bpe_to_vq = bpe_to_vq
+
+    def _vq_decoder(self, vq_model):
+        if vq_model is None:
+            return None
+        from .detokenizers import ChameleonVQ
+        if isinstance(vq_model, dict):
+            sd = vq_model.get("state_dict", vq_model)            # (vqgan.ckpt keeps its tensors under "state_dict")
+            vq_model = ChameleonVQ()
+            vq_model.load_state_dict(sd)
+        if not isinstance(vq_model, ChameleonVQ):
+            raise TypeError(f"vq_model: a sjd_amd.detokenizers.ChameleonVQ or a state dict in vqgan.ckpt keys, got {type(vq_model).__name__}")
+        return vq_model.to(self.device).eval()
+
+    @staticmethod
+    def default_bpe_to_vq(ids):
+        """BPE id -> VQ code of the image span: id - 4 over the contiguous image ids 4..8195 (IMAGE_ID_LO / IMAGE_ID_HI), the range the
+        reference reads from its text_tokenizer.json (JL:879-886) and the mapping jacobi_iteration_anhole.decode_image_tokens uses.  An
+        ASSUMPTION about that file, which is not available here: it lists the image tokens in code order.  The real table, built from the
+        file, overrides it through the constructor's bpe_to_vq."""
+        return ids - IMAGE_ID_LO
 
     @staticmethod
     def _load(model_path):
@@ -158,8 +195,18 @@ class FlexARInferenceSolver:
         return out
 
     @torch.no_grad()
-    def generate_ids(self, prompt_ids: List[int], max_gen_len: int, logits_processor=None, streamer=None, temperature=1.0):
-        """IS:335-354 on token ids: GenerationConfig(max_new_tokens, do_sample, eos 8710) -> model._sample."""
+    def generate_ids(self, prompt_ids: List[int], max_gen_len: int, logits_processor=None, streamer=None, temperature=1.0, decode=False):
+        """IS:335-354 on token ids: GenerationConfig(max_new_tokens, do_sample, eos 8710) -> model._sample.
+        decode=True: decode_ids of the result, (text ids, [PIL.Image]) -- an image span that opens in the prompt (<image-start> h w) is closed
+        by the generated ids, so the prompt's last open span is put in front of them."""
+        if decode:
+            ids = self.generate_ids(prompt_ids, max_gen_len, logits_processor, streamer, temperature)
+            prompt_ids = list(prompt_ids)
+            if IMAGE_START in prompt_ids:
+                k = len(prompt_ids) - 1 - prompt_ids[::-1].index(IMAGE_START)
+                if IMAGE_END not in prompt_ids[k:]:
+                    ids = prompt_ids[k:] + ids
+            return self.decode_ids(ids)
         from transformers import GenerationConfig
         if logits_processor is None:
             logits_processor = self.create_logits_processor()
@@ -184,7 +231,9 @@ class FlexARInferenceSolver:
         """reference IS:299-354 -> (text, [PIL.Image]).  Needs the reference's item processor (tokenizer + VQ decoder)."""
         if self.item_processor is None:
             raise NotImplementedError("tokenizer / VQ-GAN assets are not part of the SJD hot path; use generate_ids(prompt_ids, ...) "
-                                      "or construct the solver with item_processor=<reference FlexARItemProcessor>")
+                                      "or construct the solver with item_processor=<reference FlexARItemProcessor>"
+                                      + ("" if self.vq_model is None else "; with vq_model= set, generate_ids(prompt_ids, ..., decode=True) "
+                                         "returns (text ids, [PIL.Image]) -- only the text tokenizer is missing"))
         conversations = [{"from": "human", "value": q} if i % 2 == 0 else {"from": "gpt", "value": a}
                          for q, a in qas for i in range(2)]
         item = {"image": images, "conversations": conversations}
@@ -202,10 +251,50 @@ class FlexARInferenceSolver:
         return TextStreamer(self.item_processor.tokenizer)
 
     def decode_image(self, tokens: List[int]):
-        """reference IS:402-403"""
+        """reference IS:402-403.  Without the reference's item processor but with vq_model=: its decode_image restated (_decode_image_vq)."""
+        if self.item_processor is None and self.vq_model is not None:
+            return self._decode_image_vq(tokens)
         if self.item_processor is None:
             raise NotImplementedError("decode_image() needs the reference's item processor (VQ-GAN decoder); sjd_amd.detokenizers holds the decoders themselves")
         return self.item_processor.decode_image(tokens)
+
+    def _decode_image_vq(self, tokens):
+        """reference lumina_mgpt/data/item_processor.py:179-211 on this package's decoder: [<image-start>] h w body [<image-end>] with
+        h_grids = h - 8804, w_grids = w - 8804, a latent of (2 h_grids) x (2 w_grids) codes, the body one row of w_latent BPE ids plus the
+        line token per latent row.  ValueError names what is wrong with a span the reference's assert (or an index error) would stop at."""
+        tokens = [int(t) for t in tokens]
+        if tokens and tokens[0] == IMAGE_START:
+            tokens = tokens[1:]
+        if tokens and tokens[-1] == IMAGE_END:
+            tokens = tokens[:-1]
+        if len(tokens) < 2:
+            raise ValueError(f"image span: wrong length, {len(tokens)} ids between the start and end tokens, the two size tokens are missing")
+        h_grids, w_grids = tokens[0] - GRID_BASE, tokens[1] - GRID_BASE
+        if h_grids < 1 or w_grids < 1:
+            raise ValueError(f"image span: the size tokens {tokens[0]}, {tokens[1]} give {h_grids} x {w_grids} grids (size token = {GRID_BASE} + grids)")
+        body = tokens[2:]
+        h_lat, w_lat = 2 * h_grids, 2 * w_grids
+        if len(body) != h_lat * (w_lat + 1):
+            raise ValueError(f"image span: wrong length, {len(body)} ids after the size tokens, but {h_grids} x {w_grids} grids are {h_lat} rows "
+                             f"of {w_lat} image ids plus a line token = {h_lat * (w_lat + 1)}")
+        body = torch.tensor(body, dtype=torch.int64).view(h_lat, w_lat + 1)
+        bad = (body[:, -1] != IMAGE_NEW_LINE).nonzero()
+        if len(bad):
+            r = int(bad[0, 0])
+            raise ValueError(f"image span: missing line token, row {r} of the latent ends with {int(body[r, -1])}, not {IMAGE_NEW_LINE}")
+        ids = body[:, :-1].reshape(-1)
+        out = (ids < IMAGE_ID_LO) | (ids >= IMAGE_ID_HI)
+        if bool(out.any()):
+            k = int(out.nonzero()[0, 0])
+            raise ValueError(f"image span: id {int(ids[k])} at row {k // w_lat}, column {k % w_lat} is outside the image range "
+                             f"{IMAGE_ID_LO}..{IMAGE_ID_HI - 1}")
+        table = self.bpe_to_vq
+        codes = self.default_bpe_to_vq(ids) if table is None else (table(ids) if callable(table) else table[ids])
+        codes = torch.as_tensor(codes, dtype=torch.int64)
+        n_codes = self.vq_model.quantize.embedding.num_embeddings
+        if int(codes.min()) < 0 or int(codes.max()) >= n_codes:
+            raise ValueError(f"image span: bpe_to_vq maps into {int(codes.min())}..{int(codes.max())}, but the VQ codebook has {n_codes} entries")
+        return self.vq_model.pil_from_img_toks(codes.to(self.device), h_lat, w_lat)
 
     @staticmethod
     def create_image_grid(images, rows, cols):
@@ -218,12 +307,15 @@ class FlexARInferenceSolver:
         return grid
 
     def decode_ids(self, tokens: List[int]):
-        """reference IS:356-400: split at <racm3:break>(8197) ... <eoss>(8196) spans; images go through item_processor.decode_image."""
+        """reference IS:356-400: split at <racm3:break>(8197) ... <eoss>(8196) spans; images go through item_processor.decode_image, or,
+        without an item processor, through vq_model (PIL images; the text stays a list of ids: there is no tokenizer).  With neither, the
+        spans come back as id lists."""
+        decode = self.item_processor is not None or self.vq_model is not None
         text_ids, images, i = [], [], 0
         while i < len(tokens):
             if tokens[i] == 8197 and 8196 in tokens[i:]:
                 j = tokens.index(8196, i)
-                images.append(self.item_processor.decode_image(tokens[i:j + 1]) if self.item_processor is not None else tokens[i:j + 1])
+                images.append(self.decode_image(tokens[i:j + 1]) if decode else tokens[i:j + 1])
                 i = j + 1
             else:
                 text_ids.append(tokens[i])

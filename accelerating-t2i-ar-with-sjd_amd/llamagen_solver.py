@@ -206,12 +206,19 @@ class LlamaGenSolver:
         return sample(logits, noise_device=self.noise_device, **sampling_kwargs)[0], T
 
     @torch.no_grad()
-    def generate(self, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cfg_interval=-1, **sampling_kwargs):
+    def generate(self, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cfg_interval=-1, vq_model=None, qzshape=None, **sampling_kwargs):
         """cond with N > 1 prompts: cfg_scale, temperature, top_k and top_p each take a number (as ever) or N values, one per prompt
-        (_generate_many)."""
+        (_generate_many).
+
+        vq_model: None -> the ids, LongTensor [N, max_new_tokens], as ever.  A detokenizers.LlamaGenVQ -> (ids, images): images uint8
+        [N, H, W, 3] on the model's device, image j = to_uint8(vq_model.decode_code(ids[j], (1, e_dim, h, w))).  qzshape: (e_dim, h, w) or
+        (N, e_dim, h, w) of the latent; default: the codebook's width and a square of max_new_tokens codes.  With N > 1 every image is
+        decoded on the batch engine's side stream as soon as its prompt ends, under the window forwards of the others."""
         model = self.model
+        if vq_model is not None:
+            qzshape = self._qzshape(vq_model, qzshape, cond.shape[0], max_new_tokens)
         if cond.shape[0] > 1:
-            return self._generate_many(cond, max_new_tokens, emb_masks, cfg_scale, **sampling_kwargs)
+            return self._generate_many(cond, max_new_tokens, emb_masks, cfg_scale, vq_model=vq_model, qzshape=qzshape, **sampling_kwargs)
         for name in _PER_PROMPT_ARGS:
             per_prompt_values(name, cfg_scale if name == "cfg_scale" else sampling_kwargs.get(name), 1)
         if model.model_type == 'c2i':
@@ -245,7 +252,25 @@ class LlamaGenSolver:
                                 cache_position=T + 1)
         generated = outputs[:, -max_new_tokens:]
         model.clear_kvcache()
+        if vq_model is not None:
+            from .detokenizers import to_uint8
+            return generated, to_uint8(vq_model.decode_code(generated.reshape(-1), (1,) + qzshape))
         return generated
+
+    @staticmethod
+    def _qzshape(vq_model, qzshape, n_prompts, max_new_tokens):
+        """generate()'s qzshape -> (e_dim, h, w) of one image's latent"""
+        if qzshape is None:
+            side = int(round(max_new_tokens ** 0.5))
+            qzshape = (vq_model.quantize.embedding.weight.shape[1], side, side)
+        qzshape = tuple(int(x) for x in qzshape)
+        if len(qzshape) == 4:
+            if qzshape[0] != n_prompts:
+                raise ValueError(f"qzshape {qzshape} is for {qzshape[0]} images, but generate() got {n_prompts} prompts")
+            qzshape = qzshape[1:]
+        if len(qzshape) != 3 or qzshape[1] * qzshape[2] != max_new_tokens:
+            raise ValueError(f"qzshape {qzshape}: (e_dim, h, w) with h * w = max_new_tokens = {max_new_tokens}")
+        return qzshape
 
     def slots_for(self, n_prompts, n_batch):
         """prompts per window forward: prompts_per_forward, or what the row limit allows: 256 rows; an fp16 backbone that was not packed for them
@@ -255,7 +280,7 @@ class LlamaGenSolver:
         slots = self.prompts_per_forward or max(1, (256 if wide else 128) // (n_batch * model.max_num_new_tokens))
         return max(1, min(int(slots), n_prompts))
 
-    def _generate_many(self, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, **sampling_kwargs):
+    def _generate_many(self, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, vq_model=None, qzshape=None, **sampling_kwargs):
         """N > 1 prompts (class ids [N], or caption embeddings [N, T, C] with emb_masks [N, T]): slots_for(N) of them share every window
         forward (SJDBatchEngine), the rest enter as slots finish.  Returns LongTensor [N, max_new_tokens] in prompt order.
 
@@ -315,8 +340,19 @@ class LlamaGenSolver:
         generation_config = GenerationConfig(max_new_tokens=T + max_new_tokens, max_length=T + max_new_tokens, temperature=1.0,
                                              top_k=None, do_sample=True, return_dict_in_generate=False)
         procs = [self.create_logits_processor(**{k: v[j] for k, v in per.items()}) for j in range(N)]
+        detok = None
+        if vq_model is not None:
+            from .detokenizers import to_uint8
+            detok = lambda ids: to_uint8(vq_model.decode_code(ids[-max_new_tokens:], (1,) + qzshape))[0]
+            # one image of this shape BEFORE the queue starts: the convolution library searches its kernels on the first call of a shape, which
+            # takes seconds; here it runs on an idle device and not on the side stream next to the window forwards
+            detok(torch.zeros(max_new_tokens, dtype=torch.long, device=dev))
         outputs = model._sample_many(specs, procs, [MaxlenCriteria(max_new_tokens)], generation_config, slots,
-                                     guidance_scales=None if scales is None else [float(x) for x in scales])
+                                     guidance_scales=None if scales is None else [float(x) for x in scales], detokenize=detok)
+        if detok is not None:
+            outputs, images = outputs
         generated = outputs[:, -max_new_tokens:]
         model.clear_kvcache()
+        if detok is not None:
+            return generated, torch.stack(images)
         return generated

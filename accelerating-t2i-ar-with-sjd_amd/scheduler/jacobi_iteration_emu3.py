@@ -62,11 +62,37 @@ def renew_sampler_forward(model_class):
                 raise NotImplementedError
             return out
 
+        @torch.no_grad()
+        def decode_image_tokens(self, ids):
+            """The generated ids of ONE image -> pixels [1, 3, 8h, 8w] in [-1, 1] (the counterpart of the Anole pipeline's decode_image_tokens).
+            h, w, the line / end tokens and the first visual id come from the grammar object renew_solver built (Emu3PrefixConstrainedLogitsHelper):
+            h rows of w visual ids, each closed by the line token, then optionally the frame, image and sequence end tokens (and padding), which
+            are dropped.  Needs renew_solver(..., vq_model=<sjd_amd.detokenizers.Emu3VisionVQ>)."""
+            fn, vq = self.__dict__.get("_emu3_grammar"), self.__dict__.get("vq_model")
+            if vq is None:
+                raise RuntimeError("no VQ decoder attached: pass renew_solver(model, processor, vq_model=sjd_amd.detokenizers.Emu3VisionVQ(...), ...)")
+            h, w = int(fn.height), int(fn.width)
+            lo, n_vis = int(fn.visual_tokens[0]), len(fn.visual_tokens)
+            ids = torch.as_tensor(ids, dtype=torch.long).reshape(-1)
+            body, tail = ids[:h * (w + 1)], ids[h * (w + 1):].tolist()
+            if body.numel() != h * (w + 1):
+                raise ValueError(f"Emu3 image: {ids.numel()} ids, but {h} rows of {w} visual ids plus a line token are {h * (w + 1)}")
+            ends = [int(fn.eof_token), int(fn.eoi_token), int(fn.eos_token)]
+            if tail[:3] != ends[:len(tail[:3])] or any(t != int(fn.pad_token) for t in tail[3:]):
+                raise ValueError(f"Emu3 image: {tail[:4]} follow the {h} rows, not the frame / image / sequence end tokens {ends} (then padding)")
+            body = body.view(h, w + 1)
+            if bool((body[:, -1] != int(fn.eol_token)).any()):
+                raise ValueError(f"Emu3 image: a row of {w} visual ids does not end with the line token {int(fn.eol_token)}")
+            codes = body[:, :-1] - lo
+            if int(codes.min()) < 0 or int(codes.max()) >= n_vis:
+                raise ValueError(f"Emu3 image: an id outside the visual range {lo}..{lo + n_vis - 1}")
+            return vq.decode(codes[None].to(next(vq.parameters()).device))
+
     return JacobiModel
 
 
-def renew_solver(model, processor, **jacobi_param_dict):
-    """reference JE:370-412 -> (model, LogitsProcessorList)"""
+def renew_solver(model, processor, vq_model=None, **jacobi_param_dict):
+    """reference JE:370-412 -> (model, LogitsProcessorList).  vq_model: a sjd_amd.detokenizers.Emu3VisionVQ for model.decode_image_tokens."""
     h = jacobi_param_dict.pop('h', None)
     w = jacobi_param_dict.pop('w', None)
     jacobi_param_dict.pop('neg_inputs', None)
@@ -77,5 +103,7 @@ def renew_solver(model, processor, **jacobi_param_dict):
     model._init_new_params(**jacobi_param_dict)
     model.__class__ = renew_sampler_forward(model.__class__)
     model._init_new_params(visual_tokens=constrained_fn.visual_tokens, **jacobi_param_dict)
+    # (through __dict__: an nn.Module attribute would register the decoder as a sub-module of the backbone and change its state dict)
+    model.__dict__["_emu3_grammar"], model.__dict__["vq_model"] = constrained_fn, vq_model
     from transformers.generation.logits_process import LogitsProcessorList
     return model, LogitsProcessorList([constrained_fn])

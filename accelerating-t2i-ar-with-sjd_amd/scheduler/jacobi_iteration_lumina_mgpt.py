@@ -372,13 +372,15 @@ def renew_sampler(model_class):
             return torch.tensor([seq], dtype=torch.long, device=dev)
 
         @torch.no_grad()
-        def _sample_many(self, specs, logits_processors, stopping_criteria, generation_config, n_slots, guidance_scales=None):
+        def _sample_many(self, specs, logits_processors, stopping_criteria, generation_config, n_slots, guidance_scales=None, detokenize=None):
             """Several LlamaGen prompts through ONE window forward per iteration (SJDBatchEngine): specs[j] carries prompt j's conditioning
             (WindowSpec.cond_embeds: the engine prefills it into a slot's cache rows and draws the first image token), logits_processors[j]
             its processor list.  n_slots prompts share a forward; further prompts enter as slots finish (continuous batching).  The cache
             for n_slots x CFG rows must be allocated.  Prompt j's generators are seeded self.seed + j.  Returns LongTensor [N, tokens] in
             prompt order; self.last_sjd_stats = the N DecodeStats.  guidance_scales: None (self.guidance_scale for every prompt), or N values --
-            prompt j's windows then combine with guidance_scales[j] (one SJDConfig per prompt; its seed stays self.seed + j)."""
+            prompt j's windows then combine with guidance_scales[j] (one SJDConfig per prompt; its seed stays self.seed + j).
+            detokenize: None, or a callable (prompt's ids, 1-d LongTensor on the device) -> image tensor, run on the engine's side stream as
+            each prompt ends (SJDBatchEngine.decode_many); the return value is then (ids [N, tokens], [N images in prompt order])."""
             from ..engine_batch import SJDBatchEngine
             if self.prefix_token_sampler_scheme not in ("speculative_jacobi", "jacobi"):
                 raise ValueError(f"prefix_token_sampler_scheme: {self.prefix_token_sampler_scheme}")
@@ -419,13 +421,18 @@ def renew_sampler(model_class):
                     raise ValueError(f"guidance_scales has {len(guidance_scales)} values for {N} prompts")
                 cfg = [dataclasses.replace(cfg, guidance_scale=float(g), seed=None if self.seed is None else self.seed + j)
                        for j, g in enumerate(guidance_scales)]
-            results = eng.decode_many([[] for _ in range(N)], specs, grammars, cfg)
+            images = None
+            if detokenize is None:
+                results = eng.decode_many([[] for _ in range(N)], specs, grammars, cfg)
+            else:
+                results, images = eng.decode_many([[] for _ in range(N)], specs, grammars, cfg, detokenize=detokenize)
             self.last_sjd_stats = [st for _, st in results]
             for seq, st in results:
                 print("Time elapsed inner: ", st.seconds)                                                # JL:1218-1220, once per prompt
                 print("gen loop num (NFE): ", st.nfe)
                 print("tokens length: ", len(seq))
-            return torch.tensor([seq for seq, _ in results], dtype=torch.long, device=dev)
+            ids = torch.tensor([seq for seq, _ in results], dtype=torch.long, device=dev)
+            return ids if detokenize is None else (ids, images)
 
     if not hasattr(model_class, "generate"):
         # this package's backbones are plain nn.Modules: give them the HF-shaped entry point the drivers call

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """End-to-end class-conditional LlamaGen generation with Speculative Jacobi Decoding on one MI355X: the flow of the reference's
 test_llamagen.py (model registry -> renew_llamagen / renew_sampler -> LlamaGenSolver.generate -> VQ decode -> image file), with the
-reference's import lines.  Checkpoints: pass --gpt-ckpt / --vq-ckpt (the reference's files load unchanged: same state-dict keys);
+reference's import lines.  The VQ decoder goes into generate(vq_model=): it returns the pixels next to the ids, and with several labels
+every image is decoded on a side stream as soon as its label's tokens are complete, under the window forwards of the others.
+Checkpoints: pass --gpt-ckpt / --vq-ckpt (the reference's files load unchanged: same state-dict keys);
 without them both networks get synthetic weights, which exercises every step but of course draws noise.
 
     python examples/llamagen_c2i.py --class-id 207 --out sample.png
@@ -96,22 +98,20 @@ def main():
     solver = LlamaGenSolver(model=gpt, image_top_k=a.top_k, image_top_p=a.top_p, prompts_per_forward=a.prompts_per_forward)
     torch.manual_seed(a.seed)
     t0 = time.time()
-    index_sample = solver.generate(torch.tensor(a.class_id, device=dev), latent ** 2, None, cfg_scale=a.cfg_scale, temperature=1.0,
-                                   top_k=a.top_k, top_p=a.top_p, sample_logits=True)
+    index_sample, images = solver.generate(torch.tensor(a.class_id, device=dev), latent ** 2, None, cfg_scale=a.cfg_scale, temperature=1.0,
+                                           top_k=a.top_k, top_p=a.top_p, sample_logits=True, vq_model=vq, qzshape=(8, latent, latent))
     torch.cuda.synchronize()
     dt = time.time() - t0
     stats = gpt.last_sjd_stats if isinstance(gpt.last_sjd_stats, list) else [gpt.last_sjd_stats]
     n_tok = index_sample.numel()
     for c, st in zip(a.class_id, stats):
         print(f"class {c}: {index_sample.shape[1]} image tokens in {st.nfe} forward passes ({index_sample.shape[1] / max(st.nfe, 1):.2f} tokens/step)")
-    print(f"{n_tok} image tokens in {dt:.2f} s ({n_tok / dt:.0f} tokens/s)")
+    print(f"{n_tok} image tokens and {len(images)} decoded images in {dt:.2f} s ({n_tok / dt:.0f} tokens/s)")
 
-    from sjd_amd.detokenizers import to_uint8
     from PIL import Image
-    for row, path in zip(index_sample, out_paths(a.out, a.class_id)):
-        samples = vq.decode_code(row.reshape(-1), (1, 8, latent, latent))                # [-1, 1]   (test_llamagen.py:182)
-        Image.fromarray(to_uint8(samples)[0].cpu().numpy()).save(path)
-        print(f"wrote {path} ({samples.shape[-1]}x{samples.shape[-2]})")
+    for img, path in zip(images, out_paths(a.out, a.class_id)):                          # uint8 [H, W, 3]   (test_llamagen.py:182-183)
+        Image.fromarray(img.cpu().numpy()).save(path)
+        print(f"wrote {path} ({img.shape[1]}x{img.shape[0]})")
 
 
 if __name__ == "__main__":

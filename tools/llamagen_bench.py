@@ -14,6 +14,11 @@
             the fraction of 8 TB/s each step streams; then F2's table rotary at 256 rows, GPT-XL shape: four heads per wave against one
             (SJD_F2_ONE_HEAD), us per launch from a hipGraph of back-to-back launches.  --only GPT-3B: the same legs for GPT-3B c2i 384px alone
             (pad_head_dim=True; above one prompt padded_batch=True), without the F2 part.
+  --batch --detok   tokens -> pixels of a queue of whole GPT-B c2i 256px images (synthetic weights, a synthetic-weight VQ-16 in fp32) at 1 / 2 / 4 / 8
+            prompts per forward (SJDBatchEngine, continuous batching over max(8, 2 x prompts) images): ms per image of the detokenizer alone,
+            images/s with the images decoded serially after decode_many, images/s with decode_many(detokenize=) (every image decoded on the
+            engine's side stream as its prompt ends).  The two queue legs alternate over --rounds rounds; medians, the per-round values and
+            the spread between rounds are reported (profiles/llamagen_detok.json).  Replaces the --batch table: the default output is unchanged.
   --step    the fused step alone (one preset, --steps timed iterations): what the rocprofv3 by-shape table is taken from.
   --fused3b GPT-3B c2i 384px (24 layers, 32 heads of 100 stored 128 wide: enable_fused(pad_head_dim=True)), window 16, CFG, bf16: fused ms per SJD
             step over --rounds rounds (median), the packed bytes a step streams and their fraction of 8 TB/s.  No ATen leg: un-fused GPT-3B does
@@ -329,6 +334,90 @@ def batch(args):
             json.dump(out, f, indent=1)
 
 
+def detok(args):
+    from llamagen.tokenizer.tokenizer_image.vq_model import VQ_models
+    from sjd_amd.detokenizers import to_uint8
+    from sjd_amd.engine import SJDConfig, WindowSpec
+    from sjd_amd.engine_batch import SJDBatchEngine
+    from sjd_amd.grammar import TopKTopPGrammar
+    import sjd_amd.synthetic as synthetic
+    dev = torch.device("cuda:0")
+    preset, mt, size = CONFIGS[0]
+    latent, w = size // 16, args.window
+    vq = synthetic.fill_state_dict_conv(VQ_models["VQ-16"](codebook_size=16384, codebook_embed_dim=8).eval(), seed=1).to(dev)
+    decode = lambda ids: to_uint8(vq.decode_code(ids[-latent * latent:], (1, 8, latent, latent)))[0]
+    counts = [int(c) for c in args.counts.split(",")]
+    out = dict(preset=preset, model_type=mt, image_size=size, window=w, cfg=True, dtype="bf16", vq="VQ-16 fp32, synthetic weights", rounds=args.rounds,
+               counts={})
+    # the detokenizer alone: one image per call on the default stream, nothing else on the device
+    ids0 = torch.randint(0, 16384, (latent * latent,), device=dev, generator=torch.Generator(dev).manual_seed(0))
+    for _ in range(3):
+        decode(ids0)
+    alone = []
+    for _ in range(args.rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(10):
+            decode(ids0)
+        e1.record()
+        torch.cuda.synchronize()
+        alone.append(e0.elapsed_time(e1) / 10)
+    out["detok_ms_per_image"] = round(statistics.median(alone), 3)
+    out["detok_ms_per_image_rounds"] = [round(x, 3) for x in alone]
+    print(json.dumps(dict(detok_ms_per_image=out["detok_ms_per_image"], rounds=out["detok_ms_per_image_rounds"])), flush=True)
+    base = _make(preset, mt, size, dev)
+    for P in counts:
+        m = _make(preset, mt, size, dev)
+        m.load_state_dict(base.state_dict())
+        rows = P * 2 * w
+        m.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256))
+        T, N = m.args.cls_token_num, m.args.block_size
+        m.setup_cache(batch=2 * P, s_max=((T + N + w + 32 + 31) // 32) * 32)
+        eng = SJDBatchEngine(m, m.args.vocab_size, dev, P, max_window=w, use_graph=True)
+        Q = max(8, 2 * P)
+        cfg = SJDConfig(jacobi_loop_interval_l=1, jacobi_loop_interval_r=N - w - 2, max_num_new_tokens=w, guidance_scale=4.0, seed=3, max_length=N)
+
+        def queue(overlap):
+            specs = [WindowSpec(first_tokens=None, first_positions=None, key_start=torch.zeros(2, dtype=torch.int32),
+                                pos_offset=torch.zeros(2, dtype=torch.long), kv_base=T,
+                                cond_embeds=m.embed_condition(torch.tensor([(207 + 101 * j) % 1000, m.args.num_classes], device=dev)),
+                                cond_sampling=dict(cfg_scale=4.0, top_k=1000, top_p=1.0)) for j in range(Q)]
+            grammars = [TopKTopPGrammar(1000, 1.0) for _ in range(Q)]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if overlap:
+                res, images = eng.decode_many([[] for _ in specs], specs, grammars, cfg, detokenize=decode)
+            else:
+                res = eng.decode_many([[] for _ in specs], specs, grammars, cfg)
+                images = [decode(torch.tensor(seq, dtype=torch.long, device=dev)) for seq, _ in res]
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            assert len(images) == Q and all(im.shape == (size, size, 3) for im in images)
+            return Q / dt, [seq for seq, _ in res]
+
+        ips = dict(serial=[], overlap=[])
+        _, a = queue(False)                      # untimed: graph captures, convolution algorithm search
+        _, b = queue(True)
+        assert a == b, "the overlapped queue decodes the tokens of the serial one"
+        for _ in range(args.rounds):
+            for leg in ("serial", "overlap"):
+                ips[leg].append(queue(leg == "overlap")[0])
+        med = {k: statistics.median(v) for k, v in ips.items()}
+        rec = dict(prompts_per_forward=P, images=Q, images_per_s={k: round(v, 2) for k, v in med.items()},
+                   images_per_s_rounds={k: [round(x, 2) for x in v] for k, v in ips.items()},
+                   spread_between_rounds={k: round((max(v) - min(v)) / med[k], 3) for k, v in ips.items()},
+                   overlap_vs_serial=round(med["overlap"] / med["serial"], 3),
+                   detok_share_of_serial=round(out["detok_ms_per_image"] * 1e-3 * med["serial"], 3))
+        print(json.dumps(rec), flush=True)
+        out["counts"][str(P)] = rec
+        del eng, m
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def step(args):
     dev = torch.device("cuda:0")
     preset, mt, size = next(c for c in CONFIGS + [CONFIG_3B] if c[0] == args.preset)
@@ -383,6 +472,7 @@ def main():
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--fused3b", action="store_true")
+    ap.add_argument("--detok", action="store_true", help="--batch: the tokens -> pixels queue (detokenizer alone, serial, overlapped) instead of the step table")
     ap.add_argument("--cfg-from", default="", help="--fused3b: a --sweep output whose `best` lines give the G1 launch shapes")
     ap.add_argument("--prompts", type=int, default=1, help="--step: prompts per forward (SJDBatchEngine above 1)")
     ap.add_argument("--preset", default="GPT-XL", choices=list(PRESETS))
@@ -400,7 +490,9 @@ def main():
         sweep(args)
     if args.ab:
         ab(args)
-    if args.batch:
+    if args.batch and args.detok:
+        detok(args)
+    elif args.batch:
         batch(args)
     if args.step:
         step(args)
