@@ -606,6 +606,12 @@ class ChameleonBackbone(nn.Module):
     # the same on the 12-bit stream (Emu3 in bf16, round 4): 256-workgroup launches for q|k|v and o, step-major packing -- 11.75 / 10.25 / 19.85 us
     # against 12.15 / 10.66 / 20.19 (tools/g1z_bench.py --sweep --emu3 --rows 64, profiles/r4_g1z_sweep_emu3_64rows.jsonl)
     G1_CFG_EMU3_Z = dict(qkv=(512, 6, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(896, 8, True))
+    # the 8-bit e4m3 stream (enable_fused(weights="e4m3"), kernels G1q / G1sq): UNTUNED -- the 12-bit sets with every chunk cut to what G1q stages whole
+    # in LDS at the architecture's row count (Emu3: 64 rows, KC <= 1280, so its gate|up runs unfused as G1q + F3 in four chunks); no launch-shape
+    # sweep was run for this format.  G1_CFG_Q8's gate|up keeps the two K halves of 2048 that the fused 32-row launch (G1sq) streams; a window of
+    # 33..64 rows (a draft window of 32 with CFG, the prefill of a 17..32-token prompt) reads that step-major copy in chunks of 1024 (_q8_chunk)
+    G1_CFG_Q8 = dict(qkv=(1024, 6, True), o=(512, 6, False), gate_up=(2048, 8, True), down=(768, 8, False))
+    G1_CFG_EMU3_Q8 = dict(qkv=(512, 6, True), o=(512, 4, True), gate_up=(1024, 8, True), down=(896, 8, True))
     # 30B-class Chameleon (hidden 8192, intermediate 22016, GQA 64 / 8: q|k|v 10240 columns, gate|up 44032, down K 22016); chunks <= 2560 so that
     # the 32-row window stages its chunk in LDS.  The fastest shapes of `tools/swin30b_bench.py --sweep` at 32 rows on one MI355X
     # (profiles/g1_30b_sweep.jsonl), us per launch uncompressed / 12-bit: q|k|v 30.4 / 25.2, o 23.8 / 20.3, gate|up 120.5 / 98.9, down 62.9 / 50.4
@@ -645,10 +651,28 @@ class ChameleonBackbone(nn.Module):
         with torch.cuda.stream(self._pf_stream):
             self._ops.weight_prefetch(self._packed[li + dl][nxt], blocks)
 
+    def _q8_chunk(self, name, T, K_):
+        """split-K chunk of projection `name` for a T-row window.  Under enable_fused(weights=...) kernel G1q stages the whole activation chunk in
+        LDS: <= 2560 columns up to 32 rows, <= 1280 at 33..64.  A projection packed with a longer chunk (G1_CFG_Q8's gate|up: two K halves of 2048, the
+        copy the fused 32-row launch streams) is read at 33..64 rows in HALVED chunks until they fit: a step-major packing whose chunks are whole
+        record pairs (K and the chunk multiples of 32) is the same bytes under either chunking -- pair after pair, every tile per pair.  The
+        "e4m3_as_bf16" twin takes the same chunks (pack_weight's step-major stream has the same property), so the two stay bit-identical.
+        ValueError where no such chunk exists."""
+        KC, _, sm = self.G1_CFG[name]
+        if getattr(self, "weights", None) is None or T <= 32 or min(KC, K_) <= 1280:
+            return KC
+        kc = KC
+        while kc > 1280 and sm and K_ % 32 == 0 and kc % 64 == 0:
+            kc //= 2
+        if kc > 1280:
+            raise ValueError(f"weights={self.weights!r}: a {T}-row window needs {name} chunks of <= 1280 columns (kernel G1q stages the chunk in LDS), or a "
+                             f"step-major packing with K and the chunk multiples of 32 / 64 that halved chunks can read; G1_CFG[{name!r}] = {self.G1_CFG[name]}")
+        return kc
+
     def _g1(self, li, x_, name, N_, K_):
         cfg = self.G1_CFG[name]
         self._prefetch(li, name, "g1")
-        out = self._ops.skinny_gemm(x_, self._packed[li][name], N_, K_, cfg[0], cfg[1], cfg[2])
+        out = self._ops.skinny_gemm(x_, self._packed[li][name], N_, K_, self._q8_chunk(name, x_.shape[0], K_), cfg[1], cfg[2])
         self._prefetch(li, name, "after")
         return out
 
@@ -656,7 +680,7 @@ class ChameleonBackbone(nn.Module):
         if self._pf_on:
             torch.cuda.current_stream().wait_stream(self._pf_stream)       # every forked branch rejoins (hipGraph capture needs it)
 
-    def enable_fused(self, ops, gemm="torch", fold_norm=True, compress=None):
+    def enable_fused(self, ops, gemm="torch", fold_norm=True, compress=None, weights=None):
         """Switch to the fused HIP glue path (F1-F3): q|k|v and gate|up projections become single GEMMs whose weights are
         concatenated once; the original parameters are re-pointed at slices of the fused tensors (state-dict unchanged,
         no extra memory).  gemm="sjd": the window forward (<= 32 rows) also runs its four per-layer projections on the
@@ -664,7 +688,42 @@ class ChameleonBackbone(nn.Module):
         weights); other shapes (prefill) keep hipBLASLt.  `ops` is sjd_amd.ops (raises if libsjd_hip.so is missing).
         compress (default: on for bf16 weights, SJD_G1Z=0 switches it off): the packed copy is kept in the LOSSLESS 12-bit stream format of
         kernels G1z / G1sz (ops.pack_weight_z: 25 % fewer bytes through the fabric that bounds the window forward, bit-identical results);
-        a matrix that does not fit the format (fp16, or a unit with too many out-of-window weights) stays uncompressed."""
+        a matrix that does not fit the format (fp16, or a unit with too many out-of-window weights) stays uncompressed.
+        weights (default None: the packed copy holds the checkpoint's values, as above):
+          "e4m3"          the four per-layer projections (q|k|v, o, gate|up, down) are QUANTISED -- after norm folding -- to OCP e4m3 with one
+                          power-of-two scale per output column (ops.quantize_e4m3) and streamed at one byte per weight by kernels G1q / G1sq
+                          (ops.pack_weight_q8): half of bf16's bytes, two thirds of the 12-bit stream's.  LOSSY, taken knowingly: `compress` is
+                          ignored for them; lm_head is never quantised (12-bit or uncompressed as above).  Launch shapes: G1_CFG_Q8 /
+                          G1_CFG_EMU3_Q8 unless the caller set G1_CFG.  compress_stats gains q8_matrices, q8_bytes_packed and rel_rms_error
+                          (the largest over the matrices of RMS(w - dequant) / RMS(w)) -- what there is to judge a checkpoint by: what e4m3
+                          weights do to image quality on a real checkpoint has NOT been measured.
+          "e4m3_as_bf16"  the same quantisation, the DEQUANTISED values packed uncompressed (G1 / G1s): the verification and A/B twin -- the
+                          same values at two bytes each, so every token agrees with "e4m3".
+        Only the window forward (inputs of at most 64 rows) reads the 8-bit copy: the prompt prefill (hipBLASLt on the 16-bit parameters) is
+        NOT quantised.  SJD's draft and verify both run the window forward, so the sampler stays exact with respect to ITS model -- and that
+        model is the quantised one.  8-bit weights serve bf16 backbones with gemm="sjd", no swin-norm / model_parallel_size > 1, at most 64
+        window rows (one prompt per forward): anything else raises ValueError.  Chunks: every G1_CFG chunk <= 2560 columns (checked here); at
+        33..64 rows kernel G1q stages <= 1280, and a projection packed with a longer chunk is read in halved chunks where its packing allows it
+        (step-major, see _q8_chunk: the default sets do) -- a forward that cannot raises ValueError before its first launch."""
+        if weights not in (None, "e4m3", "e4m3_as_bf16"):
+            raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16'")
+        if weights is not None:
+            if gemm != "sjd":
+                raise ValueError(f"weights={weights!r} needs gemm='sjd': the 8-bit stream is read by the hand-written projection kernels only (got gemm={gemm!r})")
+            if self.args.swin_norm or self.args.model_parallel_size > 1:
+                raise ValueError(f"weights={weights!r} is not served for swin-norm backbones (swin_norm=True or model_parallel_size > 1)")
+            if self.lm_head.weight.dtype != torch.bfloat16:
+                raise ValueError(f"weights={weights!r} needs bf16 weights (got {self.lm_head.weight.dtype}): the dequantised values are bf16 numbers, "
+                                 "fp16's exponent range does not hold them")
+        q8_cfg = self.__dict__.get("G1_CFG")
+        if weights is not None:
+            if q8_cfg is None:
+                q8_cfg = dict(self.G1_CFG_EMU3_Q8 if self.n_kv_heads != self.n_heads else self.G1_CFG_Q8)
+            if any(c[0] > 2560 for c in q8_cfg.values()):          # (validated before anything is assigned: a refused call leaves the backbone as it was)
+                raise ValueError(f"weights={weights!r}: kernel G1q stages the whole activation chunk in LDS -- every G1_CFG chunk must be <= 2560 columns "
+                                 f"(windows of 33..64 rows: <= 1280, or a step-major packing that a halved chunk reads, see _q8_chunk); got {q8_cfg}")
+            self.G1_CFG = q8_cfg
+        self.weights = weights
         self._ops = ops
         self._gemm = gemm
         # swin-norm layers have no norm in front of a projection: nothing to fold (the unfolded window path, F1 in its post-norm form)
@@ -679,7 +738,7 @@ class ChameleonBackbone(nn.Module):
                 self.G1_CFG = dict(self.G1_CFG_EMU3)
             elif self.compress and self.lm_head.weight.dtype == torch.bfloat16:
                 self.G1_CFG = dict(self.G1_CFG_Z)
-        if self.compress and self.lm_head.weight.dtype == torch.bfloat16 and self.G1_CFG == self.G1_CFG_EMU3:
+        if weights is None and self.compress and self.lm_head.weight.dtype == torch.bfloat16 and self.G1_CFG == self.G1_CFG_EMU3:
             self.G1_CFG = dict(self.G1_CFG_EMU3_Z)          # (also when the caller named the architecture's set: the packing below follows it)
         if "HEAD_CFG" not in self.__dict__ and self.vocab_size >= 131072:
             self.HEAD_CFG = self.HEAD_CFG_WIDE
@@ -710,6 +769,23 @@ class ChameleonBackbone(nn.Module):
             st["raw_units"] = st.get("raw_units", 0) + z.stats.get("raw_units", 0)            # (round 6: units that travel verbatim, ops.PackedZ)
             st["max_exceptions_per_unit"] = max(st.get("max_exceptions_per_unit", 0), z.stats.get("max_exceptions", 0))
             return z
+
+        def pack_q8(w, kc, sm, gateup=False):         # the layer projections under weights="e4m3" / "e4m3_as_bf16"
+            st = self.compress_stats
+            st["matrices"] += 1
+            st["bytes_raw"] += w.numel() * w.element_size()
+            z = ops.pack_weight_q8(w, kc, sm, gateup=gateup)
+            st["q8_matrices"] = st.get("q8_matrices", 0) + 1
+            st["rel_rms_error"] = max(st.get("rel_rms_error", 0.0), z.stats["rel_rms_error"])
+            if weights == "e4m3_as_bf16":
+                st["bytes_packed"] += w.numel() * w.element_size()
+                return ops.pack_weight(z.dequant(), kc, sm)
+            st["bytes_packed"] += z.nbytes()
+            st["q8_bytes_packed"] = st.get("q8_bytes_packed", 0) + z.nbytes()
+            return z
+        pack_head = pack
+        if weights is not None:
+            pack = pack_q8
         self._packed = []
         self._fused = []
         with torch.no_grad():
@@ -746,11 +822,17 @@ class ChameleonBackbone(nn.Module):
                     # that ONE tile (round 5: 14 real rows x 2048 weights "out of window" in the last tile, every other unit <= 60)
                     wf = torch.cat([wf, wf[-1:].expand(pad, -1)], dim=0)
                 self._head_cols = V + pad
-                self._packed_head = pack(wf, self.HEAD_CFG[0], self.HEAD_CFG[2])
+                self._packed_head = pack_head(wf, self.HEAD_CFG[0], self.HEAD_CFG[2])
                 del wf
         self._inv_freq32 = self.inv_freq.float().contiguous()
         self.buffers_version = getattr(self, "buffers_version", 0) + 1          # ... and the packed weights' (engine._check_graph_buffers)
         return self
+
+    def packed_bytes(self, head=True):
+        """bytes of packed weights one window forward streams: the four projections of every layer and (head=True) the whole output head"""
+        size = lambda w: w.nbytes() if isinstance(w, (self._ops.PackedZ, self._ops.PackedQ8)) else w.numel() * w.element_size()
+        per = sum(size(w) for d in self._packed for w in d.values())
+        return per + (size(self._packed_head) if head and self._packed_head is not None else 0)
 
     HEAD_CFG = (1024, 4, True)         # G1 launch shape of the output head: (split-K chunk, column tiles per workgroup, step-major)
     # vocabularies whose image window is tens of thousands of columns (Emu3: 32768 of 184622): two K chunks, so that K2 sums two planes per
@@ -835,10 +917,11 @@ class ChameleonBackbone(nn.Module):
         #  4.89 against 5.06 ms per step with four prompts, profiles/r3_g1_tiled8.txt; `gateup_fused = "tall"` forces the fused kernel there)
         want_fused = getattr(self, "gateup_fused", _GATEUP_FUSED_DEFAULT)
         fuse_mlp = want_fused and (T <= 64 or want_fused == "tall") and not self._pf_on and ops.gateup_silu_ok(T, inter, hid, cfg["gate_up"][0],
-                                                                                                                   isinstance(self._packed[0]["gate_up"], ops.PackedZ))
+                                                                                                                   isinstance(self._packed[0]["gate_up"], ops.PackedZ),
+                                                                                                                   getattr(self, "weights", None) is not None)      # (the bf16 twin takes the 8-bit route)
         # o / down with F1r as their tail (one launch each; the reducing kernel wants whole 512-column slices per workgroup pair: 8 waves)
         red = getattr(self, "reduce_fused", _REDUCE_FUSED_DEFAULT) and not self._pf_on
-        raw = lambda name: not isinstance(self._packed[0][name], ops.PackedZ)        # (the reducing kernel streams the uncompressed packing)
+        raw = lambda name: not isinstance(self._packed[0][name], (ops.PackedZ, ops.PackedQ8)) and getattr(self, "weights", None) is None        # (the reducing kernel streams the uncompressed packing)
         h_dev = self.lm_head.weight.device
         red_o = red and raw("o") and ops.skinny_gemm_reduce_ok(T, hid, H * D, cfg["o"][0], 8, h_dev)
         red_d = red and raw("down") and ops.skinny_gemm_reduce_ok(T, hid, inter, cfg["down"][0], 8, h_dev)
@@ -893,7 +976,7 @@ class ChameleonBackbone(nn.Module):
         cap = 2560 if T <= 32 else 1 << 30     # the staged activation chunk of a 32-row window must fit in LDS; taller windows are sub-tiled when it does not
         if any(c[0] > cap for c in cfg.values()):
             raise ValueError(f"G1_CFG chunk sizes must be <= {cap} for a {T}-row window")
-        g1 = lambda x_, name, N_, K_: ops.skinny_gemm(x_, self._packed[li][name], N_, K_, cfg[name][0], cfg[name][1], cfg[name][2])
+        g1 = lambda x_, name, N_, K_: ops.skinny_gemm(x_, self._packed[li][name], N_, K_, self._q8_chunk(name, T, K_), cfg[name][1], cfg[name][2])
         H, Hkv, D, hid, inter = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size
         params = getattr(self.attn, "params", None)
         h = self.model.embed_tokens(tokens).view(T, -1).contiguous()
@@ -923,6 +1006,12 @@ class ChameleonBackbone(nn.Module):
 
     def _forward_window_fused(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
         T_ = tokens.shape[0] * tokens.shape[1]
+        if getattr(self, "weights", None) == "e4m3" and 64 < T_ <= 256 and tokens.shape[1] <= 32:
+            raise ValueError(f"weights='e4m3' serves draft windows of at most 64 rows (one prompt per forward); got {T_} rows")
+        if getattr(self, "weights", None) is not None and self._gemm == "sjd" and 32 < T_ <= 64:          # (refuse before the first launch, not in the middle of a layer)
+            H_, Hkv_, D_, hid_, inter_ = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size
+            for name_, K_ in (("qkv", hid_), ("o", H_ * D_), ("gate_up", hid_), ("down", inter_)):
+                self._q8_chunk(name_, T_, K_)
         # G1 serves windows: <= 64 rows, or <= 256 rows of up to eight prompts' draft windows (n <= 32 rows per batch row; 129..256 rows: round 5, the
         # uncompressed packing on kernel G1w -- G1_CFG_256ROW); longer inputs are prefill
         if self._gemm == "sjd" and (T_ <= 64 or (T_ <= 128 and tokens.shape[1] <= 32) or

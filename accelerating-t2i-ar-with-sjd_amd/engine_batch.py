@@ -83,6 +83,9 @@ class SJDBatchEngine:
         if getattr(bargs, "swin_norm", False) or getattr(bargs, "model_parallel_size", 1) != 1:
             raise ValueError("SJDBatchEngine does not serve swin-norm backbones (swin_norm=True or model_parallel_size > 1, the 30B-class "
                              "Chameleon form): decode them one prompt at a time with SJDEngine / FlexARInferenceSolver")
+        if getattr(backbone, "weights", None) == "e4m3":
+            raise ValueError("SJDBatchEngine does not serve a backbone packed with enable_fused(weights='e4m3'): 8-bit weights serve one prompt per "
+                             "forward (at most 64 window rows) in this version -- decode with SJDEngine, or pack with weights=None")
         L.load()                                   # fail loudly if the HIP extension is missing
         if max_window > L.MAX_WINDOW:
             raise ValueError(f"max_window {max_window} > {L.MAX_WINDOW}")

@@ -508,6 +508,116 @@ def pack_weight_z(weight, KC, step_major=False, gateup=False):
     return PackedZ(data, exc, N, K, KC, step_major, total, raw_index, raw_tiles, raw_view, stats)
 
 
+class PackedQ8:
+    """A packed weight in the 8-bit (OCP e4m3fn) stream format of kernels G1q / G1sq (see pack_weight_q8): `data` uint8 [N * K + 4 * N] = the
+    records, one byte per weight, then the fp32 column scales [N] at byte offset N * K.  LOSSY: the kernels multiply by dequant(), exactly."""
+
+    dtype = torch.bfloat16          # the activation type the kernels take (and the type of dequant())
+
+    def __init__(self, data, N, K, KC, step_major, stats=None):
+        self.data, self.N, self.K, self.KC, self.step_major = data, int(N), int(K), int(KC), bool(step_major)
+        self.stats = stats or {}
+
+    def numel(self):
+        return self.N * self.K
+
+    def nbytes(self):
+        return self.data.numel()
+
+    def reads_as(self, KC):
+        """can a launch with split-K chunk KC stream this buffer?  The chunk it was packed with -- or, step-major with K and both chunks multiples of
+        32, any other: every chunk is then whole record pairs and the buffer is [pair][tile] throughout, whatever the chunking"""
+        return KC == self.KC or (self.step_major and self.K % 32 == 0 and self.KC % 32 == 0 and KC % 32 == 0)
+
+    def scales(self):
+        """fp32 [N] view of the column scales inside `data`"""
+        return self.data[self.N * self.K:].view(torch.float32)
+
+    def codes(self):
+        """uint8 [N, K]: the e4m3 codes read back from the packed records (the inverse of pack_weight_q8's permutation)"""
+        N, K, KC, T = self.N, self.K, self.KC, self.N // 32
+        cols, off = [], 0
+        for k0 in range(0, K, KC):
+            kc = min(KC, K - k0)
+            S = kc // 16
+            P = S // 2
+            blk = self.data[off:off + N * kc]
+            off += N * kc
+            if self.step_major:
+                pr, hf = blk[:P * T * 1024].reshape(P, T, 1024).permute(1, 0, 2), blk[P * T * 1024:].reshape(T, (S - 2 * P) * 512)
+            else:
+                u = blk.reshape(T, S * 512)
+                pr, hf = u[:, :P * 1024].reshape(T, P, 1024), u[:, P * 1024:]
+            st = pr.reshape(T, P, 64, 2, 8).permute(0, 1, 3, 2, 4).reshape(T, 2 * P, 64, 8)          # [t, s, lane, j]
+            st = torch.cat([st, hf.reshape(T, S - 2 * P, 64, 8)], dim=1)
+            cols.append(st.reshape(T, S, 2, 32, 8).permute(0, 3, 1, 2, 4).reshape(N, kc))            # [t, s, h, r, j] -> [t, r, s, h, j]
+        return torch.cat(cols, dim=1).contiguous()
+
+    def dequant(self):
+        """bf16 [N, K]: the weight the kernels multiply by, read back from the packed buffer (exact: 3 mantissa bits times a power of two)"""
+        return (self.codes().view(FP8).float() * self.scales()[:, None]).to(torch.bfloat16)
+
+
+Q8_MIN_SCALE_EXP = -117     # 2^-9 (the smallest e4m3 magnitude) * 2^-117 = 2^-126: every dequantised value is a NORMAL bf16 number or zero
+
+
+def quantize_e4m3(weight):
+    """[N, K] bf16 weight -> (q uint8 [N, K] of OCP e4m3fn codes, scale fp32 [N]): one power-of-two scale per output column n (row of `weight`),
+    scale[n] = 2^ceil(log2(amax_n / 448)) (1 for an all-zero column; never below 2^-117, so that q * scale has no bf16 denormals),
+    q = e4m3(w / scale), round to nearest even.  |w / scale| <= 448 by construction: nothing saturates and the NaN codes 0x7f / 0xff never
+    appear.  q * scale is exactly representable in bf16.  fp16 (whose exponent range does not hold the scaled values in general) raises."""
+    if weight.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_e4m3: bf16 weights only (got {weight.dtype}): the dequantised values are bf16 numbers, fp16's exponent range does not hold them")
+    if weight.dim() != 2:
+        raise ValueError("quantize_e4m3: a [N, K] matrix")
+    w = weight.float()
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("quantize_e4m3: the weight has non-finite values")
+    amax = w.abs().amax(dim=1)
+    m, e = torch.frexp(amax)                                      # amax = m * 2^e, m in [0.5, 1); 448 = 0.875 * 2^9
+    exp = (e - 9 + (m > 0.875).to(e.dtype)).clamp(min=Q8_MIN_SCALE_EXP)
+    scale = torch.where(amax > 0, torch.ldexp(torch.ones_like(amax), exp), torch.ones_like(amax))
+    q = (w / scale[:, None]).to(FP8).view(torch.uint8)
+    return q, scale
+
+
+def pack_weight_q8(weight, KC, step_major=False, gateup=False):
+    """[N, K] bf16 weight -> PackedQ8: quantize_e4m3(weight) in pack_weight(weight, KC, step_major)'s (k-chunk, 32-column tile, k-step, lane,
+    element) order at ONE BYTE per weight, then the fp32 column scales [N] at byte offset N * K (a multiple of 512) of the same buffer -- what
+    sjd_skinny_gemm / sjd_skinny_gemm_cols / sjd_gateup_silu stream under SJD_G1_W8_E4M3 (kernels G1q / G1sq, csrc/sjd_gemm_q8.h).
+    Byte layout: the k-steps of a unit (chunk c, tile t) travel in PAIRS -- pair p (1024 B) = 64 lanes x 16 B {the lane's 8 bytes of k-step 2p, its
+    8 bytes of k-step 2p + 1}, lane l = 32 h + r, byte j = q[32 t + r][k0 + 16 s + 8 h + j] -- and an odd last k-step (a ragged last chunk) is a HALF
+    record of 512 B = 64 lanes x 8 B behind the pairs: no padding.  Tile-major: a unit is S * 512 contiguous bytes; step_major: a chunk holds
+    pair 0 of every tile, pair 1 of every tile, ..., then the half record of every tile.  A chunk starts at byte k0 * N.
+    gateup=True: `weight` is [Wg; Wu] packed with KC = K / 2 for sjd_gateup_silu.
+    stats: rel_rms_error (RMS of w - dequant over RMS of w), scale_exp_min / scale_exp_max (log2 of the smallest / largest column scale)."""
+    q, scale = quantize_e4m3(weight)
+    N, K = weight.shape
+    assert N % 32 == 0 and K % 16 == 0 and KC % 16 == 0
+    T = N // 32
+    assert not gateup or (2 * KC == K and T % 2 == 0)
+    parts = []
+    for k0 in range(0, K, KC):
+        kc = min(KC, K - k0)
+        S = kc // 16
+        P = S // 2
+        b = q[:, k0:k0 + kc].reshape(T, 32, S, 2, 8).permute(0, 2, 3, 1, 4).reshape(T, S, 64, 8)     # [t, s, lane = 32 h + r, j]
+        pr = b[:, :2 * P].reshape(T, P, 2, 64, 8).permute(0, 1, 3, 2, 4).reshape(T, P, 1024)          # (lane, k-step of the pair, j)
+        hf = b[:, 2 * P:].reshape(T, (S - 2 * P) * 512)
+        if step_major:
+            parts += [pr.permute(1, 0, 2).reshape(-1), hf.reshape(-1)]
+        else:
+            parts.append(torch.cat([pr.reshape(T, P * 1024), hf], dim=1).reshape(-1))
+    data = torch.cat(parts + [scale.contiguous().view(torch.uint8)]).contiguous()
+    wf = weight.float()
+    deq = q.view(FP8).float() * scale[:, None]
+    rms = float(wf.pow(2).mean().sqrt())
+    lg = torch.log2(scale)
+    stats = dict(rel_rms_error=(float((wf - deq).pow(2).mean().sqrt()) / rms) if rms > 0 else 0.0,
+                 scale_exp_min=int(lg.min()), scale_exp_max=int(lg.max()))
+    return PackedQ8(data, N, K, KC, step_major, stats)
+
+
 def _same_16bit_type(x, w_packed, what):
     """the kernels read the packed records as the activation's type: bf16 rows against fp16 records (or the reverse) would multiply garbage"""
     wd = getattr(w_packed, "dtype", None)
@@ -526,7 +636,7 @@ def skinny_gemm(x, w_packed, N, K, KC, waves=4, step_major=False):
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N * K
     _same_16bit_type(x, w_packed, "skinny_gemm")
-    if isinstance(w_packed, PackedZ):
+    if isinstance(w_packed, (PackedZ, PackedQ8)):
         return skinny_gemm_cols(x, w_packed, N, K, KC, 0, N, waves, step_major)
     nc = (K + KC - 1) // KC
     out = torch.empty(nc, _prows(M), N, dtype=torch.float32, device=x.device)
@@ -578,7 +688,7 @@ _PREFETCH_SINK = {}
 def weight_prefetch(w_packed, blocks=128, nbytes=None):
     """Read `w_packed` (a G1 packed weight) on the CURRENT stream and discard it: pulls the lines into the Infinity Cache ahead of
     the G1 launch that streams them (call it on a side stream forked from the forward, see ChameleonBackbone._prefetch)."""
-    if isinstance(w_packed, PackedZ):
+    if isinstance(w_packed, (PackedZ, PackedQ8)):
         w_packed = w_packed.data
     dev = w_packed.device
     sink = _PREFETCH_SINK.get(dev)
@@ -686,6 +796,11 @@ def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_m
                                           _dtype_code(x.dtype), N_packed, col0 // 32, _raw_units(w_packed), _stream()), "sjd_skinny_gemm_z")
         return Partials(out, nc, n_cols)
     _same_16bit_type(x, w_packed, "skinny_gemm_cols")
+    if isinstance(w_packed, PackedQ8):          # G1q: the scales ride behind the records of the same buffer
+        assert (w_packed.N, w_packed.step_major) == (N_packed, bool(step_major)) and w_packed.reads_as(KC)
+        L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed.data), _ptr(out), M, n_cols, K, KC, waves, int(step_major),
+                                             _dtype_code(x.dtype) | L.G1_W8_E4M3, N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols (e4m3 weights)")
+        return Partials(out, nc, n_cols)
     L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed), _ptr(out), M, n_cols, K, KC, waves, int(step_major), _dtype_code(x.dtype),
                                          N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols")
     return Partials(out, nc, n_cols)
@@ -973,10 +1088,12 @@ def silu_mul(gate_up, rows=None, dtype=None, row_norm=None):
     return y
 
 
-def gateup_silu_ok(T, inter, hidden, KC, packed_z=False):
+def gateup_silu_ok(T, inter, hidden, KC, packed_z=False, packed_q8=False):
     """shapes kernel G1s serves (see sjd_gateup_silu): a <= 32-row window -- or a <= 64-row one (draft window 32 with CFG, two prompts per
     forward) at hidden >= 1024, or a <= 128-row one (three / four prompts per forward) at hidden 4096 over the uncompressed packing --,
-    the gate|up weight packed in two K halves"""
+    the gate|up weight packed in two K halves; over the 8-bit packing (packed_q8: kernel G1sq) a <= 32-row window only"""
+    if packed_q8:
+        return T <= 32 and hidden in (512, 1024, 2048, 4096) and 2 * KC == hidden and inter % 64 == 0
     rows_ok = T <= 32 or (T <= 64 and hidden >= 1024) or (T <= 128 and hidden == 4096 and not packed_z)
     return rows_ok and hidden in (512, 1024, 2048, 4096) and 2 * KC == hidden and inter % 64 == 0
 
@@ -992,6 +1109,12 @@ def gateup_silu(x, w_packed, inter, hidden, step_major=False, row_norm=None):
         assert w_packed.n_raw == 0 or w_packed.raw_tiles is not None, "a gate|up weight with raw units must be packed with gateup=True"
         L.check(L.load().sjd_gateup_silu_z(_ptr(x), _ptr(w_packed.data), _ptr(w_packed.exc), w_packed.cap, _ptr(y), T, inter, hidden, int(step_major),
                                           _dtype_code(x.dtype), _row_norm(row_norm), _raw_units(w_packed, gateup=True), _stream()), "sjd_gateup_silu_z")
+        return y
+    if isinstance(w_packed, PackedQ8):          # G1sq
+        _same_16bit_type(x, w_packed, "gateup_silu")
+        assert (w_packed.N, w_packed.KC, w_packed.step_major) == (2 * inter, hidden // 2, bool(step_major))
+        L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed.data), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype) | L.G1_W8_E4M3,
+                                        _row_norm(row_norm), _stream()), "sjd_gateup_silu (e4m3 weights)")
         return y
     L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype),
                                     _row_norm(row_norm), _stream()), "sjd_gateup_silu")

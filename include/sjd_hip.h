@@ -69,13 +69,27 @@ extern "C" {
  *   SJD_K1_HEAD_DIM_100   heads STORED 128 wide (D = 128) whose columns 100..127 are zero in q, K and V: the softmax scale is 1/sqrt(100),
  *                         the logical head dim, in place of 1/sqrt(D); the pad columns add nothing to q k^T and the output's pad columns
  *                         are zero.  Valid with D = 128, H == H_kv and dtype bf16 / fp16 only -- SJD_ERR_UNSUPPORTED otherwise, from the
- *                         fp32 variant and from the fp8-cache entry points. */
+ *                         fp32 variant and from the fp8-cache entry points.
+ * A mode bit of the window projections (sjd_skinny_gemm, sjd_skinny_gemm_cols, sjd_gateup_silu; replaces the same call sites as G1 / G1s: q_proj / k_proj /
+ * v_proj, o_proj, gate_proj / up_proj, down_proj of the reference's modeling_chameleon.py:527-529, 579, 193-195):
+ *   SJD_G1_W8_E4M3        `w_packed` points at an 8-bit weight stream (sjd_amd.ops.pack_weight_q8; kernels G1q / G1sq, csrc/sjd_gemm_q8.h): N_packed * K
+ *                         bytes of OCP e4m3fn codes in the record order of the 16-bit packing at one byte per weight -- the k-steps of a (k-chunk,
+ *                         32-column tile) unit in 1024-byte pairs (64 lanes x {8 bytes of k-step 2p, 8 bytes of k-step 2p + 1}), an odd last k-step as
+ *                         a 512-byte half record behind them, no padding; a chunk starts at byte k0 * N_packed -- then the fp32 column scales
+ *                         [N_packed] (powers of two) at byte offset N_packed * K (sjd_skinny_gemm: N * K; sjd_gateup_silu: 2 * I * K, `w_packed` =
+ *                         [Wg; Wu] packed with KC = K / 2).  The kernels rebuild the bf16 operand code * scale exactly, so the planes / the 16-bit
+ *                         output are bit for bit what the same call writes for the 16-bit packing of the dequantised weight: the format's loss is
+ *                         the host-side quantiser's alone.  Valid with SJD_DTYPE_BF16 only; M <= 64 with min(KC, K) <= 2560 (M <= 32) / <= 1280
+ *                         (sjd_gateup_silu: M <= 32, K in {512, 1024, 2048, 4096}); everything else, and every other entry point given the bit,
+ *                         returns SJD_ERR_UNSUPPORTED.  SJD_VERSION did not move with it: a library without the bit returns SJD_ERR_UNSUPPORTED
+ *                         for it, which is the probe. */
 #define SJD_DTYPE_MASK 0xff
 #define SJD_F1_POST_NORM 0x100
 #define SJD_F2_ROPE_TABLE 0x200
 #define SJD_F2_HEAD_PAD128 0x400
 #define SJD_K1_HEAD_DIM_100 0x800
 #define SJD_F2_ONE_HEAD 0x1000
+#define SJD_G1_W8_E4M3 0x2000
 #define SJD_QKN_SHARDS_SHIFT 16
 #define SJD_QKN_SHARDS_MASK (0xff << SJD_QKN_SHARDS_SHIFT)
 #define SJD_QKN_SHARDS(mp) ((int)(mp) << SJD_QKN_SHARDS_SHIFT)

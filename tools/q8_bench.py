@@ -1,0 +1,170 @@
+#!/usr/bin/env python3
+"""The 8-bit (e4m3) weight stream against the uncompressed and the lossless 12-bit one, in ONE process, the legs alternating, three rounds,
+median and spread (min .. max over the rounds) per leg.
+
+  --launch  per launch: the four Lumina-7B projection shapes at 32 rows and the Emu3-8B ones at 64, each leg at the launch shape the backbone
+            uses for it (G1_CFG / G1_CFG_Z / G1_CFG_Q8 and the _EMU3 sets), launches replayed from a hipGraph over `--copies` weight sets so that
+            every launch streams from HBM; gate|up as the backbone runs it (the fused launch where it is served, else the projection + F3).
+            Bytes: algorithmic (the bf16 matrix) and stored (what the leg's format holds), and stored bytes / time as a fraction of 8 TB/s.
+  --step    per step: Lumina-mGPT-7B 768x768, draft window 16, CFG, bf16 -- the default 12-bit packing (enable_fused as bench.py calls it) against
+            enable_fused(weights="e4m3"), two backbones with the same synthetic weights, each decoded through a real lead-in so that the timed
+            iterations are centred on the mean KV length (bench.py's method), ms per SJD iteration.
+
+One JSON document on stdout (and in --out)."""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")          # as bench.py: read by the HIP runtime when it is loaded
+import torch  # noqa: E402
+
+import sjd_amd._lib as L  # noqa: E402
+import sjd_amd.backbones as BB  # noqa: E402
+import sjd_amd.ops as ops  # noqa: E402
+from g1_bench import timed_graph  # noqa: E402
+
+PEAK = 8.0e12
+
+
+def spread(xs):
+    return dict(median=round(statistics.median(xs), 3), min=round(min(xs), 3), max=round(max(xs), 3), rounds=[round(x, 3) for x in xs])
+
+
+def launch_legs(a, dev, lib):
+    C = BB.ChameleonBackbone
+    arch = [("lumina7b", 32, dict(qkv=(12288, 4096), o=(4096, 4096), gate_up=(22016, 4096), down=(4096, 11008)), (C.G1_CFG, C.G1_CFG_Z, C.G1_CFG_Q8)),
+            ("emu3_8b", 64, dict(qkv=(6144, 4096), o=(4096, 4096), gate_up=(28672, 4096), down=(4096, 14336)), (C.G1_CFG_EMU3, C.G1_CFG_EMU3_Z, C.G1_CFG_EMU3_Q8))]
+    out = []
+    for model, rows, shapes, cfgs in arch:
+        for name, (N, K) in shapes.items():
+            if a.only and name not in a.only.split(","):
+                continue
+            x = torch.randn(rows, K, device=dev).to(torch.bfloat16)
+            ws = [(torch.randn(N, K, device=dev) / K ** 0.5).to(torch.bfloat16) for _ in range(a.copies)]
+            legs = {}
+            for tag, cfg in zip(("bf16", "z12", "q8"), cfgs):
+                KC, waves, sm = cfg[name]
+                gu = name == "gate_up" and 2 * KC == K
+                if tag == "bf16":
+                    pk = [ops.pack_weight(w, KC, sm) for w in ws]
+                    stored = N * K * 2
+                elif tag == "z12":
+                    pk = [ops.pack_weight_z(w, KC, sm, gateup=gu) for w in ws]
+                    stored = pk[0].nbytes()
+                else:
+                    pk = [ops.pack_weight_q8(w, KC, sm, gateup=gu) for w in ws]
+                    stored = pk[0].nbytes()
+                fused = gu and ops.gateup_silu_ok(rows, N // 2, K, KC, tag == "z12", tag == "q8")
+                if fused:
+                    run = lambda i, pk=pk, sm=sm: ops.gateup_silu(x, pk[i % a.copies], N // 2, K, sm)
+                elif name == "gate_up":
+                    run = lambda i, pk=pk, KC=KC, waves=waves, sm=sm: ops.silu_mul(ops.skinny_gemm(x, pk[i % a.copies], N, K, KC, waves, sm), rows=rows, dtype=x.dtype)
+                else:
+                    run = lambda i, pk=pk, KC=KC, waves=waves, sm=sm: ops.skinny_gemm(x, pk[i % a.copies], N, K, KC, waves, sm)
+                legs[tag] = dict(run=run, stored=stored, cfg=[KC, waves, int(sm)], launch="fused gate|up + SiLU" if fused else ("projection + F3" if name == "gate_up" else "projection"),
+                                 us=[], keep=pk)
+            del ws
+            for _ in range(a.rounds):                     # alternating: bf16, 12-bit, 8-bit, and round again
+                for tag in ("bf16", "z12", "q8"):
+                    legs[tag]["us"].append(timed_graph(legs[tag]["run"], a.launches, lib)[1] * 1e3)
+            rec = dict(model=model, rows=rows, shape=name, N=N, K=K, algorithmic_bytes=N * K * 2)
+            for tag, lg in legs.items():
+                s = spread(lg["us"])
+                rec[tag] = dict(cfg=lg["cfg"], launch=lg["launch"], us=s, stored_bytes=lg["stored"],
+                                frac_of_8TBps_on_stored_bytes=round(lg["stored"] / (s["median"] * 1e-6) / PEAK, 4),
+                                frac_of_8TBps_on_algorithmic_bytes=round(N * K * 2 / (s["median"] * 1e-6) / PEAK, 4))
+            rec["q8_over_z12"] = round(rec["q8"]["us"]["median"] / rec["z12"]["us"]["median"], 4)
+            rec["q8_over_bf16"] = round(rec["q8"]["us"]["median"] / rec["bf16"]["us"]["median"], 4)
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+            del legs
+            torch.cuda.empty_cache()
+    return out
+
+
+def step_legs(a, dev):
+    import bench
+    from sjd_amd.engine import SJDEngine
+    base = bench.parse(["--gpus", "1", "--steps", str(a.steps), "--warmup", str(a.warmup)])
+    base.model, base.window, base.prompts_per_gpu, base.n_split = "lumina7b", 16, 1, 0
+    legs = {}
+    for tag in ("z12", "q8"):
+        b = copy.copy(base)
+        b.no_fused = tag == "q8"                          # (the q8 leg calls enable_fused itself, on the same synthetic weights)
+        model, margs, attn = bench.build_model(b, dev)
+        if tag == "q8":
+            model.enable_fused(ops, gemm="sjd", weights="e4m3")
+        w = bench.workload_of(b, margs, 0, dev)
+        P, n_img = w["P"], w["n_img"]
+        model.setup_cache(batch=2, s_max=((P + n_img + 2 * 16 + 64 + 31) // 32) * 32)
+        eng = SJDEngine(model, margs.vocab_size, dev, max_window=16, use_graph=True)
+        pin0 = getattr(attn, "_pin_regime", None)
+        for pin in ("keysplit", "colsplit"):             # the graphs of both K1 regimes are captured before any clock starts (bench.py's other_config)
+            if hasattr(attn, "_pin_regime"):
+                attn._pin_regime = pin
+            eng.decode(w["prompt"], w["spec"], copy.deepcopy(w["grammar"]), w["cfg"], warmup_iters=0, timed_iters=a.warmup + 8)
+        if hasattr(attn, "_pin_regime"):
+            attn._pin_regime = pin0
+        torch.cuda.synchronize()
+        legs[tag] = dict(model=model, eng=eng, w=w, ms=[], kv=[], tok=[],
+                         lead=int(P + n_img // 2 - w["tau_est"] * (a.steps / 2.0 + a.warmup)))
+    sync = torch.cuda.synchronize
+    for _ in range(a.rounds):
+        for tag in ("z12", "q8"):
+            lg = legs[tag]
+            w = lg["w"]
+            _, st = lg["eng"].decode(w["prompt"], w["spec"], copy.deepcopy(w["grammar"]), w["cfg"], warmup_iters=a.warmup, timed_iters=a.steps,
+                                     on_timed_start=sync, on_timed_end=sync, lead_in_kv=lg["lead"])
+            lg["ms"].append(st.seconds / max(st.timed_nfe, 1) * 1e3)
+            lg["kv"].append([st.kv_len_start, st.kv_len])
+            lg["tok"].append(round(st.tokens / max(st.timed_nfe, 1), 3))
+    rec = dict(workload="Lumina-mGPT-7B architecture 768x768 (synthetic weights), 1 prompt, draft window 16, CFG 3.0 (32 rows per forward), bf16, 16-bit KV cache",
+               steps=a.steps, warmup=a.warmup, rounds=a.rounds, order="alternating z12, q8 per round; one process, one device")
+    for tag, lg in legs.items():
+        m = lg["model"]
+        rec[tag] = dict(weights=m.weights, G1_CFG={k: list(v) for k, v in m.G1_CFG.items()}, ms_per_step=spread(lg["ms"]), kv_len=lg["kv"], tokens_per_step=lg["tok"],
+                        layer_bytes_per_step=m.packed_bytes(head=False), compress_stats={k: v for k, v in m.compress_stats.items() if not isinstance(v, dict)})
+    z, q = rec["z12"]["ms_per_step"], rec["q8"]["ms_per_step"]
+    rec["q8_minus_z12_ms"] = round(q["median"] - z["median"], 4)
+    rec["largest_spread_between_rounds_ms"] = round(max(z["max"] - z["min"], q["max"] - q["min"]), 4)
+    rec["gain_exceeds_spread"] = bool(z["median"] - q["median"] > rec["largest_spread_between_rounds_ms"])
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--launch", action="store_true")
+    ap.add_argument("--step", action="store_true")
+    ap.add_argument("--launches", type=int, default=48)
+    ap.add_argument("--copies", type=int, default=8)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--warmup", type=int, default=16)
+    ap.add_argument("--only", default="")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    lib = L.load()
+    doc = dict(device=torch.cuda.get_device_name(0), peak_TBps=8.0)
+    if a.launch:
+        doc["per_launch"] = launch_legs(a, dev, lib)
+        doc["per_launch_method"] = (f"{a.launches} launches per hipGraph over {a.copies} weight sets, the graph replayed three times and the middle time taken; "
+                                    f"{a.rounds} rounds alternating bf16 / 12-bit / 8-bit; us per launch: median, min, max over the rounds")
+    if a.step:
+        doc["per_step"] = step_legs(a, dev)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
