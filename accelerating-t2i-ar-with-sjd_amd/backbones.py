@@ -612,6 +612,12 @@ class ChameleonBackbone(nn.Module):
     # 33..64 rows (a draft window of 32 with CFG, the prefill of a 17..32-token prompt) reads that step-major copy in chunks of 1024 (_q8_chunk)
     G1_CFG_Q8 = dict(qkv=(1024, 6, True), o=(512, 6, False), gate_up=(2048, 8, True), down=(768, 8, False))
     G1_CFG_EMU3_Q8 = dict(qkv=(512, 6, True), o=(512, 4, True), gate_up=(1024, 8, True), down=(896, 8, True))
+    # the 8-bit stream for several prompts per forward (enable_fused(weights=..., max_rows=128 / 256)): UNTUNED -- G1_CFG_256ROW / G1_CFG_EMU3 as they are,
+    # except o on three column tiles (kernel G1wq, like G1w, has no form of three row tiles x two column tiles: 65..96 rows).  ONE packed copy serves every row
+    # count: <= 32 rows on G1q / G1sq (every chunk <= 2560; gate|up in the two K halves the fused launch streams), 33..64 on G1q in halved chunks
+    # (_q8_chunk: all step-major, K and the chunks multiples of 32 / 64), 65..256 on G1wq with these chunks and tile counts.  No sweep was run.
+    G1_CFG_Q8_WIDE = dict(qkv=(2048, 4, True), o=(1024, 3, True), gate_up=(2048, 8, True), down=(1408, 4, True))
+    G1_CFG_EMU3_Q8_WIDE = dict(qkv=(1024, 4, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(1792, 4, True))
     # 30B-class Chameleon (hidden 8192, intermediate 22016, GQA 64 / 8: q|k|v 10240 columns, gate|up 44032, down K 22016); chunks <= 2560 so that
     # the 32-row window stages its chunk in LDS.  The fastest shapes of `tools/swin30b_bench.py --sweep` at 32 rows on one MI355X
     # (profiles/g1_30b_sweep.jsonl), us per launch uncompressed / 12-bit: q|k|v 30.4 / 25.2, o 23.8 / 20.3, gate|up 120.5 / 98.9, down 62.9 / 50.4
@@ -661,6 +667,8 @@ class ChameleonBackbone(nn.Module):
         KC, _, sm = self.G1_CFG[name]
         if getattr(self, "weights", None) is None or T <= 32 or min(KC, K_) <= 1280:
             return KC
+        if T > 64 and getattr(self, "max_rows", 64) > 64:          # (kernels G1wq / G1w stream the activation in stages: the packed chunk as it is)
+            return KC
         kc = KC
         while kc > 1280 and sm and K_ % 32 == 0 and kc % 64 == 0:
             kc //= 2
@@ -680,7 +688,30 @@ class ChameleonBackbone(nn.Module):
         if self._pf_on:
             torch.cuda.current_stream().wait_stream(self._pf_stream)       # every forked branch rejoins (hipGraph capture needs it)
 
-    def enable_fused(self, ops, gemm="torch", fold_norm=True, compress=None, weights=None):
+    def _q8_wide_check(self, cfg, head_cfg, max_rows, dims=None):
+        """enable_fused(weights=..., max_rows > 64): can ONE packed copy with launch shapes `cfg` serve every row count up to max_rows?  dims: the
+        projections' (N, K) -- this backbone's by default.  ValueError names what cannot; nothing is assigned."""
+        if dims is None:
+            H, Hkv, D, hid, inter = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size
+            dims = dict(qkv=((H + 2 * Hkv) * D, hid), o=(hid, H * D), gate_up=(2 * inter, hid), down=(hid, inter))
+        for name, (KC, tiles, sm) in cfg.items():
+            K_ = dims[name][1]
+            if tiles not in self.G1_WIDE_TILES or tiles == 2:
+                raise ValueError(f"max_rows={max_rows}: windows of more than 64 rows take 3, 4, 6 or 8 column tiles per workgroup on the 8-bit stream (kernel G1wq "
+                                 f"has no form of three row tiles x two tiles); G1_CFG[{name!r}] = {(KC, tiles, sm)}")
+            if K_ % 32 or KC % 32:
+                raise ValueError(f"max_rows={max_rows}: kernel G1wq streams whole record pairs -- K and the chunk must be multiples of 32; G1_CFG[{name!r}] = "
+                                 f"{(KC, tiles, sm)} with K = {K_}")
+            kc = min(KC, K_)
+            while kc > 1280 and sm and kc % 64 == 0:          # (_q8_chunk's rule for 33..64 rows)
+                kc //= 2
+            if kc > 1280:
+                raise ValueError(f"max_rows={max_rows}: the same packed copy serves windows of 33..64 rows, where kernel G1q needs chunks of <= 1280 columns or a "
+                                 f"step-major packing that halved chunks read (_q8_chunk); G1_CFG[{name!r}] = {(KC, tiles, sm)}")
+        if max_rows > 128 and head_cfg[1] not in self.G1_WIDE_TILES:
+            raise ValueError(f"max_rows={max_rows}: the output head runs on kernel G1w at 129..256 rows -- HEAD_CFG[1] must be one of {self.G1_WIDE_TILES}, got {head_cfg}")
+
+    def enable_fused(self, ops, gemm="torch", fold_norm=True, compress=None, weights=None, max_rows=None):
         """Switch to the fused HIP glue path (F1-F3): q|k|v and gate|up projections become single GEMMs whose weights are
         concatenated once; the original parameters are re-pointed at slices of the fused tensors (state-dict unchanged,
         no extra memory).  gemm="sjd": the window forward (<= 32 rows) also runs its four per-layer projections on the
@@ -704,9 +735,20 @@ class ChameleonBackbone(nn.Module):
         model is the quantised one.  8-bit weights serve bf16 backbones with gemm="sjd", no swin-norm / model_parallel_size > 1, at most 64
         window rows (one prompt per forward): anything else raises ValueError.  Chunks: every G1_CFG chunk <= 2560 columns (checked here); at
         33..64 rows kernel G1q stages <= 1280, and a projection packed with a longer chunk is read in halved chunks where its packing allows it
-        (step-major, see _q8_chunk: the default sets do) -- a forward that cannot raises ValueError before its first launch."""
+        (step-major, see _q8_chunk: the default sets do) -- a forward that cannot raises ValueError before its first launch.
+        max_rows (with weights only; default None = 64): 128 or 256 packs for several prompts per forward (SJDBatchEngine: rows = prompts x CFG batch x
+        window) -- windows of 65..max_rows rows run on kernel G1wq, the 8-bit form of G1w ("e4m3_as_bf16": G1w itself, on the same launch shapes; the
+        two stay token-identical).  Launch shapes: G1_CFG_Q8_WIDE / G1_CFG_EMU3_Q8_WIDE (UNTUNED) unless the caller set G1_CFG; ONE packed copy serves
+        every row count, so every tile count must be 3, 4, 6 or 8, every chunk <= 2560 and readable in chunks of <= 1280 at 33..64 rows, K and the
+        chunks multiples of 32 -- checked here, before anything is assigned.  max_rows=256: lm_head is packed UNCOMPRESSED whatever `compress` says
+        (129..256 rows have no 12-bit kernel) and HEAD_CFG[1] must be 2, 3, 4, 6 or 8.  Whether the 8-bit stream is faster than what those row
+        counts run otherwise is a measurement, not a promise: README.md."""
         if weights not in (None, "e4m3", "e4m3_as_bf16"):
             raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16'")
+        if max_rows is not None and weights is None:
+            raise ValueError(f"max_rows={max_rows!r} goes with weights='e4m3' / 'e4m3_as_bf16' (without it the packed copy serves the row counts of its G1_CFG)")
+        if max_rows not in (None, 64, 128, 256):
+            raise ValueError(f"max_rows is 64, 128 or 256, got {max_rows!r}")
         if weights is not None:
             if gemm != "sjd":
                 raise ValueError(f"weights={weights!r} needs gemm='sjd': the 8-bit stream is read by the hand-written projection kernels only (got gemm={gemm!r})")
@@ -717,12 +759,23 @@ class ChameleonBackbone(nn.Module):
                                  "fp16's exponent range does not hold them")
         q8_cfg = self.__dict__.get("G1_CFG")
         if weights is not None:
+            wide = max_rows is not None and max_rows > 64
             if q8_cfg is None:
-                q8_cfg = dict(self.G1_CFG_EMU3_Q8 if self.n_kv_heads != self.n_heads else self.G1_CFG_Q8)
+                if wide:
+                    q8_cfg = dict(self.G1_CFG_EMU3_Q8_WIDE if self.n_kv_heads != self.n_heads else self.G1_CFG_Q8_WIDE)
+                else:
+                    q8_cfg = dict(self.G1_CFG_EMU3_Q8 if self.n_kv_heads != self.n_heads else self.G1_CFG_Q8)
             if any(c[0] > 2560 for c in q8_cfg.values()):          # (validated before anything is assigned: a refused call leaves the backbone as it was)
                 raise ValueError(f"weights={weights!r}: kernel G1q stages the whole activation chunk in LDS -- every G1_CFG chunk must be <= 2560 columns "
                                  f"(windows of 33..64 rows: <= 1280, or a step-major packing that a halved chunk reads, see _q8_chunk); got {q8_cfg}")
+            if wide:
+                head_cfg = self.__dict__.get("HEAD_CFG") or (self.HEAD_CFG_WIDE if self.vocab_size >= 131072 else self.HEAD_CFG)
+                self._q8_wide_check(q8_cfg, head_cfg, max_rows)
             self.G1_CFG = q8_cfg
+            self.max_rows, self._max_rows_given = int(max_rows) if max_rows is not None else 64, max_rows is not None
+        else:
+            self.__dict__.pop("max_rows", None)
+            self._max_rows_given = False
         self.weights = weights
         self._ops = ops
         self._gemm = gemm
@@ -786,6 +839,8 @@ class ChameleonBackbone(nn.Module):
         pack_head = pack
         if weights is not None:
             pack = pack_q8
+            if self.max_rows > 128:          # 129..256 rows: the head runs on kernel G1w, which streams the uncompressed packing
+                pack_head = lambda w, kc, sm: ops.pack_weight(w, kc, sm)
         self._packed = []
         self._fused = []
         with torch.no_grad():
@@ -1006,7 +1061,10 @@ class ChameleonBackbone(nn.Module):
 
     def _forward_window_fused(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
         T_ = tokens.shape[0] * tokens.shape[1]
-        if getattr(self, "weights", None) == "e4m3" and 64 < T_ <= 256 and tokens.shape[1] <= 32:
+        q8_rows = getattr(self, "max_rows", 64) if getattr(self, "weights", None) is not None else 64
+        if getattr(self, "weights", None) == "e4m3" and q8_rows < T_ <= 256 and tokens.shape[1] <= 32:
+            if q8_rows > 64:
+                raise ValueError(f"weights='e4m3' serves draft windows of at most {q8_rows} rows (max_rows={q8_rows}); got {T_} rows")
             raise ValueError(f"weights='e4m3' serves draft windows of at most 64 rows (one prompt per forward); got {T_} rows")
         if getattr(self, "weights", None) is not None and self._gemm == "sjd" and 32 < T_ <= 64:          # (refuse before the first launch, not in the middle of a layer)
             H_, Hkv_, D_, hid_, inter_ = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size

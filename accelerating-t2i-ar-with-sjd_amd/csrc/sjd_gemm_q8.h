@@ -14,7 +14,8 @@
 //       buffer holds exactly N * K weight bytes;
 //   tile-major: a unit is S * 512 contiguous bytes (pairs, then the half record); step-major: the chunk holds pair 0 of every tile, pair 1
 //       of every tile, ..., then the half record of every tile.
-// No headers, no exceptions, no raw units, no fix-up launch.  bf16; M <= 64 (G1q) / M <= 32 (G1sq): see the launchers.
+// No headers, no exceptions, no raw units, no fix-up launch.  bf16; M <= 64 (G1q) / M <= 32 (G1sq): see the launchers.  65..256 rows: kernel G1wq, the
+// 8-bit form of G1w (csrc/sjd_gemm_wide.h, template parameter Q), for K and KC multiples of 32 (whole pairs, no half records).
 #pragma once
 
 typedef __attribute__((ext_vector_type(2))) __bf16 g1q_bf16x2;
@@ -278,14 +279,14 @@ __global__ __launch_bounds__(512) void g1q_gateup_silu(const unsigned short *__r
 }
 
 // SJD_G1_W8_E4M3 on sjd_skinny_gemm / sjd_skinny_gemm_cols (which have checked the common arguments): M <= 64 with the whole activation chunk in
-// LDS -- min(KC, K) <= 2560 up to 32 rows, <= 1280 at 33..64.  The scales sit behind the N_packed * K record bytes.
+// LDS -- min(KC, K) <= 2560 up to 32 rows, <= 1280 at 33..64; 65..256 rows go to g1wq_launch.  The scales sit behind the N_packed * K record bytes.
 static int g1q_launch(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int waves, int step_major, int n_tiles, int tile0,
                       hipStream_t s)
 {
     if (N < 32) return SJD_ERR_BAD_ARG;
     const int n_out = N / 32, n_chunks = (K + KC - 1) / KC;
     if (tile0 < 0 || tile0 + n_out > n_tiles) return SJD_ERR_BAD_ARG;
-    if (M > 64) return SJD_ERR_UNSUPPORTED;
+    if (M > 64) return g1wq_launch(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);       // 65..256 rows: G1wq (csrc/sjd_gemm_wide.h) or unsupported
     const int MT = M <= 32 ? 1 : 2;
     const size_t lds = (size_t)MT * ((KC < K ? KC : K) / 16) * 1024;
     if (lds > 160 * 1024) return SJD_ERR_UNSUPPORTED;

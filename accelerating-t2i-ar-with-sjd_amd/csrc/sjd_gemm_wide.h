@@ -80,6 +80,16 @@ __device__ __forceinline__ u32x4 gw_wload(u32x4 rsrc, unsigned voff, unsigned so
     return r;
 }
 
+// (8-bit form) one fp32 column scale per lane, issued and counted by hand like the headers of the 12-bit form, and the wait that ties its register
+__device__ __forceinline__ float gw_gload1(const void *p)
+{
+    float r;
+    asm volatile("global_load_dword %0, %1, off" : "=v"(r) : "v"(p) : "memory");
+    return r;
+}
+template <int N> __device__ __forceinline__ void gw_wait_regs(float &a) { asm volatile("s_waitcnt vmcnt(%1)" : "+v"(a) : "n"(N) : "memory"); }
+__device__ __forceinline__ u32x4 g1q_operand(unsigned b0, unsigned b1, float sc);        // csrc/sjd_gemm_q8.h
+
 __device__ __forceinline__ unsigned gw_lds_addr(const void *p)
 {
     return (unsigned)(unsigned long)((__attribute__((address_space(3))) const unsigned char *)p);
@@ -102,12 +112,21 @@ template <int DT> __device__ __forceinline__ f32x16 gw_fake_mma(u32x4 a, u32x4 b
 // decodes BOTH operands of its pair (its registers are then free for the refill) and waits one group less deep (the codes are one k-step younger than the
 // low bytes); an odd k-step waits for nothing.  The unit headers are requested in front of the prologue and waited for behind it without draining it.
 // WIDE: headers of 128 entries.  Raw units (a header count of -1) decode to garbage here: the entry points run the fix-up launch (sjd_gemm_raw.h) behind this one.
-template <int DT, int MT, int CT, int NW, int SUB, int NS, int RW, int WPS, bool Z = false, bool WIDE = false>
+// Q ("G1wq"): the weights arrive as the 8-bit e4m3 stream of kernels G1q / G1sq (csrc/sjd_gemm_q8.h: 1024-byte record PAIRS of two k-steps, 64 lanes x
+// 16 B, fp32 column scales behind the N_packed * K record bytes; K and KC multiples of 32, so every unit is whole pairs) and are rebuilt into the SAME B
+// operands (g1q_operand: four conversions per k-step): the planes of the uncompressed form on pack_weight(dequant()), bit for bit, at half the weight
+// bytes.  The ring is one u32x4 per tile and pair (R / 2 registers per tile); the pair R k-steps ahead is requested behind an even k-step's last MFMA, and
+// an odd k-step issues an out-of-range DMA piece into the scratch KiB in its place (the prologue's trick: one instruction, no traffic, no register
+// written), so every k-step still has one vector-memory operation per tile and N_W0 / N_WL / N_A stand as they are.  An even k-step waits for its pair
+// (issued R k-steps earlier, at the same position: the plain counts) and decodes both operands; an odd one waits for nothing.  Pairs past a unit's end
+// read as zero through the descriptor range, code 0 decodes to +0.0.  The scales are requested in front of the prologue and waited for behind it.
+template <int DT, int MT, int CT, int NW, int SUB, int NS, int RW, int WPS, bool Z = false, bool WIDE = false, bool Q = false>
 __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__restrict__ x, const u32x4 *__restrict__ wp, float *__restrict__ out,
                                                         int M, int N, int K, int KC, int n_tiles, int rec_stride, int tile0, int ldx, int xmap,
                                                         const u32x2 *__restrict__ exc, int exc_cap)
 {
     static_assert(!Z || (DT == SJD_DTYPE_BF16 && SUB % 2 == 0 && (RW * SUB) % 2 == 0), "the 12-bit stream: bf16, whole record pairs per stage and ring");
+    static_assert(!Q || (!Z && DT == SJD_DTYPE_BF16 && SUB % 2 == 0 && (RW * SUB) % 2 == 0), "the 8-bit stream: bf16, whole record pairs per stage and ring");
     static_assert(SUB == 2 || SUB == 4 || SUB == 8, "a stage is 2, 4 or 8 k-steps");
     static_assert(CT == 1 || CT == 2, "one or two column tiles per wave");
     // The weight ring is RW stages (R k-steps) deep, the activation ring LA = NS - 1 stages ahead.  LA > RW matters: vmcnt retires in order, so the
@@ -171,6 +190,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
     u32x4 wr[CT];
     int t_out[CT];
     [[maybe_unused]] u32x2 hra[CT], hrb[CT];                                     // (Z) this lane's header entries of the tiles' units
+    [[maybe_unused]] float qs[CT];                                               // (Q) this lane's column scale of each tile
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
         t_out[c] = (bx * NW + w) * CT + c;
@@ -182,6 +202,11 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
             const u32x2 *e = exc + ((size_t)chunk * n_tiles + t) * (size_t)exc_cap;
             hra[c] = gw_gload2(e + min(lane, exc_cap - 1));
             if constexpr (WIDE) hrb[c] = gw_gload2(e + 64 + lane); else hrb[c] = u32x2{0xffffffffu, 0xffffffffu};
+        } else if constexpr (Q) {          // a chunk starts at byte k0 * N_packed; tile-major: a unit is steps * 512 contiguous bytes, step-major: pair p of every tile
+            const unsigned char *wq = reinterpret_cast<const unsigned char *>(wp);
+            const size_t tile_off = (rec_stride == 1) ? (size_t)t * steps * 512 : (size_t)t * 1024;
+            wr[c] = gw_rsrc(wq + (size_t)k0 * ((size_t)n_tiles * 32) + tile_off, has ? (unsigned)(pairs - 1) * rsb + 1024u : 0u);
+            qs[c] = gw_gload1(reinterpret_cast<const float *>(wq + (size_t)n_tiles * 32 * K) + 32 * t + (lane & 31));
         } else {
             const size_t tile_off = (rec_stride == 1) ? (size_t)t * steps : (size_t)t;
 #ifdef GW_NO_W            // (timing probe, results invalid: no weight stream -- every record out of range)
@@ -232,13 +257,18 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
         const unsigned voff = (int)xcol[i] < chunk_cols - sa * (SUB * 16) ? xoff[i] : 0x7fff0000u;
         gw_dma16(xr, voff, soff, dst);
     };
-    u32x4 W[CT][Z ? R / 2 : R];              // plain: one record per k-step of the ring; Z: the low bytes of one record pair per two k-steps
+    u32x4 W[CT][(Z || Q) ? R / 2 : R];       // plain: one record per k-step of the ring; Z: the low bytes of one record pair per two k-steps; Q: the pair
     [[maybe_unused]] u32x2 WC[CT][R / 2];    // (Z) ... and its codes
-    [[maybe_unused]] u32x4 Bn[CT];           // (Z) the odd k-step's operand, decoded with the even one's
+    [[maybe_unused]] u32x4 Bn[CT];           // (Z, Q) the odd k-step's operand, decoded with the even one's
     // (Z) record load of ring k-step ks: even -> the pair's low bytes, odd -> its codes
     auto z_load = [&](int c, int ks_ring, unsigned pair_abs) {
         if ((ks_ring & 1) == 0) W[c][ks_ring >> 1] = gw_wload(wr[c], wvoff, pair_abs * rsb);
         else WC[c][ks_ring >> 1] = gw_wload2(wr[c], 1024u + (unsigned)lane * 8u, pair_abs * rsb);
+    };
+    // (Q) record load of ring k-step ks: even -> the pair, odd -> an out-of-range piece into the scratch KiB (counted, no traffic, no register)
+    auto q_load = [&](int c, int ks_ring, unsigned pair_abs) {
+        if ((ks_ring & 1) == 0) W[c][ks_ring >> 1] = gw_wload(wr[c], wvoff, pair_abs * rsb);
+        else gw_dma16(xr, 0x7fff0000u, 0u, scratch);
     };
     f32x16 acc[CT][MT];
 #pragma unroll
@@ -258,12 +288,12 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
             const int ks = (v - (LA - RW)) * SUB + u;         // k-step of this group's records
 #pragma unroll
             for (int c = 0; c < CT - 1; ++c) {
-                if (ks >= 0) { if constexpr (Z) z_load(c, ks, (unsigned)(ks >> 1)); else W[c][ks] = gw_wload(wr[c], wvoff, (unsigned)ks * rsb); }
+                if (ks >= 0) { if constexpr (Z) z_load(c, ks, (unsigned)(ks >> 1)); else if constexpr (Q) q_load(c, ks, (unsigned)(ks >> 1)); else W[c][ks] = gw_wload(wr[c], wvoff, (unsigned)ks * rsb); }
                 else gw_dma16(xr, 0x7fff0000u, 0u, scratch);
             }
 #pragma unroll
             for (int d = 0; d < DPK; ++d) dma_piece(v, piece0 + (unsigned)(v * SLOT), u, d);
-            if (ks >= 0) { if constexpr (Z) z_load(CT - 1, ks, (unsigned)(ks >> 1)); else W[CT - 1][ks] = gw_wload(wr[CT - 1], wvoff, (unsigned)ks * rsb); }
+            if (ks >= 0) { if constexpr (Z) z_load(CT - 1, ks, (unsigned)(ks >> 1)); else if constexpr (Q) q_load(CT - 1, ks, (unsigned)(ks >> 1)); else W[CT - 1][ks] = gw_wload(wr[CT - 1], wvoff, (unsigned)ks * rsb); }
             else gw_dma16(xr, 0x7fff0000u, 0u, scratch);
         }
     // (Z) the unit headers: requested in front of the prologue, complete once no more than the prologue's own LA * SUB * GRP operations are outstanding
@@ -274,6 +304,10 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
             gw_wait_regs<LA * SUB * GRP>(hra[c], hrb[c]);
             hd[c] = g1z_header<WIDE>(g1z_hraw{hra[c], hrb[c]}, lane, exc_cap);
         }
+    }
+    if constexpr (Q) {         // the column scales: likewise
+#pragma unroll
+        for (int c = 0; c < CT; ++c) gw_wait_regs<LA * SUB * GRP>(qs[c]);
     }
     SJD_TR(1);
     // one k-step: the MFMAs in tile-major order, ONE other instruction group behind each of them (a single wave per SIMD issues in order: what is
@@ -294,6 +328,13 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
                     W[c][r >> 1] = g1z_operand<WIDE>(W[c][r >> 1].x, W[c][r >> 1].y, WC[c][r >> 1].x, s_abs, hd[c], lane);      // (held in the pair's own registers until its last MFMA)
                 }
                 b = (r & 1) == 0 ? W[c][r >> 1] : Bn[c];
+            } else if constexpr (Q) {
+                if (mt == 0 && (r & 1) == 0) {            // an even k-step: its pair was requested R k-steps ago at this position
+                    if (c == CT - 1) gw_wait_regs<N_WL>(W[c][r >> 1]); else gw_wait_regs<N_W0>(W[c][r >> 1]);
+                    Bn[c] = g1q_operand(W[c][r >> 1].z, W[c][r >> 1].w, qs[c]);
+                    W[c][r >> 1] = g1q_operand(W[c][r >> 1].x, W[c][r >> 1].y, qs[c]);      // (held in the pair's own register until its last MFMA)
+                }
+                b = (r & 1) == 0 ? W[c][r >> 1] : Bn[c];
             } else {
                 if (mt == 0) {
                     if (c == CT - 1) gw_wait_regs<N_WL>(W[c][r]); else gw_wait_regs<N_W0>(W[c][r]);
@@ -305,6 +346,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
             if (i >= D0 && ((i - D0) % DSTR) == 0 && (i - D0) / DSTR < DPK) dma_piece(st + LA, sb_refill, u, (i - D0) / DSTR);
             if (mt == MT - 1) {
                 if constexpr (Z) z_load(c, r, (unsigned)((st * SUB + u + R) >> 1));
+                else if constexpr (Q) q_load(c, r, (unsigned)((st * SUB + u + R) >> 1));
                 else W[c][r] = gw_wload(wr[c], wvoff, (unsigned)(st * SUB + u + R) * rsb);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -402,4 +444,47 @@ static int g1_wide_launch_z(const void *x, const void *wz, const void *exc, int 
     if (exc_cap > 64) SJD_G1WZ(true); else SJD_G1WZ(false);
 #undef SJD_G1WZ
     return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+}
+
+// G1wq: the same over the 8-bit e4m3 stream (wq: record pairs, then the fp32 column scales at byte N_packed * K); bf16, K and KC multiples of 32
+template <int MT, int CT, int NW, int SUB, int NS, int RW, int WPS>
+static int g1_wide_launch_q(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int n_tiles, int step_major, int tile0, hipStream_t s)
+{
+    const int n_out = N / 32, n_chunks = (K + KC - 1) / KC;
+    const dim3 grid((n_out + NW * CT - 1) / (NW * CT), n_chunks), block(64 * NW);
+    constexpr size_t lds = g1_wide_lds<MT, SUB, NS>();
+    static_assert(lds <= 160 * 1024, "the activation ring must fit in LDS");
+    constexpr int xmap = MT > 4;
+    auto kern = g1_wide<SJD_DTYPE_BF16, MT, CT, NW, SUB, NS, RW, WPS, false, false, true>;
+    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, (const unsigned short *)x, (const u32x4 *)wq, out, M, N, K, KC, n_tiles, step_major ? n_tiles : 1, tile0, K, xmap,
+                       (const u32x2 *)nullptr, 0);
+    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+}
+
+// SJD_G1_W8_E4M3 at 65..256 rows (g1q_launch, which has checked the column window): `waves` = column tiles per workgroup, the template shapes of the
+// uncompressed dispatch (g1_launch) per row-tile count; three row tiles x two tiles has no G1w form.  Anything else: SJD_ERR_UNSUPPORTED before a launch.
+template <int MT>
+static int g1wq_tiles(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int waves, int step_major, int n_tiles, int tile0, hipStream_t s)
+{
+    switch (waves) {
+    case 2: if constexpr (MT != 3) return g1_wide_launch_q<MT, 1, 2, 4, 3, 2, 1>(x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s); else return SJD_ERR_UNSUPPORTED;
+    case 3: return g1_wide_launch_q<MT, 1, 3, 4, 3, 2, 1>(x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+    case 4: return g1_wide_launch_q<MT, 1, 4, 4, 3, 2, 1>(x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+    case 6: return g1_wide_launch_q<MT, 2, 3, 4, 3, 2, 1>(x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+    case 8: return g1_wide_launch_q<MT, 2, 4, 4, 3, 2, 1>(x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+    default: return SJD_ERR_UNSUPPORTED;
+    }
+}
+static int g1wq_launch(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int waves, int step_major, int n_tiles, int tile0, hipStream_t s)
+{
+    if (M <= 64 || M > 256 || (K % 32) != 0 || (KC % 32) != 0) return SJD_ERR_UNSUPPORTED;
+    switch ((M + 31) / 32) {
+    case 3: return g1wq_tiles<3>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
+    case 4: return g1wq_tiles<4>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
+    case 5: return g1wq_tiles<5>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
+    case 6: return g1wq_tiles<6>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
+    case 7: return g1wq_tiles<7>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
+    default: return g1wq_tiles<8>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
+    }
 }

@@ -83,7 +83,12 @@ class SJDBatchEngine:
         if getattr(bargs, "swin_norm", False) or getattr(bargs, "model_parallel_size", 1) != 1:
             raise ValueError("SJDBatchEngine does not serve swin-norm backbones (swin_norm=True or model_parallel_size > 1, the 30B-class "
                              "Chameleon form): decode them one prompt at a time with SJDEngine / FlexARInferenceSolver")
-        if getattr(backbone, "weights", None) == "e4m3":
+        q8_rows = getattr(backbone, "max_rows", 64) if getattr(backbone, "_max_rows_given", False) else None       # enable_fused(weights=..., max_rows=...)
+        if getattr(backbone, "weights", None) == "e4m3" and q8_rows is not None and q8_rows < n_prompts * n_batch * max_window <= 256:
+            raise ValueError(f"the backbone was packed for windows of at most max_rows={q8_rows} rows, but n_prompts * n_batch * max_window = "
+                             f"{n_prompts * n_batch * max_window}: call enable_fused(ops, gemm='sjd', weights='e4m3', "
+                             f"max_rows={128 if n_prompts * n_batch * max_window <= 128 else 256}), or use fewer prompts per forward")
+        if getattr(backbone, "weights", None) == "e4m3" and q8_rows is None:
             raise ValueError("SJDBatchEngine does not serve a backbone packed with enable_fused(weights='e4m3'): 8-bit weights serve one prompt per "
                              "forward (at most 64 window rows) in this version -- decode with SJDEngine, or pack with weights=None")
         L.load()                                   # fail loudly if the HIP extension is missing

@@ -632,7 +632,9 @@ def _prows(M):
 
 def skinny_gemm(x, w_packed, N, K, KC, waves=4, step_major=False):
     """x [M <= 256, K] bf16/fp16 -> Partials([n_chunks, 32 * ceil(M / 32), N] fp32).  waves = column tiles per workgroup: 1..16 up to 64 rows, <= 8 up to
-    128 rows; 129..256 rows (bf16 or fp16, uncompressed packing) run on kernel G1w: 2, 3, 4, 6 or 8."""
+    128 rows; 129..256 rows (bf16 or fp16, uncompressed packing) run on kernel G1w: 2, 3, 4, 6 or 8.  A PackedQ8 weight (bf16): up to 64 rows on kernel
+    G1q (min(KC, K) <= 2560 up to 32 rows, <= 1280 above); 65..256 rows on kernel G1wq with 2, 3, 4, 6 or 8 tiles (not 2 at 65..96 rows), K and KC
+    multiples of 32 -- the planes of the same call on pack_weight(w_packed.dequant(), KC, step_major), bit for bit."""
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N * K
     _same_16bit_type(x, w_packed, "skinny_gemm")
@@ -785,7 +787,8 @@ def _raw_units(w_packed, gateup=False):
 
 
 def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_major=True):
-    """G1 over the vocabulary columns [col0, col0 + n_cols) (32-aligned) of a weight packed with N_packed columns -> Partials [n_chunks, R, n_cols]."""
+    """G1 over the vocabulary columns [col0, col0 + n_cols) (32-aligned) of a weight packed with N_packed columns -> Partials [n_chunks, R, n_cols].
+    Row counts and `waves` per packing as skinny_gemm (PackedZ: up to 128 rows; PackedQ8: up to 256, kernels G1q / G1wq)."""
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N_packed * K and col0 % 32 == 0 and n_cols % 32 == 0
     nc = (K + KC - 1) // KC

@@ -80,8 +80,10 @@ extern "C" {
  *                         [Wg; Wu] packed with KC = K / 2).  The kernels rebuild the bf16 operand code * scale exactly, so the planes / the 16-bit
  *                         output are bit for bit what the same call writes for the 16-bit packing of the dequantised weight: the format's loss is
  *                         the host-side quantiser's alone.  Valid with SJD_DTYPE_BF16 only; M <= 64 with min(KC, K) <= 2560 (M <= 32) / <= 1280
- *                         (sjd_gateup_silu: M <= 32, K in {512, 1024, 2048, 4096}); everything else, and every other entry point given the bit,
- *                         returns SJD_ERR_UNSUPPORTED.  SJD_VERSION did not move with it: a library without the bit returns SJD_ERR_UNSUPPORTED
+ *                         (sjd_gateup_silu: M <= 32, K in {512, 1024, 2048, 4096}); sjd_skinny_gemm / sjd_skinny_gemm_cols also 65 <= M <= 256 (kernel
+ *                         G1wq, the 8-bit form of G1w, csrc/sjd_gemm_wide.h) with `waves` = column tiles per workgroup in {2, 3, 4, 6, 8} (not 2 at
+ *                         65..96 rows), K % 32 == 0 and KC % 32 == 0 (whole pairs, no half records), any KC; everything else, and every other entry
+ *                         point given the bit, returns SJD_ERR_UNSUPPORTED before any launch.  SJD_VERSION did not move with it: a library without the bit returns SJD_ERR_UNSUPPORTED
  *                         for it, which is the probe. */
 #define SJD_DTYPE_MASK 0xff
 #define SJD_F1_POST_NORM 0x100

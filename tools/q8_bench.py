@@ -10,6 +10,13 @@ median and spread (min .. max over the rounds) per leg.
             enable_fused(weights="e4m3"), two backbones with the same synthetic weights, each decoded through a real lead-in so that the timed
             iterations are centred on the mean KV length (bench.py's method), ms per SJD iteration.
 
+  --batch   several prompts per forward (SJDBatchEngine): the same workload with 2 / 4 / 8 prompts sharing the window forward (64 / 128 / 256 rows) --
+            enable_fused(weights="e4m3", max_rows=64 / 128 / 256) against what those row counts run otherwise: the default 12-bit stream at 2 / 4
+            prompts (G1_CFG_64ROW / G1_CFG_128ROW), compress=False at 8 (G1_CFG_256ROW) -- and at 4 as well, which is what bench.py runs there.  Per
+            prompt count one backbone per leg with the same synthetic
+            weights, the timed iterations centred on the mean KV length by a warm-up of whole window iterations; ms per shared window forward, packed
+            bytes per step, and us per launch of the four projections as each backbone runs them (its own 32 packed layers in turn, from a hipGraph).
+
 One JSON document on stdout (and in --out)."""
 import argparse
 import copy
@@ -138,10 +145,96 @@ def step_legs(a, dev):
     return rec
 
 
+def batch_launches(a, model, rows, dev, lib):
+    """us per launch of the four projections of `model` at `rows` window rows, as its window forward runs them"""
+    m = model.args
+    H, Hkv, D, hid, inter = model.n_heads, model.n_kv_heads, model.head_dim, m.hidden_size, m.intermediate_size
+    out = {}
+    for name, (N, K) in dict(qkv=((H + 2 * Hkv) * D, hid), o=(hid, H * D), gate_up=(2 * inter, hid), down=(hid, inter)).items():
+        KC0, waves, sm = model.G1_CFG[name]
+        KC = model._q8_chunk(name, rows, K)
+        pk = [d[name] for d in model._packed]
+        x = torch.randn(rows, K, device=dev).to(torch.bfloat16)
+        fused = name == "gate_up" and rows <= 64 and ops.gateup_silu_ok(rows, inter, hid, KC0, isinstance(pk[0], ops.PackedZ), model.weights is not None)
+        if fused:
+            run = lambda i: ops.gateup_silu(x, pk[i % len(pk)], inter, hid, sm)
+        elif name == "gate_up":
+            run = lambda i: ops.silu_mul(ops.skinny_gemm(x, pk[i % len(pk)], N, K, KC, waves, sm), rows=rows, dtype=x.dtype)
+        else:
+            run = lambda i: ops.skinny_gemm(x, pk[i % len(pk)], N, K, KC, waves, sm)
+        us = [timed_graph(run, a.launches, lib)[1] * 1e3 for _ in range(a.rounds)]
+        size = pk[0].nbytes() if isinstance(pk[0], (ops.PackedZ, ops.PackedQ8)) else pk[0].numel() * pk[0].element_size()
+        out[name] = dict(cfg=[KC, waves, int(sm)], launch="fused gate|up + SiLU" if fused else ("projection + F3" if name == "gate_up" else "projection"),
+                         us=spread(us), stored_bytes=size, frac_of_8TBps_on_stored_bytes=round(size / (statistics.median(us) * 1e-6) / PEAK, 4))
+    return out
+
+
+def batch_legs(a, dev, lib):
+    import bench
+    from sjd_amd.engine_batch import SJDBatchEngine
+    from sjd_amd.frontends import lumina_prompt, lumina_window_spec
+    out = []
+    for PP in [int(v) for v in a.prompts.split(",")]:
+        rows = 2 * PP * 16
+        base = bench.parse(["--gpus", "1", "--steps", str(a.steps), "--warmup", str(a.warmup)])
+        base.model, base.window, base.prompts_per_gpu, base.n_split = "lumina7b", 16, PP, 0
+        legs = {}
+        tags = (("z12",) if rows <= 64 else ("z12", "bf16") if rows <= 128 else ("bf16",)) + ("q8",)      # (four prompts: bench.py itself runs compress=False)
+        for tag in tags:
+            b = copy.copy(base)
+            b.no_fused = True                             # (each leg calls enable_fused itself, on the same synthetic weights)
+            if tag == "q8":
+                b.prompts_per_gpu = 1                     # (no G1_CFG of the caller's: enable_fused takes its 8-bit set)
+            model, margs, attn = bench.build_model(b, dev)
+            if tag == "q8":
+                model.enable_fused(ops, gemm="sjd", weights="e4m3", max_rows=64 if rows <= 64 else 128 if rows <= 128 else 256)
+            else:
+                model.enable_fused(ops, gemm="sjd", compress=False if tag == "bf16" else None)
+            w = bench.workload_of(base, margs, 0, dev)
+            P, n_img = w["P"], w["n_img"]
+            model.setup_cache(batch=2 * PP, s_max=((P + n_img + 2 * 16 + 64 + 31) // 32) * 32)
+            eng = SJDBatchEngine(model, margs.vocab_size, dev, PP, max_window=16, use_graph=True)
+            prompts = [lumina_prompt(P, w["grid"], w["grid"], seed=1234 + i) for i in range(PP)]
+            legs[tag] = dict(model=model, eng=eng, w=w, prompts=prompts, specs=[lumina_window_spec(p_, dev) for p_ in prompts], ms=[], tok=[], kv=[],
+                             warm=max(a.warmup, int(n_img / 2 / w["tau_est"] - a.steps / 2)))
+        sync = torch.cuda.synchronize
+        for rnd in range(a.rounds + 1):                   # round 0 is untimed practice: every hipGraph of the decode is captured in it
+            for tag in tags:
+                lg = legs[tag]
+                w = lg["w"]
+                res = lg["eng"].decode_many(lg["prompts"], lg["specs"], [copy.deepcopy(w["grammar"]) for _ in range(PP)], w["cfg"], warmup_iters=lg["warm"],
+                                            timed_iters=a.steps, on_timed_start=sync, on_timed_end=sync)
+                rs = lg["eng"].run_stats
+                if rnd:
+                    lg["ms"].append(rs["seconds"] / max(rs["timed_iterations"], 1) * 1e3)
+                    lg["tok"].append(round(rs["tokens"] / max(rs["timed_iterations"], 1), 3))
+                    lg["kv"].append([len(seq) for seq, _ in res])
+        rec = dict(prompts_per_forward=PP, rows=rows, steps=a.steps, warmup_iterations=legs["q8"]["warm"], rounds=a.rounds,
+                   order="alternating " + ", ".join(tags) + " per round after one untimed round; one process, one device",
+                   today="z12" if rows <= 128 else "bf16")
+        for tag, lg in legs.items():
+            m = lg["model"]
+            rec[tag] = dict(weights=m.weights, compress=bool(m.compress), max_rows=getattr(m, "max_rows", None), G1_CFG={k: list(v) for k, v in m.G1_CFG.items()},
+                            ms_per_step=spread(lg["ms"]), tokens_per_step=lg["tok"], sequence_len_at_end=lg["kv"], layer_bytes_per_step=m.packed_bytes(head=False),
+                            bytes_per_step_with_head=m.packed_bytes(), per_launch=batch_launches(a, m, rows, dev, lib))
+        q = rec["q8"]["ms_per_step"]
+        rec["largest_spread_between_rounds_ms"] = round(max(rec[tag]["ms_per_step"]["max"] - rec[tag]["ms_per_step"]["min"] for tag in tags), 4)
+        for tag in tags[:-1]:
+            rec[f"q8_minus_{tag}_ms"] = round(q["median"] - rec[tag]["ms_per_step"]["median"], 4)
+            rec[f"q8_minus_{tag}_exceeds_spread"] = bool(abs(rec[f"q8_minus_{tag}_ms"]) > rec["largest_spread_between_rounds_ms"])
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+        del legs, model, eng
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launch", action="store_true")
     ap.add_argument("--step", action="store_true")
+    ap.add_argument("--batch", action="store_true")
+    ap.add_argument("--prompts", default="2,4,8", help="--batch: prompts per forward, comma separated")
     ap.add_argument("--launches", type=int, default=48)
     ap.add_argument("--copies", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=3)
@@ -159,6 +252,10 @@ def main():
                                     f"{a.rounds} rounds alternating bf16 / 12-bit / 8-bit; us per launch: median, min, max over the rounds")
     if a.step:
         doc["per_step"] = step_legs(a, dev)
+    if a.batch:
+        doc["per_batch_step"] = batch_legs(a, dev, lib)
+        doc["per_batch_step_workload"] = ("Lumina-mGPT-7B architecture 768x768 (synthetic weights), 2 / 4 / 8 prompts sharing one window forward, draft window 16, "
+                                          "CFG 3.0, bf16, 16-bit KV cache")
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
