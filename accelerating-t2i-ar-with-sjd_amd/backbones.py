@@ -28,6 +28,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
+from . import launch_shapes as LS
+
 import logging as _logging
 import os as _os
 _log = _logging.getLogger("sjd_amd.backbones")
@@ -73,6 +75,19 @@ def _head_logits(linear, x, cols):
     w = linear.weight[cols[0]:cols[1]]
     b = linear.bias[cols[0]:cols[1]] if linear.bias is not None else None
     return F.linear(x, w, b).float()
+
+
+def _head_partials(model, h, delta, cols, n, hid, eps, sumsq=None):
+    """final residual add + the output head of a fused backbone as G1 split-K partials over the column window `cols` -> ops.HeadOut (K2 applies
+    the folded final RMSNorm as a row scale while it reads them).  sumsq: the statistics of h when the residual add is already done."""
+    ops = model._ops
+    if sumsq is None:
+        sumsq = ops.residual_sumsq(h, delta)
+    lo, hi = cols if cols is not None else (0, model.vocab_size)
+    lo32, hi32 = (lo // 32) * 32, min(model._head_cols, ((hi + 31) // 32) * 32)
+    kc, tiles, sm = model.HEAD_CFG
+    part = ops.skinny_gemm_cols(h, model._packed_head, model._head_cols, hid, kc, lo32, hi32 - lo32, tiles, sm)
+    return ops.HeadOut(part, lo32, n if h.shape[0] > n else 0, h.dtype, row_norm=(sumsq, hid, eps))
 
 
 class StaticKVCache:
@@ -272,40 +287,11 @@ class LlamaGenBackbone(nn.Module):
             return self._forward_window_g1(tokens, positions, kv_len, key_start, cols, head_partials)
         return self.forward_embeds(self.tok_embeddings(tokens), positions, kv_len, key_start, cols=cols)
 
-    # G1 launch shapes of the window forward (<= 64 rows): (split-K chunk, column tiles per workgroup, step-major packing) per projection and for
-    # the output head.  `tools/llamagen_bench.py --sweep` at 32 rows, GPT-XL (profiles/llamagen_g1_sweep.jsonl): per projection the fastest shape
-    # with at most eight split-K planes (one batch of plane loads in F1r / F2 / F3), us per launch q|k|v 5.36, o 4.46, gate|up 6.64, down 6.35,
-    # head 10.09 (the launch-alone optimum, KC 128, is 0.3 - 1.4 us faster but leaves 10 - 28 planes for the consumer to sum)
-    G1_CFG_LLAMAGEN = dict(qkv=(256, 2, True), o=(256, 2, False), gate_up=(320, 2, False), down=(512, 2, False))
-    HEAD_CFG = (640, 4, True)
-    # Several prompts per forward (SJDBatchEngine): 65..128 and 129..256 window rows run on G1's sub-tiled kernels / kernel G1w, whose workgroups
-    # take 2, 3, 4, 6 or 8 column tiles.  The packed layout depends on the split-K chunk, so the set is chosen when the weights are packed:
-    # enable_fused(..., max_rows=128 / 256); forward_window then serves windows of up to that many rows on the HIP path.
-    # `tools/llamagen_bench.py --sweep --rows 128 / 256`, GPT-XL (profiles/llamagen_g1_sweep_128rows.jsonl, _256rows.jsonl): per projection the
-    # fastest shape with at most eight planes -- us per launch at 128 rows q|k|v 6.92, o 5.36, gate|up 8.68, down 7.27, head 12.54; at 256 rows
-    # 9.80, 8.16, 12.31, 11.18, 17.87 (the 32-row set at 256 rows would still run: every tile count above is one kernel G1w takes)
-    G1_CFG_LLAMAGEN_128ROW = dict(qkv=(320, 2, False), o=(256, 2, False), gate_up=(320, 4, True), down=(512, 2, False))
-    HEAD_CFG_128ROW = (640, 4, True)
-    G1_CFG_LLAMAGEN_256ROW = dict(qkv=(256, 4, False), o=(256, 2, False), gate_up=(320, 4, True), down=(512, 4, False))
-    HEAD_CFG_256ROW = (640, 4, True)
-    G1_WIDE_TILES = (2, 3, 4, 6, 8)
-    # GPT-3B (dim 3200, 32 heads of 100 stored 128 wide: pad_head_dim=True; inter 8704; the o projection's K is 32 * 128 = 4096): the KC 256 / 320 / 512
-    # of the sets above would leave 13 / 10 / 17 planes, so the chunks are the smallest multiples of 16 that give eight -- 400 for hidden 3200, 512 for
-    # the o projection, 1088 for the down projection.  `tools/llamagen_bench.py --sweep --preset GPT-3B` at 32 rows (profiles/llamagen_g1_sweep_3b.jsonl):
-    # per projection the fastest shape with at most eight planes, us per launch q|k|v 12.83 (five planes), o 8.28, gate|up 20.81 (three planes),
-    # down 13.69, head 19.51; against the smallest-chunk set (400, 2) / (512, 2) / (400, 2) / (1088, 2) + head (640, 4) the fused step goes
-    # 2.19 -> 1.89 ms (profiles/llamagen_3b.json)
-    G1_CFG_LLAMAGEN_3B = dict(qkv=(640, 8, True), o=(512, 4, False), gate_up=(1088, 8, True), down=(1088, 4, True))
-    HEAD_CFG_3B = (1088, 8, True)
-    # GPT-3B with several prompts per forward (enable_fused(pad_head_dim=True, padded_batch=True, max_rows=128 / 256)): the same rule at 128 and 256 rows --
-    # `tools/llamagen_bench.py --sweep --preset GPT-3B --rows 128 / 256` (profiles/llamagen_g1_sweep_3b_128rows.jsonl, _256rows.jsonl), per projection the
-    # fastest shape with at most eight planes (chunk >= 400 / 512 / 1088 for K = 3200 / 4096 / 8704) among kernel G1w's column-tile counts; us per launch
-    # at 128 rows q|k|v 16.80 (three planes), o 9.68, gate|up 26.54, down 16.56, head 24.82 (two planes); at 256 rows 25.45, 14.40, 37.97, 23.14, 35.56.
-    # (q|k|v's 9600 columns are 300 tiles: 75 workgroups of four; the head's 512 tiles by four; fp16 at 65..128 rows keeps the sub-tiled kernels on these shapes)
-    G1_CFG_LLAMAGEN_3B_128ROW = dict(qkv=(1088, 4, False), o=(512, 4, False), gate_up=(1088, 8, False), down=(1088, 4, True))
-    HEAD_CFG_3B_128ROW = (1600, 4, True)
-    G1_CFG_LLAMAGEN_3B_256ROW = dict(qkv=(1088, 4, False), o=(512, 4, True), gate_up=(1088, 8, True), down=(1088, 4, True))
-    HEAD_CFG_3B_256ROW = (1600, 4, True)
+    # the tuned launch-shape sets under the names tools and tests read (launch_shapes.py holds them, with where each came from)
+    (G1_CFG_LLAMAGEN, HEAD_CFG), (G1_CFG_LLAMAGEN_3B, HEAD_CFG_3B) = LS.LLAMAGEN_SETS[False, 64], LS.LLAMAGEN_SETS[True, 64]
+    (G1_CFG_LLAMAGEN_128ROW, HEAD_CFG_128ROW), (G1_CFG_LLAMAGEN_3B_128ROW, HEAD_CFG_3B_128ROW) = LS.LLAMAGEN_SETS[False, 128], LS.LLAMAGEN_SETS[True, 128]
+    (G1_CFG_LLAMAGEN_256ROW, HEAD_CFG_256ROW), (G1_CFG_LLAMAGEN_3B_256ROW, HEAD_CFG_3B_256ROW) = LS.LLAMAGEN_SETS[False, 256], LS.LLAMAGEN_SETS[True, 256]
+    G1_WIDE_TILES = LS.WIDE_TILES
     HEAD_PAD = 128                # storage head dim of a padded model (the K1 / F2 shape of Lumina-7B: 32 heads, D 128, H == H_kv)
 
     @staticmethod
@@ -355,19 +341,17 @@ class LlamaGenBackbone(nn.Module):
             # (the plain call keeps what it did before fp16 was served at 129..256 rows: nobody gets launch shapes that were never swept for fp16 unasked)
             raise ValueError("LlamaGenBackbone.enable_fused: max_rows=256 packs bf16 weights; it keeps fp16 windows of at most 128 rows unless "
                              "untuned_fp16=True (kernel G1 serves fp16 at 129..256 rows on the launch shapes swept in bf16)")
-        if max_rows > 64 or pad100:  # (the default keeps packing exactly what it packed before: a G1_CFG / HEAD_CFG set by the caller still wins)
-            sfx = ("_3B" if pad100 else "") + (f"_{max_rows}ROW" if max_rows > 64 else "")          # G1_CFG_LLAMAGEN_3B, _128ROW, _3B_128ROW, ...
-            if "G1_CFG" not in self.__dict__:
-                self.G1_CFG = dict(getattr(self, "G1_CFG_LLAMAGEN" + sfx))
-            if "HEAD_CFG" not in self.__dict__:
-                self.HEAD_CFG = tuple(getattr(self, "HEAD_CFG" + sfx))
+        # (a G1_CFG / HEAD_CFG set by the caller still wins)
+        g1_cfg, head_cfg = LS.LLAMAGEN_SETS[pad100, max_rows]
+        g1_cfg = self.__dict__.get("G1_CFG") or dict(g1_cfg)          # (the default keeps packing exactly what it packed before: the class's HEAD_CFG)
+        head_cfg = self.__dict__.get("HEAD_CFG") or (head_cfg if max_rows > 64 or pad100 else None)
         if max_rows > 64:
-            bad = [k for k, c_ in list(self.G1_CFG.items()) + [("head", self.HEAD_CFG)] if c_[1] not in self.G1_WIDE_TILES]
+            bad = [name for name, _ in LS.check_set(g1_cfg, head_cfg or self.HEAD_CFG, max_rows)]
             if bad:
-                raise ValueError(f"windows of more than 64 rows take {self.G1_WIDE_TILES} column tiles per workgroup; offending launch shapes: {bad}")
-        if "G1_CFG" not in self.__dict__:
-            self.G1_CFG = dict(self.G1_CFG_LLAMAGEN)
-        c = self.G1_CFG
+                raise ValueError(f"windows of more than 64 rows take {LS.WIDE_TILES} column tiles per workgroup; offending launch shapes: {bad}")
+        c = self.G1_CFG = g1_cfg
+        if head_cfg is not None:
+            self.HEAD_CFG = tuple(head_cfg)
         fold = lambda w, g: (w.float() * g.float()[None, :]).to(w.dtype)      # W' = W diag(gamma)
         wo_of = (lambda w: self._pad_o_weight(w, self.n_heads, self.head_dim, self.HEAD_PAD)) if pad100 else (lambda w: w)
         self._packed, self._fused = [], []
@@ -402,8 +386,7 @@ class LlamaGenBackbone(nn.Module):
 
     def packed_bytes(self):
         """bytes of packed weights one fused window forward streams (every layer and the whole output head)"""
-        per = sum(w.numel() * w.element_size() for d in self._packed for w in d.values())
-        return per + self._packed_head.numel() * self._packed_head.element_size()
+        return sum(LS.packed_nbytes(w) for d in self._packed for w in d.values()) + LS.packed_nbytes(self._packed_head)
 
     def _forward_window_g1(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
         ops, B, n = self._ops, tokens.shape[0], tokens.shape[1]
@@ -433,12 +416,7 @@ class LlamaGenBackbone(nn.Module):
                 act = ops.silu_mul(g1(h, li, "gate_up", 2 * inter, hid), rows=T, dtype=h.dtype, row_norm=rn)
             delta = g1(act, li, "down", hid, inter)
         if head_partials:
-            sumsq = ops.residual_sumsq(h, delta)
-            lo, hi = cols if cols is not None else (0, self.vocab_size)
-            lo32, hi32 = (lo // 32) * 32, min(self._head_cols, ((hi + 31) // 32) * 32)
-            part = ops.skinny_gemm_cols(h, self._packed_head, self._head_cols, hid, self.HEAD_CFG[0], lo32, hi32 - lo32, self.HEAD_CFG[1],
-                                        self.HEAD_CFG[2])
-            return ops.HeadOut(part, lo32, n if T > n else 0, h.dtype, row_norm=(sumsq, hid, eps))
+            return _head_partials(self, h, delta, cols, n, hid, eps)
         x = ops.add_rmsnorm(h, delta, self.norm.weight, eps)
         return _head_logits(self.output, x, cols).view(B, n, -1)
 
@@ -572,57 +550,11 @@ class ChameleonBackbone(nn.Module):
         emb = torch.cat((freqs, freqs), dim=-1)
         return emb.cos().to(dtype)[:, :, None, :], emb.sin().to(dtype)[:, :, None, :]
 
-    # G1 launch shape per projection: (split-K chunk, column tiles per workgroup, step-major packing) -- tuned on MI355X with
-    # tools/g1_bench.py so that every launch gives the 256 CUs ~1000+ balanced waves
-    G1_CFG = dict(qkv=(896, 8, True), o=(512, 6, False), gate_up=(2048, 8, True), down=(896, 8, False))
-    # the same for the 12-bit weight stream (G1z): the launch-shape sweep of tools/g1z_bench.py --sweep and an end-to-end A/B on one box
-    # (profiles/r3_g1z_microbench.txt: 3.068 / 3.090 -> 3.044 ms per step); taken by enable_fused when the caller has not set G1_CFG itself
-    G1_CFG_Z = dict(qkv=(1024, 6, True), o=(512, 6, False), gate_up=(2048, 8, True), down=(768, 8, False))
-    # the same for 64-row windows (two prompts per forward, or a draft window of 32): the staged chunk is twice as tall, so KC <= 1280;
-    # set `model.G1_CFG = model.G1_CFG_64ROW` before enable_fused (the packing depends on KC).  Tuned end to end at Lumina-7B shapes.
-    # (round 3: gate|up packed in two K halves = the copy kernel G1s streams, which now serves 64 rows; (1024, 12) was the G1 + F3 shape)
-    # (late round 6: o on four column tiles per workgroup -- on the 12-bit stream that launch shape runs on kernel G1w's 12-bit form, the one place it beats
-    #  G1z: two prompts per forward 3.50 -> 3.44 ms per step, profiles/r6_g1wz_o_64rows_ab.txt; round 2's shape: o (512, 8, False))
-    G1_CFG_64ROW = dict(qkv=(896, 8, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(896, 8, False))       # profiles/r2_g1_launch_shape_sweep_64rows.jsonl
-    # 65..128-row windows (three / four prompts per forward): the activation is sub-tiled, so KC is free again, but <= 8 waves.  Round 3:
-    # 4-wave workgroups run on g1_skinny_gemm_tiled8 (8-step sub-tiles, two workgroups per CU, weight ring refilled in place) -- q|k|v,
-    # o and down are faster there (28.1 / 15.8 / 28.4 -> 25.7 / 12.2 / 24.0 us); 8-wave workgroups run on the same kernel with one workgroup
-    # per CU (gate|up 49.4 -> 43.3 us, profiles/r3_g1_tiled8.txt); four prompts per forward 5.55 -> 4.89 ms per step on one box
-    # (late round 6: bf16 windows of 65..128 rows run on kernel G1w as well -- the second number is then its column tiles per workgroup -- with gate|up
-    #  on six tiles and down in chunks of 1408: four prompts 4.43 -> 4.26 ms per step, three 4.05 -> 3.95 on one box, profiles/r6_g1w_128rows_ab.txt;
-    #  round 5's shapes: gate_up (2048, 8), down (1376, 4).  fp16 and the 12-bit stream keep the sub-tiled kernels on the same shapes.)
-    G1_CFG_128ROW = dict(qkv=(2048, 4, True), o=(896, 4, True), gate_up=(2048, 6, True), down=(1408, 4, True))
-    # 129..256-row windows (five to eight prompts per forward): kernel G1w (csrc/sjd_gemm_wide.h, round 6) -- the second number is the column tiles
-    # per workgroup: 2, 3, 4 (one per wave) or 6, 8 (two per wave).  tools/g1w_bench.py at 256 rows (profiles/r6_g1w_sweep.txt), us per launch against
-    # round 5's g1_skinny_gemm_tiled8: q|k|v 34.3 / 46.1, o 19.6 / 23.4, gate|up 58.4 / 84.4, down 31.3 / 38.2 (hipBLASLt: 50.4 / 19.1 / 65.9 / 52.7); o with
-    # four planes instead of (512, 4)'s eight: 16.4 us alone, but 7.18 against 7.37 ms per step (F1r sums the planes; profiles/r6_g1w_cfg_ab.txt)
-    G1_CFG_256ROW = dict(qkv=(2048, 4, True), o=(1024, 2, True), gate_up=(2048, 8, True), down=(1408, 4, True))
-    G1_WIDE_TILES = (2, 3, 4, 6, 8)
-    # Emu3-Gen 8B (GQA 32/8: the q|k|v projection has 6144 columns; draft window 32 -> 64 rows), tuned end to end with bench.py --model emu3_8b
-    # (late round 6: 33..64-row windows on the uncompressed stream run on kernel G1w -- the second number is its column tiles per workgroup -- with its own
-    #  shapes: per launch q|k|v 12.8 / 13.6 us, o 9.4 / 11.2, down 22.5 / 25.2 against round 2's (512, 8) / (512, 8) / (896, 8) on the whole-chunk kernel,
-    #  profiles/r6_g1w_sweep_64rows_emu3.jsonl; Emu3 in fp16 4.37 -> 4.17 ms per step, profiles/r6_g1w_64rows_emu3_ab.txt)
-    G1_CFG_EMU3 = dict(qkv=(1024, 4, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(1792, 4, True))
-    # the same on the 12-bit stream (Emu3 in bf16, round 4): 256-workgroup launches for q|k|v and o, step-major packing -- 11.75 / 10.25 / 19.85 us
-    # against 12.15 / 10.66 / 20.19 (tools/g1z_bench.py --sweep --emu3 --rows 64, profiles/r4_g1z_sweep_emu3_64rows.jsonl)
-    G1_CFG_EMU3_Z = dict(qkv=(512, 6, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(896, 8, True))
-    # the 8-bit e4m3 stream (enable_fused(weights="e4m3"), kernels G1q / G1sq): UNTUNED -- the 12-bit sets with every chunk cut to what G1q stages whole
-    # in LDS at the architecture's row count (Emu3: 64 rows, KC <= 1280, so its gate|up runs unfused as G1q + F3 in four chunks); no launch-shape
-    # sweep was run for this format.  G1_CFG_Q8's gate|up keeps the two K halves of 2048 that the fused 32-row launch (G1sq) streams; a window of
-    # 33..64 rows (a draft window of 32 with CFG, the prefill of a 17..32-token prompt) reads that step-major copy in chunks of 1024 (_q8_chunk)
-    G1_CFG_Q8 = dict(qkv=(1024, 6, True), o=(512, 6, False), gate_up=(2048, 8, True), down=(768, 8, False))
-    G1_CFG_EMU3_Q8 = dict(qkv=(512, 6, True), o=(512, 4, True), gate_up=(1024, 8, True), down=(896, 8, True))
-    # the 8-bit stream for several prompts per forward (enable_fused(weights=..., max_rows=128 / 256)): UNTUNED -- G1_CFG_256ROW / G1_CFG_EMU3 as they are,
-    # except o on three column tiles (kernel G1wq, like G1w, has no form of three row tiles x two column tiles: 65..96 rows).  ONE packed copy serves every row
-    # count: <= 32 rows on G1q / G1sq (every chunk <= 2560; gate|up in the two K halves the fused launch streams), 33..64 on G1q in halved chunks
-    # (_q8_chunk: all step-major, K and the chunks multiples of 32 / 64), 65..256 on G1wq with these chunks and tile counts.  No sweep was run.
-    G1_CFG_Q8_WIDE = dict(qkv=(2048, 4, True), o=(1024, 3, True), gate_up=(2048, 8, True), down=(1408, 4, True))
-    G1_CFG_EMU3_Q8_WIDE = dict(qkv=(1024, 4, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(1792, 4, True))
-    # 30B-class Chameleon (hidden 8192, intermediate 22016, GQA 64 / 8: q|k|v 10240 columns, gate|up 44032, down K 22016); chunks <= 2560 so that
-    # the 32-row window stages its chunk in LDS.  The fastest shapes of `tools/swin30b_bench.py --sweep` at 32 rows on one MI355X
-    # (profiles/g1_30b_sweep.jsonl), us per launch uncompressed / 12-bit: q|k|v 30.4 / 25.2, o 23.8 / 20.3, gate|up 120.5 / 98.9, down 62.9 / 50.4
-    G1_CFG_30B = dict(qkv=(1536, 8, True), o=(1536, 8, False), gate_up=(2048, 8, True), down=(1536, 8, False))
-    G1_CFG_30B_Z = dict(qkv=(1792, 8, True), o=(1280, 8, True), gate_up=(2048, 8, True), down=(1536, 8, True))
+    # launch_shapes.py's tuned sets under the names bench.py, tools and tests read; G1_CFG / HEAD_CFG: the default when neither the caller nor LS.default_shapes sets another
+    G1_CFG, G1_CFG_Z, G1_CFG_64ROW, G1_CFG_128ROW, G1_CFG_256ROW = LS.G1_CFG, LS.G1_CFG_Z, LS.G1_CFG_64ROW, LS.G1_CFG_128ROW, LS.G1_CFG_256ROW
+    G1_CFG_EMU3, G1_CFG_EMU3_Z, G1_CFG_Q8, G1_CFG_EMU3_Q8 = LS.G1_CFG_EMU3, LS.G1_CFG_EMU3_Z, LS.G1_CFG_Q8, LS.G1_CFG_EMU3_Q8
+    G1_CFG_Q8_WIDE, G1_CFG_EMU3_Q8_WIDE, G1_CFG_30B, G1_CFG_30B_Z = LS.G1_CFG_Q8_WIDE, LS.G1_CFG_EMU3_Q8_WIDE, LS.G1_CFG_30B, LS.G1_CFG_30B_Z
+    HEAD_CFG, HEAD_CFG_WIDE, G1_WIDE_TILES = LS.HEAD_CFG, LS.HEAD_CFG_WIDE, LS.WIDE_TILES
 
     # Weight prefetch plan of the G1 window forward: projection -> (workgroups of the prefetch kernel, when it is issued).  The packed
     # weights of projection j+1 are read into the Infinity Cache on a side stream (a parallel branch of the forward hipGraph)
@@ -658,24 +590,8 @@ class ChameleonBackbone(nn.Module):
             self._ops.weight_prefetch(self._packed[li + dl][nxt], blocks)
 
     def _q8_chunk(self, name, T, K_):
-        """split-K chunk of projection `name` for a T-row window.  Under enable_fused(weights=...) kernel G1q stages the whole activation chunk in
-        LDS: <= 2560 columns up to 32 rows, <= 1280 at 33..64.  A projection packed with a longer chunk (G1_CFG_Q8's gate|up: two K halves of 2048, the
-        copy the fused 32-row launch streams) is read at 33..64 rows in HALVED chunks until they fit: a step-major packing whose chunks are whole
-        record pairs (K and the chunk multiples of 32) is the same bytes under either chunking -- pair after pair, every tile per pair.  The
-        "e4m3_as_bf16" twin takes the same chunks (pack_weight's step-major stream has the same property), so the two stay bit-identical.
-        ValueError where no such chunk exists."""
-        KC, _, sm = self.G1_CFG[name]
-        if getattr(self, "weights", None) is None or T <= 32 or min(KC, K_) <= 1280:
-            return KC
-        if T > 64 and getattr(self, "max_rows", 64) > 64:          # (kernels G1wq / G1w stream the activation in stages: the packed chunk as it is)
-            return KC
-        kc = KC
-        while kc > 1280 and sm and K_ % 32 == 0 and kc % 64 == 0:
-            kc //= 2
-        if kc > 1280:
-            raise ValueError(f"weights={self.weights!r}: a {T}-row window needs {name} chunks of <= 1280 columns (kernel G1q stages the chunk in LDS), or a "
-                             f"step-major packing with K and the chunk multiples of 32 / 64 that halved chunks can read; G1_CFG[{name!r}] = {self.G1_CFG[name]}")
-        return kc
+        """split-K chunk of projection `name` for a T-row window of K_ columns (LS.chunk_for_rows); ValueError where none exists"""
+        return LS.chunk_for_rows(name, self.G1_CFG[name], T, K_, getattr(self, "weights", None), getattr(self, "max_rows", 64))
 
     def _g1(self, li, x_, name, N_, K_):
         cfg = self.G1_CFG[name]
@@ -694,22 +610,14 @@ class ChameleonBackbone(nn.Module):
         if dims is None:
             H, Hkv, D, hid, inter = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size
             dims = dict(qkv=((H + 2 * Hkv) * D, hid), o=(hid, H * D), gate_up=(2 * inter, hid), down=(hid, inter))
-        for name, (KC, tiles, sm) in cfg.items():
-            K_ = dims[name][1]
-            if tiles not in self.G1_WIDE_TILES or tiles == 2:
-                raise ValueError(f"max_rows={max_rows}: windows of more than 64 rows take 3, 4, 6 or 8 column tiles per workgroup on the 8-bit stream (kernel G1wq "
-                                 f"has no form of three row tiles x two tiles); G1_CFG[{name!r}] = {(KC, tiles, sm)}")
-            if K_ % 32 or KC % 32:
-                raise ValueError(f"max_rows={max_rows}: kernel G1wq streams whole record pairs -- K and the chunk must be multiples of 32; G1_CFG[{name!r}] = "
-                                 f"{(KC, tiles, sm)} with K = {K_}")
-            kc = min(KC, K_)
-            while kc > 1280 and sm and kc % 64 == 0:          # (_q8_chunk's rule for 33..64 rows)
-                kc //= 2
-            if kc > 1280:
-                raise ValueError(f"max_rows={max_rows}: the same packed copy serves windows of 33..64 rows, where kernel G1q needs chunks of <= 1280 columns or a "
-                                 f"step-major packing that halved chunks read (_q8_chunk); G1_CFG[{name!r}] = {(KC, tiles, sm)}")
-        if max_rows > 128 and head_cfg[1] not in self.G1_WIDE_TILES:
-            raise ValueError(f"max_rows={max_rows}: the output head runs on kernel G1w at 129..256 rows -- HEAD_CFG[1] must be one of {self.G1_WIDE_TILES}, got {head_cfg}")
+        for name, why in LS.check_set(cfg, head_cfg, max_rows, q8_dims=dims)[:1]:
+            shape = f"G1_CFG[{name!r}] = {cfg.get(name)}"
+            raise ValueError(f"max_rows={max_rows}: " + (
+                f"the output head runs on kernel G1w at 129..256 rows -- HEAD_CFG[1] must be one of {LS.WIDE_TILES}, got {head_cfg}" if name == "head" else
+                f"windows of more than 64 rows take 3, 4, 6 or 8 column tiles per workgroup on the 8-bit stream (kernel G1wq has no form of three row tiles x two tiles); {shape}"
+                if why == "tiles" else f"kernel G1wq streams whole record pairs -- K and the chunk must be multiples of 32; {shape} with K = {dims[name][1]}" if why == "pairs" else
+                f"the same packed copy serves windows of 33..64 rows, where kernel G1q needs chunks of <= {LS.CHUNK_CAP_64ROW} columns or a step-major packing that halved "
+                f"chunks read (_q8_chunk); {shape}"))
 
     def enable_fused(self, ops, gemm="torch", fold_norm=True, compress=None, weights=None, max_rows=None):
         """Switch to the fused HIP glue path (F1-F3): q|k|v and gate|up projections become single GEMMs whose weights are
@@ -733,16 +641,15 @@ class ChameleonBackbone(nn.Module):
         Only the window forward (inputs of at most 64 rows) reads the 8-bit copy: the prompt prefill (hipBLASLt on the 16-bit parameters) is
         NOT quantised.  SJD's draft and verify both run the window forward, so the sampler stays exact with respect to ITS model -- and that
         model is the quantised one.  8-bit weights serve bf16 backbones with gemm="sjd", no swin-norm / model_parallel_size > 1, at most 64
-        window rows (one prompt per forward): anything else raises ValueError.  Chunks: every G1_CFG chunk <= 2560 columns (checked here); at
-        33..64 rows kernel G1q stages <= 1280, and a projection packed with a longer chunk is read in halved chunks where its packing allows it
-        (step-major, see _q8_chunk: the default sets do) -- a forward that cannot raises ValueError before its first launch.
+        window rows (one prompt per forward): anything else raises ValueError.  Chunks: every G1_CFG chunk <= LS.CHUNK_CAP_32ROW columns (checked here); at
+        33..64 rows kernel G1q stages <= LS.CHUNK_CAP_64ROW, and a projection packed with a longer chunk is read in halved chunks where its packing allows
+        it (step-major, see LS.chunk_for_rows: the default sets do) -- a forward that cannot raises ValueError before its first launch.
         max_rows (with weights only; default None = 64): 128 or 256 packs for several prompts per forward (SJDBatchEngine: rows = prompts x CFG batch x
         window) -- windows of 65..max_rows rows run on kernel G1wq, the 8-bit form of G1w ("e4m3_as_bf16": G1w itself, on the same launch shapes; the
-        two stay token-identical).  Launch shapes: G1_CFG_Q8_WIDE / G1_CFG_EMU3_Q8_WIDE (UNTUNED) unless the caller set G1_CFG; ONE packed copy serves
-        every row count, so every tile count must be 3, 4, 6 or 8, every chunk <= 2560 and readable in chunks of <= 1280 at 33..64 rows, K and the
-        chunks multiples of 32 -- checked here, before anything is assigned.  max_rows=256: lm_head is packed UNCOMPRESSED whatever `compress` says
-        (129..256 rows have no 12-bit kernel) and HEAD_CFG[1] must be 2, 3, 4, 6 or 8.  Whether the 8-bit stream is faster than what those row
-        counts run otherwise is a measurement, not a promise: README.md."""
+        two stay token-identical).  Launch shapes: LS.default_shapes (UNTUNED sets) unless the caller set G1_CFG; ONE packed copy serves
+        every row count, so it must pass LS.check_set -- checked here, before anything is assigned.  max_rows=256: lm_head is packed UNCOMPRESSED
+        whatever `compress` says (the 12-bit stream ends at LS.Z_MAX_ROWS rows) and HEAD_CFG[1] must be one of LS.WIDE_TILES.  Whether the 8-bit
+        stream is faster than what those row counts run otherwise is a measurement, not a promise: README.md."""
         if weights not in (None, "e4m3", "e4m3_as_bf16"):
             raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16'")
         if max_rows is not None and weights is None:
@@ -757,44 +664,32 @@ class ChameleonBackbone(nn.Module):
             if self.lm_head.weight.dtype != torch.bfloat16:
                 raise ValueError(f"weights={weights!r} needs bf16 weights (got {self.lm_head.weight.dtype}): the dequantised values are bf16 numbers, "
                                  "fp16's exponent range does not hold them")
-        q8_cfg = self.__dict__.get("G1_CFG")
-        if weights is not None:
-            wide = max_rows is not None and max_rows > 64
-            if q8_cfg is None:
-                if wide:
-                    q8_cfg = dict(self.G1_CFG_EMU3_Q8_WIDE if self.n_kv_heads != self.n_heads else self.G1_CFG_Q8_WIDE)
-                else:
-                    q8_cfg = dict(self.G1_CFG_EMU3_Q8 if self.n_kv_heads != self.n_heads else self.G1_CFG_Q8)
-            if any(c[0] > 2560 for c in q8_cfg.values()):          # (validated before anything is assigned: a refused call leaves the backbone as it was)
-                raise ValueError(f"weights={weights!r}: kernel G1q stages the whole activation chunk in LDS -- every G1_CFG chunk must be <= 2560 columns "
-                                 f"(windows of 33..64 rows: <= 1280, or a step-major packing that a halved chunk reads, see _q8_chunk); got {q8_cfg}")
-            if wide:
-                head_cfg = self.__dict__.get("HEAD_CFG") or (self.HEAD_CFG_WIDE if self.vocab_size >= 131072 else self.HEAD_CFG)
-                self._q8_wide_check(q8_cfg, head_cfg, max_rows)
-            self.G1_CFG = q8_cfg
+        if compress is None:
+            compress = _os.environ.get("SJD_G1Z", "1") != "0"
+        compress = bool(compress) and gemm == "sjd"
+        # the caller has not chosen launch shapes: the tuned set of the architecture, stream and row count (None: the class default as it stands)
+        g1_cfg, head_cfg = LS.default_shapes(self.lm_head.weight.dtype, self.__dict__.get("G1_CFG"), self.__dict__.get("HEAD_CFG"), self.args.hidden_size >= 8192,
+                                             self.n_kv_heads != self.n_heads, compress, weights, max_rows, self.vocab_size)
+        if weights is not None:          # (validated before anything is assigned: a refused call leaves the backbone as it was)
+            if any(c[0] > LS.CHUNK_CAP_32ROW for c in g1_cfg.values()):
+                raise ValueError(f"weights={weights!r}: kernel G1q stages the whole activation chunk in LDS -- every G1_CFG chunk must be <= {LS.CHUNK_CAP_32ROW} columns "
+                                 f"(windows of 33..64 rows: <= {LS.CHUNK_CAP_64ROW}, or a step-major packing that a halved chunk reads, see _q8_chunk); got {g1_cfg}")
+            if max_rows is not None and max_rows > 64:
+                self._q8_wide_check(g1_cfg, head_cfg or self.HEAD_CFG, max_rows)
             self.max_rows, self._max_rows_given = int(max_rows) if max_rows is not None else 64, max_rows is not None
         else:
             self.__dict__.pop("max_rows", None)
             self._max_rows_given = False
+        if g1_cfg is not None:
+            self.G1_CFG = g1_cfg
+        if head_cfg is not None:
+            self.HEAD_CFG = head_cfg
         self.weights = weights
         self._ops = ops
         self._gemm = gemm
         # swin-norm layers have no norm in front of a projection: nothing to fold (the unfolded window path, F1 in its post-norm form)
         self._fold_norm = bool(fold_norm) and gemm == "sjd" and not self.args.swin_norm
-        if compress is None:
-            compress = _os.environ.get("SJD_G1Z", "1") != "0"
-        self.compress = bool(compress) and gemm == "sjd"
-        if "G1_CFG" not in self.__dict__:      # the caller has not chosen launch shapes: take the tuned set of the architecture
-            if self.args.hidden_size >= 8192:
-                self.G1_CFG = dict(self.G1_CFG_30B_Z if self.compress and self.lm_head.weight.dtype == torch.bfloat16 else self.G1_CFG_30B)
-            elif self.n_kv_heads != self.n_heads:
-                self.G1_CFG = dict(self.G1_CFG_EMU3)
-            elif self.compress and self.lm_head.weight.dtype == torch.bfloat16:
-                self.G1_CFG = dict(self.G1_CFG_Z)
-        if weights is None and self.compress and self.lm_head.weight.dtype == torch.bfloat16 and self.G1_CFG == self.G1_CFG_EMU3:
-            self.G1_CFG = dict(self.G1_CFG_EMU3_Z)          # (also when the caller named the architecture's set: the packing below follows it)
-        if "HEAD_CFG" not in self.__dict__ and self.vocab_size >= 131072:
-            self.HEAD_CFG = self.HEAD_CFG_WIDE
+        self.compress = compress
         self.compress_stats = dict(matrices=0, compressed=0, bytes_raw=0, bytes_packed=0, exceptions=0)
 
         def pack(w, kc, sm, gateup=False):
@@ -885,27 +780,16 @@ class ChameleonBackbone(nn.Module):
 
     def packed_bytes(self, head=True):
         """bytes of packed weights one window forward streams: the four projections of every layer and (head=True) the whole output head"""
-        size = lambda w: w.nbytes() if isinstance(w, (self._ops.PackedZ, self._ops.PackedQ8)) else w.numel() * w.element_size()
-        per = sum(size(w) for d in self._packed for w in d.values())
-        return per + (size(self._packed_head) if head and self._packed_head is not None else 0)
+        per = sum(LS.packed_nbytes(w) for d in self._packed for w in d.values())
+        return per + (LS.packed_nbytes(self._packed_head) if head and self._packed_head is not None else 0)
 
-    HEAD_CFG = (1024, 4, True)         # G1 launch shape of the output head: (split-K chunk, column tiles per workgroup, step-major)
-    # vocabularies whose image window is tens of thousands of columns (Emu3: 32768 of 184622): two K chunks, so that K2 sums two planes per
-    # column instead of four, eight tiles per workgroup; Emu3 4.65 -> 4.62 ms per step (bench.py, SJD_HEAD_CFG sweep, one box)
-    HEAD_CFG_WIDE = (2048, 8, True)
     supports_head_partials = True
 
     def _head_partials(self, h, delta, cols, n, sumsq=None):
         """final residual add + the output head as G1 split-K partials over the column window `cols` -> ops.HeadOut (K2 applies the folded
         final RMSNorm as a row scale and the 16-bit rounding of the lm_head output while it reads them).  sumsq: the statistics of h when the
         last down projection already did the residual add (its reducing tail)"""
-        ops, hid = self._ops, self.args.hidden_size
-        if sumsq is None:
-            sumsq = ops.residual_sumsq(h, delta)
-        lo, hi = cols if cols is not None else (0, self.vocab_size)
-        lo32, hi32 = (lo // 32) * 32, min(self._head_cols, ((hi + 31) // 32) * 32)
-        part = ops.skinny_gemm_cols(h, self._packed_head, self._head_cols, hid, self.HEAD_CFG[0], lo32, hi32 - lo32, self.HEAD_CFG[1], self.HEAD_CFG[2])
-        return ops.HeadOut(part, lo32, n if h.shape[0] > n else 0, h.dtype, row_norm=(sumsq, hid, self.args.rms_norm_eps))
+        return _head_partials(self, h, delta, cols, n, self.args.hidden_size, self.args.rms_norm_eps, sumsq)
 
     @torch.no_grad()
     def calibrate_kv_scales(self, tokens, positions, key_start, headroom=4.0):
@@ -1028,7 +912,7 @@ class ChameleonBackbone(nn.Module):
         into the consuming glue kernel (F2 / F1 / F3 / F1)."""
         ops, B, n = self._ops, tokens.shape[0], tokens.shape[1]
         T, eps, cfg = B * n, self.args.rms_norm_eps, self.G1_CFG
-        cap = 2560 if T <= 32 else 1 << 30     # the staged activation chunk of a 32-row window must fit in LDS; taller windows are sub-tiled when it does not
+        cap = LS.CHUNK_CAP_32ROW if T <= 32 else 1 << 30     # the staged activation chunk of a 32-row window must fit in LDS; taller windows are sub-tiled when it does not
         if any(c[0] > cap for c in cfg.values()):
             raise ValueError(f"G1_CFG chunk sizes must be <= {cap} for a {T}-row window")
         g1 = lambda x_, name, N_, K_: ops.skinny_gemm(x_, self._packed[li][name], N_, K_, self._q8_chunk(name, T, K_), cfg[name][1], cfg[name][2])
@@ -1061,10 +945,10 @@ class ChameleonBackbone(nn.Module):
 
     def _forward_window_fused(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
         T_ = tokens.shape[0] * tokens.shape[1]
-        q8_rows = getattr(self, "max_rows", 64) if getattr(self, "weights", None) is not None else 64
-        if getattr(self, "weights", None) == "e4m3" and q8_rows < T_ <= 256 and tokens.shape[1] <= 32:
-            if q8_rows > 64:
-                raise ValueError(f"weights='e4m3' serves draft windows of at most {q8_rows} rows (max_rows={q8_rows}); got {T_} rows")
+        no = LS.serves_rows(self, T_, tokens.shape[1])
+        if no is not None and no[0] == "max_rows":          # (an 8-bit copy packed for fewer rows: there is no 16-bit copy to fall back on)
+            if no[1] > 64:
+                raise ValueError(f"weights='e4m3' serves draft windows of at most {no[1]} rows (max_rows={no[1]}); got {T_} rows")
             raise ValueError(f"weights='e4m3' serves draft windows of at most 64 rows (one prompt per forward); got {T_} rows")
         if getattr(self, "weights", None) is not None and self._gemm == "sjd" and 32 < T_ <= 64:          # (refuse before the first launch, not in the middle of a layer)
             H_, Hkv_, D_, hid_, inter_ = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size
@@ -1072,9 +956,7 @@ class ChameleonBackbone(nn.Module):
                 self._q8_chunk(name_, T_, K_)
         # G1 serves windows: <= 64 rows, or <= 256 rows of up to eight prompts' draft windows (n <= 32 rows per batch row; 129..256 rows: round 5, the
         # uncompressed packing on kernel G1w -- G1_CFG_256ROW); longer inputs are prefill
-        if self._gemm == "sjd" and (T_ <= 64 or (T_ <= 128 and tokens.shape[1] <= 32) or
-                                    (T_ <= 256 and tokens.shape[1] <= 32 and self._packed and not isinstance(self._packed[0]["qkv"], self._ops.PackedZ)
-                                     and all(c[1] in self.G1_WIDE_TILES for c in self.G1_CFG.values()))):
+        if no is None:
             if self._fold_norm:
                 return self._forward_window_g1_folded(tokens, positions, kv_len, key_start, cols, head_partials)
             return self._forward_window_g1(tokens, positions, kv_len, key_start, cols)     # (swin-norm backbones: always here)

@@ -27,6 +27,18 @@
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
+// The launch sequence of every projection kernel in this file, sjd_gemm_wide.h and sjd_gemm_q8.h: raise the kernel's dynamic-LDS limit where the launch
+// needs more than the 64 KiB a kernel gets unasked, launch, and map hipGetLastError() to SJD_OK / SJD_ERR_LAUNCH.  One argument per kernel parameter
+// (a pointer to a kernel carries no default arguments).
+template <typename... P, typename... A>
+static int g1_launch_kernel(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args)
+{
+    static_assert(sizeof...(P) == sizeof...(A), "one argument per kernel parameter");
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, static_cast<P>(args)...);
+    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+}
+
 // phase timestamps of g1_skinny_gemm (tools/phase_trace.py, -DSJD_TRACE; compiled out otherwise), see sjd_attention.hip
 #ifdef SJD_TRACE
 __device__ unsigned long long g_g1_trace[4096][8];
@@ -651,8 +663,7 @@ __global__ __launch_bounds__(256) void g1_prefetch(const u32x4 *__restrict__ p, 
 extern "C" int sjd_weight_prefetch(const void *w, int64_t nbytes, int blocks, void *sink, void *stream)
 {
     if (!w || !sink || nbytes < 16 || blocks < 1 || blocks > 4096) return SJD_ERR_BAD_ARG;
-    hipLaunchKernelGGL(g1_prefetch, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const u32x4 *)w, (size_t)(nbytes / 16), (unsigned *)sink);
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+    return g1_launch_kernel(g1_prefetch, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, (size_t)(nbytes / 16), sink);
 }
 
 // ------------------------------------------------------------------------------------------------ L2 head pull (round 5, sjd_l2_prefetch.h)
@@ -670,8 +681,7 @@ __global__ void g1_xcc_map(int *out)
 extern "C" int sjd_debug_xcc_map(int32_t *out, int gx, int gy, void *stream)
 {
     if (!out || gx < 1 || gy < 1) return SJD_ERR_BAD_ARG;
-    hipLaunchKernelGGL(g1_xcc_map, dim3(gx, gy), dim3(64), 0, (hipStream_t)stream, out);
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+    return g1_launch_kernel(g1_xcc_map, dim3(gx, gy), dim3(64), 0, (hipStream_t)stream, out);
 }
 
 // the grid sjd_skinny_gemm_z launches for these arguments (kept next to it: see SJD_G1Z_LAUNCH / SJD_G1ZT below)
@@ -730,8 +740,7 @@ extern "C" int64_t sjd_l2_head_bytes(const sjd_l2_head *d)
 extern "C" int sjd_weight_prefetch_head(const sjd_l2_head *head, int blocks, void *stream)
 {
     if (!head || !head->wz || blocks < 8 || (blocks % 8) || blocks > 4096) return SJD_ERR_BAD_ARG;
-    hipLaunchKernelGGL(g1_l2_head_pull, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *head);
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+    return g1_launch_kernel(g1_l2_head_pull, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *head);
 }
 
 // ------------------------------------------------------------------------------------------------ G1s (gate|up + SiLU * up in one launch)
@@ -1471,20 +1480,13 @@ static int g1sz_launch(const void *x, const void *wz, const void *exc, int exc_c
 #define SJD_G1SZ_CASE(SP_, MT_) SJD_G1SZ_CASE_W(SP_, MT_, false) SJD_G1SZ_CASE_W(SP_, MT_, true)
 #define SJD_G1SZ_CASE_W(SP_, MT_, W_) \
     if (SP == SP_ && MT == MT_ && (exc_cap > 64) == W_) { \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1z_gateup_silu_tall<SP_, MT_, false, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((g1z_gateup_silu_tall<SP_, MT_, false, W_>), grid, block, lds, s, (const unsigned short *)x, (const unsigned char *)wz, (const u32x2 *)exc, \
-                           (unsigned short *)y, M, I, K, rec_stride | (exc_cap << 16), ss, sl, ih, eps); \
-        if (hipGetLastError() != hipSuccess) return SJD_ERR_LAUNCH; \
-        return g1sz_raw_inline(SP_, MT_) ? SJD_OK : g1_raw_gateup_launch(x, raw, y, M, I, K, rn, s); \
+        const int rc = g1_launch_kernel(g1z_gateup_silu_tall<SP_, MT_, false, W_>, grid, block, lds, s, x, wz, exc, y, M, I, K, rec_stride | (exc_cap << 16), ss, sl, ih, eps); \
+        return rc != SJD_OK || g1sz_raw_inline(SP_, MT_) ? rc : g1_raw_gateup_launch(x, raw, y, M, I, K, rn, s); \
     }
 #define SJD_G1SZ_CASE32(SP_) SJD_G1SZ_CASE32_W(SP_, false) SJD_G1SZ_CASE32_W(SP_, true)
 #define SJD_G1SZ_CASE32_W(SP_, W_) \
-    if (SP == SP_ && MT == 1 && (exc_cap > 64) == W_) { \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1z_gateup_silu<SP_, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((g1z_gateup_silu<SP_, W_>), grid, block, lds, s, (const unsigned short *)x, (const unsigned char *)wz, (const u32x2 *)exc, \
-                           (unsigned short *)y, M, I, K, rec_stride | (exc_cap << 16), ss, sl, ih, eps); \
-        return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH; \
-    }
+    if (SP == SP_ && MT == 1 && (exc_cap > 64) == W_) \
+        return g1_launch_kernel(g1z_gateup_silu<SP_, W_>, grid, block, lds, s, x, wz, exc, y, M, I, K, rec_stride | (exc_cap << 16), ss, sl, ih, eps);
     SJD_G1SZ_CASE32(8) SJD_G1SZ_CASE32(16) SJD_G1SZ_CASE32(32) SJD_G1SZ_CASE32(64)
 #undef SJD_G1SZ_CASE32
 #undef SJD_G1SZ_CASE32_W
@@ -1521,19 +1523,10 @@ static int g1s_launch(const void *x, const void *w_packed, void *y, int M, int I
     const int sl = rn ? rn->slices : 0;
     const float ih = rn ? 1.0f / (float)rn->hidden : 0.f, eps = rn ? rn->eps : 0.f;
 #define SJD_G1S_CASE(SP_, MT_, DB_) \
-    if (SP == SP_ && MT == MT_ && db == DB_) { \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1_gateup_silu_tall<DT, SP_, MT_, DB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((g1_gateup_silu_tall<DT, SP_, MT_, DB_>), grid, block, lds, s, (const unsigned short *)x, (const u32x4 *)w_packed, (unsigned short *)y, \
-                           M, I, K, rec_stride, ss, sl, ih, eps); \
-        return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH; \
-    }
+    if (SP == SP_ && MT == MT_ && db == DB_) \
+        return g1_launch_kernel(g1_gateup_silu_tall<DT, SP_, MT_, DB_>, grid, block, lds, s, x, w_packed, y, M, I, K, rec_stride, ss, sl, ih, eps);
 #define SJD_G1S_CASE32(SP_) \
-    if (SP == SP_ && MT == 1) { \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1_gateup_silu<DT, SP_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((g1_gateup_silu<DT, SP_>), grid, block, lds, s, (const unsigned short *)x, (const u32x4 *)w_packed, (unsigned short *)y, \
-                           M, I, K, rec_stride, ss, sl, ih, eps); \
-        return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH; \
-    }
+    if (SP == SP_ && MT == 1) return g1_launch_kernel(g1_gateup_silu<DT, SP_>, grid, block, lds, s, x, w_packed, y, M, I, K, rec_stride, ss, sl, ih, eps);
     SJD_G1S_CASE32(8) SJD_G1S_CASE32(16) SJD_G1S_CASE32(32) SJD_G1S_CASE32(64)
 #undef SJD_G1S_CASE32
     SJD_G1S_CASE(8, 2, false) SJD_G1S_CASE(8, 2, true) SJD_G1S_CASE(16, 2, true) SJD_G1S_CASE(8, 4, true)
@@ -1948,26 +1941,20 @@ extern "C" int sjd_skinny_gemm_z(const void *x, const void *wz, const void *exc,
     if (MT > 2 || lds > 160 * 1024) {             // sub-tiled activation (65..128 rows, or a 64-row window with a tall K chunk): <= 8 waves, no raw path
         if (waves > 8) return SJD_ERR_BAD_ARG;
         const size_t lds_t = (size_t)2 * MT * G1_SUB * 1024;
-#define SJD_G1ZT(MT_, W_) do { \
-            (void)hipFuncSetAttribute((const void *)g1z_skinny_gemm_tiled<MT_, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t); \
-            hipLaunchKernelGGL((g1z_skinny_gemm_tiled<MT_, W_>), grid, block, lds_t, s, (const unsigned short *)x, (const unsigned char *)wz, \
-                               (const u32x2 *)exc, out, M, N, K, KC, n_tiles, rs, tile0, waves | (exc_cap << 16)); } while (0)
+#define SJD_G1ZT(MT_, W_) \
+        return then_raw_fixup(g1_launch_kernel(g1z_skinny_gemm_tiled<MT_, W_>, grid, block, lds_t, s, x, wz, exc, out, M, N, K, KC, n_tiles, rs, tile0, waves | (exc_cap << 16)))
         if (exc_cap > 64) { if (MT == 2) SJD_G1ZT(2, true); else if (MT == 3) SJD_G1ZT(3, true); else if (MT == 4) SJD_G1ZT(4, true); else return SJD_ERR_UNSUPPORTED; }
         else { if (MT == 2) SJD_G1ZT(2, false); else if (MT == 3) SJD_G1ZT(3, false); else if (MT == 4) SJD_G1ZT(4, false); else return SJD_ERR_UNSUPPORTED; }
 #undef SJD_G1ZT
-        return then_raw_fixup(hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH);
     }
     // g1z_skinny_gemm multiplies raw units in the kernel
-#define SJD_G1Z_LAUNCH_W(MT_, MAXT_, W_) do { \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1z_skinny_gemm<MT_, MAXT_, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((g1z_skinny_gemm<MT_, MAXT_, W_>), grid, block, lds, s, (const unsigned short *)x, (const unsigned char *)wz, \
-                           (const u32x2 *)exc, out, M, N, K, KC, n_tiles, rs, tile0, waves | (exc_cap << 16)); } while (0)
+#define SJD_G1Z_LAUNCH_W(MT_, MAXT_, W_) \
+    return g1_launch_kernel(g1z_skinny_gemm<MT_, MAXT_, W_>, grid, block, lds, s, x, wz, exc, out, M, N, K, KC, n_tiles, rs, tile0, waves | (exc_cap << 16))
 #define SJD_G1Z_LAUNCH(MT_, MAXT_) do { if (exc_cap > 64) SJD_G1Z_LAUNCH_W(MT_, MAXT_, true); else SJD_G1Z_LAUNCH_W(MT_, MAXT_, false); } while (0)
     if (MT == 1) { if (waves <= 8) SJD_G1Z_LAUNCH(1, 512); else SJD_G1Z_LAUNCH(1, 1024); }
     else { if (waves <= 8) SJD_G1Z_LAUNCH(2, 512); else SJD_G1Z_LAUNCH(2, 1024); }
 #undef SJD_G1Z_LAUNCH
 #undef SJD_G1Z_LAUNCH_W
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
 }
 
 extern "C" int sjd_gemm_num_chunks(int K, int KC) { return (K + KC - 1) / KC; }
@@ -1987,27 +1974,15 @@ static int g1_launch(const void *x, const void *w_packed, float *out, int M, int
         // gate|up 39.0 / 43.1, down 22.5 / 25.2 against the kernels below (profiles/r6_g1w_sweep_64rows_emu3.jsonl); `waves` = column tiles per
         // workgroup: 2, 3, 4, 6, 8.  Same chunking and accumulation order: bit-identical planes.
         if (M > 32) {
-            switch (waves) {
-            case 2: return g1_wide_launch<DT, MT, 1, 2, 4, 3, 2, 2>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-            case 3: return g1_wide_launch<DT, MT, 1, 3, 4, 3, 2, 2>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-            case 4: return g1_wide_launch<DT, MT, 1, 4, 4, 3, 2, 2>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-            case 6: return g1_wide_launch<DT, MT, 2, 3, 4, 3, 2, 2>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-            case 8: return g1_wide_launch<DT, MT, 2, 4, 4, 3, 2, 2>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-            default: break;
-            }
+            const int rc = g1_wide_by_tiles<DT, MT, 2>(waves, x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+            if (rc != G1W_NO_FORM) return rc;          // (any other tile count: the kernels below)
         }
     }
     if constexpr (MT > 4) {      // 129..256-row windows (five to eight prompts per forward), both 16-bit types: G1w (sjd_gemm_wide.h, round 6).  `waves` = column tiles per
         // workgroup: 2, 3, 4 (one per wave) or 6, 8 (two per wave: every activation fragment read from LDS feeds two MFMAs); stages of four k-steps,
         // three ring slots (96 KiB + 1), weight ring of eight k-steps.
-        switch (waves) {
-        case 2: return g1_wide_launch<DT, MT, 1, 2, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-        case 3: return g1_wide_launch<DT, MT, 1, 3, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-        case 4: return g1_wide_launch<DT, MT, 1, 4, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-        case 6: return g1_wide_launch<DT, MT, 2, 3, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-        case 8: return g1_wide_launch<DT, MT, 2, 4, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-        default: return SJD_ERR_BAD_ARG;
-        }
+        const int rc = g1_wide_by_tiles<DT, MT, 1>(waves, x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+        return rc == G1W_NO_FORM ? SJD_ERR_BAD_ARG : rc;
     } else
     if constexpr (MT >= 2) if (MT > 2 || lds_whole > 160 * 1024) {     // sub-tiled activation: no limit on KC
         if (waves > 8) return SJD_ERR_BAD_ARG;
@@ -2016,48 +1991,26 @@ static int g1_launch(const void *x, const void *w_packed, float *out, int M, int
             // launch than the sub-tiled kernels (profiles/r6_g1w_sweep_128rows.jsonl: q|k|v 23.1 / 24.5, o 11.6 / 12.4, gate|up 37.2 / 40.4, down 21.9 / 24.2 us);
             // `waves` = column tiles per workgroup: 2, 3, 4, 6, 8; any other count, or fp16, keeps the sub-tiled kernels below.
             // Same chunking and accumulation order: the planes are the sub-tiled kernels', bit for bit.
-            if (M > 64) {
-                if constexpr (MT == 4) if (waves == 2) return g1_wide_launch<DT, MT, 1, 2, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-                switch (waves) {          // (three row tiles x two waves: a k-step has too few MFMAs to carry its DMA pieces -- the sub-tiled kernel keeps that shape)
-                case 3: return g1_wide_launch<DT, MT, 1, 3, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-                case 4: return g1_wide_launch<DT, MT, 1, 4, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-                case 6: return g1_wide_launch<DT, MT, 2, 3, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-                case 8: return g1_wide_launch<DT, MT, 2, 4, 4, 3, 2, 1>(x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-                default: break;
-                }
+            if (M > 64) {          // (G1w has no two-tile form at three row tiles, only at four: the sub-tiled kernel keeps that shape)
+                const int rc = g1_wide_by_tiles<DT, MT, 1>(waves, x, w_packed, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+                if (rc != G1W_NO_FORM) return rc;
             }
         }
-        if constexpr (MT > 2) {
-            auto tiled8 = [&](auto nw) {              // g1_skinny_gemm_tiled8 with nw = 4 or 8 waves per workgroup: 8-step sub-tiles (4 waves: two workgroups per CU)
-                constexpr int NW = decltype(nw)::value;
-                const size_t lds_8 = (size_t)2 * MT * 8 * 1024;
-                (void)hipFuncSetAttribute((const void *)g1_skinny_gemm_tiled8<DT, MT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_8);
-                hipLaunchKernelGGL((g1_skinny_gemm_tiled8<DT, MT, NW>), grid, block, lds_8, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K,
-                                   KC, n_tiles, step_major ? n_tiles : 1, tile0);
-                return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
-            };
-            if (waves == 4) return tiled8(std::integral_constant<int, 4>{});
-            if (waves == 8) return tiled8(std::integral_constant<int, 8>{});
+        const int rs = step_major ? n_tiles : 1;
+        if constexpr (MT > 2) {      // g1_skinny_gemm_tiled8 with 4 or 8 waves per workgroup: 8-step sub-tiles (4 waves: two workgroups per CU)
+            const size_t lds_8 = (size_t)2 * MT * 8 * 1024;
+            if (waves == 4) return g1_launch_kernel(g1_skinny_gemm_tiled8<DT, MT, 4>, grid, block, lds_8, s, x, w_packed, out, M, N, K, KC, n_tiles, rs, tile0);
+            if (waves == 8) return g1_launch_kernel(g1_skinny_gemm_tiled8<DT, MT, 8>, grid, block, lds_8, s, x, w_packed, out, M, N, K, KC, n_tiles, rs, tile0);
         }
-        const size_t lds_t = (size_t)2 * MT * G1_SUB * 1024;
-        (void)hipFuncSetAttribute((const void *)g1_skinny_gemm_tiled<DT, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
-        hipLaunchKernelGGL((g1_skinny_gemm_tiled<DT, MT>), grid, block, lds_t, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K, KC,
-                           n_tiles, step_major ? n_tiles : 1, tile0, waves);
-        return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+        return g1_launch_kernel(g1_skinny_gemm_tiled<DT, MT>, grid, block, (size_t)2 * MT * G1_SUB * 1024, s, x, w_packed, out, M, N, K, KC, n_tiles, rs, tile0, waves);
     }
     if constexpr (MT <= 2) {
         const size_t lds = lds_whole;
+        const int rs = step_major ? n_tiles : 1;
         if (lds > 160 * 1024) return SJD_ERR_BAD_ARG;
-        if (waves <= 8) {
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1_skinny_gemm<DT, MT, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((g1_skinny_gemm<DT, MT, 512>), grid, block, lds, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K, KC,
-                               n_tiles, step_major ? n_tiles : 1, tile0, waves);
-        } else {
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1_skinny_gemm<DT, MT, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((g1_skinny_gemm<DT, MT, 1024>), grid, block, lds, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K, KC,
-                               n_tiles, step_major ? n_tiles : 1, tile0, waves);
-        }
-        return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+        if (waves <= 8)
+            return g1_launch_kernel(g1_skinny_gemm<DT, MT, 512>, grid, block, lds, s, x, w_packed, out, M, N, K, KC, n_tiles, rs, tile0, waves, nullptr, nullptr, nullptr);
+        return g1_launch_kernel(g1_skinny_gemm<DT, MT, 1024>, grid, block, lds, s, x, w_packed, out, M, N, K, KC, n_tiles, rs, tile0, waves, nullptr, nullptr, nullptr);
     }
     return SJD_ERR_UNSUPPORTED;
 }
@@ -2066,22 +2019,12 @@ static int g1_launch(const void *x, const void *w_packed, float *out, int M, int
 static int g1_dispatch(const void *x, const void *w_packed, float *out, int M, int N, int K, int KC, int waves, int step_major, int dtype, int np, int tile0,
                        hipStream_t s)
 {
-    if (dtype == SJD_DTYPE_BF16 && M <= 32) return g1_launch<SJD_DTYPE_BF16, 1>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_F16 && M <= 32) return g1_launch<SJD_DTYPE_F16, 1>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_BF16 && M <= 64) return g1_launch<SJD_DTYPE_BF16, 2>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_F16 && M <= 64) return g1_launch<SJD_DTYPE_F16, 2>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_BF16 && M <= 96) return g1_launch<SJD_DTYPE_BF16, 3>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_F16 && M <= 96) return g1_launch<SJD_DTYPE_F16, 3>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_BF16 && M <= 128) return g1_launch<SJD_DTYPE_BF16, 4>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_F16 && M <= 128) return g1_launch<SJD_DTYPE_F16, 4>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_BF16 && M <= 160) return g1_launch<SJD_DTYPE_BF16, 5>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_F16 && M <= 160) return g1_launch<SJD_DTYPE_F16, 5>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_BF16 && M <= 192) return g1_launch<SJD_DTYPE_BF16, 6>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_F16 && M <= 192) return g1_launch<SJD_DTYPE_F16, 6>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_BF16 && M <= 224) return g1_launch<SJD_DTYPE_BF16, 7>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_F16 && M <= 224) return g1_launch<SJD_DTYPE_F16, 7>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_BF16) return g1_launch<SJD_DTYPE_BF16, 8>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);
-    if (dtype == SJD_DTYPE_F16) return g1_launch<SJD_DTYPE_F16, 8>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0);       // (both entries have checked M <= 256)
+    auto rows = [&](auto dt) {          // (both entries have checked M <= 256: eight row tiles at the most)
+        return g1_by_row_tiles<1, 8>(M, [&](auto mt) {
+            return g1_launch<decltype(dt)::value, decltype(mt)::value>(x, w_packed, out, M, N, K, KC, waves, step_major, s, np, tile0); });
+    };
+    if (dtype == SJD_DTYPE_BF16) return rows(std::integral_constant<int, SJD_DTYPE_BF16>{});
+    if (dtype == SJD_DTYPE_F16) return rows(std::integral_constant<int, SJD_DTYPE_F16>{});
     return SJD_ERR_UNSUPPORTED;
 }
 
@@ -2135,16 +2078,11 @@ extern "C" int sjd_skinny_gemm_reduce(const void *x, const void *w_packed, float
     if (lds > 160 * 1024) return SJD_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int rs = step_major ? n_out : 1;
-    if (dtype == SJD_DTYPE_BF16) {
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1_skinny_gemm<SJD_DTYPE_BF16, 1, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((g1_skinny_gemm<SJD_DTYPE_BF16, 1, 512>), grid, block, lds, s, (const unsigned short *)x, (const u32x4 *)w_packed, workspace,
-                           M, N, K, KC, n_out, rs, 0, waves, (unsigned short *)h, sumsq, ticket);
-    } else if (dtype == SJD_DTYPE_F16) {
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1_skinny_gemm<SJD_DTYPE_F16, 1, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((g1_skinny_gemm<SJD_DTYPE_F16, 1, 512>), grid, block, lds, s, (const unsigned short *)x, (const u32x4 *)w_packed, workspace,
-                           M, N, K, KC, n_out, rs, 0, waves, (unsigned short *)h, sumsq, ticket);
-    } else return SJD_ERR_UNSUPPORTED;
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+    if (dtype == SJD_DTYPE_BF16)
+        return g1_launch_kernel(g1_skinny_gemm<SJD_DTYPE_BF16, 1, 512>, grid, block, lds, s, x, w_packed, workspace, M, N, K, KC, n_out, rs, 0, waves, h, sumsq, ticket);
+    if (dtype == SJD_DTYPE_F16)
+        return g1_launch_kernel(g1_skinny_gemm<SJD_DTYPE_F16, 1, 512>, grid, block, lds, s, x, w_packed, workspace, M, N, K, KC, n_out, rs, 0, waves, h, sumsq, ticket);
+    return SJD_ERR_UNSUPPORTED;
 }
 
 // Kernel G1w over the 12-bit stream (late round 6 experiment, csrc/sjd_gemm_wide.h `Z`): bit-identical planes, measured SLOWER than what the product runs
@@ -2287,7 +2225,6 @@ __global__ __launch_bounds__(384) void o_merge_prologue_probe(const float *__res
 extern "C" int sjd_o_merge_prologue_probe(const float *part, float *sink, int n_split, int rows, int mode, void *stream)
 {
     if (!part || !sink || n_split < 1 || n_split > 4 || rows < 1 || rows > 32) return SJD_ERR_BAD_ARG;
-    hipLaunchKernelGGL(o_merge_prologue_probe, dim3(22, 8), dim3(384), 0, (hipStream_t)stream, part, sink, n_split, rows, mode);
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+    return g1_launch_kernel(o_merge_prologue_probe, dim3(22, 8), dim3(384), 0, (hipStream_t)stream, part, sink, n_split, rows, mode);
 }
 #endif  // SJD_EXPERIMENTAL

@@ -293,14 +293,10 @@ static int g1q_launch(const void *x, const void *wq, float *out, int M, int N, i
     const float *scales = reinterpret_cast<const float *>(static_cast<const unsigned char *>(wq) + (size_t)n_tiles * 32 * K);
     const dim3 grid((n_out + waves - 1) / waves, n_chunks), block(waves * 64);
     const int rs = step_major ? n_tiles : 1;
-#define SJD_G1Q_LAUNCH(MT_, MAXT_) do { \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1q_skinny_gemm<MT_, MAXT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((g1q_skinny_gemm<MT_, MAXT_>), grid, block, lds, s, (const unsigned short *)x, (const unsigned char *)wq, scales, out, \
-                           M, N, K, KC, n_tiles, rs, tile0, waves); } while (0)
+#define SJD_G1Q_LAUNCH(MT_, MAXT_) return g1_launch_kernel(g1q_skinny_gemm<MT_, MAXT_>, grid, block, lds, s, x, wq, scales, out, M, N, K, KC, n_tiles, rs, tile0, waves)
     if (MT == 1) { if (waves <= 8) SJD_G1Q_LAUNCH(1, 512); else SJD_G1Q_LAUNCH(1, 1024); }
     else { if (waves <= 8) SJD_G1Q_LAUNCH(2, 512); else SJD_G1Q_LAUNCH(2, 1024); }
 #undef SJD_G1Q_LAUNCH
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
 }
 
 // SJD_G1_W8_E4M3 on sjd_gateup_silu (which has checked the common arguments): M <= 32; the scales sit behind the 2 I * K record bytes.
@@ -317,12 +313,7 @@ static int g1sq_launch(const void *x, const void *wq, void *y, int M, int I, int
     const int sl = rn ? rn->slices : 0;
     const float ih = rn ? 1.0f / (float)rn->hidden : 0.f, eps = rn ? rn->eps : 0.f;
 #define SJD_G1SQ_CASE(SP_) \
-    if (SP == SP_) { \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)g1q_gateup_silu<SP_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((g1q_gateup_silu<SP_>), grid, block, lds, s, (const unsigned short *)x, (const unsigned char *)wq, scales, \
-                           (unsigned short *)y, M, I, K, rec_stride, ss, sl, ih, eps); \
-        return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH; \
-    }
+    if (SP == SP_) return g1_launch_kernel(g1q_gateup_silu<SP_>, grid, block, lds, s, x, wq, scales, y, M, I, K, rec_stride, ss, sl, ih, eps);
     SJD_G1SQ_CASE(8) SJD_G1SQ_CASE(16) SJD_G1SQ_CASE(32) SJD_G1SQ_CASE(64)
 #undef SJD_G1SQ_CASE
     return SJD_ERR_UNSUPPORTED;

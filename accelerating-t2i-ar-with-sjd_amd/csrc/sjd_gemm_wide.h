@@ -416,14 +416,11 @@ static int g1_wide_launch(const void *x, const void *w_packed, float *out, int M
     const dim3 grid((n_out + NW * CT - 1) / (NW * CT), n_chunks), block(64 * NW);
     constexpr size_t lds = g1_wide_lds<MT, SUB, NS>();
     static_assert(lds <= 160 * 1024, "the activation ring must fit in LDS");
-    auto kern = g1_wide<DT, MT, CT, NW, SUB, NS, RW, WPS>;
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     // (the XCD-aware map pays where the activation outgrows an XCD's L2 share: eight prompts 6.75 -> 6.58 ms per step, two alternations on one box; at 128
     //  rows and below it is neutral end to end and costs the gate|up launch 3 us alone: plain map there.  profiles/r6_g1w_xmap_ab.txt)
     constexpr int xmap = MT > 4;
-    hipLaunchKernelGGL(kern, grid, block, lds, s, (const unsigned short *)x, (const u32x4 *)w_packed, out, M, N, K, KC, n_tiles, step_major ? n_tiles : 1, tile0, ldx > 0 ? ldx : K, xmap,
-                       (const u32x2 *)nullptr, 0);
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+    return g1_launch_kernel(g1_wide<DT, MT, CT, NW, SUB, NS, RW, WPS>, grid, block, lds, s, x, w_packed, out, M, N, K, KC, n_tiles, step_major ? n_tiles : 1, tile0,
+                            ldx > 0 ? ldx : K, xmap, nullptr, 0);
 }
 
 // the same over the 12-bit stream (wz: record pairs, exc: unit headers of exc_cap entries); bf16
@@ -436,14 +433,11 @@ static int g1_wide_launch_z(const void *x, const void *wz, const void *exc, int 
     constexpr size_t lds = g1_wide_lds<MT, SUB, NS>();
     static_assert(lds <= 160 * 1024, "the activation ring must fit in LDS");
     constexpr int xmap = MT > 4;
-#define SJD_G1WZ(WIDE_) do { \
-        auto kern = g1_wide<SJD_DTYPE_BF16, MT, CT, NW, SUB, NS, RW, WPS, true, WIDE_>; \
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, (const unsigned short *)x, (const u32x4 *)wz, out, M, N, K, KC, n_tiles, step_major ? n_tiles : 1, tile0, K, xmap, \
-                           (const u32x2 *)exc, exc_cap); } while (0)
+#define SJD_G1WZ(WIDE_) \
+    return g1_launch_kernel(g1_wide<SJD_DTYPE_BF16, MT, CT, NW, SUB, NS, RW, WPS, true, WIDE_>, grid, block, lds, s, x, wz, out, M, N, K, KC, n_tiles, \
+                            step_major ? n_tiles : 1, tile0, K, xmap, exc, exc_cap)
     if (exc_cap > 64) SJD_G1WZ(true); else SJD_G1WZ(false);
 #undef SJD_G1WZ
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
 }
 
 // G1wq: the same over the 8-bit e4m3 stream (wq: record pairs, then the fp32 column scales at byte N_packed * K); bf16, K and KC multiples of 32
@@ -455,36 +449,50 @@ static int g1_wide_launch_q(const void *x, const void *wq, float *out, int M, in
     constexpr size_t lds = g1_wide_lds<MT, SUB, NS>();
     static_assert(lds <= 160 * 1024, "the activation ring must fit in LDS");
     constexpr int xmap = MT > 4;
-    auto kern = g1_wide<SJD_DTYPE_BF16, MT, CT, NW, SUB, NS, RW, WPS, false, false, true>;
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, (const unsigned short *)x, (const u32x4 *)wq, out, M, N, K, KC, n_tiles, step_major ? n_tiles : 1, tile0, K, xmap,
-                       (const u32x2 *)nullptr, 0);
-    return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
+    return g1_launch_kernel(g1_wide<SJD_DTYPE_BF16, MT, CT, NW, SUB, NS, RW, WPS, false, false, true>, grid, block, lds, s, x, wq, out, M, N, K, KC, n_tiles,
+                            step_major ? n_tiles : 1, tile0, K, xmap, nullptr, 0);
+}
+
+// Column tiles per workgroup -> the G1w instantiation (stages of four k-steps, three ring slots, weight ring of two stages): 2, 3, 4 tiles run one per
+// wave, 6 and 8 two per wave.  WPS: workgroups per SIMD the register budget allows; Q: the 8-bit stream (g1_wide_launch_q, bf16).  G1W_NO_FORM, with
+// nothing launched, for a count kernel G1w does not take -- the caller falls back or refuses.
+constexpr int G1W_NO_FORM = 1;          // internal: every caller maps it to an SJD_* code or a fall-back -- it must never leave this translation unit
+static_assert(G1W_NO_FORM != SJD_OK && G1W_NO_FORM != SJD_ERR_BAD_ARG && G1W_NO_FORM != SJD_ERR_UNSUPPORTED && G1W_NO_FORM != SJD_ERR_LAUNCH, "not a return code");
+template <int DT, int MT, int WPS, bool Q = false>
+static int g1_wide_by_tiles(int tiles, const void *x, const void *w, float *out, int M, int N, int K, int KC, int n_tiles, int step_major, int tile0, hipStream_t s)
+{
+    auto launch = [&](auto ct, auto nw) {
+        constexpr int CT = decltype(ct)::value, NW = decltype(nw)::value;
+        if constexpr (Q) return g1_wide_launch_q<MT, CT, NW, 4, 3, 2, WPS>(x, w, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+        else return g1_wide_launch<DT, MT, CT, NW, 4, 3, 2, WPS>(x, w, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+    };
+    using one = std::integral_constant<int, 1>;
+    using two = std::integral_constant<int, 2>;
+    switch (tiles) {
+    // (three row tiles x two waves: a k-step has too few MFMAs to carry its DMA pieces -- no two-tile form at three row tiles)
+    case 2: if constexpr (MT != 3) return launch(one{}, two{}); else return G1W_NO_FORM;
+    case 3: return launch(one{}, std::integral_constant<int, 3>{});
+    case 4: return launch(one{}, std::integral_constant<int, 4>{});
+    case 6: return launch(two{}, std::integral_constant<int, 3>{});
+    case 8: return launch(two{}, std::integral_constant<int, 4>{});
+    default: return G1W_NO_FORM;
+    }
+}
+
+// f(std::integral_constant<int, MT>) for the row-tile count MT = ceil(M / 32) in [LO, HI]: the one place a row count becomes a template argument
+template <int LO, int HI, typename F>
+static int g1_by_row_tiles(int M, F &&f)
+{
+    if constexpr (LO < HI) { if (M > 32 * LO) return g1_by_row_tiles<LO + 1, HI>(M, f); }
+    return f(std::integral_constant<int, LO>{});
 }
 
 // SJD_G1_W8_E4M3 at 65..256 rows (g1q_launch, which has checked the column window): `waves` = column tiles per workgroup, the template shapes of the
-// uncompressed dispatch (g1_launch) per row-tile count; three row tiles x two tiles has no G1w form.  Anything else: SJD_ERR_UNSUPPORTED before a launch.
-template <int MT>
-static int g1wq_tiles(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int waves, int step_major, int n_tiles, int tile0, hipStream_t s)
-{
-    switch (waves) {
-    case 2: if constexpr (MT != 3) return g1_wide_launch_q<MT, 1, 2, 4, 3, 2, 1>(x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s); else return SJD_ERR_UNSUPPORTED;
-    case 3: return g1_wide_launch_q<MT, 1, 3, 4, 3, 2, 1>(x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-    case 4: return g1_wide_launch_q<MT, 1, 4, 4, 3, 2, 1>(x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-    case 6: return g1_wide_launch_q<MT, 2, 3, 4, 3, 2, 1>(x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-    case 8: return g1_wide_launch_q<MT, 2, 4, 4, 3, 2, 1>(x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s);
-    default: return SJD_ERR_UNSUPPORTED;
-    }
-}
+// uncompressed dispatch (g1_launch) per row-tile count.  Anything G1wq has no form for: SJD_ERR_UNSUPPORTED before a launch.
 static int g1wq_launch(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int waves, int step_major, int n_tiles, int tile0, hipStream_t s)
 {
     if (M <= 64 || M > 256 || (K % 32) != 0 || (KC % 32) != 0) return SJD_ERR_UNSUPPORTED;
-    switch ((M + 31) / 32) {
-    case 3: return g1wq_tiles<3>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
-    case 4: return g1wq_tiles<4>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
-    case 5: return g1wq_tiles<5>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
-    case 6: return g1wq_tiles<6>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
-    case 7: return g1wq_tiles<7>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
-    default: return g1wq_tiles<8>(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);
-    }
+    const int rc = g1_by_row_tiles<3, 8>(M, [&](auto mt) {
+        return g1_wide_by_tiles<SJD_DTYPE_BF16, decltype(mt)::value, 1, true>(waves, x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s); });
+    return rc == G1W_NO_FORM ? SJD_ERR_UNSUPPORTED : rc;
 }

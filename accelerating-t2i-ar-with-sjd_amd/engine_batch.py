@@ -25,6 +25,7 @@ import os
 import torch
 
 from . import _lib as L
+from . import launch_shapes as LS
 from . import ops
 from .engine import DecodeStats, SJDConfig, WindowSpec, warn_no_grid, capture_graph
 from .grammar import spatial_fresh_tokens
@@ -83,49 +84,44 @@ class SJDBatchEngine:
         if getattr(bargs, "swin_norm", False) or getattr(bargs, "model_parallel_size", 1) != 1:
             raise ValueError("SJDBatchEngine does not serve swin-norm backbones (swin_norm=True or model_parallel_size > 1, the 30B-class "
                              "Chameleon form): decode them one prompt at a time with SJDEngine / FlexARInferenceSolver")
-        q8_rows = getattr(backbone, "max_rows", 64) if getattr(backbone, "_max_rows_given", False) else None       # enable_fused(weights=..., max_rows=...)
-        if getattr(backbone, "weights", None) == "e4m3" and q8_rows is not None and q8_rows < n_prompts * n_batch * max_window <= 256:
-            raise ValueError(f"the backbone was packed for windows of at most max_rows={q8_rows} rows, but n_prompts * n_batch * max_window = "
-                             f"{n_prompts * n_batch * max_window}: call enable_fused(ops, gemm='sjd', weights='e4m3', "
-                             f"max_rows={128 if n_prompts * n_batch * max_window <= 128 else 256}), or use fewer prompts per forward")
-        if getattr(backbone, "weights", None) == "e4m3" and q8_rows is None:
-            raise ValueError("SJDBatchEngine does not serve a backbone packed with enable_fused(weights='e4m3'): 8-bit weights serve one prompt per "
-                             "forward (at most 64 window rows) in this version -- decode with SJDEngine, or pack with weights=None")
+        rows = n_prompts * n_batch * max_window
+        to = 128 if rows <= 128 else 256                                 # the max_rows a refusal names: the set packed for that many rows
+        why, detail = LS.serves_rows(backbone, rows, head=True) or (None, None)          # (launch_shapes.py: what a packed backbone serves, and why not)
+        if getattr(backbone, "weights", None) == "e4m3":                 # enable_fused(weights=..., max_rows=...)
+            if not getattr(backbone, "_max_rows_given", False):
+                raise ValueError("SJDBatchEngine does not serve a backbone packed with enable_fused(weights='e4m3'): 8-bit weights serve one prompt per "
+                                 "forward (at most 64 window rows) in this version -- decode with SJDEngine, or pack with weights=None")
+            if why == "max_rows":
+                raise ValueError(f"the backbone was packed for windows of at most max_rows={detail} rows, but n_prompts * n_batch * max_window = "
+                                 f"{rows}: call enable_fused(ops, gemm='sjd', weights='e4m3', max_rows={to}), or use fewer prompts per forward")
         L.load()                                   # fail loudly if the HIP extension is missing
         if max_window > L.MAX_WINDOW:
             raise ValueError(f"max_window {max_window} > {L.MAX_WINDOW}")
-        if n_prompts * n_batch * max_window > 256:
+        if rows > LS.WINDOW_MAX_ROWS:
             raise ValueError("the window forward (G1, F1-F3) serves at most 256 rows: n_prompts * n_batch * max_window <= 256")
-        rows = n_prompts * n_batch * max_window
-        if hasattr(backbone, "tok_embeddings") and hasattr(backbone, "embed_condition"):          # LlamaGen
-            # its window forward leaves the HIP path above the row count the weights were packed for (LlamaGenBackbone.forward_window) and
-            # would fall onto ATen silently: not bit-identical to the oracle replays, and no head partials for K2
-            if getattr(backbone, "_ops", None) is None:
-                raise ValueError("SJDBatchEngine serves a LlamaGen backbone on the fused HIP path only: call "
-                                 f"model.enable_fused(ops, gemm='sjd', max_rows=...) first ({rows} window rows per forward here"
-                                 + ("; head_dim 100: with pad_head_dim=True, padded_batch=True)" if getattr(backbone, "head_dim", 0) == 100 else ")"))
-            # (a head_dim-100 backbone stored 128 wide is packed for more than 64 rows on request only: the refusals name both arguments)
-            padded = ", pad_head_dim=True, padded_batch=True" if getattr(backbone, "_head_pad", None) else ""
-            if backbone.output.weight.dtype == torch.float16 and rows > 128 and getattr(backbone, "max_rows", 64) < rows:
-                raise ValueError(f"the backbone was packed for fp16 windows of at most {getattr(backbone, 'max_rows', 64)} rows, but n_prompts * n_batch * max_window = {rows}: "
-                                 f"call enable_fused(ops, gemm='sjd', max_rows=256, untuned_fp16=True{padded}), or use fewer prompts per forward")
-            if getattr(backbone, "max_rows", 64) < rows:
-                raise ValueError(f"the backbone was packed for windows of at most max_rows={getattr(backbone, 'max_rows', 64)} rows, but "
-                                 f"n_prompts * n_batch * max_window = {rows}: call enable_fused(ops, gemm='sjd', max_rows={128 if rows <= 128 else 256}{padded})")
-        if rows > 128 and getattr(backbone, "_gemm", None) == "sjd" and getattr(backbone, "_packed", None):
-            # 129..256 window rows run on kernel G1w (csrc/sjd_gemm_wide.h): the uncompressed packing, 2 / 3 / 4 / 6 / 8 column tiles per
-            # workgroup for every projection AND the output head.  Anything else used to fall onto the library-GEMM prefill path silently
-            # (slower, not bit-identical to the oracle replays) or to fail at the first forward: say so here instead.
-            tiles = getattr(backbone, "G1_WIDE_TILES", (2, 3, 4, 6, 8))
-            bad = [k for k, c in backbone.G1_CFG.items() if c[1] not in tiles]
-            if getattr(backbone, "_packed_head", None) is not None and backbone.HEAD_CFG[1] not in tiles:
-                bad.append("lm_head (HEAD_CFG)")
-            if isinstance(backbone._packed[0]["qkv"], ops.PackedZ):
-                raise ValueError(f"{rows} window rows per forward need the uncompressed packing: enable_fused(ops, gemm='sjd', compress=False) "
-                                 "(the 12-bit stream serves up to 128 rows)")
-            if bad:
-                raise ValueError(f"{rows} window rows per forward run on kernel G1w with {tiles} column tiles per workgroup; set "
-                                 f"model.G1_CFG = dict(model.G1_CFG_256ROW) before enable_fused -- offending launch shapes: {bad}")
+        # a LlamaGen window forward leaves the HIP path above the row count the weights were packed for (LlamaGenBackbone.forward_window) and
+        # would fall onto ATen silently: not bit-identical to the oracle replays, and no head partials for K2
+        if why == "unfused":
+            raise ValueError("SJDBatchEngine serves a LlamaGen backbone on the fused HIP path only: call "
+                             f"model.enable_fused(ops, gemm='sjd', max_rows=...) first ({rows} window rows per forward here"
+                             + ("; head_dim 100: with pad_head_dim=True, padded_batch=True)" if getattr(backbone, "head_dim", 0) == 100 else ")"))
+        # (a head_dim-100 backbone stored 128 wide is packed for more than 64 rows on request only: the refusals name both arguments)
+        padded = ", pad_head_dim=True, padded_batch=True" if getattr(backbone, "_head_pad", None) else ""
+        if why == "fp16":
+            raise ValueError(f"the backbone was packed for fp16 windows of at most {detail} rows, but n_prompts * n_batch * max_window = {rows}: "
+                             f"call enable_fused(ops, gemm='sjd', max_rows=256, untuned_fp16=True{padded}), or use fewer prompts per forward")
+        if why == "max_rows":
+            raise ValueError(f"the backbone was packed for windows of at most max_rows={detail} rows, but "
+                             f"n_prompts * n_batch * max_window = {rows}: call enable_fused(ops, gemm='sjd', max_rows={to}{padded})")
+        # 129..256 window rows run on kernel G1w (csrc/sjd_gemm_wide.h): the uncompressed packing, LS.WIDE_TILES column tiles per workgroup
+        # for every projection AND the output head.  Anything else used to fall onto the library-GEMM prefill path silently
+        # (slower, not bit-identical to the oracle replays) or to fail at the first forward: say so here instead.
+        if why == "12-bit":
+            raise ValueError(f"{rows} window rows per forward need the uncompressed packing: enable_fused(ops, gemm='sjd', compress=False) "
+                             "(the 12-bit stream serves up to 128 rows)")
+        if why == "tiles":
+            raise ValueError(f"{rows} window rows per forward run on kernel G1w with {LS.WIDE_TILES} column tiles per workgroup; set "
+                             f"model.G1_CFG = dict(model.G1_CFG_256ROW) before enable_fused -- offending launch shapes: {detail}")
         self.backbone, self.V, self.device = backbone, int(vocab_size), torch.device(device)
         self.P, self.nb, self.Lmax, self.B = n_prompts, n_batch, max_window, n_prompts * n_batch
         self.use_graph, self.narrow_head = use_graph, narrow_head

@@ -1,0 +1,190 @@
+"""Launch shapes (split-K chunk, column tiles per workgroup, step-major packing) of the window projections: the tuned sets, the kernels' limits, and
+what serves which rows.  The packed layout depends on the chunk, so a set is chosen when the weights are packed (enable_fused)."""
+import torch
+
+# ------------------------------------------------------------------------------------------ the kernels' limits
+WIDE_TILES = (2, 3, 4, 6, 8)      # column tiles per workgroup kernel G1w / G1wq takes: 2, 3, 4 (one per wave) or 6, 8 (two per wave)
+CHUNK_CAP_32ROW = 2560            # columns of an activation chunk a <= 32-row window stages whole in LDS (G1, G1z, G1q)
+CHUNK_CAP_64ROW = 1280            # the same at 33..64 rows: the staged chunk is twice as tall
+Z_MAX_ROWS = 128                  # the 12-bit stream (G1z / G1sz) serves windows of up to 128 rows
+WINDOW_MAX_ROWS = 256             # the window path (G1, F1-F3) as a whole; above 64 rows a batch row holds at most 32 of them (longer inputs are prefill)
+Z_MAX_KC = 4096                   # the 12-bit packer: the k-step of an exception is 7 + 1 bits of its position
+
+# ------------------------------------------------------------------------------------------ Chameleon / Lumina-mGPT / Emu3
+# G1 launch shape per projection: (split-K chunk, column tiles per workgroup, step-major packing) -- tuned on MI355X with
+# tools/g1_bench.py so that every launch gives the 256 CUs ~1000+ balanced waves
+G1_CFG = dict(qkv=(896, 8, True), o=(512, 6, False), gate_up=(2048, 8, True), down=(896, 8, False))
+# the same for the 12-bit weight stream (G1z): the launch-shape sweep of tools/g1z_bench.py --sweep and an end-to-end A/B on one box
+# (profiles/r3_g1z_microbench.txt: 3.068 / 3.090 -> 3.044 ms per step); taken by enable_fused when the caller has not set G1_CFG itself
+G1_CFG_Z = dict(qkv=(1024, 6, True), o=(512, 6, False), gate_up=(2048, 8, True), down=(768, 8, False))
+# the same for 64-row windows (two prompts per forward, or a draft window of 32): the staged chunk is twice as tall, so KC <= 1280;
+# set `model.G1_CFG = model.G1_CFG_64ROW` before enable_fused (the packing depends on KC).  Tuned end to end at Lumina-7B shapes.
+# (round 3: gate|up packed in two K halves = the copy kernel G1s streams, which now serves 64 rows; (1024, 12) was the G1 + F3 shape)
+# (late round 6: o on four column tiles per workgroup -- on the 12-bit stream that launch shape runs on kernel G1w's 12-bit form, the one place it beats
+#  G1z: two prompts per forward 3.50 -> 3.44 ms per step, profiles/r6_g1wz_o_64rows_ab.txt; round 2's shape: o (512, 8, False))
+G1_CFG_64ROW = dict(qkv=(896, 8, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(896, 8, False))       # profiles/r2_g1_launch_shape_sweep_64rows.jsonl
+# 65..128-row windows (three / four prompts per forward): the activation is sub-tiled, so KC is free again, but <= 8 waves.  Round 3:
+# 4-wave workgroups run on g1_skinny_gemm_tiled8 (8-step sub-tiles, two workgroups per CU, weight ring refilled in place) -- q|k|v,
+# o and down are faster there (28.1 / 15.8 / 28.4 -> 25.7 / 12.2 / 24.0 us); 8-wave workgroups run on the same kernel with one workgroup
+# per CU (gate|up 49.4 -> 43.3 us, profiles/r3_g1_tiled8.txt); four prompts per forward 5.55 -> 4.89 ms per step on one box
+# (late round 6: bf16 windows of 65..128 rows run on kernel G1w as well -- the second number is then its column tiles per workgroup -- with gate|up
+#  on six tiles and down in chunks of 1408: four prompts 4.43 -> 4.26 ms per step, three 4.05 -> 3.95 on one box, profiles/r6_g1w_128rows_ab.txt;
+#  round 5's shapes: gate_up (2048, 8), down (1376, 4).  fp16 and the 12-bit stream keep the sub-tiled kernels on the same shapes.)
+G1_CFG_128ROW = dict(qkv=(2048, 4, True), o=(896, 4, True), gate_up=(2048, 6, True), down=(1408, 4, True))
+# 129..256-row windows (five to eight prompts per forward): kernel G1w (csrc/sjd_gemm_wide.h, round 6) -- the second number is the column tiles
+# per workgroup: 2, 3, 4 (one per wave) or 6, 8 (two per wave).  tools/g1w_bench.py at 256 rows (profiles/r6_g1w_sweep.txt), us per launch against
+# round 5's g1_skinny_gemm_tiled8: q|k|v 34.3 / 46.1, o 19.6 / 23.4, gate|up 58.4 / 84.4, down 31.3 / 38.2 (hipBLASLt: 50.4 / 19.1 / 65.9 / 52.7); o with
+# four planes instead of (512, 4)'s eight: 16.4 us alone, but 7.18 against 7.37 ms per step (F1r sums the planes; profiles/r6_g1w_cfg_ab.txt)
+G1_CFG_256ROW = dict(qkv=(2048, 4, True), o=(1024, 2, True), gate_up=(2048, 8, True), down=(1408, 4, True))
+# Emu3-Gen 8B (GQA 32/8: the q|k|v projection has 6144 columns; draft window 32 -> 64 rows), tuned end to end with bench.py --model emu3_8b
+# (late round 6: 33..64-row windows on the uncompressed stream run on kernel G1w -- the second number is its column tiles per workgroup -- with its own
+#  shapes: per launch q|k|v 12.8 / 13.6 us, o 9.4 / 11.2, down 22.5 / 25.2 against round 2's (512, 8) / (512, 8) / (896, 8) on the whole-chunk kernel,
+#  profiles/r6_g1w_sweep_64rows_emu3.jsonl; Emu3 in fp16 4.37 -> 4.17 ms per step, profiles/r6_g1w_64rows_emu3_ab.txt)
+G1_CFG_EMU3 = dict(qkv=(1024, 4, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(1792, 4, True))
+# the same on the 12-bit stream (Emu3 in bf16, round 4): 256-workgroup launches for q|k|v and o, step-major packing -- 11.75 / 10.25 / 19.85 us
+# against 12.15 / 10.66 / 20.19 (tools/g1z_bench.py --sweep --emu3 --rows 64, profiles/r4_g1z_sweep_emu3_64rows.jsonl)
+G1_CFG_EMU3_Z = dict(qkv=(512, 6, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(896, 8, True))
+# the 8-bit e4m3 stream (enable_fused(weights="e4m3"), kernels G1q / G1sq): UNTUNED -- the 12-bit sets with every chunk cut to what G1q stages whole
+# in LDS at the architecture's row count (Emu3: 64 rows, KC <= 1280, so its gate|up runs unfused as G1q + F3 in four chunks); no launch-shape
+# sweep was run for this format.  G1_CFG_Q8's gate|up keeps the two K halves of 2048 that the fused 32-row launch (G1sq) streams; a window of
+# 33..64 rows (a draft window of 32 with CFG, the prefill of a 17..32-token prompt) reads that step-major copy in chunks of 1024 (chunk_for_rows)
+G1_CFG_Q8 = dict(qkv=(1024, 6, True), o=(512, 6, False), gate_up=(2048, 8, True), down=(768, 8, False))
+G1_CFG_EMU3_Q8 = dict(qkv=(512, 6, True), o=(512, 4, True), gate_up=(1024, 8, True), down=(896, 8, True))
+# the 8-bit stream for several prompts per forward (enable_fused(weights=..., max_rows=128 / 256)): UNTUNED -- G1_CFG_256ROW / G1_CFG_EMU3 as they are,
+# except o on three column tiles (kernel G1wq, like G1w, has no form of three row tiles x two column tiles: 65..96 rows).  ONE packed copy serves every row
+# count: <= 32 rows on G1q / G1sq (every chunk <= 2560; gate|up in the two K halves the fused launch streams), 33..64 on G1q in halved chunks
+# (chunk_for_rows: all step-major, K and the chunks multiples of 32 / 64), 65..256 on G1wq with these chunks and tile counts.  No sweep was run.
+G1_CFG_Q8_WIDE = dict(qkv=(2048, 4, True), o=(1024, 3, True), gate_up=(2048, 8, True), down=(1408, 4, True))
+G1_CFG_EMU3_Q8_WIDE = dict(qkv=(1024, 4, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(1792, 4, True))
+# 30B-class Chameleon (hidden 8192, intermediate 22016, GQA 64 / 8: q|k|v 10240 columns, gate|up 44032, down K 22016); chunks <= 2560 so that
+# the 32-row window stages its chunk in LDS.  The fastest shapes of `tools/swin30b_bench.py --sweep` at 32 rows on one MI355X
+# (profiles/g1_30b_sweep.jsonl), us per launch uncompressed / 12-bit: q|k|v 30.4 / 25.2, o 23.8 / 20.3, gate|up 120.5 / 98.9, down 62.9 / 50.4
+G1_CFG_30B = dict(qkv=(1536, 8, True), o=(1536, 8, False), gate_up=(2048, 8, True), down=(1536, 8, False))
+G1_CFG_30B_Z = dict(qkv=(1792, 8, True), o=(1280, 8, True), gate_up=(2048, 8, True), down=(1536, 8, True))
+HEAD_CFG = (1024, 4, True)         # G1 launch shape of the output head: (split-K chunk, column tiles per workgroup, step-major)
+# vocabularies whose image window is tens of thousands of columns (Emu3: 32768 of 184622): two K chunks, so that K2 sums two planes per
+# column instead of four, eight tiles per workgroup; Emu3 4.65 -> 4.62 ms per step (bench.py, SJD_HEAD_CFG sweep, one box)
+HEAD_CFG_WIDE = (2048, 8, True)
+
+# ------------------------------------------------------------------------------------------ LlamaGen
+LLAMAGEN_SETS = {      # (head_dim 100 stored 128 wide, max_rows) -> (G1_CFG, HEAD_CFG)
+    # G1 launch shapes of the window forward (<= 64 rows): (split-K chunk, column tiles per workgroup, step-major packing) per projection and for
+    # the output head.  `tools/llamagen_bench.py --sweep` at 32 rows, GPT-XL (profiles/llamagen_g1_sweep.jsonl): per projection the fastest shape
+    # with at most eight split-K planes (one batch of plane loads in F1r / F2 / F3), us per launch q|k|v 5.36, o 4.46, gate|up 6.64, down 6.35,
+    # head 10.09 (the launch-alone optimum, KC 128, is 0.3 - 1.4 us faster but leaves 10 - 28 planes for the consumer to sum)
+    (False, 64): (dict(qkv=(256, 2, True), o=(256, 2, False), gate_up=(320, 2, False), down=(512, 2, False)), (640, 4, True)),
+    # Several prompts per forward (SJDBatchEngine): 65..128 and 129..256 window rows run on G1's sub-tiled kernels / kernel G1w, whose workgroups
+    # take 2, 3, 4, 6 or 8 column tiles.  The packed layout depends on the split-K chunk, so the set is chosen when the weights are packed:
+    # enable_fused(..., max_rows=128 / 256); forward_window then serves windows of up to that many rows on the HIP path.
+    # `tools/llamagen_bench.py --sweep --rows 128 / 256`, GPT-XL (profiles/llamagen_g1_sweep_128rows.jsonl, _256rows.jsonl): per projection the
+    # fastest shape with at most eight planes -- us per launch at 128 rows q|k|v 6.92, o 5.36, gate|up 8.68, down 7.27, head 12.54; at 256 rows
+    # 9.80, 8.16, 12.31, 11.18, 17.87 (the 32-row set at 256 rows would still run: every tile count above is one kernel G1w takes)
+    (False, 128): (dict(qkv=(320, 2, False), o=(256, 2, False), gate_up=(320, 4, True), down=(512, 2, False)), (640, 4, True)),
+    (False, 256): (dict(qkv=(256, 4, False), o=(256, 2, False), gate_up=(320, 4, True), down=(512, 4, False)), (640, 4, True)),
+    # GPT-3B (dim 3200, 32 heads of 100 stored 128 wide: pad_head_dim=True; inter 8704; the o projection's K is 32 * 128 = 4096): the KC 256 / 320 / 512
+    # of the sets above would leave 13 / 10 / 17 planes, so the chunks are the smallest multiples of 16 that give eight -- 400 for hidden 3200, 512 for
+    # the o projection, 1088 for the down projection.  `tools/llamagen_bench.py --sweep --preset GPT-3B` at 32 rows (profiles/llamagen_g1_sweep_3b.jsonl):
+    # per projection the fastest shape with at most eight planes, us per launch q|k|v 12.83 (five planes), o 8.28, gate|up 20.81 (three planes),
+    # down 13.69, head 19.51; against the smallest-chunk set (400, 2) / (512, 2) / (400, 2) / (1088, 2) + head (640, 4) the fused step goes
+    # 2.19 -> 1.89 ms (profiles/llamagen_3b.json)
+    (True, 64): (dict(qkv=(640, 8, True), o=(512, 4, False), gate_up=(1088, 8, True), down=(1088, 4, True)), (1088, 8, True)),
+    # GPT-3B with several prompts per forward (enable_fused(pad_head_dim=True, padded_batch=True, max_rows=128 / 256)): the same rule at 128 and 256 rows --
+    # `tools/llamagen_bench.py --sweep --preset GPT-3B --rows 128 / 256` (profiles/llamagen_g1_sweep_3b_128rows.jsonl, _256rows.jsonl), per projection the
+    # fastest shape with at most eight planes (chunk >= 400 / 512 / 1088 for K = 3200 / 4096 / 8704) among kernel G1w's column-tile counts; us per launch
+    # at 128 rows q|k|v 16.80 (three planes), o 9.68, gate|up 26.54, down 16.56, head 24.82 (two planes); at 256 rows 25.45, 14.40, 37.97, 23.14, 35.56.
+    # (q|k|v's 9600 columns are 300 tiles: 75 workgroups of four; the head's 512 tiles by four; fp16 at 65..128 rows keeps the sub-tiled kernels on these shapes)
+    (True, 128): (dict(qkv=(1088, 4, False), o=(512, 4, False), gate_up=(1088, 8, False), down=(1088, 4, True)), (1600, 4, True)),
+    (True, 256): (dict(qkv=(1088, 4, False), o=(512, 4, True), gate_up=(1088, 8, True), down=(1088, 4, True)), (1600, 4, True)),
+}
+
+
+def default_shapes(dtype, g1_given, head_given, wide_hidden, gqa, compress, weights, max_rows, vocab_size):
+    """(G1_CFG, HEAD_CFG) ChameleonBackbone.enable_fused packs with; *_given: the caller's (it wins); wide_hidden: 30B class; gqa: Emu3; None: the class default stays"""
+    z = compress and dtype == torch.bfloat16          # the 12-bit stream
+    head = head_given or (HEAD_CFG_WIDE if vocab_size >= 131072 else None)
+    if weights is not None:
+        wide = (G1_CFG_EMU3_Q8_WIDE if gqa else G1_CFG_Q8_WIDE) if (max_rows or 64) > 64 else None
+        return g1_given or dict(wide or (G1_CFG_EMU3_Q8 if gqa else G1_CFG_Q8)), head
+    g1 = g1_given or (dict(G1_CFG_30B_Z if z else G1_CFG_30B) if wide_hidden else dict(G1_CFG_EMU3) if gqa else dict(G1_CFG_Z) if z else None)
+    return (dict(G1_CFG_EMU3_Z) if z and g1 == G1_CFG_EMU3 else g1), head          # (also when the caller named Emu3's set: the packing follows the stream)
+
+
+def halved_chunk(kc, K, step_major):
+    """`kc` halved until it is <= CHUNK_CAP_64ROW, as far as the packing allows (the caller checks the result)"""
+    while kc > CHUNK_CAP_64ROW and step_major and K % 32 == 0 and kc % 64 == 0:
+        kc //= 2
+    return kc
+
+
+# Under enable_fused(weights=...) kernel G1q stages the whole activation chunk in LDS: <= CHUNK_CAP_32ROW columns up to 32 rows, <= CHUNK_CAP_64ROW at
+# 33..64.  A projection packed with a longer chunk (G1_CFG_Q8's gate|up: two K halves of 2048, the copy the fused 32-row launch streams) is read at
+# 33..64 rows in HALVED chunks until they fit: a step-major packing whose chunks are whole record pairs (K and the chunk multiples of 32) is the same
+# bytes under either chunking -- pair after pair, every tile per pair.  The "e4m3_as_bf16" twin takes the same chunks (pack_weight's step-major stream
+# has the same property), so the two stay bit-identical.
+def chunk_for_rows(name, shape, T, K, weights=None, max_rows=64):
+    """split-K chunk of projection `name` (launch shape `shape`) for a T-row window; ValueError where no such chunk exists"""
+    KC, _, sm = shape
+    if weights is None or T <= 32 or min(KC, K) <= CHUNK_CAP_64ROW or (T > 64 and max_rows > 64):          # (G1wq / G1w stream the activation in stages)
+        return KC
+    kc = halved_chunk(KC, K, sm)
+    if kc > CHUNK_CAP_64ROW:
+        raise ValueError(f"weights={weights!r}: a {T}-row window needs {name} chunks of <= {CHUNK_CAP_64ROW} columns (kernel G1q stages the chunk in LDS), or a "
+                         f"step-major packing with K and the chunk multiples of 32 / 64 that halved chunks can read; G1_CFG[{name!r}] = {tuple(shape)}")
+    return kc
+
+
+def check_set(cfg, head_cfg, max_rows, q8_dims=None, head_name="head"):
+    """[(name, why)]: what keeps the set from serving windows of up to max_rows (> 64) rows.  why: "tiles" (G1w / G1wq does not take the count); with q8_dims (the
+    projections' (N, K): ONE 8-bit copy serves every row count) also "pairs" (K or the chunk no multiple of 32) and "chunk" (none that 33..64 rows can stage)"""
+    bad = []
+    for name, (KC, tiles, sm) in cfg.items():
+        K_ = q8_dims[name][1] if q8_dims else 0
+        if tiles not in WIDE_TILES or (q8_dims and tiles == 2):
+            bad.append((name, "tiles"))
+        elif q8_dims and (K_ % 32 or KC % 32):
+            bad.append((name, "pairs"))
+        elif q8_dims and halved_chunk(min(KC, K_), K_, sm) > CHUNK_CAP_64ROW:
+            bad.append((name, "chunk"))
+    if head_cfg is not None and (not q8_dims or max_rows > Z_MAX_ROWS) and head_cfg[1] not in WIDE_TILES:          # (up to 128 rows the 8-bit stream's head keeps its own kernels)
+        bad.append((head_name, "tiles"))
+    return bad
+
+
+def llamagen_row_limit(backbone):
+    """window rows a LlamaGen backbone can be asked for: fp16 keeps 128 unless it was packed for more (enable_fused(max_rows=256, untuned_fp16=True))"""
+    return WINDOW_MAX_ROWS if backbone.output.weight.dtype == torch.bfloat16 or getattr(backbone, "max_rows", 64) >= WINDOW_MAX_ROWS else Z_MAX_ROWS
+
+
+def serves_rows(backbone, rows, window=1, head=False):
+    """None when the packed `backbone` serves `rows` window rows (`window` per batch row) on the HIP path, else (why, detail): "unfused", "max_rows" / "fp16" (the
+    rows it was packed for), "12-bit" (that stream's limit), "tiles" (check_set's names; head: the output head's too) or "prefill" (library GEMMs take it)"""
+    if hasattr(backbone, "tok_embeddings") and hasattr(backbone, "embed_condition"):          # LlamaGen: up to the rows its weights were packed for
+        if getattr(backbone, "_ops", None) is None:
+            return "unfused", None
+        limit, fp16 = getattr(backbone, "max_rows", 64), backbone.output.weight.dtype == torch.float16 and rows > Z_MAX_ROWS
+        return ("fp16" if fp16 else "max_rows", limit) if rows > limit else None
+    weights, packed = getattr(backbone, "weights", None), getattr(backbone, "_packed", None)
+    limit = getattr(backbone, "max_rows", 64) if weights is not None else 64
+    if weights == "e4m3" and limit < rows <= WINDOW_MAX_ROWS and window <= 32:
+        return "max_rows", limit
+    if getattr(backbone, "_gemm", None) != "sjd" or rows > WINDOW_MAX_ROWS or (rows > 64 and window > 32) or (rows > Z_MAX_ROWS and not packed):
+        return "prefill", None
+    if rows <= Z_MAX_ROWS:
+        return None
+    if isinstance(packed[0]["qkv"], backbone._ops.PackedZ):
+        return "12-bit", Z_MAX_ROWS
+    bad = check_set(backbone.G1_CFG, backbone.HEAD_CFG if head and getattr(backbone, "_packed_head", None) is not None else None, rows, head_name="lm_head (HEAD_CFG)")
+    return ("tiles", [name for name, _ in bad]) if bad else None
+
+
+# shapes kernel G1s serves (see sjd_gateup_silu): a <= 32-row window -- or a <= 64-row one (draft window 32 with CFG, two prompts per forward) at
+# hidden >= 1024, or a <= 128-row one (three / four prompts per forward) at hidden 4096 over the uncompressed packing --, the gate|up weight packed in
+# two K halves; over the 8-bit packing (packed_q8: kernel G1sq) a <= 32-row window only
+def gateup_silu_ok(T, inter, hidden, KC, packed_z=False, packed_q8=False):
+    rows_ok = T <= 32 or (not packed_q8 and ((T <= 64 and hidden >= 1024) or (T <= Z_MAX_ROWS and hidden == 4096 and not packed_z)))
+    return rows_ok and hidden in (512, 1024, 2048, 4096) and 2 * KC == hidden and inter % 64 == 0
+
+
+def packed_nbytes(w):
+    """bytes of one packed weight: a tensor (pack_weight) or a PackedZ / PackedQ8, which know their own"""
+    return w.numel() * w.element_size() if isinstance(w, torch.Tensor) else w.nbytes()

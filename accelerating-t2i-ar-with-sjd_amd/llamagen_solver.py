@@ -4,6 +4,7 @@ from the global RNG, LS:75-104)."""
 import torch
 from torch.nn import functional as F
 
+from . import launch_shapes as LS
 from .scheduler.logit_processor_3dim import TopKLogitsWarper, TopPLogitsWarper3d
 
 
@@ -276,8 +277,7 @@ class LlamaGenSolver:
         """prompts per window forward: prompts_per_forward, or what the row limit allows: 256 rows; an fp16 backbone that was not packed for them
         (enable_fused(max_rows=256, untuned_fp16=True)) keeps its 128"""
         model = self.model
-        wide = model.output.weight.dtype == torch.bfloat16 or getattr(model, "max_rows", 64) >= 256
-        slots = self.prompts_per_forward or max(1, (256 if wide else 128) // (n_batch * model.max_num_new_tokens))
+        slots = self.prompts_per_forward or max(1, LS.llamagen_row_limit(model) // (n_batch * model.max_num_new_tokens))
         return max(1, min(int(slots), n_prompts))
 
     def _generate_many(self, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, vq_model=None, qzshape=None, **sampling_kwargs):

@@ -5,6 +5,9 @@ import os
 import torch
 
 from . import _lib as L
+from . import launch_shapes as LS
+
+gateup_silu_ok = LS.gateup_silu_ok          # the shapes kernels G1s / G1sz / G1sq serve
 
 
 def _stream():
@@ -396,7 +399,7 @@ def pack_weight_z(weight, KC, step_major=False, gateup=False):
     A unit with more than 127 exceptions (zero rows, pruned blocks, weights spanning more than sixteen binades) is RAW (round 6; the packer
     used to decline the whole matrix): see PackedZ.  gateup=True: `weight` is [Wg; Wu] packed with KC = K / 2 for sjd_gateup_silu_z -- a raw
     unit makes the packer list its whole (gate tile, up tile) pair, both K halves."""
-    if weight.dtype != torch.bfloat16 or KC > 4096:
+    if weight.dtype != torch.bfloat16 or KC > LS.Z_MAX_KC:
         return None
     N, K = weight.shape
     assert N % 32 == 0 and K % 16 == 0 and KC % 16 == 0
@@ -631,10 +634,10 @@ def _prows(M):
 
 
 def skinny_gemm(x, w_packed, N, K, KC, waves=4, step_major=False):
-    """x [M <= 256, K] bf16/fp16 -> Partials([n_chunks, 32 * ceil(M / 32), N] fp32).  waves = column tiles per workgroup: 1..16 up to 64 rows, <= 8 up to
-    128 rows; 129..256 rows (bf16 or fp16, uncompressed packing) run on kernel G1w: 2, 3, 4, 6 or 8.  A PackedQ8 weight (bf16): up to 64 rows on kernel
-    G1q (min(KC, K) <= 2560 up to 32 rows, <= 1280 above); 65..256 rows on kernel G1wq with 2, 3, 4, 6 or 8 tiles (not 2 at 65..96 rows), K and KC
-    multiples of 32 -- the planes of the same call on pack_weight(w_packed.dequant(), KC, step_major), bit for bit."""
+    """x [M <= LS.WINDOW_MAX_ROWS, K] bf16/fp16 -> Partials([n_chunks, 32 * ceil(M / 32), N] fp32).  waves = column tiles per workgroup: 1..16 up to 64 rows,
+    <= 8 up to 128 rows; above that (bf16 or fp16, uncompressed packing) kernel G1w takes LS.WIDE_TILES.  A PackedQ8 weight (bf16): up to 64 rows on kernel
+    G1q (min(KC, K) <= LS.CHUNK_CAP_32ROW up to 32 rows, <= LS.CHUNK_CAP_64ROW above); 65 rows and more on kernel G1wq with LS.WIDE_TILES (not 2 at 65..96
+    rows), K and KC multiples of 32 -- the planes of the same call on pack_weight(w_packed.dequant(), KC, step_major), bit for bit."""
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N * K
     _same_16bit_type(x, w_packed, "skinny_gemm")
@@ -788,7 +791,7 @@ def _raw_units(w_packed, gateup=False):
 
 def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_major=True):
     """G1 over the vocabulary columns [col0, col0 + n_cols) (32-aligned) of a weight packed with N_packed columns -> Partials [n_chunks, R, n_cols].
-    Row counts and `waves` per packing as skinny_gemm (PackedZ: up to 128 rows; PackedQ8: up to 256, kernels G1q / G1wq)."""
+    Row counts and `waves` per packing as skinny_gemm (PackedZ: up to LS.Z_MAX_ROWS rows; PackedQ8: up to LS.WINDOW_MAX_ROWS, kernels G1q / G1wq)."""
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N_packed * K and col0 % 32 == 0 and n_cols % 32 == 0
     nc = (K + KC - 1) // KC
@@ -1091,16 +1094,6 @@ def silu_mul(gate_up, rows=None, dtype=None, row_norm=None):
     return y
 
 
-def gateup_silu_ok(T, inter, hidden, KC, packed_z=False, packed_q8=False):
-    """shapes kernel G1s serves (see sjd_gateup_silu): a <= 32-row window -- or a <= 64-row one (draft window 32 with CFG, two prompts per
-    forward) at hidden >= 1024, or a <= 128-row one (three / four prompts per forward) at hidden 4096 over the uncompressed packing --,
-    the gate|up weight packed in two K halves; over the 8-bit packing (packed_q8: kernel G1sq) a <= 32-row window only"""
-    if packed_q8:
-        return T <= 32 and hidden in (512, 1024, 2048, 4096) and 2 * KC == hidden and inter % 64 == 0
-    rows_ok = T <= 32 or (T <= 64 and hidden >= 1024) or (T <= 128 and hidden == 4096 and not packed_z)
-    return rows_ok and hidden in (512, 1024, 2048, 4096) and 2 * KC == hidden and inter % 64 == 0
-
-
 def gateup_silu(x, w_packed, inter, hidden, step_major=False, row_norm=None):
     """G1s: silu(r * gate(x)) * (r * up(x)) [T, inter] in ONE launch -- the gate|up projection (w_packed = pack_weight([Wg; Wu], hidden / 2,
     step_major)) with F3 as its epilogue; bit-identical to silu_mul(skinny_gemm(x, w_packed, 2 * inter, hidden, hidden / 2), row_norm=...)."""
@@ -1132,7 +1125,7 @@ def mlp_pair_ok(T, inter, hidden, gu_packed, dn_packed, KC_dn, waves_dn, device)
     projection in eight-tile workgroups with a K chunk that is a multiple of 64, the whole launch resident at once"""
     if not (isinstance(gu_packed, PackedZ) and isinstance(dn_packed, PackedZ)) or gu_packed.n_raw or dn_packed.n_raw:
         return False
-    if T > 32 or hidden != 4096 or inter % 64 or KC_dn % 64 or KC_dn > 2560 or waves_dn != 8 or gu_packed.KC != hidden // 2 or dn_packed.KC != KC_dn:
+    if T > 32 or hidden != 4096 or inter % 64 or KC_dn % 64 or KC_dn > LS.CHUNK_CAP_32ROW or waves_dn != 8 or gu_packed.KC != hidden // 2 or dn_packed.KC != KC_dn:
         return False
     grid = max(inter // 64, ((hidden // 32 + 7) // 8) * ((inter + KC_dn - 1) // KC_dn))
     return grid <= torch.cuda.get_device_properties(device).multi_processor_count

@@ -127,6 +127,32 @@ def test_g1_skinny_gemm(dev, dtype, M, N, K, KC, waves, step_major):
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_g1_row_tile_ladder(dev, dtype):
+    """every boundary the (dtype, row tiles, column tiles) dispatch of sjd_skinny_gemm decides on: each side of every multiple of 32 rows, the tile
+    counts kernel G1w takes and one it does not (5: the sub-tiled kernels up to 128 rows, SJD_ERR_BAD_ARG above), both packings -- against
+    test_g1_skinny_gemm's reference and tolerance."""
+    import sjd_amd._lib as L
+    import sjd_amd.ops as ops
+    N, K, KC = 256, 512, 256
+    g = torch.Generator().manual_seed(N + K)
+    x256 = torch.randn(256, K, generator=g).to(dtype).to(dev)
+    w = (torch.randn(N, K, generator=g) / K ** 0.5).to(dtype).to(dev)
+    ref256 = x256.float() @ w.float().t()
+    for step_major in (False, True):
+        wp = ops.pack_weight(w, KC, step_major)
+        for M in (1, 32, 33, 64, 65, 96, 97, 128, 129, 160, 161, 192, 193, 224, 225, 256):
+            x = x256[:M].contiguous()
+            for tiles in (2, 3, 4, 5, 6, 8):
+                if tiles == 5 and M >= 129:
+                    with pytest.raises(L.SjdLibraryError, match=r"sjd_skinny_gemm failed: .*\(-1\)"):
+                        ops.skinny_gemm(x, wp, N, K, KC, waves=tiles, step_major=step_major)
+                    continue
+                part = ops.skinny_gemm(x, wp, N, K, KC, waves=tiles, step_major=step_major)
+                assert part.n_chunks == 2 and part.data.shape[1] == ((M + 31) // 32) * 32, (M, tiles, step_major)
+                torch.testing.assert_close(part.data.sum(0)[:M], ref256[:M], atol=2e-3, rtol=2e-3, msg=lambda m: f"M={M} tiles={tiles} step_major={step_major}: {m}")
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("M,N,K,KC", [(128, 4096, 11008, 896), (96, 12288, 4096, 896), (128, 22016, 4096, 2048), (100, 512, 1376, 256),
                                         (128, 64, 96, 32), (128, 4096, 4096, 1040), (65, 256, 176, 64), (128, 6144, 4096, 512), (64, 6144, 4096, 2048)])
 @pytest.mark.parametrize("waves,step_major", [(8, True), (8, False), (6, False), (3, True), (4, True), (4, False)])
