@@ -16,6 +16,7 @@ F2_HEAD_PAD128 = 0x400         # with F2_ROPE_TABLE and D = 100: 100-wide source
 K1_HEAD_DIM_100 = 0x800        # the 16-bit K1 entry points: D = 128 storage with zero pad columns, softmax scale 1/sqrt(100)
 F2_ONE_HEAD = 0x1000           # F2 above 64 rows of split-K planes: one head per wave in place of four (same bits; the parity tests compare them)
 G1_W8_E4M3 = 0x2000            # sjd_skinny_gemm / _cols / sjd_gateup_silu: w_packed is an 8-bit e4m3 stream with its column scales behind it (ops.PackedQ8)
+G1_W4_MXFP4 = 0x4000           # the same three: w_packed is an MXFP4 stream (e2m1 codes, the e8m0 block scales behind them: ops.PackedQ4)
 QKN_SHARDS_SHIFT = 16
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -554,6 +554,7 @@ class ChameleonBackbone(nn.Module):
     G1_CFG, G1_CFG_Z, G1_CFG_64ROW, G1_CFG_128ROW, G1_CFG_256ROW = LS.G1_CFG, LS.G1_CFG_Z, LS.G1_CFG_64ROW, LS.G1_CFG_128ROW, LS.G1_CFG_256ROW
     G1_CFG_EMU3, G1_CFG_EMU3_Z, G1_CFG_Q8, G1_CFG_EMU3_Q8 = LS.G1_CFG_EMU3, LS.G1_CFG_EMU3_Z, LS.G1_CFG_Q8, LS.G1_CFG_EMU3_Q8
     G1_CFG_Q8_WIDE, G1_CFG_EMU3_Q8_WIDE, G1_CFG_30B, G1_CFG_30B_Z = LS.G1_CFG_Q8_WIDE, LS.G1_CFG_EMU3_Q8_WIDE, LS.G1_CFG_30B, LS.G1_CFG_30B_Z
+    G1_CFG_Q4, G1_CFG_EMU3_Q4 = LS.G1_CFG_Q4, LS.G1_CFG_EMU3_Q4
     HEAD_CFG, HEAD_CFG_WIDE, G1_WIDE_TILES = LS.HEAD_CFG, LS.HEAD_CFG_WIDE, LS.WIDE_TILES
 
     # Weight prefetch plan of the G1 window forward: projection -> (workgroups of the prefetch kernel, when it is issued).  The packed
@@ -638,6 +639,13 @@ class ChameleonBackbone(nn.Module):
                           weights do to image quality on a real checkpoint has NOT been measured.
           "e4m3_as_bf16"  the same quantisation, the DEQUANTISED values packed uncompressed (G1 / G1s): the verification and A/B twin -- the
                           same values at two bytes each, so every token agrees with "e4m3".
+          "mxfp4"         the same four projections QUANTISED to OCP MXFP4 -- e2m1 codes with one power-of-two (e8m0) scale per output column and
+                          block of 32 consecutive k (ops.quantize_mxfp4) -- and streamed at 4.25 bits per weight by kernels G1q4 / G1sq4
+                          (ops.pack_weight_q4).  LOSSY and COARSER than e4m3 (one mantissa bit); what it does to image quality on a real checkpoint
+                          has NOT been measured.  Launch shapes: G1_CFG_Q4 / G1_CFG_EMU3_Q4 (UNTUNED) unless the caller set G1_CFG; K and every chunk
+                          must be multiples of LS.Q4_GRANULE.  At most 64 window rows: max_rows is None or 64 (there is no wide form).  compress_stats
+                          gains q4_matrices, q4_bytes_packed and the format's rel_rms_error.
+          "mxfp4_as_bf16" its verification twin: the dequantised values packed uncompressed, the same chunks and the same fused / unfused route.
         Only the window forward (inputs of at most 64 rows) reads the 8-bit copy: the prompt prefill (hipBLASLt on the 16-bit parameters) is
         NOT quantised.  SJD's draft and verify both run the window forward, so the sampler stays exact with respect to ITS model -- and that
         model is the quantised one.  8-bit weights serve bf16 backbones with gemm="sjd", no swin-norm / model_parallel_size > 1, at most 64
@@ -650,8 +658,11 @@ class ChameleonBackbone(nn.Module):
         every row count, so it must pass LS.check_set -- checked here, before anything is assigned.  max_rows=256: lm_head is packed UNCOMPRESSED
         whatever `compress` says (the 12-bit stream ends at LS.Z_MAX_ROWS rows) and HEAD_CFG[1] must be one of LS.WIDE_TILES.  Whether the 8-bit
         stream is faster than what those row counts run otherwise is a measurement, not a promise: README.md."""
-        if weights not in (None, "e4m3", "e4m3_as_bf16"):
-            raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16'")
+        if weights not in (None, "e4m3", "e4m3_as_bf16") + LS.Q4_WEIGHTS:
+            raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16', 'mxfp4' or 'mxfp4_as_bf16'")
+        q4 = weights in LS.Q4_WEIGHTS
+        if q4 and max_rows not in (None, 64):
+            raise ValueError(f"weights={weights!r} serves windows of at most 64 rows (kernels G1q4 / G1sq4 have no wide form): max_rows is None or 64, got {max_rows!r}")
         if max_rows is not None and weights is None:
             raise ValueError(f"max_rows={max_rows!r} goes with weights='e4m3' / 'e4m3_as_bf16' (without it the packed copy serves the row counts of its G1_CFG)")
         if max_rows not in (None, 64, 128, 256):
@@ -671,6 +682,15 @@ class ChameleonBackbone(nn.Module):
         g1_cfg, head_cfg = LS.default_shapes(self.lm_head.weight.dtype, self.__dict__.get("G1_CFG"), self.__dict__.get("HEAD_CFG"), self.args.hidden_size >= 8192,
                                              self.n_kv_heads != self.n_heads, compress, weights, max_rows, self.vocab_size)
         if weights is not None:          # (validated before anything is assigned: a refused call leaves the backbone as it was)
+            if q4:
+                H, Hkv, D, hid, inter = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size
+                dims = dict(qkv=((H + 2 * Hkv) * D, hid), o=(hid, H * D), gate_up=(2 * inter, hid), down=(hid, inter))
+                for name, why in LS.q4_chunk_errors(g1_cfg, dims)[:1]:
+                    raise ValueError(f"weights={weights!r}: " + (
+                        f"the MXFP4 stream travels in whole ring trips -- K and the chunk must be multiples of {LS.Q4_GRANULE}" if why == "granule" else
+                        f"kernel G1q4 stages the whole activation chunk in LDS -- every G1_CFG chunk must be <= {LS.CHUNK_CAP_32ROW} columns" if why == "chunk" else
+                        f"windows of 33..64 rows need chunks of <= {LS.CHUNK_CAP_64ROW} columns, or a step-major packing whose halved chunk is a multiple of {LS.Q4_GRANULE}")
+                        + f"; G1_CFG[{name!r}] = {g1_cfg[name]} with K = {dims[name][1]}")
             if any(c[0] > LS.CHUNK_CAP_32ROW for c in g1_cfg.values()):
                 raise ValueError(f"weights={weights!r}: kernel G1q stages the whole activation chunk in LDS -- every G1_CFG chunk must be <= {LS.CHUNK_CAP_32ROW} columns "
                                  f"(windows of 33..64 rows: <= {LS.CHUNK_CAP_64ROW}, or a step-major packing that a halved chunk reads, see _q8_chunk); got {g1_cfg}")
@@ -722,14 +742,15 @@ class ChameleonBackbone(nn.Module):
             st = self.compress_stats
             st["matrices"] += 1
             st["bytes_raw"] += w.numel() * w.element_size()
-            z = ops.pack_weight_q8(w, kc, sm, gateup=gateup)
-            st["q8_matrices"] = st.get("q8_matrices", 0) + 1
+            z = ops.pack_weight_q4(w, kc, sm, gateup=gateup) if q4 else ops.pack_weight_q8(w, kc, sm, gateup=gateup)
+            tag = "q4" if q4 else "q8"
+            st[tag + "_matrices"] = st.get(tag + "_matrices", 0) + 1
             st["rel_rms_error"] = max(st.get("rel_rms_error", 0.0), z.stats["rel_rms_error"])
-            if weights == "e4m3_as_bf16":
+            if weights.endswith("_as_bf16"):
                 st["bytes_packed"] += w.numel() * w.element_size()
                 return ops.pack_weight(z.dequant(), kc, sm)
             st["bytes_packed"] += z.nbytes()
-            st["q8_bytes_packed"] = st.get("q8_bytes_packed", 0) + z.nbytes()
+            st[tag + "_bytes_packed"] = st.get(tag + "_bytes_packed", 0) + z.nbytes()
             return z
         pack_head = pack
         if weights is not None:
@@ -860,7 +881,7 @@ class ChameleonBackbone(nn.Module):
                                                                                                                    getattr(self, "weights", None) is not None)      # (the bf16 twin takes the 8-bit route)
         # o / down with F1r as their tail (one launch each; the reducing kernel wants whole 512-column slices per workgroup pair: 8 waves)
         red = getattr(self, "reduce_fused", _REDUCE_FUSED_DEFAULT) and not self._pf_on
-        raw = lambda name: not isinstance(self._packed[0][name], (ops.PackedZ, ops.PackedQ8)) and getattr(self, "weights", None) is None        # (the reducing kernel streams the uncompressed packing)
+        raw = lambda name: not isinstance(self._packed[0][name], (ops.PackedZ, ops.PackedQ8, ops.PackedQ4)) and getattr(self, "weights", None) is None        # (the reducing kernel streams the uncompressed packing)
         h_dev = self.lm_head.weight.device
         red_o = red and raw("o") and ops.skinny_gemm_reduce_ok(T, hid, H * D, cfg["o"][0], 8, h_dev)
         red_d = red and raw("down") and ops.skinny_gemm_reduce_ok(T, hid, inter, cfg["down"][0], 8, h_dev)
@@ -947,6 +968,8 @@ class ChameleonBackbone(nn.Module):
         T_ = tokens.shape[0] * tokens.shape[1]
         no = LS.serves_rows(self, T_, tokens.shape[1])
         if no is not None and no[0] == "max_rows":          # (an 8-bit copy packed for fewer rows: there is no 16-bit copy to fall back on)
+            if getattr(self, "weights", None) in LS.Q4_WEIGHTS:
+                raise ValueError(f"weights={self.weights!r} serves draft windows of at most 64 rows (kernels G1q4 / G1sq4 have no wide form); got {T_} rows")
             if no[1] > 64:
                 raise ValueError(f"weights='e4m3' serves draft windows of at most {no[1]} rows (max_rows={no[1]}); got {T_} rows")
             raise ValueError(f"weights='e4m3' serves draft windows of at most 64 rows (one prompt per forward); got {T_} rows")

@@ -1124,6 +1124,7 @@ __device__ __forceinline__ g1z_pair g1z_load(__amdgpu_buffer_rsrc_t wr, unsigned
 
 #include "sjd_gemm_wide.h"          // (kernel G1w: behind the declarations of the 12-bit decode it shares with G1z)
 #include "sjd_gemm_q8.h"            // (kernels G1q / G1sq: the 8-bit e4m3 stream, SJD_G1_W8_E4M3)
+#include "sjd_gemm_q4.h"            // (kernels G1q4 / G1sq4: the MXFP4 stream, SJD_G1_W4_MXFP4)
 
 template <int SP, bool WIDE>
 __global__ __launch_bounds__(512) void g1z_gateup_silu(const unsigned short *__restrict__ x, const unsigned char *__restrict__ wz,
@@ -1544,6 +1545,9 @@ extern "C" int sjd_gateup_silu(const void *x, const void *w_packed, void *y, int
     if (row_norm && (!row_norm->sumsq || row_norm->slices < 1 || row_norm->hidden < 1)) return SJD_ERR_BAD_ARG;
     if (row_norm && row_norm->slices > 8) return SJD_ERR_UNSUPPORTED;      // the kernel sums one batch of eight 512-column slices
     if (M > 128 || (I % 64) != 0 || !(K == 512 || K == 1024 || K == 2048 || K == 4096) || (M > 32 && K == 512) || (M > 64 && K != 4096)) return SJD_ERR_UNSUPPORTED;
+    if ((dtype & SJD_G1_W8_E4M3) && (dtype & SJD_G1_W4_MXFP4)) return SJD_ERR_BAD_ARG;          // one weight stream per call
+    if (dtype & SJD_G1_W4_MXFP4)                                           // w_packed = ops.pack_weight_q4([Wg; Wu], K / 2, step_major, gateup=True): G1sq4
+        return dtype == (SJD_DTYPE_BF16 | SJD_G1_W4_MXFP4) ? g1sq4_launch(x, w_packed, y, M, I, K, step_major, row_norm, (hipStream_t)stream) : SJD_ERR_UNSUPPORTED;
     if (dtype & SJD_G1_W8_E4M3)                                            // w_packed = ops.pack_weight_q8([Wg; Wu], K / 2, step_major, gateup=True): G1sq
         return dtype == (SJD_DTYPE_BF16 | SJD_G1_W8_E4M3) ? g1sq_launch(x, w_packed, y, M, I, K, step_major, row_norm, (hipStream_t)stream) : SJD_ERR_UNSUPPORTED;
     if (dtype == SJD_DTYPE_BF16) return g1s_launch<SJD_DTYPE_BF16>(x, w_packed, y, M, I, K, step_major, row_norm, (hipStream_t)stream);
@@ -2035,6 +2039,10 @@ extern "C" int sjd_skinny_gemm_cols(const void *x, const void *w_packed, float *
     if (!x || !w_packed || !out || M < 1 || M > 256 || N < 32 || (N % 32) != 0 || (N_packed % 32) != 0 || (K % 16) != 0 || KC < 16 || (KC % 16) != 0)
         return SJD_ERR_BAD_ARG;
     if (waves < 1 || waves > 16) return SJD_ERR_BAD_ARG;
+    if ((dtype & SJD_G1_W8_E4M3) && (dtype & SJD_G1_W4_MXFP4)) return SJD_ERR_BAD_ARG;          // one weight stream per call
+    if (dtype & SJD_G1_W4_MXFP4)                                           // w_packed = ops.pack_weight_q4: G1q4 (csrc/sjd_gemm_q4.h)
+        return dtype == (SJD_DTYPE_BF16 | SJD_G1_W4_MXFP4) ? g1q4_launch(x, w_packed, out, M, N, K, KC, waves, step_major, N_packed / 32, tile0, (hipStream_t)stream)
+                                                           : SJD_ERR_UNSUPPORTED;
     if (dtype & SJD_G1_W8_E4M3)                                            // w_packed = ops.pack_weight_q8: G1q (csrc/sjd_gemm_q8.h)
         return dtype == (SJD_DTYPE_BF16 | SJD_G1_W8_E4M3) ? g1q_launch(x, w_packed, out, M, N, K, KC, waves, step_major, N_packed / 32, tile0, (hipStream_t)stream)
                                                           : SJD_ERR_UNSUPPORTED;
@@ -2047,6 +2055,10 @@ extern "C" int sjd_skinny_gemm(const void *x, const void *w_packed, float *out, 
 {
     if (!x || !w_packed || !out || M < 1 || M > 256 || (N % 32) != 0 || (K % 16) != 0 || KC < 16 || (KC % 16) != 0) return SJD_ERR_BAD_ARG;
     if (waves < 1 || waves > 16) return SJD_ERR_BAD_ARG;       // (the staged activation chunk must fit in LDS: min(KC, K) <= 2560 / 1280)
+    if ((dtype & SJD_G1_W8_E4M3) && (dtype & SJD_G1_W4_MXFP4)) return SJD_ERR_BAD_ARG;
+    if (dtype & SJD_G1_W4_MXFP4)
+        return dtype == (SJD_DTYPE_BF16 | SJD_G1_W4_MXFP4) ? g1q4_launch(x, w_packed, out, M, N, K, KC, waves, step_major, N / 32, 0, (hipStream_t)stream)
+                                                           : SJD_ERR_UNSUPPORTED;
     if (dtype & SJD_G1_W8_E4M3)
         return dtype == (SJD_DTYPE_BF16 | SJD_G1_W8_E4M3) ? g1q_launch(x, w_packed, out, M, N, K, KC, waves, step_major, N / 32, 0, (hipStream_t)stream)
                                                           : SJD_ERR_UNSUPPORTED;

@@ -1,0 +1,334 @@
+// sjd_gemm_q4.h -- G1q4 / G1sq4: the window projections streamed from OCP MXFP4 weights (e2m1 codes, one e8m0 scale per 32 weights along K):
+// 4.25 bits per weight.  Included by sjd_gemm.hip behind sjd_gemm_q8.h, whose structure (G1q / G1sq) these kernels keep.
+//
+// The format (sjd_amd.ops.pack_weight_q4): ONE buffer = the code records (N_packed * K / 2 bytes), then the scale bytes (N_packed * K / 32) behind them.
+// Weight w[n][k] is stored as code q (sign, 2 exponent bits, 1 mantissa bit: 0, 0.5, 1, 1.5, 2, 3, 4, 6) times scale[n][k / 32] = 2^(byte - 127),
+// so q * scale is exactly a bf16 value: the kernels rebuild the bf16 MFMA operand bit for bit (v_cvt_scalef32_pk_bf16_fp4, the scale in the
+// conversion: four conversions per eight weights, as many as the e4m3 decode, from half the bytes) and run the MFMA sequence of G1 / G1s, so the
+// planes / the 16-bit output are those of sjd_skinny_gemm / sjd_gateup_silu on pack_weight(q * scale), bit for bit.  All the loss is in the
+// host-side quantiser.
+//   K GRANULE g = 128: K and every chunk are multiples of 128 columns = eight k-steps = two records = four scale blocks.  A unit is then whole
+//       records AND whole scale dwords: the kernels have no tail path (no half record, no odd pair) -- the packer and the launchers refuse the rest.
+//   unit (k-chunk c, 32-column tile t), S = its k-steps: k-step s, lane l = 32 h + r, element j = q[32 t + r][k0 + 16 s + 8 h + j] (pack_weight's
+//       element order); the eight codes of (s, l) are FOUR bytes, byte i = code 2i in the low nibble, code 2i + 1 in the high nibble;
+//   RECORD R (1024 B) = k-steps 4R .. 4R + 3: 64 lanes x 16 B {the lane's four bytes of k-step 4R, of 4R + 1, of 4R + 2, of 4R + 3} -- one aligned
+//       16-byte load per lane; a chunk starts at byte k0 * N_packed / 2;
+//   tile-major: a unit is S * 256 contiguous bytes; step-major: the chunk holds record 0 of every tile, record 1 of every tile, ...
+//   scales, at byte N_packed * K / 2: per unit and TRIP q (eight k-steps) 128 bytes = 32 columns x 4 bytes, byte b of column r = the e8m0 scale of
+//       the column's block 4q + b of the chunk (k-steps 8q + 2b and 8q + 2b + 1, both lane halves) -- a lane takes a trip's scales with one aligned
+//       dword load; the trips of a unit are laid out like its records (a chunk starts at scale byte k0 * N_packed / 32; tile-major: S / 8
+//       consecutive 128-byte groups per unit; step-major: trip 0 of every tile, trip 1 of every tile, ...).
+// bf16; M <= 64 (G1q4) / M <= 32 (G1sq4): see the launchers.  No wide (65..256-row) form.
+#pragma once
+
+#define G1Q4_DEPTH 16          // k-steps a wave keeps in flight: a ring of four records, the 4 KiB per wave that G1q's ring of eight k-steps holds
+
+// the MFMA B operand (eight bf16) of one k-step from its four code bytes and the block's scale
+__device__ __forceinline__ u32x4 g1q4_operand(unsigned c, float sc)
+{
+    u32x4 d;
+    d.x = __builtin_bit_cast(unsigned, (g1q_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 0));
+    d.y = __builtin_bit_cast(unsigned, (g1q_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 1));
+    d.z = __builtin_bit_cast(unsigned, (g1q_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 2));
+    d.w = __builtin_bit_cast(unsigned, (g1q_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 3));
+    return d;
+}
+
+// the float 2^(byte - 127) of scale byte B (0..3) of a trip's dword: the e8m0 byte IS the float's exponent field
+template <int B>
+__device__ __forceinline__ float g1q4_scale(unsigned sd)
+{
+    return __builtin_bit_cast(float, (B == 0 ? sd << 23 : B == 1 ? sd << 15 : B == 2 ? sd << 7 : sd >> 1) & 0x7f800000u);
+}
+
+// one HALF TRIP: the eight k-steps of two ring records against the scale dword `sd`; a_read(a, u) fetches the A fragments of the trip's k-step u
+// (the next one is read ahead of the current MFMA); the caller refills the two records and the dword behind it
+template <int MT, typename AR>
+__device__ __forceinline__ void g1q4_half_trip(f32x16 (&acc)[MT], const u32x4 &rec0, const u32x4 &rec1, unsigned sd, AR a_read)
+{
+    constexpr int DT = SJD_DTYPE_BF16;
+    u32x4 a[2][MT];
+    a_read(a[0], 0);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        if (u + 1 < 8) a_read(a[(u + 1) & 1], u + 1);
+        const u32x4 &rec = u < 4 ? rec0 : rec1;
+        const unsigned c = (u & 3) == 0 ? rec.x : (u & 3) == 1 ? rec.y : (u & 3) == 2 ? rec.z : rec.w;
+        const float sc = (u >> 1) == 0 ? g1q4_scale<0>(sd) : (u >> 1) == 1 ? g1q4_scale<1>(sd) : (u >> 1) == 2 ? g1q4_scale<2>(sd) : g1q4_scale<3>(sd);
+        const u32x4 b = g1q4_operand(c, sc);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[mt] = G1Mfma<DT>::mma(a[u & 1][mt], b, acc[mt]);
+    }
+}
+
+// G1q4: g1q_skinny_gemm's structure (whole activation chunk in LDS, one buffer descriptor per unit -- loads past its end move nothing --, a register
+// ring refilled unconditionally behind its consumer, non-temporal loads) over the 4-bit stream.  The record's byte offset rides in the per-lane
+// offset of the load, the part of the address the descriptor's range check covers.  A unit is whole records and whole scale dwords
+// (steps % 8 == 0): the half trips past a unit's end are skipped by uniform branches, there is nothing else at the end of a unit.
+template <int MT, int MAXT>
+__global__ __launch_bounds__(MAXT) void g1q4_skinny_gemm(const unsigned short *__restrict__ x, const unsigned char *__restrict__ wq,
+                                                         const unsigned char *__restrict__ scales, float *__restrict__ out, int M, int N, int K, int KC,
+                                                         int n_tiles, int rec_stride, int tile0, int n_waves)
+{
+    constexpr int D = MAXT <= 512 ? G1Q4_DEPTH : 8;
+    constexpr int DR = D / 4;                                     // ring records
+    constexpr int HT = D / 8;                                     // half trips per ring trip
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u32x4 *xl = reinterpret_cast<u32x4 *>(smem);
+    const int chunk = blockIdx.y;
+    const int k0 = chunk * KC;
+    const int steps = min(KC, K - k0) / 16;                       // a multiple of eight (the launcher has checked K and KC)
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int t_out = blockIdx.x * n_waves + w;
+    const bool has_tile = t_out < N / 32;
+    const int t = has_tile ? tile0 + t_out : 0;
+    const unsigned char *cb = wq + (size_t)k0 * ((size_t)n_tiles * 16);
+    const unsigned char *sb = scales + (size_t)k0 * (size_t)n_tiles;
+    const unsigned rsb = (unsigned)rec_stride * 1024u, ssb = (unsigned)rec_stride * 128u;      // bytes from a record / a trip's scales to the next
+    const unsigned char *first = cb + (rec_stride == 1 ? (size_t)t * steps * 256 : (size_t)t * 1024);
+    const unsigned char *sfirst = sb + (rec_stride == 1 ? (size_t)t * steps * 16 : (size_t)t * 128);
+    const __amdgpu_buffer_rsrc_t wr = g1z_unit_rsrc(first, has_tile ? (unsigned)(steps / 4 - 1) * rsb + 1024u : 0u);
+    const __amdgpu_buffer_rsrc_t sr = g1z_unit_rsrc(sfirst, has_tile ? (unsigned)(steps / 8 - 1) * ssb + 128u : 0u);
+    auto w_load = [&](int r) -> u32x4 { return __builtin_amdgcn_raw_buffer_load_b128(wr, (unsigned)lane * 16u + (unsigned)r * rsb, 0u, G1Z_AUX); };
+    auto s_load = [&](int q) -> unsigned { return __builtin_amdgcn_raw_buffer_load_b32(sr, (unsigned)(lane & 31) * 4u + (unsigned)q * ssb, 0u, G1Z_AUX); };
+    u32x4 ring[DR];
+    unsigned scr[HT];
+    const int ppr = 2 * steps;
+    const int nth = n_waves * 64;
+    constexpr int STAGE = MAXT <= 512 ? 2 * G1_STAGE : G1_STAGE;
+    const int dm = nth / ppr, dj = nth - dm * ppr;
+    int pm = threadIdx.x / ppr, pj = threadIdx.x - pm * ppr;
+    auto advance = [&](int &m, int &j) { m += dm; j += dj; if (j >= ppr) { j -= ppr; ++m; } };
+    auto x_load = [&](int m, int j) -> u32x4 {
+        return (m < M) ? *reinterpret_cast<const u32x4 *>(x + (size_t)m * K + k0 + 8 * j) : u32x4{0u, 0u, 0u, 0u};
+    };
+    auto x_store = [&](int m, int j, u32x4 val) {
+        const int s = j >> 1;
+        if (m < 32 * MT) xl[((m >> 5) * steps + s) * 64 + g1_slot(j & 1, m & 31, s)] = val;
+    };
+    {   // first activation batch, the first D k-steps and their scales right behind it (all unconditional)
+        u32x4 val[STAGE];
+        int m = pm, j = pj;
+#pragma unroll
+        for (int i = 0; i < STAGE; ++i) { val[i] = x_load(m, j); advance(m, j); }
+#pragma unroll
+        for (int h = 0; h < HT; ++h) {          // (the order the loop refills them in)
+            ring[2 * h] = w_load(2 * h);
+            ring[2 * h + 1] = w_load(2 * h + 1);
+            scr[h] = s_load(h);
+        }
+        m = pm; j = pj;
+#pragma unroll
+        for (int i = 0; i < STAGE; ++i) { x_store(m, j, val[i]); advance(m, j); }
+        pm = m; pj = j;
+    }
+    while (pm < 32 * MT) {
+        u32x4 val[G1_STAGE];
+        int m = pm, j = pj;
+#pragma unroll
+        for (int i = 0; i < G1_STAGE; ++i) { val[i] = x_load(m, j); advance(m, j); }
+        m = pm; j = pj;
+#pragma unroll
+        for (int i = 0; i < G1_STAGE; ++i) { x_store(m, j, val[i]); advance(m, j); }
+        pm = m; pj = j;
+    }
+    __syncthreads();
+    if (!has_tile) return;
+    f32x16 acc[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[mt][r] = 0.0f;
+    const int xs = steps * 64;
+    // ring trips of D k-steps: a consumed record is refilled with the one D k-steps further on, the scale dword of a half trip with the one D k-steps
+    // further on, both unconditionally (past the unit's end: an instruction, no traffic)
+    for (int s0 = 0; s0 < steps; s0 += D) {
+#pragma unroll
+        for (int h = 0; h < HT; ++h) {
+            const int sh = s0 + 8 * h;
+            if (sh < steps)          // (uniform: the last trip of a unit of an odd number of half trips)
+                g1q4_half_trip<MT>(acc, ring[2 * h], ring[2 * h + 1], scr[h], [&](u32x4 (&a)[MT], int u) {
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) a[mt] = xl[mt * xs + (sh + u) * 64 + g1_slot(lane >> 5, lane & 31, u)];
+                });
+            ring[2 * h] = w_load(sh / 4 + DR);          // (outside the branch: every path through the loop issues the same loads, so its waits count exactly)
+            ring[2 * h + 1] = w_load(sh / 4 + 1 + DR);
+            scr[h] = s_load(sh / 8 + HT);
+        }
+    }
+    float *o = out + ((size_t)chunk * (32 * MT)) * N + (size_t)t_out * 32 + (lane & 31);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            o[(size_t)m * N] = acc[mt][r];
+        }
+}
+
+// G1sq4: g1q_gateup_silu over the 4-bit stream -- eight waves = two K halves x {gate, up} x two column tiles, two activation phases per K half,
+// the epilogue of sjd_mlp_epilogue.h on the planes in LDS.  A K half has 2 SP k-steps (K / 32: a multiple of eight for every K served).
+template <int SP>
+__global__ __launch_bounds__(512) void g1q4_gateup_silu(const unsigned short *__restrict__ x, const unsigned char *__restrict__ wq,
+                                                        const unsigned char *__restrict__ scales, unsigned short *__restrict__ y, int M, int I, int K,
+                                                        int rec_stride, const float *__restrict__ row_sumsq, int rs_slices, float rs_inv_hidden,
+                                                        float rs_eps)
+{
+    constexpr int DT = SJD_DTYPE_BF16;
+    constexpr int D = SP >= G1Q4_DEPTH ? G1Q4_DEPTH : 8;
+    constexpr int DR = D / 4, HT = D / 8;
+    static_assert(SP % D == 0 && D % 8 == 0, "a phase is whole trips; g1_slot(.., s) depends on s & 7");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u32x4 *xl = reinterpret_cast<u32x4 *>(smem);
+    __shared__ float rsc[32];
+    constexpr int PPS = 2 * SP;
+    constexpr int NPT = (32 * 2 * PPS) / 512;
+    static_assert(NPT >= 1, "at least one piece per thread");
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int kh = w >> 2, q = w & 3;
+    const int n_gate = I / 32, n_tiles = 2 * n_gate;
+    const int t_act = 2 * blockIdx.x + (q & 1);
+    const int t = (q < 2 ? 0 : n_gate) + t_act;
+    constexpr int recs = SP / 2, trips = SP / 4;                 // records / scale dwords of a K half (2 SP k-steps)
+    const unsigned char *cb = wq + (size_t)kh * (K / 2) * ((size_t)n_tiles * 16);
+    const unsigned char *sb = scales + (size_t)kh * (K / 2) * (size_t)n_tiles;
+    const unsigned rsb = (unsigned)rec_stride * 1024u, ssb = (unsigned)rec_stride * 128u;
+    const unsigned char *first = cb + (rec_stride == 1 ? (size_t)t * recs * 1024 : (size_t)t * 1024);
+    const unsigned char *sfirst = sb + (rec_stride == 1 ? (size_t)t * trips * 128 : (size_t)t * 128);
+    const __amdgpu_buffer_rsrc_t wr = g1z_unit_rsrc(first, (unsigned)(recs - 1) * rsb + 1024u);
+    const __amdgpu_buffer_rsrc_t sr = g1z_unit_rsrc(sfirst, (unsigned)(trips - 1) * ssb + 128u);
+    auto w_load = [&](int r) -> u32x4 { return __builtin_amdgcn_raw_buffer_load_b128(wr, (unsigned)lane * 16u + (unsigned)r * rsb, 0u, G1Z_AUX); };
+    auto s_load = [&](int qq) -> unsigned { return __builtin_amdgcn_raw_buffer_load_b32(sr, (unsigned)(lane & 31) * 4u + (unsigned)qq * ssb, 0u, G1Z_AUX); };
+    auto x_load = [&](int ph, int i) -> u32x4 {
+        const int v = i * 512 + threadIdx.x;
+        const int m = v / (2 * PPS), hh = (v / PPS) & 1, j = v % PPS;
+        return (m < M) ? *reinterpret_cast<const u32x4 *>(x + (size_t)m * K + hh * (K / 2) + ph * (K / 4) + 8 * j) : u32x4{0u, 0u, 0u, 0u};
+    };
+    auto x_store = [&](int i, u32x4 val) {
+        const int v = i * 512 + threadIdx.x;
+        const int m = v / (2 * PPS), hh = (v / PPS) & 1, j = v % PPS;
+        xl[(hh * SP + (j >> 1)) * 64 + g1_slot(j & 1, m, j >> 1)] = val;
+    };
+    u32x4 ring[DR];
+    unsigned scr[HT];
+    u32x4 val[NPT];
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) val[i] = x_load(0, i);
+    float ssv[8];
+    {
+        const float *ssp = row_sumsq ? row_sumsq : reinterpret_cast<const float *>(x);
+#pragma unroll
+        for (int qq = 0; qq < 8; ++qq) ssv[qq] = ssp[(size_t)(row_sumsq ? min(qq, rs_slices - 1) : 0) * 32 + (threadIdx.x & 31)];
+    }
+#pragma unroll
+    for (int h = 0; h < HT; ++h) {
+        ring[2 * h] = w_load(2 * h);
+        ring[2 * h + 1] = w_load(2 * h + 1);
+        scr[h] = s_load(h);
+    }
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) x_store(i, val[i]);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) val[i] = x_load(1, i);
+    if (threadIdx.x < 32) {
+        float tsum = 0.f;
+#pragma unroll
+        for (int qq = 0; qq < 8; ++qq) tsum += (qq < rs_slices) ? ssv[qq] : 0.f;
+        rsc[threadIdx.x] = row_sumsq ? rsqrtf(__builtin_fmaf(tsum, rs_inv_hidden, rs_eps)) : 1.0f;
+    }
+    f32x16 acc[1];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[0][r] = 0.0f;
+    const u32x4 *xa = xl + (size_t)kh * SP * 64;
+    // one ring trip: k-steps s0 .. s0 + D - 1 of the K half, staged as LDS records l0 .. of the current phase; every consumed record and scale
+    // dword is refilled with the one D k-steps further on (unconditional; past the unit's end: no traffic)
+    auto trip = [&](int l0, int s0) {
+#pragma unroll
+        for (int h = 0; h < HT; ++h) {
+            const int sh = s0 + 8 * h, lh = l0 + 8 * h;
+            g1q4_half_trip<1>(acc, ring[2 * h], ring[2 * h + 1], scr[h],
+                [&](u32x4 (&a)[1], int u) { a[0] = xa[(lh + u) * 64 + g1_slot(lane >> 5, lane & 31, u)]; });
+            ring[2 * h] = w_load(sh / 4 + DR);
+            ring[2 * h + 1] = w_load(sh / 4 + 1 + DR);
+            scr[h] = s_load(sh / 8 + HT);
+        }
+    };
+    for (int g = 0; g < SP / D; ++g) trip(g * D, g * D);                      // ---- phase 0
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) x_store(i, val[i]);
+    __syncthreads();
+    for (int g = 0; g < SP / D; ++g) trip(g * D, SP + g * D);                 // ---- phase 1
+    __syncthreads();
+    constexpr int RP = 36;
+    float *red = reinterpret_cast<float *>(smem);
+    {
+        float *mine = red + (size_t)(kh * 4 + q) * 32 * RP + (lane & 31);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mine[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * RP] = acc[0][r];
+    }
+    __syncthreads();
+    {
+        const int a = threadIdx.x >> 8, m = (threadIdx.x >> 3) & 31, c4 = (threadIdx.x & 7) * 4;
+        auto plane = [&](int kh_, int q_) { return *reinterpret_cast<const float4 *>(red + ((size_t)(kh_ * 4 + q_) * 32 + m) * RP + c4); };
+        const float4 g0 = plane(0, a), g1 = plane(1, a), u0 = plane(0, 2 + a), u1 = plane(1, 2 + a);
+        const float gs[4] = {g0.x, g0.y, g0.z, g0.w}, gt[4] = {g1.x, g1.y, g1.z, g1.w};
+        const float us_[4] = {u0.x, u0.y, u0.z, u0.w}, ut[4] = {u1.x, u1.y, u1.z, u1.w};
+        const float rr = rsc[m];
+        unsigned short o16[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float gsum = 0.f, usum = 0.f;                          // F3: planes summed in chunk order, starting from zero
+            gsum += gs[j]; gsum += gt[j];
+            usum += us_[j]; usum += ut[j];
+            o16[j] = sjd_silu_mul_elem<DT>(gsum, usum, rr);
+        }
+        if (m < M) {
+            uint2 pk{(unsigned)o16[0] | ((unsigned)o16[1] << 16), (unsigned)o16[2] | ((unsigned)o16[3] << 16)};
+            *reinterpret_cast<uint2 *>(y + (size_t)m * I + 32 * (2 * blockIdx.x + a) + c4) = pk;
+        }
+    }
+}
+
+// SJD_G1_W4_MXFP4 on sjd_skinny_gemm / sjd_skinny_gemm_cols (which have checked the common arguments): M <= 64, K and KC multiples of 128, the whole
+// activation chunk in LDS -- min(KC, K) <= 2560 up to 32 rows, <= 1280 at 33..64.  The scales sit behind the N_packed * K / 2 code bytes.
+static int g1q4_launch(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int waves, int step_major, int n_tiles, int tile0,
+                       hipStream_t s)
+{
+    if (N < 32) return SJD_ERR_BAD_ARG;
+    const int n_out = N / 32, n_chunks = (K + KC - 1) / KC;
+    if (tile0 < 0 || tile0 + n_out > n_tiles) return SJD_ERR_BAD_ARG;
+    if (M > 64 || (K % 128) != 0 || (KC % 128) != 0) return SJD_ERR_UNSUPPORTED;       // (no wide form; whole records and scale dwords only)
+    const int MT = M <= 32 ? 1 : 2;
+    const size_t lds = (size_t)MT * ((KC < K ? KC : K) / 16) * 1024;
+    if (lds > 160 * 1024) return SJD_ERR_UNSUPPORTED;
+    const unsigned char *scales = static_cast<const unsigned char *>(wq) + (size_t)n_tiles * 16 * K;
+    const dim3 grid((n_out + waves - 1) / waves, n_chunks), block(waves * 64);
+    const int rs = step_major ? n_tiles : 1;
+#define SJD_G1Q4_LAUNCH(MT_, MAXT_) return g1_launch_kernel(g1q4_skinny_gemm<MT_, MAXT_>, grid, block, lds, s, x, wq, scales, out, M, N, K, KC, n_tiles, rs, tile0, waves)
+    if (MT == 1) { if (waves <= 8) SJD_G1Q4_LAUNCH(1, 512); else SJD_G1Q4_LAUNCH(1, 1024); }
+    else { if (waves <= 8) SJD_G1Q4_LAUNCH(2, 512); else SJD_G1Q4_LAUNCH(2, 1024); }
+#undef SJD_G1Q4_LAUNCH
+}
+
+// SJD_G1_W4_MXFP4 on sjd_gateup_silu (which has checked the common arguments: K in {512, 1024, 2048, 4096}, so a K half is a multiple of 128): M <= 32;
+// the scales sit behind the I * K code bytes.
+static int g1sq4_launch(const void *x, const void *wq, void *y, int M, int I, int K, int step_major, const sjd_row_norm *rn, hipStream_t s)
+{
+    if (M > 32) return SJD_ERR_UNSUPPORTED;
+    const int SP = K / 64;
+    const dim3 grid(I / 64), block(512);
+    const size_t lds_x = (size_t)2 * SP * 1024, lds_red = (size_t)8 * 32 * 36 * sizeof(float);
+    const size_t lds = lds_x > lds_red ? lds_x : lds_red;
+    const int rec_stride = step_major ? 2 * (I / 32) : 1;
+    const unsigned char *scales = static_cast<const unsigned char *>(wq) + (size_t)I * K;
+    const float *ss = rn ? rn->sumsq : nullptr;
+    const int sl = rn ? rn->slices : 0;
+    const float ih = rn ? 1.0f / (float)rn->hidden : 0.f, eps = rn ? rn->eps : 0.f;
+#define SJD_G1SQ4_CASE(SP_) \
+    if (SP == SP_) return g1_launch_kernel(g1q4_gateup_silu<SP_>, grid, block, lds, s, x, wq, scales, y, M, I, K, rec_stride, ss, sl, ih, eps);
+    SJD_G1SQ4_CASE(8) SJD_G1SQ4_CASE(16) SJD_G1SQ4_CASE(32) SJD_G1SQ4_CASE(64)
+#undef SJD_G1SQ4_CASE
+    return SJD_ERR_UNSUPPORTED;
+}

@@ -94,6 +94,10 @@ class SJDBatchEngine:
             if why == "max_rows":
                 raise ValueError(f"the backbone was packed for windows of at most max_rows={detail} rows, but n_prompts * n_batch * max_window = "
                                  f"{rows}: call enable_fused(ops, gemm='sjd', weights='e4m3', max_rows={to}), or use fewer prompts per forward")
+        if getattr(backbone, "weights", None) in LS.Q4_WEIGHTS and rows > LS.Q4_MAX_ROWS:          # enable_fused(weights="mxfp4" / "mxfp4_as_bf16")
+            raise ValueError(f"a backbone packed with enable_fused(weights={backbone.weights!r}) serves at most {LS.Q4_MAX_ROWS} window rows per forward (kernels "
+                             f"G1q4 / G1sq4 have no wide form), but n_prompts * n_batch * max_window = {rows}: use fewer prompts per forward, or weights='e4m3' "
+                             "with max_rows=128 / 256")
         L.load()                                   # fail loudly if the HIP extension is missing
         if max_window > L.MAX_WINDOW:
             raise ValueError(f"max_window {max_window} > {L.MAX_WINDOW}")

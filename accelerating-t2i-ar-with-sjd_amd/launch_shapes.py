@@ -56,6 +56,13 @@ G1_CFG_EMU3_Q8 = dict(qkv=(512, 6, True), o=(512, 4, True), gate_up=(1024, 8, Tr
 # (chunk_for_rows: all step-major, K and the chunks multiples of 32 / 64), 65..256 on G1wq with these chunks and tile counts.  No sweep was run.
 G1_CFG_Q8_WIDE = dict(qkv=(2048, 4, True), o=(1024, 3, True), gate_up=(2048, 8, True), down=(1408, 4, True))
 G1_CFG_EMU3_Q8_WIDE = dict(qkv=(1024, 4, True), o=(512, 4, True), gate_up=(2048, 8, True), down=(1792, 4, True))
+# the MXFP4 stream (enable_fused(weights="mxfp4"), kernels G1q4 / G1sq4): UNTUNED -- copies of the 8-bit sets (every chunk a multiple of Q4_GRANULE, <= 2560, and one
+# that halves to <= 1280 for 33..64 rows); no launch-shape sweep was run for this format
+G1_CFG_Q4 = dict(G1_CFG_Q8)
+G1_CFG_EMU3_Q4 = dict(G1_CFG_EMU3_Q8)
+Q4_GRANULE = 128                  # K granule of the MXFP4 stream (ops.pack_weight_q4): K and every chunk are multiples of it
+Q4_WEIGHTS = ("mxfp4", "mxfp4_as_bf16")
+Q4_MAX_ROWS = 64                  # kernels G1q4 / G1sq4 have no wide form
 # 30B-class Chameleon (hidden 8192, intermediate 22016, GQA 64 / 8: q|k|v 10240 columns, gate|up 44032, down K 22016); chunks <= 2560 so that
 # the 32-row window stages its chunk in LDS.  The fastest shapes of `tools/swin30b_bench.py --sweep` at 32 rows on one MI355X
 # (profiles/g1_30b_sweep.jsonl), us per launch uncompressed / 12-bit: q|k|v 30.4 / 25.2, o 23.8 / 20.3, gate|up 120.5 / 98.9, down 62.9 / 50.4
@@ -102,6 +109,8 @@ def default_shapes(dtype, g1_given, head_given, wide_hidden, gqa, compress, weig
     """(G1_CFG, HEAD_CFG) ChameleonBackbone.enable_fused packs with; *_given: the caller's (it wins); wide_hidden: 30B class; gqa: Emu3; None: the class default stays"""
     z = compress and dtype == torch.bfloat16          # the 12-bit stream
     head = head_given or (HEAD_CFG_WIDE if vocab_size >= 131072 else None)
+    if weights in Q4_WEIGHTS:
+        return g1_given or dict(G1_CFG_EMU3_Q4 if gqa else G1_CFG_Q4), head
     if weights is not None:
         wide = (G1_CFG_EMU3_Q8_WIDE if gqa else G1_CFG_Q8_WIDE) if (max_rows or 64) > 64 else None
         return g1_given or dict(wide or (G1_CFG_EMU3_Q8 if gqa else G1_CFG_Q8)), head
@@ -114,6 +123,22 @@ def halved_chunk(kc, K, step_major):
     while kc > CHUNK_CAP_64ROW and step_major and K % 32 == 0 and kc % 64 == 0:
         kc //= 2
     return kc
+
+
+def q4_chunk_errors(cfg, dims):
+    """[(name, why)]: what keeps launch shapes `cfg` from the MXFP4 stream, dims = the projections' (N, K).  why: "granule" (K or the chunk no multiple of
+    Q4_GRANULE), "chunk" (above CHUNK_CAP_32ROW), "halved" (no chunk that 33..64 rows can stage: the halved chunk must itself be whole granules)"""
+    bad = []
+    for name, (KC, _, sm) in cfg.items():
+        K_ = dims[name][1]
+        kc = min(KC, K_)
+        if K_ % Q4_GRANULE or KC % Q4_GRANULE:
+            bad.append((name, "granule"))
+        elif kc > CHUNK_CAP_32ROW:
+            bad.append((name, "chunk"))
+        elif halved_chunk(kc, K_, sm) > CHUNK_CAP_64ROW or halved_chunk(kc, K_, sm) % Q4_GRANULE:
+            bad.append((name, "halved"))
+    return bad
 
 
 # Under enable_fused(weights=...) kernel G1q stages the whole activation chunk in LDS: <= CHUNK_CAP_32ROW columns up to 32 rows, <= CHUNK_CAP_64ROW at
@@ -167,6 +192,8 @@ def serves_rows(backbone, rows, window=1, head=False):
     limit = getattr(backbone, "max_rows", 64) if weights is not None else 64
     if weights == "e4m3" and limit < rows <= WINDOW_MAX_ROWS and window <= 32:
         return "max_rows", limit
+    if weights in Q4_WEIGHTS and rows > Q4_MAX_ROWS:          # (neither the 4-bit copy nor its twin was packed for more: there is no other copy to serve them)
+        return ("max_rows", Q4_MAX_ROWS) if rows <= WINDOW_MAX_ROWS and window <= 32 else ("prefill", None)
     if getattr(backbone, "_gemm", None) != "sjd" or rows > WINDOW_MAX_ROWS or (rows > 64 and window > 32) or (rows > Z_MAX_ROWS and not packed):
         return "prefill", None
     if rows <= Z_MAX_ROWS:

@@ -621,6 +621,149 @@ def pack_weight_q8(weight, KC, step_major=False, gateup=False):
     return PackedQ8(data, N, K, KC, step_major, stats)
 
 
+Q4_GRANULE = 128            # K granule of the MXFP4 stream: K and every chunk are whole ring trips of eight k-steps = two records = one scale dword per column
+Q4_MIN_SCALE_EXP = -125     # 0.5 (the smallest non-zero e2m1 magnitude) * 2^-125 = 2^-126: every dequantised value is a NORMAL bf16 number or zero
+Q4_MAX_SCALE_EXP = 125      # 6 (the largest) * 2^125 is a finite bf16 number; 4 * 2^126 would not be
+_E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+_E2M1_MIDPOINTS = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)       # between code i and i + 1; a tie goes to the even code
+
+
+def quantize_mxfp4(weight):
+    """[N, K] bf16 weight (K % 32 == 0) -> (codes uint8 [N, K / 2], scale_exp uint8 [N, K / 32]): OCP MXFP4.  One e8m0 scale per output column n (row of
+    `weight`) and block of 32 consecutive k: scale = 2^ceil(log2(amax_block / 6)) (1 for an all-zero block; never below 2^-125, so that 0.5 * scale, the
+    smallest non-zero dequantised value, is a normal bf16 number), stored as the byte log2(scale) + 127.  Codes are e2m1 -- sign << 3 | index into
+    {0, 0.5, 1, 1.5, 2, 3, 4, 6} -- of w / scale, round to nearest even; two per byte, even k in the low nibble.  amax <= 6 * scale by construction:
+    nothing saturates.  code * scale is exactly a bf16 number, and |w - code * scale| <= max(scale, |w|) / 4 for every element (the grid's step is
+    0.5 up to 2, 1 up to 4, 2 up to 6: half a step is <= scale / 4 below 2 and <= |w| / 4 above).  fp16 raises; so does a block whose scale would
+    exceed 2^125 (|w| above 6 * 2^125)."""
+    if weight.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_mxfp4: bf16 weights only (got {weight.dtype}): the dequantised values are bf16 numbers, fp16's exponent range does not hold them")
+    if weight.dim() != 2 or weight.shape[1] % 32:
+        raise ValueError("quantize_mxfp4: a [N, K] matrix with K a multiple of 32 (one scale per block of 32)")
+    w = weight.float()
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("quantize_mxfp4: the weight has non-finite values")
+    N, K = w.shape
+    blk = w.reshape(N, K // 32, 32)
+    amax = blk.abs().amax(dim=2)
+    m, e = torch.frexp(amax)                                      # amax = m * 2^e, m in [0.5, 1); 6 = 0.75 * 2^3
+    exp = (e - 3 + (m > 0.75).to(e.dtype)).clamp(min=Q4_MIN_SCALE_EXP)
+    exp = torch.where(amax > 0, exp, torch.zeros_like(exp))
+    if int(exp.max()) > Q4_MAX_SCALE_EXP:
+        raise ValueError(f"quantize_mxfp4: a block needs a scale above 2^{Q4_MAX_SCALE_EXP} (|w| > 6 * 2^{Q4_MAX_SCALE_EXP}): code * scale would not be a bf16 number")
+    inv = ((127 - exp).to(torch.int32) << 23).view(torch.float32)          # 1 / scale, built from its exponent bits: exact on every device (a pow() need not be)
+    v = blk.abs() * inv[:, :, None]                               # exact: a power of two
+    idx = torch.zeros_like(v, dtype=torch.uint8)
+    for i, mid in enumerate(_E2M1_MIDPOINTS):
+        idx += ((v >= mid) if i % 2 else (v > mid)).to(torch.uint8)
+    nib = (idx | (torch.signbit(blk).to(torch.uint8) << 3)).reshape(N, K)
+    codes = (nib[:, 0::2] | (nib[:, 1::2] << 4)).contiguous()
+    return codes, (exp + 127).to(torch.uint8)
+
+
+def dequantize_mxfp4(codes, scale_exp):
+    """(codes uint8 [N, K / 2], scale_exp uint8 [N, K / 32]) -> bf16 [N, K]: code * scale, exactly (a -0 code stays -0)"""
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    nib = torch.stack([codes & 0xF, codes >> 4], dim=2).reshape(N, K).long()
+    lut = torch.tensor(_E2M1_VALUES + tuple(-x for x in _E2M1_VALUES), dtype=torch.float32, device=codes.device)
+    scale = (scale_exp.to(torch.int32) << 23).view(torch.float32)          # the e8m0 byte is the float's exponent field: what the kernels do
+    return (lut[nib].reshape(N, K // 32, 32) * scale[:, :, None]).reshape(N, K).to(torch.bfloat16)
+
+
+class PackedQ4:
+    """A packed weight in the MXFP4 stream format of kernels G1q4 / G1sq4 (see pack_weight_q4): `data` uint8 [N * K / 2 + N * K / 32] = the code
+    records, four bits per weight, then the e8m0 scale bytes at byte offset N * K / 2.  LOSSY: the kernels multiply by dequant(), exactly."""
+
+    dtype = torch.bfloat16          # the activation type the kernels take (and the type of dequant())
+
+    def __init__(self, data, N, K, KC, step_major, stats=None):
+        self.data, self.N, self.K, self.KC, self.step_major = data, int(N), int(K), int(KC), bool(step_major)
+        self.stats = stats or {}
+
+    def numel(self):
+        return self.N * self.K
+
+    def nbytes(self):
+        return self.data.numel()
+
+    def reads_as(self, KC):
+        """can a launch with split-K chunk KC stream this buffer?  The chunk it was packed with -- or, step-major, any other multiple of the granule:
+        every chunk is then whole records and whole scale groups and the buffer is [record][tile], then [trip][tile], throughout, whatever the chunking"""
+        return KC == self.KC or (self.step_major and self.KC % Q4_GRANULE == 0 and KC % Q4_GRANULE == 0)
+
+    def _chunks(self):
+        return [(k0, min(self.KC, self.K - k0)) for k0 in range(0, self.K, self.KC)]
+
+    def codes(self):
+        """uint8 [N, K / 2]: the e2m1 codes, two per byte, read back from the packed records (the inverse of pack_weight_q4's permutation)"""
+        N, T = self.N, self.N // 32
+        cols, off = [], 0
+        for _, kc in self._chunks():
+            S = kc // 16
+            blk = self.data[off:off + N * kc // 2]
+            off += N * kc // 2
+            rec = blk.reshape(S // 4, T, 1024).permute(1, 0, 2) if self.step_major else blk.reshape(T, S // 4, 1024)
+            st = rec.reshape(T, S // 4, 64, 4, 4).permute(0, 1, 3, 2, 4).reshape(T, S, 2, 32, 4)         # [t, R, lane, i, b] -> [t, s, h, r, b]
+            cols.append(st.permute(0, 3, 1, 2, 4).reshape(N, kc // 2))
+        return torch.cat(cols, dim=1).contiguous()
+
+    def scale_exp(self):
+        """uint8 [N, K / 32]: the e8m0 scale bytes read back from behind the records"""
+        N, T = self.N, self.N // 32
+        cols, off = [], self.N * self.K // 2
+        for _, kc in self._chunks():
+            Q = kc // 128
+            blk = self.data[off:off + N * kc // 32]
+            off += N * kc // 32
+            grp = blk.reshape(Q, T, 128).permute(1, 0, 2) if self.step_major else blk.reshape(T, Q, 128)
+            cols.append(grp.reshape(T, Q, 32, 4).permute(0, 2, 1, 3).reshape(N, kc // 32))
+        return torch.cat(cols, dim=1).contiguous()
+
+    def dequant(self):
+        """bf16 [N, K]: the weight the kernels multiply by, read back from the packed buffer (exact: one mantissa bit times a power of two)"""
+        return dequantize_mxfp4(self.codes(), self.scale_exp())
+
+
+def pack_weight_q4(weight, KC, step_major=False, gateup=False):
+    """[N, K] bf16 weight -> PackedQ4: quantize_mxfp4(weight) in pack_weight(weight, KC, step_major)'s (k-chunk, 32-column tile, k-step, lane,
+    element) order at FOUR BITS per weight, then the e8m0 scale bytes at byte offset N * K / 2 of the same buffer -- what sjd_skinny_gemm /
+    sjd_skinny_gemm_cols / sjd_gateup_silu stream under SJD_G1_W4_MXFP4 (kernels G1q4 / G1sq4, csrc/sjd_gemm_q4.h).  N * K / 2 + N * K / 32 bytes.
+    K granule Q4_GRANULE = 128: K and KC must be multiples of 128 (ValueError otherwise) -- a unit is then whole records and whole scale dwords.
+    Byte layout: the k-steps of a unit (chunk c, tile t) travel in RECORDS of four -- record R (1024 B) = 64 lanes x 16 B {the lane's 4 bytes of
+    k-step 4R, .., of k-step 4R + 3}, lane l = 32 h + r, byte b = the codes of q[32 t + r][k0 + 16 s + 8 h + 2 b] (low nibble) and [.. + 2 b + 1] (high).
+    Tile-major: a unit is S * 256 contiguous bytes; step_major: a chunk holds record 0 of every tile, record 1 of every tile, ...  A chunk starts at
+    byte k0 * N / 2.  Scales: per unit and trip q of eight k-steps 128 bytes = 32 columns x 4 bytes (blocks 4q .. 4q + 3 of the chunk), the trips laid
+    out like the records; a chunk's scales start at scale byte k0 * N / 32.
+    gateup=True: `weight` is [Wg; Wu] packed with KC = K / 2 for sjd_gateup_silu.
+    stats: rel_rms_error (RMS of w - dequant over RMS of w), scale_exp_min / scale_exp_max (log2 of the smallest / largest block scale)."""
+    if weight.dim() != 2 or weight.shape[1] % Q4_GRANULE or KC < Q4_GRANULE or KC % Q4_GRANULE:
+        raise ValueError(f"pack_weight_q4: K and KC must be multiples of {Q4_GRANULE} (whole records and scale dwords); got K = {tuple(weight.shape)[-1]}, KC = {KC}")
+    codes, se = quantize_mxfp4(weight)
+    N, K = weight.shape
+    assert N % 32 == 0
+    T = N // 32
+    assert not gateup or (2 * KC == K and T % 2 == 0)
+    cparts, sparts = [], []
+    for k0 in range(0, K, KC):
+        kc = min(KC, K - k0)
+        S, Q = kc // 16, kc // 128
+        b = codes[:, k0 // 2:(k0 + kc) // 2].reshape(T, 32, S, 2, 4).permute(0, 2, 3, 1, 4).reshape(T, S // 4, 4, 64, 4)      # [t, R, i, lane = 32 h + r, b]
+        rec = b.permute(0, 1, 3, 2, 4).reshape(T, S // 4, 1024)
+        grp = se[:, k0 // 32:(k0 + kc) // 32].reshape(T, 32, Q, 4).permute(0, 2, 1, 3).reshape(T, Q, 128)
+        if step_major:
+            rec, grp = rec.permute(1, 0, 2), grp.permute(1, 0, 2)
+        cparts.append(rec.reshape(-1))
+        sparts.append(grp.reshape(-1))
+    data = torch.cat(cparts + sparts).contiguous()
+    assert data.numel() == N * K // 2 + N * K // 32
+    wf = weight.float()
+    deq = dequantize_mxfp4(codes, se).float()
+    rms = float(wf.pow(2).mean().sqrt())
+    stats = dict(rel_rms_error=(float((wf - deq).pow(2).mean().sqrt()) / rms) if rms > 0 else 0.0,
+                 scale_exp_min=int(se.min()) - 127, scale_exp_max=int(se.max()) - 127)
+    return PackedQ4(data, N, K, KC, step_major, stats)
+
+
 def _same_16bit_type(x, w_packed, what):
     """the kernels read the packed records as the activation's type: bf16 rows against fp16 records (or the reverse) would multiply garbage"""
     wd = getattr(w_packed, "dtype", None)
@@ -641,7 +784,7 @@ def skinny_gemm(x, w_packed, N, K, KC, waves=4, step_major=False):
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N * K
     _same_16bit_type(x, w_packed, "skinny_gemm")
-    if isinstance(w_packed, (PackedZ, PackedQ8)):
+    if isinstance(w_packed, (PackedZ, PackedQ8, PackedQ4)):
         return skinny_gemm_cols(x, w_packed, N, K, KC, 0, N, waves, step_major)
     nc = (K + KC - 1) // KC
     out = torch.empty(nc, _prows(M), N, dtype=torch.float32, device=x.device)
@@ -693,7 +836,7 @@ _PREFETCH_SINK = {}
 def weight_prefetch(w_packed, blocks=128, nbytes=None):
     """Read `w_packed` (a G1 packed weight) on the CURRENT stream and discard it: pulls the lines into the Infinity Cache ahead of
     the G1 launch that streams them (call it on a side stream forked from the forward, see ChameleonBackbone._prefetch)."""
-    if isinstance(w_packed, (PackedZ, PackedQ8)):
+    if isinstance(w_packed, (PackedZ, PackedQ8, PackedQ4)):
         w_packed = w_packed.data
     dev = w_packed.device
     sink = _PREFETCH_SINK.get(dev)
@@ -806,6 +949,11 @@ def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_m
         assert (w_packed.N, w_packed.step_major) == (N_packed, bool(step_major)) and w_packed.reads_as(KC)
         L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed.data), _ptr(out), M, n_cols, K, KC, waves, int(step_major),
                                              _dtype_code(x.dtype) | L.G1_W8_E4M3, N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols (e4m3 weights)")
+        return Partials(out, nc, n_cols)
+    if isinstance(w_packed, PackedQ4):          # G1q4: the block scales ride behind the records of the same buffer; at most 64 rows
+        assert (w_packed.N, w_packed.step_major) == (N_packed, bool(step_major)) and w_packed.reads_as(KC)
+        L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed.data), _ptr(out), M, n_cols, K, KC, waves, int(step_major),
+                                             _dtype_code(x.dtype) | L.G1_W4_MXFP4, N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols (mxfp4 weights)")
         return Partials(out, nc, n_cols)
     L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed), _ptr(out), M, n_cols, K, KC, waves, int(step_major), _dtype_code(x.dtype),
                                          N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols")
@@ -1111,6 +1259,12 @@ def gateup_silu(x, w_packed, inter, hidden, step_major=False, row_norm=None):
         assert (w_packed.N, w_packed.KC, w_packed.step_major) == (2 * inter, hidden // 2, bool(step_major))
         L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed.data), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype) | L.G1_W8_E4M3,
                                         _row_norm(row_norm), _stream()), "sjd_gateup_silu (e4m3 weights)")
+        return y
+    if isinstance(w_packed, PackedQ4):          # G1sq4
+        _same_16bit_type(x, w_packed, "gateup_silu")
+        assert (w_packed.N, w_packed.KC, w_packed.step_major) == (2 * inter, hidden // 2, bool(step_major))
+        L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed.data), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype) | L.G1_W4_MXFP4,
+                                        _row_norm(row_norm), _stream()), "sjd_gateup_silu (mxfp4 weights)")
         return y
     L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype),
                                     _row_norm(row_norm), _stream()), "sjd_gateup_silu")

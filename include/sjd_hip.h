@@ -84,6 +84,20 @@ extern "C" {
  *                         G1wq, the 8-bit form of G1w, csrc/sjd_gemm_wide.h) with `waves` = column tiles per workgroup in {2, 3, 4, 6, 8} (not 2 at
  *                         65..96 rows), K % 32 == 0 and KC % 32 == 0 (whole pairs, no half records), any KC; everything else, and every other entry
  *                         point given the bit, returns SJD_ERR_UNSUPPORTED before any launch.  SJD_VERSION did not move with it: a library without the bit returns SJD_ERR_UNSUPPORTED
+ *                         for it, which is the probe.
+ *   SJD_G1_W4_MXFP4       `w_packed` points at an OCP MXFP4 weight stream (sjd_amd.ops.pack_weight_q4; kernels G1q4 / G1sq4, csrc/sjd_gemm_q4.h): N_packed * K / 2
+ *                         bytes of e2m1 codes in the record order of the 16-bit packing at four bits per weight (two codes per byte, the even element in
+ *                         the low nibble) -- the k-steps of a (k-chunk, 32-column tile) unit in 1024-byte records of FOUR k-steps (64 lanes x {4 bytes of
+ *                         k-step 4R, .., 4 bytes of k-step 4R + 3}); a chunk starts at byte k0 * N_packed / 2 -- then the e8m0 scale bytes (one per output
+ *                         column and block of 32 consecutive k: scale = 2^(byte - 127)) at byte offset N_packed * K / 2, per unit and eight k-steps 128
+ *                         bytes = 32 columns x the four scales of those k-steps, laid out like the records (sjd_gateup_silu: codes I * K bytes,
+ *                         `w_packed` = [Wg; Wu] packed with KC = K / 2).  K granule 128: K and KC must be multiples of 128 (whole records and whole
+ *                         scale dwords: the kernels have no tail path).  The kernels rebuild the bf16 operand code * scale exactly, so the planes / the
+ *                         16-bit output are bit for bit what the same call writes for the 16-bit packing of the dequantised weight: the format's loss
+ *                         (coarser than e4m3's) is the host-side quantiser's alone.  Valid with SJD_DTYPE_BF16 only; M <= 64 with min(KC, K) <= 2560
+ *                         (M <= 32) / <= 1280 (sjd_gateup_silu: M <= 32, K in {512, 1024, 2048, 4096}); there is no form for more than 64 rows.
+ *                         Everything else, and every other entry point given the bit, returns SJD_ERR_UNSUPPORTED before any launch; both weight bits
+ *                         together return SJD_ERR_BAD_ARG.  SJD_VERSION did not move with it: a library without the bit returns SJD_ERR_UNSUPPORTED
  *                         for it, which is the probe. */
 #define SJD_DTYPE_MASK 0xff
 #define SJD_F1_POST_NORM 0x100
@@ -92,6 +106,7 @@ extern "C" {
 #define SJD_K1_HEAD_DIM_100 0x800
 #define SJD_F2_ONE_HEAD 0x1000
 #define SJD_G1_W8_E4M3 0x2000
+#define SJD_G1_W4_MXFP4 0x4000
 #define SJD_QKN_SHARDS_SHIFT 16
 #define SJD_QKN_SHARDS_MASK (0xff << SJD_QKN_SHARDS_SHIFT)
 #define SJD_QKN_SHARDS(mp) ((int)(mp) << SJD_QKN_SHARDS_SHIFT)

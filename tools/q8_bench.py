@@ -17,6 +17,9 @@ median and spread (min .. max over the rounds) per leg.
             weights, the timed iterations centred on the mean KV length by a warm-up of whole window iterations; ms per shared window forward, packed
             bytes per step, and us per launch of the four projections as each backbone runs them (its own 32 packed layers in turn, from a hipGraph).
 
+  --mxfp4   adds an MXFP4 leg ("q4": enable_fused(weights="mxfp4"), kernels G1q4 / G1sq4, launch shapes G1_CFG_Q4 / G1_CFG_EMU3_Q4) to --launch and --step:
+            the legs then alternate 12-bit / e4m3 / mxfp4 (per launch: bf16 first), and the record compares the mxfp4 leg with the e4m3 leg of the same run.
+
 One JSON document on stdout (and in --out)."""
 import argparse
 import copy
@@ -45,8 +48,9 @@ def spread(xs):
 
 def launch_legs(a, dev, lib):
     C = BB.ChameleonBackbone
-    arch = [("lumina7b", 32, dict(qkv=(12288, 4096), o=(4096, 4096), gate_up=(22016, 4096), down=(4096, 11008)), (C.G1_CFG, C.G1_CFG_Z, C.G1_CFG_Q8)),
-            ("emu3_8b", 64, dict(qkv=(6144, 4096), o=(4096, 4096), gate_up=(28672, 4096), down=(4096, 14336)), (C.G1_CFG_EMU3, C.G1_CFG_EMU3_Z, C.G1_CFG_EMU3_Q8))]
+    arch = [("lumina7b", 32, dict(qkv=(12288, 4096), o=(4096, 4096), gate_up=(22016, 4096), down=(4096, 11008)), (C.G1_CFG, C.G1_CFG_Z, C.G1_CFG_Q8, C.G1_CFG_Q4)),
+            ("emu3_8b", 64, dict(qkv=(6144, 4096), o=(4096, 4096), gate_up=(28672, 4096), down=(4096, 14336)), (C.G1_CFG_EMU3, C.G1_CFG_EMU3_Z, C.G1_CFG_EMU3_Q8, C.G1_CFG_EMU3_Q4))]
+    tags = ("bf16", "z12", "q8") + (("q4",) if a.mxfp4 else ())
     out = []
     for model, rows, shapes, cfgs in arch:
         for name, (N, K) in shapes.items():
@@ -55,7 +59,7 @@ def launch_legs(a, dev, lib):
             x = torch.randn(rows, K, device=dev).to(torch.bfloat16)
             ws = [(torch.randn(N, K, device=dev) / K ** 0.5).to(torch.bfloat16) for _ in range(a.copies)]
             legs = {}
-            for tag, cfg in zip(("bf16", "z12", "q8"), cfgs):
+            for tag, cfg in zip(tags, cfgs):
                 KC, waves, sm = cfg[name]
                 gu = name == "gate_up" and 2 * KC == K
                 if tag == "bf16":
@@ -64,10 +68,13 @@ def launch_legs(a, dev, lib):
                 elif tag == "z12":
                     pk = [ops.pack_weight_z(w, KC, sm, gateup=gu) for w in ws]
                     stored = pk[0].nbytes()
-                else:
+                elif tag == "q8":
                     pk = [ops.pack_weight_q8(w, KC, sm, gateup=gu) for w in ws]
                     stored = pk[0].nbytes()
-                fused = gu and ops.gateup_silu_ok(rows, N // 2, K, KC, tag == "z12", tag == "q8")
+                else:
+                    pk = [ops.pack_weight_q4(w, KC, sm, gateup=gu) for w in ws]
+                    stored = pk[0].nbytes()
+                fused = gu and ops.gateup_silu_ok(rows, N // 2, K, KC, tag == "z12", tag in ("q8", "q4"))
                 if fused:
                     run = lambda i, pk=pk, sm=sm: ops.gateup_silu(x, pk[i % a.copies], N // 2, K, sm)
                 elif name == "gate_up":
@@ -78,7 +85,7 @@ def launch_legs(a, dev, lib):
                                  us=[], keep=pk)
             del ws
             for _ in range(a.rounds):                     # alternating: bf16, 12-bit, 8-bit, and round again
-                for tag in ("bf16", "z12", "q8"):
+                for tag in tags:
                     legs[tag]["us"].append(timed_graph(legs[tag]["run"], a.launches, lib)[1] * 1e3)
             rec = dict(model=model, rows=rows, shape=name, N=N, K=K, algorithmic_bytes=N * K * 2)
             for tag, lg in legs.items():
@@ -88,6 +95,8 @@ def launch_legs(a, dev, lib):
                                 frac_of_8TBps_on_algorithmic_bytes=round(N * K * 2 / (s["median"] * 1e-6) / PEAK, 4))
             rec["q8_over_z12"] = round(rec["q8"]["us"]["median"] / rec["z12"]["us"]["median"], 4)
             rec["q8_over_bf16"] = round(rec["q8"]["us"]["median"] / rec["bf16"]["us"]["median"], 4)
+            if a.mxfp4:
+                rec["q4_over_q8"] = round(rec["q4"]["us"]["median"] / rec["q8"]["us"]["median"], 4)
             print(json.dumps(rec), flush=True)
             out.append(rec)
             del legs
@@ -101,12 +110,13 @@ def step_legs(a, dev):
     base = bench.parse(["--gpus", "1", "--steps", str(a.steps), "--warmup", str(a.warmup)])
     base.model, base.window, base.prompts_per_gpu, base.n_split = "lumina7b", 16, 1, 0
     legs = {}
-    for tag in ("z12", "q8"):
+    tags = ("z12", "q8") + (("q4",) if a.mxfp4 else ())
+    for tag in tags:
         b = copy.copy(base)
-        b.no_fused = tag == "q8"                          # (the q8 leg calls enable_fused itself, on the same synthetic weights)
+        b.no_fused = tag != "z12"                         # (the q8 / q4 legs call enable_fused themselves, on the same synthetic weights)
         model, margs, attn = bench.build_model(b, dev)
-        if tag == "q8":
-            model.enable_fused(ops, gemm="sjd", weights="e4m3")
+        if tag != "z12":
+            model.enable_fused(ops, gemm="sjd", weights="e4m3" if tag == "q8" else "mxfp4")
         w = bench.workload_of(b, margs, 0, dev)
         P, n_img = w["P"], w["n_img"]
         model.setup_cache(batch=2, s_max=((P + n_img + 2 * 16 + 64 + 31) // 32) * 32)
@@ -123,7 +133,7 @@ def step_legs(a, dev):
                          lead=int(P + n_img // 2 - w["tau_est"] * (a.steps / 2.0 + a.warmup)))
     sync = torch.cuda.synchronize
     for _ in range(a.rounds):
-        for tag in ("z12", "q8"):
+        for tag in tags:
             lg = legs[tag]
             w = lg["w"]
             _, st = lg["eng"].decode(w["prompt"], w["spec"], copy.deepcopy(w["grammar"]), w["cfg"], warmup_iters=a.warmup, timed_iters=a.steps,
@@ -132,7 +142,7 @@ def step_legs(a, dev):
             lg["kv"].append([st.kv_len_start, st.kv_len])
             lg["tok"].append(round(st.tokens / max(st.timed_nfe, 1), 3))
     rec = dict(workload="Lumina-mGPT-7B architecture 768x768 (synthetic weights), 1 prompt, draft window 16, CFG 3.0 (32 rows per forward), bf16, 16-bit KV cache",
-               steps=a.steps, warmup=a.warmup, rounds=a.rounds, order="alternating z12, q8 per round; one process, one device")
+               steps=a.steps, warmup=a.warmup, rounds=a.rounds, order="alternating " + ", ".join(tags) + " per round; one process, one device")
     for tag, lg in legs.items():
         m = lg["model"]
         rec[tag] = dict(weights=m.weights, G1_CFG={k: list(v) for k, v in m.G1_CFG.items()}, ms_per_step=spread(lg["ms"]), kv_len=lg["kv"], tokens_per_step=lg["tok"],
@@ -141,6 +151,11 @@ def step_legs(a, dev):
     rec["q8_minus_z12_ms"] = round(q["median"] - z["median"], 4)
     rec["largest_spread_between_rounds_ms"] = round(max(z["max"] - z["min"], q["max"] - q["min"]), 4)
     rec["gain_exceeds_spread"] = bool(z["median"] - q["median"] > rec["largest_spread_between_rounds_ms"])
+    if a.mxfp4:          # the 4-bit leg against the 8-bit leg of the SAME run: faster only if the difference exceeds the spread between this run's rounds
+        q4 = rec["q4"]["ms_per_step"]
+        rec["q4_minus_q8_ms"] = round(q4["median"] - q["median"], 4)
+        rec["largest_spread_between_rounds_ms"] = round(max(rec["largest_spread_between_rounds_ms"], q4["max"] - q4["min"]), 4)
+        rec["q4_faster_than_q8_beyond_spread"] = bool(q["median"] - q4["median"] > rec["largest_spread_between_rounds_ms"])
     print(json.dumps(rec), flush=True)
     return rec
 
@@ -234,6 +249,7 @@ def main():
     ap.add_argument("--launch", action="store_true")
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--batch", action="store_true")
+    ap.add_argument("--mxfp4", action="store_true", help="--launch / --step: add the MXFP4 leg (q4)")
     ap.add_argument("--prompts", default="2,4,8", help="--batch: prompts per forward, comma separated")
     ap.add_argument("--launches", type=int, default=48)
     ap.add_argument("--copies", type=int, default=8)
@@ -249,7 +265,7 @@ def main():
     if a.launch:
         doc["per_launch"] = launch_legs(a, dev, lib)
         doc["per_launch_method"] = (f"{a.launches} launches per hipGraph over {a.copies} weight sets, the graph replayed three times and the middle time taken; "
-                                    f"{a.rounds} rounds alternating bf16 / 12-bit / 8-bit; us per launch: median, min, max over the rounds")
+                                    f"{a.rounds} rounds alternating bf16 / 12-bit / 8-bit{' / mxfp4' if a.mxfp4 else ''}; us per launch: median, min, max over the rounds")
     if a.step:
         doc["per_step"] = step_legs(a, dev)
     if a.batch:
