@@ -79,6 +79,8 @@ template <> struct G1Mfma<SJD_DTYPE_F16> {
     { return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0); }
 };
 
+#include "sjd_gemm_parts.h"         // (the constants and launcher bodies the G1 family shares)
+
 #ifdef SJD_EXPERIMENTAL        // round-3 option (G1 with F1r as its tail)
 // ---- F1r inside the producer (round 3; VERDICT r2 "next #3", the experiment DESIGN.md 4.6 item 6 stopped short of).
 // Every workgroup of an o / down launch has written its fp32 partial tile with device-coherent stores.  The workgroups that share a
@@ -872,7 +874,7 @@ __global__ __launch_bounds__(512) void g1_gateup_silu(const unsigned short *__re
     // every thread finishes FOUR outputs: one (activation tile, row, four columns) each -- first version: the two gate waves of K half 0 did
     // all sixteen IEEE divisions per lane and 2-byte stores, 3.6 us.
     __syncthreads();                                              // the activation arena is free
-    constexpr int RP = 36;
+    constexpr int RP = G1S_RP;
     float *red = reinterpret_cast<float *>(smem);                 // [8 planes][32 rows][RP]
     {
         float *mine = red + (size_t)(kh * 4 + q) * 32 * RP + (lane & 31);
@@ -1027,7 +1029,7 @@ __global__ __launch_bounds__(512) void g1_gateup_silu_tall(const unsigned short 
     // ---- epilogue: the eight planes (tile q x K half) go through LDS (row-major, rows padded to 36 floats: conflict-free both ways), then
     // every thread finishes FOUR outputs per row tile: one (activation tile, row, four columns) each -- first version: the two gate waves
     // of K half 0 did all sixteen IEEE divisions per lane and 2-byte stores, 3.6 us.  (the last barrier of the loop freed the arena)
-    constexpr int RP = 36;
+    constexpr int RP = G1S_RP;
     float *red = reinterpret_cast<float *>(smem);                 // [8 planes][R rows][RP]
     {
         float *mine = red + (size_t)(kh * 4 + q) * R * RP + (lane & 31);
@@ -1252,7 +1254,7 @@ __global__ __launch_bounds__(512) void g1z_gateup_silu(const unsigned short *__r
     }
     SJD_TR(5);
     __syncthreads();
-    constexpr int RP = 36;
+    constexpr int RP = G1S_RP;
     float *red = reinterpret_cast<float *>(smem);
     {
         float *mine = red + (size_t)(kh * 4 + q) * 32 * RP + (lane & 31);
@@ -1429,7 +1431,7 @@ __global__ __launch_bounds__(512) void g1z_gateup_silu_tall(const unsigned short
     if constexpr (RAW_HERE) { if (z_raw) { SJD_G1SZ_PHASES(trip_raw) } else { SJD_G1SZ_PHASES(trip) } } else { SJD_G1SZ_PHASES(trip) }
 #undef SJD_G1SZ_PHASES
     SJD_TR(5);
-    constexpr int RP = 36;
+    constexpr int RP = G1S_RP;
     float *red = reinterpret_cast<float *>(smem);
     {
         float *mine = red + (size_t)(kh * 4 + q) * R * RP + (lane & 31);
@@ -1472,22 +1474,20 @@ static int g1sz_launch(const void *x, const void *wz, const void *exc, int exc_c
     const int MT = M <= 32 ? 1 : 2;
     const int SP = K / (64 * MT);                                  // one arena, 2 MT phases (double-buffered half phases measured slower: g1_gateup_silu)
     const dim3 grid(I / 64), block(512);
-    const size_t lds_x = (size_t)MT * 2 * SP * 1024, lds_red = (size_t)8 * 32 * MT * 36 * sizeof(float);
+    const size_t lds_x = (size_t)MT * 2 * SP * 1024, lds_red = g1s_epilogue_lds(MT);
     const size_t lds = lds_x > lds_red ? lds_x : lds_red;
     const int rec_stride = step_major ? 2 * (I / 32) : 1;
-    const float *ss = rn ? rn->sumsq : nullptr;
-    const int sl = rn ? rn->slices : 0;
-    const float ih = rn ? 1.0f / (float)rn->hidden : 0.f, eps = rn ? rn->eps : 0.f;
+    const g1s_norm_args n(rn);
 #define SJD_G1SZ_CASE(SP_, MT_) SJD_G1SZ_CASE_W(SP_, MT_, false) SJD_G1SZ_CASE_W(SP_, MT_, true)
 #define SJD_G1SZ_CASE_W(SP_, MT_, W_) \
     if (SP == SP_ && MT == MT_ && (exc_cap > 64) == W_) { \
-        const int rc = g1_launch_kernel(g1z_gateup_silu_tall<SP_, MT_, false, W_>, grid, block, lds, s, x, wz, exc, y, M, I, K, rec_stride | (exc_cap << 16), ss, sl, ih, eps); \
+        const int rc = g1_launch_kernel(g1z_gateup_silu_tall<SP_, MT_, false, W_>, grid, block, lds, s, x, wz, exc, y, M, I, K, rec_stride | (exc_cap << 16), n.ss, n.sl, n.ih, n.eps); \
         return rc != SJD_OK || g1sz_raw_inline(SP_, MT_) ? rc : g1_raw_gateup_launch(x, raw, y, M, I, K, rn, s); \
     }
 #define SJD_G1SZ_CASE32(SP_) SJD_G1SZ_CASE32_W(SP_, false) SJD_G1SZ_CASE32_W(SP_, true)
 #define SJD_G1SZ_CASE32_W(SP_, W_) \
     if (SP == SP_ && MT == 1 && (exc_cap > 64) == W_) \
-        return g1_launch_kernel(g1z_gateup_silu<SP_, W_>, grid, block, lds, s, x, wz, exc, y, M, I, K, rec_stride | (exc_cap << 16), ss, sl, ih, eps);
+        return g1_launch_kernel(g1z_gateup_silu<SP_, W_>, grid, block, lds, s, x, wz, exc, y, M, I, K, rec_stride | (exc_cap << 16), n.ss, n.sl, n.ih, n.eps);
     SJD_G1SZ_CASE32(8) SJD_G1SZ_CASE32(16) SJD_G1SZ_CASE32(32) SJD_G1SZ_CASE32(64)
 #undef SJD_G1SZ_CASE32
 #undef SJD_G1SZ_CASE32_W
@@ -1517,17 +1517,15 @@ static int g1s_launch(const void *x, const void *w_packed, void *y, int M, int I
     const bool db = MT >= 2 && K >= 2048;                          // double-buffered half-length phases: the fp16 / bf16 64-row kernel (see the kernel)
     const int SP = K / ((db ? 128 : 64) * MT);
     const dim3 grid(I / 64), block(512);
-    const size_t lds_x = (size_t)(db ? 2 : 1) * MT * 2 * SP * 1024, lds_red = (size_t)8 * 32 * MT * 36 * sizeof(float);
+    const size_t lds_x = (size_t)(db ? 2 : 1) * MT * 2 * SP * 1024, lds_red = g1s_epilogue_lds(MT);
     const size_t lds = lds_x > lds_red ? lds_x : lds_red;        // the epilogue's planes reuse the activation arena
     const int rec_stride = step_major ? 2 * (I / 32) : 1;
-    const float *ss = rn ? rn->sumsq : nullptr;
-    const int sl = rn ? rn->slices : 0;
-    const float ih = rn ? 1.0f / (float)rn->hidden : 0.f, eps = rn ? rn->eps : 0.f;
+    const g1s_norm_args n(rn);
 #define SJD_G1S_CASE(SP_, MT_, DB_) \
     if (SP == SP_ && MT == MT_ && db == DB_) \
-        return g1_launch_kernel(g1_gateup_silu_tall<DT, SP_, MT_, DB_>, grid, block, lds, s, x, w_packed, y, M, I, K, rec_stride, ss, sl, ih, eps);
+        return g1_launch_kernel(g1_gateup_silu_tall<DT, SP_, MT_, DB_>, grid, block, lds, s, x, w_packed, y, M, I, K, rec_stride, n.ss, n.sl, n.ih, n.eps);
 #define SJD_G1S_CASE32(SP_) \
-    if (SP == SP_ && MT == 1) return g1_launch_kernel(g1_gateup_silu<DT, SP_>, grid, block, lds, s, x, w_packed, y, M, I, K, rec_stride, ss, sl, ih, eps);
+    if (SP == SP_ && MT == 1) return g1_launch_kernel(g1_gateup_silu<DT, SP_>, grid, block, lds, s, x, w_packed, y, M, I, K, rec_stride, n.ss, n.sl, n.ih, n.eps);
     SJD_G1S_CASE32(8) SJD_G1S_CASE32(16) SJD_G1S_CASE32(32) SJD_G1S_CASE32(64)
 #undef SJD_G1S_CASE32
     SJD_G1S_CASE(8, 2, false) SJD_G1S_CASE(8, 2, true) SJD_G1S_CASE(16, 2, true) SJD_G1S_CASE(8, 4, true)

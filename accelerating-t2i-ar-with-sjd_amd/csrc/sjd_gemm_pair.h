@@ -105,7 +105,7 @@ __device__ __forceinline__ void g1zp_gateup(int bid, const unsigned short *__res
     __syncthreads();
     for (int g = 0; g < SP / TL; ++g) trip(g * TL, SP + g * TL);              // ---- phase 1
     __syncthreads();
-    constexpr int RP = 36;
+    constexpr int RP = G1S_RP;
     float *red = reinterpret_cast<float *>(smem);
     {
         float *mine = red + (size_t)(kh * 4 + q) * 32 * RP + (lane & 31);
@@ -302,8 +302,8 @@ extern "C" int sjd_mlp_pair_z(const void *x, const void *wz_gu, const void *exc_
     a.wz_gu = (const unsigned char *)wz_gu; a.exc_gu = (const u32x2 *)exc_gu;
     a.stride_cap_gu = (step_major_gu ? 2 * (I / 32) : 1) | (exc_cap_gu << 16);
     a.y = (unsigned short *)y;
-    a.row_sumsq = row_norm ? row_norm->sumsq : nullptr; a.rs_slices = row_norm ? row_norm->slices : 0;
-    a.rs_inv_hidden = row_norm ? 1.0f / (float)row_norm->hidden : 0.f; a.rs_eps = row_norm ? row_norm->eps : 0.f;
+    const g1s_norm_args n(row_norm);
+    a.row_sumsq = n.ss; a.rs_slices = n.sl; a.rs_inv_hidden = n.ih; a.rs_eps = n.eps;
     a.wz_dn = (const unsigned char *)wz_dn; a.exc_dn = (const u32x2 *)exc_dn; a.exc_cap_dn = exc_cap_dn;
     a.rec_stride_dn = step_major_dn ? hidden / 32 : 1;
     a.out = out;

@@ -261,7 +261,7 @@ __global__ __launch_bounds__(512) void g1q4_gateup_silu(const unsigned short *__
     __syncthreads();
     for (int g = 0; g < SP / D; ++g) trip(g * D, SP + g * D);                 // ---- phase 1
     __syncthreads();
-    constexpr int RP = 36;
+    constexpr int RP = G1S_RP;
     float *red = reinterpret_cast<float *>(smem);
     {
         float *mine = red + (size_t)(kh * 4 + q) * 32 * RP + (lane & 31);
@@ -296,39 +296,19 @@ __global__ __launch_bounds__(512) void g1q4_gateup_silu(const unsigned short *__
 static int g1q4_launch(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int waves, int step_major, int n_tiles, int tile0,
                        hipStream_t s)
 {
-    if (N < 32) return SJD_ERR_BAD_ARG;
-    const int n_out = N / 32, n_chunks = (K + KC - 1) / KC;
-    if (tile0 < 0 || tile0 + n_out > n_tiles) return SJD_ERR_BAD_ARG;
-    if (M > 64 || (K % 128) != 0 || (KC % 128) != 0) return SJD_ERR_UNSUPPORTED;       // (no wide form; whole records and scale dwords only)
-    const int MT = M <= 32 ? 1 : 2;
-    const size_t lds = (size_t)MT * ((KC < K ? KC : K) / 16) * 1024;
-    if (lds > 160 * 1024) return SJD_ERR_UNSUPPORTED;
-    const unsigned char *scales = static_cast<const unsigned char *>(wq) + (size_t)n_tiles * 16 * K;
-    const dim3 grid((n_out + waves - 1) / waves, n_chunks), block(waves * 64);
-    const int rs = step_major ? n_tiles : 1;
-#define SJD_G1Q4_LAUNCH(MT_, MAXT_) return g1_launch_kernel(g1q4_skinny_gemm<MT_, MAXT_>, grid, block, lds, s, x, wq, scales, out, M, N, K, KC, n_tiles, rs, tile0, waves)
-    if (MT == 1) { if (waves <= 8) SJD_G1Q4_LAUNCH(1, 512); else SJD_G1Q4_LAUNCH(1, 1024); }
-    else { if (waves <= 8) SJD_G1Q4_LAUNCH(2, 512); else SJD_G1Q4_LAUNCH(2, 1024); }
-#undef SJD_G1Q4_LAUNCH
+    return g1_stream_launch(wq, M, N, K, KC, waves, step_major, n_tiles, tile0, 16,
+        [&] { return (M > 64 || (K % 128) != 0 || (KC % 128) != 0) ? SJD_ERR_UNSUPPORTED : G1_STREAM_GO; },       // (no wide form; whole records and scale dwords only)
+        [&](auto mt, auto maxt, dim3 grid, dim3 block, size_t lds, const unsigned char *scales, int rs) {
+            return g1_launch_kernel(g1q4_skinny_gemm<decltype(mt)::value, decltype(maxt)::value>, grid, block, lds, s, x, wq, scales, out, M, N, K, KC,
+                                    n_tiles, rs, tile0, waves); });
 }
 
 // SJD_G1_W4_MXFP4 on sjd_gateup_silu (which has checked the common arguments: K in {512, 1024, 2048, 4096}, so a K half is a multiple of 128): M <= 32;
 // the scales sit behind the I * K code bytes.
 static int g1sq4_launch(const void *x, const void *wq, void *y, int M, int I, int K, int step_major, const sjd_row_norm *rn, hipStream_t s)
 {
-    if (M > 32) return SJD_ERR_UNSUPPORTED;
-    const int SP = K / 64;
-    const dim3 grid(I / 64), block(512);
-    const size_t lds_x = (size_t)2 * SP * 1024, lds_red = (size_t)8 * 32 * 36 * sizeof(float);
-    const size_t lds = lds_x > lds_red ? lds_x : lds_red;
-    const int rec_stride = step_major ? 2 * (I / 32) : 1;
-    const unsigned char *scales = static_cast<const unsigned char *>(wq) + (size_t)I * K;
-    const float *ss = rn ? rn->sumsq : nullptr;
-    const int sl = rn ? rn->slices : 0;
-    const float ih = rn ? 1.0f / (float)rn->hidden : 0.f, eps = rn ? rn->eps : 0.f;
-#define SJD_G1SQ4_CASE(SP_) \
-    if (SP == SP_) return g1_launch_kernel(g1q4_gateup_silu<SP_>, grid, block, lds, s, x, wq, scales, y, M, I, K, rec_stride, ss, sl, ih, eps);
-    SJD_G1SQ4_CASE(8) SJD_G1SQ4_CASE(16) SJD_G1SQ4_CASE(32) SJD_G1SQ4_CASE(64)
-#undef SJD_G1SQ4_CASE
-    return SJD_ERR_UNSUPPORTED;
+    return g1s_stream_launch(wq, M, I, K, step_major, 16, rn,
+        [&](auto sp, dim3 grid, dim3 block, size_t lds, const unsigned char *scales, int rec_stride, const g1s_norm_args &n) {
+            return g1_launch_kernel(g1q4_gateup_silu<decltype(sp)::value>, grid, block, lds, s, x, wq, scales, y, M, I, K, rec_stride, n.ss, n.sl, n.ih,
+                                    n.eps); });
 }

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(512) void g1q_gateup_silu(const unsigned short *__r
     __syncthreads();
     for (int g = 0; g < SP / TL; ++g) trip(g * TL, SP + g * TL);              // ---- phase 1
     __syncthreads();
-    constexpr int RP = 36;
+    constexpr int RP = G1S_RP;
     float *red = reinterpret_cast<float *>(smem);
     {
         float *mine = red + (size_t)(kh * 4 + q) * 32 * RP + (lane & 31);
@@ -283,38 +283,18 @@ __global__ __launch_bounds__(512) void g1q_gateup_silu(const unsigned short *__r
 static int g1q_launch(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int waves, int step_major, int n_tiles, int tile0,
                       hipStream_t s)
 {
-    if (N < 32) return SJD_ERR_BAD_ARG;
-    const int n_out = N / 32, n_chunks = (K + KC - 1) / KC;
-    if (tile0 < 0 || tile0 + n_out > n_tiles) return SJD_ERR_BAD_ARG;
-    if (M > 64) return g1wq_launch(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s);       // 65..256 rows: G1wq (csrc/sjd_gemm_wide.h) or unsupported
-    const int MT = M <= 32 ? 1 : 2;
-    const size_t lds = (size_t)MT * ((KC < K ? KC : K) / 16) * 1024;
-    if (lds > 160 * 1024) return SJD_ERR_UNSUPPORTED;
-    const float *scales = reinterpret_cast<const float *>(static_cast<const unsigned char *>(wq) + (size_t)n_tiles * 32 * K);
-    const dim3 grid((n_out + waves - 1) / waves, n_chunks), block(waves * 64);
-    const int rs = step_major ? n_tiles : 1;
-#define SJD_G1Q_LAUNCH(MT_, MAXT_) return g1_launch_kernel(g1q_skinny_gemm<MT_, MAXT_>, grid, block, lds, s, x, wq, scales, out, M, N, K, KC, n_tiles, rs, tile0, waves)
-    if (MT == 1) { if (waves <= 8) SJD_G1Q_LAUNCH(1, 512); else SJD_G1Q_LAUNCH(1, 1024); }
-    else { if (waves <= 8) SJD_G1Q_LAUNCH(2, 512); else SJD_G1Q_LAUNCH(2, 1024); }
-#undef SJD_G1Q_LAUNCH
+    return g1_stream_launch(wq, M, N, K, KC, waves, step_major, n_tiles, tile0, 32,
+        [&] { return M > 64 ? g1wq_launch(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s) : G1_STREAM_GO; },      // (G1wq, csrc/sjd_gemm_wide.h, or unsupported)
+        [&](auto mt, auto maxt, dim3 grid, dim3 block, size_t lds, const unsigned char *scales, int rs) {
+            return g1_launch_kernel(g1q_skinny_gemm<decltype(mt)::value, decltype(maxt)::value>, grid, block, lds, s, x, wq,
+                                    reinterpret_cast<const float *>(scales), out, M, N, K, KC, n_tiles, rs, tile0, waves); });
 }
 
 // SJD_G1_W8_E4M3 on sjd_gateup_silu (which has checked the common arguments): M <= 32; the scales sit behind the 2 I * K record bytes.
 static int g1sq_launch(const void *x, const void *wq, void *y, int M, int I, int K, int step_major, const sjd_row_norm *rn, hipStream_t s)
 {
-    if (M > 32) return SJD_ERR_UNSUPPORTED;
-    const int SP = K / 64;
-    const dim3 grid(I / 64), block(512);
-    const size_t lds_x = (size_t)2 * SP * 1024, lds_red = (size_t)8 * 32 * 36 * sizeof(float);
-    const size_t lds = lds_x > lds_red ? lds_x : lds_red;
-    const int rec_stride = step_major ? 2 * (I / 32) : 1;
-    const float *scales = reinterpret_cast<const float *>(static_cast<const unsigned char *>(wq) + (size_t)2 * I * K);
-    const float *ss = rn ? rn->sumsq : nullptr;
-    const int sl = rn ? rn->slices : 0;
-    const float ih = rn ? 1.0f / (float)rn->hidden : 0.f, eps = rn ? rn->eps : 0.f;
-#define SJD_G1SQ_CASE(SP_) \
-    if (SP == SP_) return g1_launch_kernel(g1q_gateup_silu<SP_>, grid, block, lds, s, x, wq, scales, y, M, I, K, rec_stride, ss, sl, ih, eps);
-    SJD_G1SQ_CASE(8) SJD_G1SQ_CASE(16) SJD_G1SQ_CASE(32) SJD_G1SQ_CASE(64)
-#undef SJD_G1SQ_CASE
-    return SJD_ERR_UNSUPPORTED;
+    return g1s_stream_launch(wq, M, I, K, step_major, 32, rn,
+        [&](auto sp, dim3 grid, dim3 block, size_t lds, const unsigned char *scales, int rec_stride, const g1s_norm_args &n) {
+            return g1_launch_kernel(g1q_gateup_silu<decltype(sp)::value>, grid, block, lds, s, x, wq, reinterpret_cast<const float *>(scales), y, M, I, K,
+                                    rec_stride, n.ss, n.sl, n.ih, n.eps); });
 }

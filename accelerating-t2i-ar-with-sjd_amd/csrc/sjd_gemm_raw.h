@@ -147,8 +147,8 @@ static int g1_raw_gateup_launch(const void *x, const sjd_raw_units *raw, void *y
     if (row_norm && (!row_norm->sumsq || row_norm->slices < 1 || row_norm->hidden < 1)) return SJD_ERR_BAD_ARG;
     if (row_norm && row_norm->slices > 8) return SJD_ERR_UNSUPPORTED;
     const int mt = (M + 31) / 32;
+    const g1s_norm_args n(row_norm);
     hipLaunchKernelGGL((g1_raw_gateup<SJD_DTYPE_BF16>), dim3(raw->n, mt), dim3(256), 0, s, (const unsigned short *)x, (const u32x4 *)raw->records,
-                       (const int *)raw->index, (unsigned short *)y, M, I, K, 32 * mt, row_norm ? row_norm->sumsq : nullptr, row_norm ? row_norm->slices : 0,
-                       row_norm ? 1.0f / (float)row_norm->hidden : 0.f, row_norm ? row_norm->eps : 0.f);
+                       (const int *)raw->index, (unsigned short *)y, M, I, K, 32 * mt, n.ss, n.sl, n.ih, n.eps);
     return hipGetLastError() == hipSuccess ? SJD_OK : SJD_ERR_LAUNCH;
 }
