@@ -26,6 +26,7 @@
 #include "../../include/sjd_hip.h"
 #include "sjd_coherent.h"
 #include "sjd_switches.h"
+#include "sjd_fp8.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -1252,12 +1253,10 @@ extern "C" int sjd_qkv_attention_fused_split(const float *part, int n_chunks, vo
 // Everything else (tile ranges, online softmax, masks, merge, workspace layout, k1_combine) is shared with k1_partial.
 typedef __attribute__((ext_vector_type(2))) int i32x2;
 
-__device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d)
-{
-    int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-    return (unsigned)v;
-}
+// pack4_fp8: the bare conversion, for P (at most 256 by construction); pack4_fp8_sat: the saturating one (sjd_fp8.h), for what the outside
+// world hands in -- the cache rows K3 writes and the q operand
+__device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d) { return sjd_pack4_e4m3<false>(a, b, c, d); }
+__device__ __forceinline__ unsigned pack4_fp8_sat(float a, float b, float c, float d) { return sjd_pack4_e4m3<true>(a, b, c, d); }
 __device__ __forceinline__ long as_long(unsigned lo, unsigned hi) { return (long)(((unsigned long long)hi << 32) | lo); }
 
 // ---- hi / lo operands (round 6; VERDICT r5 #2b).  The fp8 attention rounded FOUR things to e4m3's three mantissa bits: K and V (the cache: that is
@@ -1269,12 +1268,16 @@ __device__ __forceinline__ long as_long(unsigned lo, unsigned hi) { return (long
 #define K1_FP8_HILO 1
 #endif
 #define K1_LO_SCALE 16.0f
+// SAT (the q operand: q arrives unscaled, and an fp16 q without QK-norm can be anything up to 65504): hi = sat_e4m3(x), lo = sat_e4m3(16 (x - hi)),
+// so a finite q of any magnitude gives finite scores -- above 448 the operand is hi + lo / 16 <= 476 by definition, and only |q| <= 448 is exact
+// to 2^-8.  P's calls keep the bare form: the hot loop's instructions are unchanged.
+template <bool SAT = false>
 __device__ __forceinline__ void pack4_fp8_hilo(float a, float b, float c, float d, unsigned &hi, unsigned &lo)
 {
-    hi = pack4_fp8(a, b, c, d);
+    hi = sjd_pack4_e4m3<SAT>(a, b, c, d);
     const float ra = a - __builtin_amdgcn_cvt_f32_fp8((int)hi, 0), rb = b - __builtin_amdgcn_cvt_f32_fp8((int)hi, 1);
     const float rc = c - __builtin_amdgcn_cvt_f32_fp8((int)hi, 2), rd = d - __builtin_amdgcn_cvt_f32_fp8((int)hi, 3);
-    lo = pack4_fp8(ra * K1_LO_SCALE, rb * K1_LO_SCALE, rc * K1_LO_SCALE, rd * K1_LO_SCALE);
+    lo = sjd_pack4_e4m3<SAT>(ra * K1_LO_SCALE, rb * K1_LO_SCALE, rc * K1_LO_SCALE, rd * K1_LO_SCALE);
 }
 
 template <int DT> __device__ __forceinline__ float k1_to_f32(unsigned short h);
@@ -1339,7 +1342,7 @@ __global__ __launch_bounds__(64 * NW) void k1_partial_fp8(
                     f[8 + 2 * i] = k1_to_f32<DT>((unsigned short)(hi[i] & 0xffffu)); f[8 + 2 * i + 1] = k1_to_f32<DT>((unsigned short)(hi[i] >> 16));
                 }
 #pragma unroll
-                for (int i = 0; i < 4; ++i) pack4_fp8_hilo(f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3], wds[i], wdl[i]);
+                for (int i = 0; i < 4; ++i) pack4_fp8_hilo<true>(f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3], wds[i], wdl[i]);
             }
             qf[p][0] = as_long(wds[0], wds[1]);
             qf[p][1] = as_long(wds[2], wds[3]);
@@ -1505,7 +1508,8 @@ __global__ __launch_bounds__(64 * NW) void k1_partial_fp8(
 
 #include "sjd_attention_dsplit_fp8.h"
 
-// K3 for an fp8 cache: rows [kv_len, kv_len + n) <- fp8(x / scale); one thread converts 8 values (16 B in, 8 B out)
+// K3 for an fp8 cache: rows [kv_len, kv_len + n) <- sat_e4m3(x * (1 / scale)) (beyond +-448: +-448, sjd_fp8.h); one thread converts 8 values
+// (16 B in, 8 B out)
 template <int DT>
 __global__ void k3_kv_append_fp8(const u32x4 *__restrict__ k_new, const u32x4 *__restrict__ v_new, u32x2 *__restrict__ k_cache,
                                  u32x2 *__restrict__ v_cache, int B, int n_rows, int H_kv, int D8, int S_max,
@@ -1529,8 +1533,8 @@ __global__ void k3_kv_append_fp8(const u32x4 *__restrict__ k_new, const u32x4 *_
             kf[2 * j] = k1_to_f32<DT>((unsigned short)(kv[j] & 0xffffu)) * k_inv; kf[2 * j + 1] = k1_to_f32<DT>((unsigned short)(kv[j] >> 16)) * k_inv;
             vf[2 * j] = k1_to_f32<DT>((unsigned short)(vv[j] & 0xffffu)) * v_inv; vf[2 * j + 1] = k1_to_f32<DT>((unsigned short)(vv[j] >> 16)) * v_inv;
         }
-        k_cache[dst] = u32x2{pack4_fp8(kf[0], kf[1], kf[2], kf[3]), pack4_fp8(kf[4], kf[5], kf[6], kf[7])};
-        v_cache[dst] = u32x2{pack4_fp8(vf[0], vf[1], vf[2], vf[3]), pack4_fp8(vf[4], vf[5], vf[6], vf[7])};
+        k_cache[dst] = u32x2{pack4_fp8_sat(kf[0], kf[1], kf[2], kf[3]), pack4_fp8_sat(kf[4], kf[5], kf[6], kf[7])};
+        v_cache[dst] = u32x2{pack4_fp8_sat(vf[0], vf[1], vf[2], vf[3]), pack4_fp8_sat(vf[4], vf[5], vf[6], vf[7])};
     }
 }
 

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(64 * NW) void k1_dsplit_fp8(
                     f[8 + 2 * i] = k1_to_f32<DT>((unsigned short)(hi[i] & 0xffffu)); f[8 + 2 * i + 1] = k1_to_f32<DT>((unsigned short)(hi[i] >> 16));
                 }
 #pragma unroll
-                for (int i = 0; i < 4; ++i) pack4_fp8_hilo(f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3], wds[i], wdl[i]);
+                for (int i = 0; i < 4; ++i) pack4_fp8_hilo<true>(f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3], wds[i], wdl[i]);
             }
             qf[p][0] = as_long(wds[0], wds[1]);
             qf[p][1] = as_long(wds[2], wds[3]);

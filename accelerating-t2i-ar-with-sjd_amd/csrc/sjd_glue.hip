@@ -35,6 +35,7 @@ extern "C" int sjd_debug_trace_glue(int kind, unsigned long long *host_out, int 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 #include "sjd_mlp_epilogue.h"
+#include "sjd_fp8.h"
 #ifdef SJD_EXPERIMENTAL
 #include "sjd_l2_prefetch.h"
 #endif
@@ -364,7 +365,13 @@ __device__ __forceinline__ float row_sumsq_total(const float *__restrict__ row_s
 // DS (SJD_F2_HEAD_PAD128, LlamaGen GPT-3B): the STORAGE head dim of q_out and the caches where it differs from the source's D -- D = 100, DS = 128,
 // table mode only.  Lanes 0..49 own the pairs of the 100-wide source head and of the [., 50, 2] table row exactly as above; lanes 50..63 store
 // zeros into columns 100..127 of every row the kernel writes (q, k and v), so the pad columns never depend on what the buffers held.
-__device__ __forceinline__ unsigned char f2_to_fp8(float x) { return (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(x, x, 0, false) & 0xff); }
+// The byte stored is sat_e4m3(x * (1 / scale)): beyond +-448 (a key or value larger than the calibration prompt allowed for) it is +-448, not the
+// NaN code the bare conversion gives (sjd_fp8.h).
+__device__ __forceinline__ unsigned char f2_to_fp8(float x)
+{
+    x = sjd_e4m3_clamp(x);
+    return (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(x, x, 0, false) & 0xff);
+}
 
 template <int DT, int D, bool KV8, bool TBL = false, int DS = D>
 __global__ __launch_bounds__(256) void f2_qknorm_rope_append(

@@ -534,6 +534,8 @@ FP8_CASES = [
     ("fp8_gqa4_d128", 2, 8, 2, 128, 1056, 1000, 16, [3, 0], torch.float16, (1.0, 1.0)),
     ("fp8_gqa2_window32", 1, 4, 2, 128, 512, 300, 32, [0], torch.bfloat16, (1.0, 1.0)),
     ("fp8_mha_d64", 2, 12, 12, 64, 288, 200, 16, [0, 0], torch.bfloat16, (1.0, 1.0)),
+    # scales as a calibration leaves them -- no powers of two: x * fl32(1 / scale) and x / scale differ in the last bit there
+    ("fp8_mha_d128_calibrated_scales", 2, 4, 4, 128, 256, 77, 16, [0, 33], torch.bfloat16, (1.7, 0.0371)),
 ]
 
 
@@ -564,9 +566,12 @@ def test_k1_k3_fp8_kv_cache(dev, case, n_split):
     attn.kv_scale = (sk, sv)
     out = attn(0, q.to(dev), k.to(dev), v.to(dev), dcache, kv_len, key_start)
     torch.cuda.synchronize()
-    # K3: appended rows are torch's round-to-nearest-even e4m3 cast of x / scale, bit for bit; older rows untouched
-    want_k = (k.float() / sk).to(ops.FP8).permute(0, 2, 1, 3).contiguous().view(torch.uint8)
-    want_v = (v.float() / sv).to(ops.FP8).permute(0, 2, 1, 3).contiguous().view(torch.uint8)
+    # K3: appended rows are the round-to-nearest-even e4m3 cast of x * fl32(1 / scale) -- ONE fp32 multiply by the launcher's reciprocal, which is
+    # not x / scale in the last bit unless the scale is a power of two -- bit for bit; older rows untouched.  (In range, where torch's cast is
+    # right; tests/test_gpu_fp8_range.py holds the bytes beyond it to the saturating model.)
+    inv_k, inv_v = float(np.float32(1.0) / np.float32(sk)), float(np.float32(1.0) / np.float32(sv))
+    want_k = (k.float() * inv_k).to(ops.FP8).permute(0, 2, 1, 3).contiguous().view(torch.uint8)
+    want_v = (v.float() * inv_v).to(ops.FP8).permute(0, 2, 1, 3).contiguous().view(torch.uint8)
     got_k, got_v = dcache.k.cpu().view(torch.uint8)[0], dcache.v.cpu().view(torch.uint8)[0]
     assert torch.equal(got_k[:, :, kv_len:kv_len + n], want_k) and torch.equal(got_v[:, :, kv_len:kv_len + n], want_v)
     assert torch.equal(got_k[:, :, :kv_len], kc8.view(torch.uint8)[0, :, :, :kv_len])
