@@ -302,7 +302,7 @@ class LlamaGenBackbone(nn.Module):
         w[:, :, :head_dim] = wo.view(wo.shape[0], n_heads, head_dim)
         return w.view(wo.shape[0], n_heads * head_pad)
 
-    def enable_fused(self, ops, gemm="sjd", max_rows=64, untuned_fp16=False, pad_head_dim=False, padded_batch=False):
+    def enable_fused(self, ops, gemm="sjd", max_rows=64, untuned_fp16=False, pad_head_dim=False, padded_batch=False, weights=None):
         """Switch draft windows of <= max_rows rows (64, 128 or 256: rows = prompts per forward x CFG batch x window; fp16 weights take 256
         with untuned_fp16=True only: kernel G1w serves them on the launch shapes swept in bf16) to the hand-written HIP path: per layer F1r, G1 q|k|v, F2 (the interleaved rotary from a
         table, SJD_F2_ROPE_TABLE), K1, G1 o, F1r, G1 gate|up (+ F3, or G1s where ops.gateup_silu_ok allows), G1 down; then the output head
@@ -314,12 +314,30 @@ class LlamaGenBackbone(nn.Module):
         head_dim 100, nor at 64 rows); no effect at head_dim 64 / 128.  The RMSNorm gains are folded into packed copies of the weights (the
         norm becomes a row scale applied by F2 / F3 / K2, as ChameleonBackbone's folded path does).  w1 / w3 are concatenated once into
         [w1; w3] (gate | up) and re-pointed at its halves (state dict unchanged).  The prefill and longer inputs stay on forward_embeds.
-        `ops` is sjd_amd.ops.  Raises ValueError for what the kernels do not serve."""
+        weights (default None: the packed copy holds the checkpoint's values, as above) -- LOSSY, opt-in, as on ChameleonBackbone:
+          "e4m3" / "mxfp4"   the four per-layer projections are QUANTISED after norm folding (GPT-3B's wo as padded, zero pad columns included) and packed
+                          with ops.pack_weight_q8 (one byte per weight) / ops.pack_weight_q4 (4.25 bits); lm_head and the prefill keep 16-bit parameters.
+                          ONE copy serves every row count up to max_rows: <= 64 rows on kernels G1q / G1q4 (33..64 through LS.chunk_for_rows), 65..256 on
+                          G1wq / G1wq4.  gate|up runs fused (G1sq / G1sq4) only where ops.gateup_silu_ok(..., packed_q8=True) allows (<= 32 rows, hidden
+                          512 / 1024 / 2048 / 4096 packed in two K halves), else G1 + F3.  Launch shapes: LS.LLAMAGEN_QUANT_SETS (UNTUNED) unless the caller
+                          set G1_CFG; either way they must pass LS.llamagen_quant_errors -- checked here, before anything is assigned.
+          "e4m3_as_bf16" / "mxfp4_as_bf16"   the verification twins: pack_weight(dequant()) on the same chunks and the same fused / unfused route; every
+                          token agrees with the quantised copy.
+        compress_stats carries rel_rms_error (the largest over the matrices of RMS(w - dequant) / RMS(w)) and the packed bytes.  What either format does to
+        image quality on a real checkpoint has NOT been measured.  bf16 only; not with untuned_fp16; dim and the intermediate size multiples of 128
+        (mxfp4) / 32 (e4m3).
+        `ops` is sjd_amd.ops.  Raises ValueError for what the kernels do not serve -- a refused call leaves the backbone as it was."""
+        if weights not in (None,) + LS.QUANT_WEIGHTS:
+            raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16', 'mxfp4' or 'mxfp4_as_bf16'")
         if gemm != "sjd":
             raise ValueError(f"LlamaGenBackbone.enable_fused serves gemm='sjd' only (the G1 weight-streaming kernels), got gemm={gemm!r}")
         dt = self.output.weight.dtype
         if dt not in (torch.bfloat16, torch.float16):
             raise ValueError(f"LlamaGenBackbone.enable_fused needs 16-bit weights (bf16 or fp16), got {dt}")
+        if weights is not None and dt != torch.bfloat16:
+            raise ValueError(f"weights={weights!r} needs bf16 weights (got {dt}): the dequantised values are bf16 numbers, fp16's exponent range does not hold them")
+        if weights is not None and untuned_fp16:
+            raise ValueError(f"weights={weights!r} packs bf16 weights: untuned_fp16=True does not go with it")
         pad100 = bool(pad_head_dim) and self.head_dim == 100
         if self.head_dim not in (64, 128) and not pad100:
             raise ValueError(f"LlamaGenBackbone.enable_fused: head_dim {self.head_dim} is not served (F2's table rotary takes head_dim 64 or 128; "
@@ -342,16 +360,54 @@ class LlamaGenBackbone(nn.Module):
             raise ValueError("LlamaGenBackbone.enable_fused: max_rows=256 packs bf16 weights; it keeps fp16 windows of at most 128 rows unless "
                              "untuned_fp16=True (kernel G1 serves fp16 at 129..256 rows on the launch shapes swept in bf16)")
         # (a G1_CFG / HEAD_CFG set by the caller still wins)
-        g1_cfg, head_cfg = LS.LLAMAGEN_SETS[pad100, max_rows]
+        g1_cfg, head_cfg = (LS.LLAMAGEN_SETS if weights is None else LS.LLAMAGEN_QUANT_SETS)[pad100, max_rows]
         g1_cfg = self.__dict__.get("G1_CFG") or dict(g1_cfg)          # (the default keeps packing exactly what it packed before: the class's HEAD_CFG)
         head_cfg = self.__dict__.get("HEAD_CFG") or (head_cfg if max_rows > 64 or pad100 else None)
         if max_rows > 64:
             bad = [name for name, _ in LS.check_set(g1_cfg, head_cfg or self.HEAD_CFG, max_rows)]
             if bad:
                 raise ValueError(f"windows of more than 64 rows take {LS.WIDE_TILES} column tiles per workgroup; offending launch shapes: {bad}")
+        q4 = weights in LS.Q4_WEIGHTS
+        if weights is not None:          # (one quantised copy for every row count: validated before anything is assigned)
+            inter = self.layers[0].feed_forward.w1.weight.shape[0]
+            gran = LS.Q4_GRANULE if q4 else 32
+            if self.args.dim % gran or inter % gran:
+                raise ValueError(f"weights={weights!r}: dim {self.args.dim} and the intermediate size {inter} must be multiples of {gran} "
+                                 + ("(the MXFP4 stream travels in whole ring trips of eight k-steps)" if q4 else "(the e4m3 stream travels in whole record pairs)"))
+            dims = LS.llamagen_dims(self.args.dim, self.n_heads, self.head_dim, inter, self.HEAD_PAD if pad100 else None)
+            for name, why in LS.llamagen_quant_errors(g1_cfg, dims, max_rows, gran, head_cfg or self.HEAD_CFG)[:1]:
+                raise ValueError(f"weights={weights!r}, max_rows={max_rows}: " + (
+                    f"K and the chunk must be multiples of {gran}" if why == "granule" else
+                    f"kernels G1q / G1q4 stage the whole activation chunk in LDS -- every chunk must be <= {LS.CHUNK_CAP_32ROW} columns" if why == "chunk" else
+                    f"windows of 33..64 rows need a chunk of <= {LS.CHUNK_CAP_64ROW} columns, or a step-major packing whose halved chunk is a multiple of {gran}"
+                    if why == "halved" else
+                    f"the output head runs on kernel G1w above 64 rows -- HEAD_CFG[1] must be one of {LS.WIDE_TILES}" if name == "head" else
+                    "windows of more than 64 rows take 3, 4, 6 or 8 column tiles per workgroup on the quantised streams (kernels G1wq / G1wq4 have no form of "
+                    "three row tiles x two tiles)") + (f"; HEAD_CFG = {tuple(head_cfg or self.HEAD_CFG)}" if name == "head" else
+                                                       f"; G1_CFG[{name!r}] = {tuple(g1_cfg[name])} with K = {dims[name][1]}"))
         c = self.G1_CFG = g1_cfg
         if head_cfg is not None:
             self.HEAD_CFG = tuple(head_cfg)
+        self.weights = weights
+        self._max_rows_given = weights is not None          # (SJDBatchEngine: a quantised copy serves the rows it was packed for)
+        self.compress_stats = st = dict(matrices=0, bytes_raw=0, bytes_packed=0)
+
+        def pack(w, kc, sm, gateup=False):          # gateup: [Wg; Wu] in the two K halves G1sq / G1sq4 stream
+            st["matrices"] += 1
+            st["bytes_raw"] += w.numel() * w.element_size()
+            if weights is None:
+                st["bytes_packed"] += w.numel() * w.element_size()
+                return ops.pack_weight(w, kc, sm)
+            z = ops.pack_weight_q4(w, kc, sm, gateup=gateup) if q4 else ops.pack_weight_q8(w, kc, sm, gateup=gateup)
+            tag = "q4" if q4 else "q8"
+            st[tag + "_matrices"] = st.get(tag + "_matrices", 0) + 1
+            st["rel_rms_error"] = max(st.get("rel_rms_error", 0.0), z.stats["rel_rms_error"])
+            if weights.endswith("_as_bf16"):
+                st["bytes_packed"] += w.numel() * w.element_size()
+                return ops.pack_weight(z.dequant(), kc, sm)
+            st["bytes_packed"] += z.nbytes()
+            st[tag + "_bytes_packed"] = st.get(tag + "_bytes_packed", 0) + z.nbytes()
+            return z
         fold = lambda w, g: (w.float() * g.float()[None, :]).to(w.dtype)      # W' = W diag(gamma)
         wo_of = (lambda w: self._pad_o_weight(w, self.n_heads, self.head_dim, self.HEAD_PAD)) if pad100 else (lambda w: w)
         self._packed, self._fused = [], []
@@ -362,10 +418,10 @@ class LlamaGenBackbone(nn.Module):
                 ni = f.w1.weight.shape[0]
                 f.w1.weight.data, f.w3.weight.data = gu[:ni], gu[ni:]
                 self._fused.append(gu)
-                self._packed.append(dict(qkv=ops.pack_weight(fold(a.wqkv.weight, layer.attention_norm.weight), c["qkv"][0], c["qkv"][2]),
-                                         o=ops.pack_weight(wo_of(a.wo.weight), c["o"][0], c["o"][2]),
-                                         gate_up=ops.pack_weight(fold(gu, layer.ffn_norm.weight), c["gate_up"][0], c["gate_up"][2]),
-                                         down=ops.pack_weight(f.w2.weight, c["down"][0], c["down"][2])))
+                self._packed.append(dict(qkv=pack(fold(a.wqkv.weight, layer.attention_norm.weight), c["qkv"][0], c["qkv"][2]),
+                                         o=pack(wo_of(a.wo.weight), c["o"][0], c["o"][2]),
+                                         gate_up=pack(fold(gu, layer.ffn_norm.weight), c["gate_up"][0], c["gate_up"][2], gateup=2 * c["gate_up"][0] == gu.shape[1]),
+                                         down=pack(f.w2.weight, c["down"][0], c["down"][2])))
             wf = fold(self.output.weight, self.norm.weight)
             pad = (-wf.shape[0]) % 32
             if pad:          # (columns past the vocabulary are never read: K2's rules end at V)
@@ -397,8 +453,10 @@ class LlamaGenBackbone(nn.Module):
         inter = self._fused[0].shape[0] // 2
         params = getattr(self.attn, "params", None)
         kv_arg = kv_len if params is None else 0
-        g1 = lambda x_, li, name, N_, K_: ops.skinny_gemm(x_, self._packed[li][name], N_, K_, cfg[name][0], cfg[name][1], cfg[name][2])
-        fuse_mlp = ops.gateup_silu_ok(T, inter, hid, cfg["gate_up"][0])
+        wts = getattr(self, "weights", None)          # (a quantised copy and its twin: 33..64 rows read a chunk G1q / G1q4 can stage, LS.chunk_for_rows)
+        g1 = lambda x_, li, name, N_, K_: ops.skinny_gemm(x_, self._packed[li][name], N_, K_, LS.chunk_for_rows(name, cfg[name], T, K_, wts, self.max_rows),
+                                                          cfg[name][1], cfg[name][2])
+        fuse_mlp = ops.gateup_silu_ok(T, inter, hid, cfg["gate_up"][0], packed_q8=wts is not None)
         h = self.tok_embeddings(tokens).view(T, -1).contiguous()
         pos = positions.reshape(T).contiguous()
         delta = None                        # the down projection's split-K planes, summed by the next F1r

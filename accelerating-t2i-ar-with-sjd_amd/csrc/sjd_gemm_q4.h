@@ -18,7 +18,8 @@
 //       the column's block 4q + b of the chunk (k-steps 8q + 2b and 8q + 2b + 1, both lane halves) -- a lane takes a trip's scales with one aligned
 //       dword load; the trips of a unit are laid out like its records (a chunk starts at scale byte k0 * N_packed / 32; tile-major: S / 8
 //       consecutive 128-byte groups per unit; step-major: trip 0 of every tile, trip 1 of every tile, ...).
-// bf16; M <= 64 (G1q4) / M <= 32 (G1sq4): see the launchers.  No wide (65..256-row) form.
+// bf16; M <= 64 (G1q4) / M <= 32 (G1sq4): see the launchers.  65..256 rows: kernel G1wq4, the Q && WIDE form of g1_wide (csrc/sjd_gemm_wide.h), which
+// streams the same buffer -- g1q4_launch sends those row counts there.
 #pragma once
 
 #define G1Q4_DEPTH 16          // k-steps a wave keeps in flight: a ring of four records, the 4 KiB per wave that G1q's ring of eight k-steps holds
@@ -291,13 +292,16 @@ __global__ __launch_bounds__(512) void g1q4_gateup_silu(const unsigned short *__
     }
 }
 
-// SJD_G1_W4_MXFP4 on sjd_skinny_gemm / sjd_skinny_gemm_cols (which have checked the common arguments): M <= 64, K and KC multiples of 128, the whole
-// activation chunk in LDS -- min(KC, K) <= 2560 up to 32 rows, <= 1280 at 33..64.  The scales sit behind the N_packed * K / 2 code bytes.
+// SJD_G1_W4_MXFP4 on sjd_skinny_gemm / sjd_skinny_gemm_cols (which have checked the common arguments): K and KC multiples of 128; M <= 64 with the whole
+// activation chunk in LDS -- min(KC, K) <= 2560 up to 32 rows, <= 1280 at 33..64; 65..256 rows go to g1wq4_launch.  The scales sit behind the
+// N_packed * K / 2 code bytes.
 static int g1q4_launch(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int waves, int step_major, int n_tiles, int tile0,
                        hipStream_t s)
 {
     return g1_stream_launch(wq, M, N, K, KC, waves, step_major, n_tiles, tile0, 16,
-        [&] { return (M > 64 || (K % 128) != 0 || (KC % 128) != 0) ? SJD_ERR_UNSUPPORTED : G1_STREAM_GO; },       // (no wide form; whole records and scale dwords only)
+        [&] {          // (whole records and scale dwords only; 65..256 rows: G1wq4, csrc/sjd_gemm_wide.h, or unsupported)
+            if ((K % 128) != 0 || (KC % 128) != 0) return (int)SJD_ERR_UNSUPPORTED;
+            return M > 64 ? g1wq4_launch(x, wq, out, M, N, K, KC, waves, step_major, n_tiles, tile0, s) : G1_STREAM_GO; },
         [&](auto mt, auto maxt, dim3 grid, dim3 block, size_t lds, const unsigned char *scales, int rs) {
             return g1_launch_kernel(g1q4_skinny_gemm<decltype(mt)::value, decltype(maxt)::value>, grid, block, lds, s, x, wq, scales, out, M, N, K, KC,
                                     n_tiles, rs, tile0, waves); });

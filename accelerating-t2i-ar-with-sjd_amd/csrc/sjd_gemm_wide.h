@@ -89,6 +89,16 @@ __device__ __forceinline__ float gw_gload1(const void *p)
 }
 template <int N> __device__ __forceinline__ void gw_wait_regs(float &a) { asm volatile("s_waitcnt vmcnt(%1)" : "+v"(a) : "n"(N) : "memory"); }
 __device__ __forceinline__ u32x4 g1q_operand(unsigned b0, unsigned b1, float sc);        // csrc/sjd_gemm_q8.h
+// (4-bit form) one scale dword (a trip's four e8m0 bytes) per lane through the unit's scale descriptor, and the wait that ties it with a record
+__device__ __forceinline__ unsigned gw_wload1(u32x4 rsrc, unsigned voff, unsigned soff)
+{
+    unsigned r;
+    asm volatile("buffer_load_dword %0, %1, %2, %3 offen nt" : "=v"(r) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+    return r;
+}
+template <int N> __device__ __forceinline__ void gw_wait_regs(u32x4 &a, unsigned &b) { asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory"); }
+__device__ __forceinline__ u32x4 g1q4_operand(unsigned c, float sc);                      // csrc/sjd_gemm_q4.h
+template <int B> __device__ __forceinline__ float g1q4_scale(unsigned sd);
 
 __device__ __forceinline__ unsigned gw_lds_addr(const void *p)
 {
@@ -120,6 +130,22 @@ template <int DT> __device__ __forceinline__ f32x16 gw_fake_mma(u32x4 a, u32x4 b
 // written), so every k-step still has one vector-memory operation per tile and N_W0 / N_WL / N_A stand as they are.  An even k-step waits for its pair
 // (issued R k-steps earlier, at the same position: the plain counts) and decodes both operands; an odd one waits for nothing.  Pairs past a unit's end
 // read as zero through the descriptor range, code 0 decodes to +0.0.  The scales are requested in front of the prologue and waited for behind it.
+// Q && WIDE ("G1wq4"; WIDE has no other meaning without Z, and a new template parameter would rename every existing instantiation): the weights arrive
+// as the MXFP4 stream of kernels G1q4 / G1sq4 (csrc/sjd_gemm_q4.h: 1024-byte RECORDS of four k-steps, 64 lanes x 16 B, dword i = the lane's eight codes
+// of k-step 4 R + i; one e8m0 scale dword per lane and TRIP of eight k-steps behind the N_packed * K / 2 record bytes, laid out like the records; K and
+// KC multiples of 128, so every unit is whole records and trips) and are rebuilt into the SAME B operands (g1q4_operand: four conversions per k-step, in
+// front of the k-step's first MFMA): the planes of the uncompressed form on pack_weight(dequant()), bit for bit.  The ring R = 8 k-steps is exactly one
+// trip: two record registers and one scale dword per tile.  One vector-memory operation per tile and k-step as before, in the tile's slot of ring k-step r:
+//     r = 2  the NEXT trip's scale dword, into a landing register of its own (SDL; the current trip's dword was copied out of it at r = 0)
+//     r = 3  the next trip's first record, into W[c][0] -- behind the last MFMA of the fourth and last k-step that register serves, whose operand was
+//            decoded in front of that k-step's first MFMA: no load ever lands in a register that still holds undecoded codes
+//     r = 7  the next trip's second record, into W[c][1], likewise
+//     else   an out-of-range DMA piece into the scratch KiB (the Q form's odd k-steps)
+// so N_W0 / N_WL / N_A stand.  A record is waited for at its first k-step (r = 0 / r = 4), FIVE k-steps behind its request at the same position of the
+// group -- three groups less deep than the plain counts: N_WL - 3 GRP / N_W0 - 3 GRP younger operations.  The scale dword is requested one k-step BEFORE
+// the trip's first record: vmcnt retires loads in order, so the wait for the record at r = 0 covers it (both registers ride through that wait).  Nothing
+// is decoded ahead: per tile 8 (records) + 2 (scale dword, landing + current) + 4 (the operand, live for one tile's MFMAs) registers, against the Q
+// form's 16 + 1 + 8.  Records and scale dwords past a unit's end read as zero through the descriptor ranges; code 0 decodes to +0.0 under any scale.
 template <int DT, int MT, int CT, int NW, int SUB, int NS, int RW, int WPS, bool Z = false, bool WIDE = false, bool Q = false>
 __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__restrict__ x, const u32x4 *__restrict__ wp, float *__restrict__ out,
                                                         int M, int N, int K, int KC, int n_tiles, int rec_stride, int tile0, int ldx, int xmap,
@@ -127,6 +153,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
 {
     static_assert(!Z || (DT == SJD_DTYPE_BF16 && SUB % 2 == 0 && (RW * SUB) % 2 == 0), "the 12-bit stream: bf16, whole record pairs per stage and ring");
     static_assert(!Q || (!Z && DT == SJD_DTYPE_BF16 && SUB % 2 == 0 && (RW * SUB) % 2 == 0), "the 8-bit stream: bf16, whole record pairs per stage and ring");
+    constexpr bool Q4 = Q && WIDE, Q8 = Q && !WIDE;          // the 4-bit / the 8-bit stream
+    static_assert(!Q4 || RW * SUB == 8, "the 4-bit stream: the weight ring is exactly one trip of eight k-steps (two records, one scale dword)");
     static_assert(SUB == 2 || SUB == 4 || SUB == 8, "a stage is 2, 4 or 8 k-steps");
     static_assert(CT == 1 || CT == 2, "one or two column tiles per wave");
     // The weight ring is RW stages (R k-steps) deep, the activation ring LA = NS - 1 stages ahead.  LA > RW matters: vmcnt retires in order, so the
@@ -155,6 +183,9 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
     constexpr int N_W0 = (R - 1) * GRP + DPK + 1;                        // (CT = 2) tile 0: the pieces and the last record of its own group follow it
     constexpr int N_A = (LA - 1) * SUB * GRP + 1;
     static_assert(N_A <= 63 && N_WL <= 63 && N_W0 <= 63, "vmcnt is a 6-bit counter");
+    // (Q4) a record is requested at ring k-step 3 / 7 and first used at 0 / 4 of the next trip: 5 k-steps, i.e. 4 whole groups and the same partial one
+    constexpr int N_WL4 = N_WL - 3 * GRP, N_W04 = N_W0 - 3 * GRP;
+    static_assert(!Q4 || (N_WL4 == 4 * GRP + (CT - 1) && N_W04 == 4 * GRP + DPK + 1), "five k-steps between a record's request and its first use");
     static_assert(NS >= 2, "at least two slots");
     extern __shared__ __attribute__((aligned(1024))) unsigned char gw_lds[];       // NS slots, then 1 KiB of scratch
     SJD_TR(0);
@@ -185,9 +216,11 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
     const int n_stage = (steps + SUB - 1) / SUB;
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const unsigned rsb = (unsigned)rec_stride * (Z ? 1536u : 1024u);
+    [[maybe_unused]] const unsigned ssb = (unsigned)rec_stride * 128u;           // (Q4) bytes from a trip's scale group to the unit's next
     const int pairs = (steps + 1) / 2, pairs_full = (KC / 16 + 1) / 2;          // (Z) record pairs of this unit / of a full chunk's unit
     const size_t chunk_base = (size_t)chunk * n_tiles * (Z ? pairs_full : KC / 16);
     u32x4 wr[CT];
+    [[maybe_unused]] u32x4 sr[CT];                                               // (Q4) the descriptor of the unit's scale groups
     int t_out[CT];
     [[maybe_unused]] u32x2 hra[CT], hrb[CT];                                     // (Z) this lane's header entries of the tiles' units
     [[maybe_unused]] float qs[CT];                                               // (Q) this lane's column scale of each tile
@@ -202,6 +235,13 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
             const u32x2 *e = exc + ((size_t)chunk * n_tiles + t) * (size_t)exc_cap;
             hra[c] = gw_gload2(e + min(lane, exc_cap - 1));
             if constexpr (WIDE) hrb[c] = gw_gload2(e + 64 + lane); else hrb[c] = u32x2{0xffffffffu, 0xffffffffu};
+        } else if constexpr (Q4) {         // a chunk starts at byte k0 * N_packed / 2 (scales: k0 * N_packed / 32); tile-major: a unit is steps * 256 (* 16) contiguous bytes
+            const unsigned char *wq = reinterpret_cast<const unsigned char *>(wp);
+            const unsigned char *sq = wq + (size_t)n_tiles * 16 * K;
+            const size_t tile_off = (rec_stride == 1) ? (size_t)t * steps * 256 : (size_t)t * 1024;
+            const size_t stile_off = (rec_stride == 1) ? (size_t)t * steps * 16 : (size_t)t * 128;
+            wr[c] = gw_rsrc(wq + (size_t)k0 * ((size_t)n_tiles * 16) + tile_off, has ? (unsigned)(steps / 4 - 1) * rsb + 1024u : 0u);
+            sr[c] = gw_rsrc(sq + (size_t)k0 * (size_t)n_tiles + stile_off, has ? (unsigned)(steps / 8 - 1) * ssb + 128u : 0u);
         } else if constexpr (Q) {          // a chunk starts at byte k0 * N_packed; tile-major: a unit is steps * 512 contiguous bytes, step-major: pair p of every tile
             const unsigned char *wq = reinterpret_cast<const unsigned char *>(wp);
             const size_t tile_off = (rec_stride == 1) ? (size_t)t * steps * 512 : (size_t)t * 1024;
@@ -257,7 +297,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
         const unsigned voff = (int)xcol[i] < chunk_cols - sa * (SUB * 16) ? xoff[i] : 0x7fff0000u;
         gw_dma16(xr, voff, soff, dst);
     };
-    u32x4 W[CT][(Z || Q) ? R / 2 : R];       // plain: one record per k-step of the ring; Z: the low bytes of one record pair per two k-steps; Q: the pair
+    u32x4 W[CT][Q4 ? R / 4 : (Z || Q) ? R / 2 : R];       // plain: one record per k-step of the ring; Z: the low bytes of one record pair per two k-steps; Q: the pair; Q4: the record of four
+    [[maybe_unused]] unsigned SDL[CT], SDC[CT];            // (Q4) the scale dword of the next trip (landing) / of the current one
     [[maybe_unused]] u32x2 WC[CT][R / 2];    // (Z) ... and its codes
     [[maybe_unused]] u32x4 Bn[CT];           // (Z, Q) the odd k-step's operand, decoded with the even one's
     // (Z) record load of ring k-step ks: even -> the pair's low bytes, odd -> its codes
@@ -268,6 +309,13 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
     // (Q) record load of ring k-step ks: even -> the pair, odd -> an out-of-range piece into the scratch KiB (counted, no traffic, no register)
     auto q_load = [&](int c, int ks_ring, unsigned pair_abs) {
         if ((ks_ring & 1) == 0) W[c][ks_ring >> 1] = gw_wload(wr[c], wvoff, pair_abs * rsb);
+        else gw_dma16(xr, 0x7fff0000u, 0u, scratch);
+    };
+    // (Q4) the load of ring k-step ks for the trip that holds k-step `tgt` (the same ring position, R k-steps on): see the table in the header comment
+    [[maybe_unused]] const unsigned svoff = (unsigned)(lane & 31) * 4u;
+    auto q4_load = [&](int c, int ks_ring, unsigned tgt) {
+        if ((ks_ring & 7) == 2) SDL[c] = gw_wload1(sr[c], svoff, (tgt >> 3) * ssb);
+        else if ((ks_ring & 3) == 3) W[c][(ks_ring >> 2) & 1] = gw_wload(wr[c], wvoff, (tgt >> 2) * rsb);
         else gw_dma16(xr, 0x7fff0000u, 0u, scratch);
     };
     f32x16 acc[CT][MT];
@@ -288,12 +336,12 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
             const int ks = (v - (LA - RW)) * SUB + u;         // k-step of this group's records
 #pragma unroll
             for (int c = 0; c < CT - 1; ++c) {
-                if (ks >= 0) { if constexpr (Z) z_load(c, ks, (unsigned)(ks >> 1)); else if constexpr (Q) q_load(c, ks, (unsigned)(ks >> 1)); else W[c][ks] = gw_wload(wr[c], wvoff, (unsigned)ks * rsb); }
+                if (ks >= 0) { if constexpr (Z) z_load(c, ks, (unsigned)(ks >> 1)); else if constexpr (Q4) q4_load(c, ks, (unsigned)ks); else if constexpr (Q) q_load(c, ks, (unsigned)(ks >> 1)); else W[c][ks] = gw_wload(wr[c], wvoff, (unsigned)ks * rsb); }
                 else gw_dma16(xr, 0x7fff0000u, 0u, scratch);
             }
 #pragma unroll
             for (int d = 0; d < DPK; ++d) dma_piece(v, piece0 + (unsigned)(v * SLOT), u, d);
-            if (ks >= 0) { if constexpr (Z) z_load(CT - 1, ks, (unsigned)(ks >> 1)); else if constexpr (Q) q_load(CT - 1, ks, (unsigned)(ks >> 1)); else W[CT - 1][ks] = gw_wload(wr[CT - 1], wvoff, (unsigned)ks * rsb); }
+            if (ks >= 0) { if constexpr (Z) z_load(CT - 1, ks, (unsigned)(ks >> 1)); else if constexpr (Q4) q4_load(CT - 1, ks, (unsigned)ks); else if constexpr (Q) q_load(CT - 1, ks, (unsigned)(ks >> 1)); else W[CT - 1][ks] = gw_wload(wr[CT - 1], wvoff, (unsigned)ks * rsb); }
             else gw_dma16(xr, 0x7fff0000u, 0u, scratch);
         }
     // (Z) the unit headers: requested in front of the prologue, complete once no more than the prologue's own LA * SUB * GRP operations are outstanding
@@ -305,7 +353,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
             hd[c] = g1z_header<WIDE>(g1z_hraw{hra[c], hrb[c]}, lane, exc_cap);
         }
     }
-    if constexpr (Q) {         // the column scales: likewise
+    if constexpr (Q8) {        // the column scales: likewise
 #pragma unroll
         for (int c = 0; c < CT; ++c) gw_wait_regs<LA * SUB * GRP>(qs[c]);
     }
@@ -328,6 +376,24 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
                     W[c][r >> 1] = g1z_operand<WIDE>(W[c][r >> 1].x, W[c][r >> 1].y, WC[c][r >> 1].x, s_abs, hd[c], lane);      // (held in the pair's own registers until its last MFMA)
                 }
                 b = (r & 1) == 0 ? W[c][r >> 1] : Bn[c];
+            } else if constexpr (Q4) {
+                if (mt == 0) {
+                    if ((r & 3) == 0) {                   // a record's first k-step: requested five k-steps ago at this position (r = 0: the scale dword one more)
+                        u32x4 &rec = W[c][(r >> 2) & 1];
+                        if ((r & 7) == 0) {
+                            if (c == CT - 1) gw_wait_regs<N_WL4>(rec, SDL[c]); else gw_wait_regs<N_W04>(rec, SDL[c]);
+                            SDC[c] = SDL[c];              // (the landing register is free for the request at r = 2)
+                        } else {
+                            if (c == CT - 1) gw_wait_regs<N_WL4>(rec); else gw_wait_regs<N_W04>(rec);
+                        }
+                    }
+                    const u32x4 &rec = W[c][(r >> 2) & 1];
+                    const unsigned code = (r & 3) == 0 ? rec.x : (r & 3) == 1 ? rec.y : (r & 3) == 2 ? rec.z : rec.w;
+                    const int sb = (r >> 1) & 3;
+                    const float sc = sb == 0 ? g1q4_scale<0>(SDC[c]) : sb == 1 ? g1q4_scale<1>(SDC[c]) : sb == 2 ? g1q4_scale<2>(SDC[c]) : g1q4_scale<3>(SDC[c]);
+                    Bn[c] = g1q4_operand(code, sc);       // (decoded in front of the k-step's first MFMA: behind its last one the record may be refilled)
+                }
+                b = Bn[c];
             } else if constexpr (Q) {
                 if (mt == 0 && (r & 1) == 0) {            // an even k-step: its pair was requested R k-steps ago at this position
                     if (c == CT - 1) gw_wait_regs<N_WL>(W[c][r >> 1]); else gw_wait_regs<N_W0>(W[c][r >> 1]);
@@ -346,6 +412,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void g1_wide(const unsigned short *__
             if (i >= D0 && ((i - D0) % DSTR) == 0 && (i - D0) / DSTR < DPK) dma_piece(st + LA, sb_refill, u, (i - D0) / DSTR);
             if (mt == MT - 1) {
                 if constexpr (Z) z_load(c, r, (unsigned)((st * SUB + u + R) >> 1));
+                else if constexpr (Q4) q4_load(c, r, (unsigned)(st * SUB + u + R));
                 else if constexpr (Q) q_load(c, r, (unsigned)((st * SUB + u + R) >> 1));
                 else W[c][r] = gw_wload(wr[c], wvoff, (unsigned)(st * SUB + u + R) * rsb);
             }
@@ -441,7 +508,8 @@ static int g1_wide_launch_z(const void *x, const void *wz, const void *exc, int 
 }
 
 // G1wq: the same over the 8-bit e4m3 stream (wq: record pairs, then the fp32 column scales at byte N_packed * K); bf16, K and KC multiples of 32
-template <int MT, int CT, int NW, int SUB, int NS, int RW, int WPS>
+// G1wq4 (Q4 = true): the same over the MXFP4 stream (wq: records of four k-steps, then the e8m0 scale dwords at byte N_packed * K / 2); K and KC multiples of 128
+template <int MT, int CT, int NW, int SUB, int NS, int RW, int WPS, bool Q4 = false>
 static int g1_wide_launch_q(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int n_tiles, int step_major, int tile0, hipStream_t s)
 {
     const int n_out = N / 32, n_chunks = (K + KC - 1) / KC;
@@ -449,21 +517,21 @@ static int g1_wide_launch_q(const void *x, const void *wq, float *out, int M, in
     constexpr size_t lds = g1_wide_lds<MT, SUB, NS>();
     static_assert(lds <= 160 * 1024, "the activation ring must fit in LDS");
     constexpr int xmap = MT > 4;
-    return g1_launch_kernel(g1_wide<SJD_DTYPE_BF16, MT, CT, NW, SUB, NS, RW, WPS, false, false, true>, grid, block, lds, s, x, wq, out, M, N, K, KC, n_tiles,
+    return g1_launch_kernel(g1_wide<SJD_DTYPE_BF16, MT, CT, NW, SUB, NS, RW, WPS, false, Q4, true>, grid, block, lds, s, x, wq, out, M, N, K, KC, n_tiles,
                             step_major ? n_tiles : 1, tile0, K, xmap, nullptr, 0);
 }
 
 // Column tiles per workgroup -> the G1w instantiation (stages of four k-steps, three ring slots, weight ring of two stages): 2, 3, 4 tiles run one per
-// wave, 6 and 8 two per wave.  WPS: workgroups per SIMD the register budget allows; Q: the 8-bit stream (g1_wide_launch_q, bf16).  G1W_NO_FORM, with
+// wave, 6 and 8 two per wave.  WPS: workgroups per SIMD the register budget allows; Q: 8 the e4m3 stream, 4 the MXFP4 stream (g1_wide_launch_q, bf16).  G1W_NO_FORM, with
 // nothing launched, for a count kernel G1w does not take -- the caller falls back or refuses.
 constexpr int G1W_NO_FORM = 1;          // internal: every caller maps it to an SJD_* code or a fall-back -- it must never leave this translation unit
 static_assert(G1W_NO_FORM != SJD_OK && G1W_NO_FORM != SJD_ERR_BAD_ARG && G1W_NO_FORM != SJD_ERR_UNSUPPORTED && G1W_NO_FORM != SJD_ERR_LAUNCH, "not a return code");
-template <int DT, int MT, int WPS, bool Q = false>
+template <int DT, int MT, int WPS, int Q = 0>
 static int g1_wide_by_tiles(int tiles, const void *x, const void *w, float *out, int M, int N, int K, int KC, int n_tiles, int step_major, int tile0, hipStream_t s)
 {
     auto launch = [&](auto ct, auto nw) {
         constexpr int CT = decltype(ct)::value, NW = decltype(nw)::value;
-        if constexpr (Q) return g1_wide_launch_q<MT, CT, NW, 4, 3, 2, WPS>(x, w, out, M, N, K, KC, n_tiles, step_major, tile0, s);
+        if constexpr (Q != 0) return g1_wide_launch_q<MT, CT, NW, 4, 3, 2, WPS, Q == 4>(x, w, out, M, N, K, KC, n_tiles, step_major, tile0, s);
         else return g1_wide_launch<DT, MT, CT, NW, 4, 3, 2, WPS>(x, w, out, M, N, K, KC, n_tiles, step_major, tile0, s);
     };
     using one = std::integral_constant<int, 1>;
@@ -493,6 +561,15 @@ static int g1wq_launch(const void *x, const void *wq, float *out, int M, int N, 
 {
     if (M <= 64 || M > 256 || (K % 32) != 0 || (KC % 32) != 0) return SJD_ERR_UNSUPPORTED;
     const int rc = g1_by_row_tiles<3, 8>(M, [&](auto mt) {
-        return g1_wide_by_tiles<SJD_DTYPE_BF16, decltype(mt)::value, 1, true>(waves, x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s); });
+        return g1_wide_by_tiles<SJD_DTYPE_BF16, decltype(mt)::value, 1, 8>(waves, x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s); });
+    return rc == G1W_NO_FORM ? SJD_ERR_UNSUPPORTED : rc;
+}
+
+// SJD_G1_W4_MXFP4 at 65..256 rows (g1q4_launch, which has checked the column window): kernel G1wq4 on the same template shapes; K and KC whole trips.
+static int g1wq4_launch(const void *x, const void *wq, float *out, int M, int N, int K, int KC, int waves, int step_major, int n_tiles, int tile0, hipStream_t s)
+{
+    if (M <= 64 || M > 256 || (K % 128) != 0 || (KC % 128) != 0) return SJD_ERR_UNSUPPORTED;
+    const int rc = g1_by_row_tiles<3, 8>(M, [&](auto mt) {
+        return g1_wide_by_tiles<SJD_DTYPE_BF16, decltype(mt)::value, 1, 4>(waves, x, wq, out, M, N, K, KC, n_tiles, step_major, tile0, s); });
     return rc == G1W_NO_FORM ? SJD_ERR_UNSUPPORTED : rc;
 }

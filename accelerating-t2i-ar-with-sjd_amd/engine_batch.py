@@ -94,7 +94,9 @@ class SJDBatchEngine:
             if why == "max_rows":
                 raise ValueError(f"the backbone was packed for windows of at most max_rows={detail} rows, but n_prompts * n_batch * max_window = "
                                  f"{rows}: call enable_fused(ops, gemm='sjd', weights='e4m3', max_rows={to}), or use fewer prompts per forward")
-        if getattr(backbone, "weights", None) in LS.Q4_WEIGHTS and rows > LS.Q4_MAX_ROWS:          # enable_fused(weights="mxfp4" / "mxfp4_as_bf16")
+        # enable_fused(weights="mxfp4" / "mxfp4_as_bf16") on a Chameleon-family backbone: packed for 64 rows, always.  (A LlamaGen backbone's 4-bit copy serves
+        # the max_rows it was packed for -- kernel G1wq4 above 64 -- and is refused below like any other LlamaGen backbone.)
+        if getattr(backbone, "weights", None) in LS.Q4_WEIGHTS and rows > LS.Q4_MAX_ROWS and not LS.is_llamagen(backbone):
             raise ValueError(f"a backbone packed with enable_fused(weights={backbone.weights!r}) serves at most {LS.Q4_MAX_ROWS} window rows per forward (kernels "
                              f"G1q4 / G1sq4 have no wide form), but n_prompts * n_batch * max_window = {rows}: use fewer prompts per forward, or weights='e4m3' "
                              "with max_rows=128 / 256")
@@ -111,6 +113,8 @@ class SJDBatchEngine:
                              + ("; head_dim 100: with pad_head_dim=True, padded_batch=True)" if getattr(backbone, "head_dim", 0) == 100 else ")"))
         # (a head_dim-100 backbone stored 128 wide is packed for more than 64 rows on request only: the refusals name both arguments)
         padded = ", pad_head_dim=True, padded_batch=True" if getattr(backbone, "_head_pad", None) else ""
+        if LS.is_llamagen(backbone) and getattr(backbone, "weights", None) is not None:
+            padded += f", weights={backbone.weights!r}"
         if why == "fp16":
             raise ValueError(f"the backbone was packed for fp16 windows of at most {detail} rows, but n_prompts * n_batch * max_window = {rows}: "
                              f"call enable_fused(ops, gemm='sjd', max_rows=256, untuned_fp16=True{padded}), or use fewer prompts per forward")

@@ -103,6 +103,48 @@ LLAMAGEN_SETS = {      # (head_dim 100 stored 128 wide, max_rows) -> (G1_CFG, HE
     (True, 128): (dict(qkv=(1088, 4, False), o=(512, 4, False), gate_up=(1088, 8, False), down=(1088, 4, True)), (1600, 4, True)),
     (True, 256): (dict(qkv=(1088, 4, False), o=(512, 4, True), gate_up=(1088, 8, True), down=(1088, 4, True)), (1600, 4, True)),
 }
+# LlamaGenBackbone.enable_fused(weights="e4m3" / "mxfp4" / their "_as_bf16" twins): the sets above with what ONE quantised copy needs to serve every row
+# count up to max_rows (llamagen_quant_errors checks it) -- every chunk a multiple of Q4_GRANULE (320 -> 384; GPT-3B's 1088 -> 1152, which keeps its plane
+# counts: 3 for K = 3200, 8 for K = 8704), <= CHUNK_CAP_64ROW so that 33..64 rows stage it as it is, and above 64 rows 3, 4, 6 or 8 column tiles per
+# workgroup (two tiles have no form at 65..96 rows: o 2 -> 3, the other two-tile shapes -> 4).  One set per key serves both formats (128 is a multiple of
+# e4m3's 32).  UNTUNED: no launch-shape sweep was run on either stream.  The output head is not quantised and keeps the HEAD_CFG of LLAMAGEN_SETS.
+LLAMAGEN_QUANT_SETS = {
+    (False, 64): (dict(qkv=(256, 2, True), o=(256, 2, False), gate_up=(384, 2, False), down=(512, 2, False)), (640, 4, True)),
+    (False, 128): (dict(qkv=(384, 4, False), o=(256, 3, False), gate_up=(384, 4, True), down=(512, 4, False)), (640, 4, True)),
+    (False, 256): (dict(qkv=(256, 4, False), o=(256, 3, False), gate_up=(384, 4, True), down=(512, 4, False)), (640, 4, True)),
+    (True, 64): (dict(qkv=(640, 8, True), o=(512, 4, False), gate_up=(1152, 8, True), down=(1152, 4, True)), (1088, 8, True)),
+    (True, 128): (dict(qkv=(1152, 4, False), o=(512, 4, False), gate_up=(1152, 8, False), down=(1152, 4, True)), (1600, 4, True)),
+    (True, 256): (dict(qkv=(1152, 4, False), o=(512, 4, True), gate_up=(1152, 8, True), down=(1152, 4, True)), (1600, 4, True)),
+}
+QUANT_WEIGHTS = ("e4m3", "e4m3_as_bf16") + Q4_WEIGHTS
+
+
+def llamagen_dims(dim, n_head, head_dim, inter, head_pad=None):
+    """the (N, K) of a LlamaGen layer's four projections (multi-head attention; head_pad: the o projection reads heads stored that wide)"""
+    return dict(qkv=(3 * n_head * head_dim, dim), o=(dim, n_head * (head_pad or head_dim)), gate_up=(2 * inter, dim), down=(dim, inter))
+
+
+def llamagen_quant_errors(cfg, dims, max_rows, granule=128, head_cfg=None):
+    """[(name, why)]: what keeps ONE quantised copy packed on launch shapes `cfg` (dims: the projections' (N, K)) from serving every row count up to
+    max_rows.  why: "granule" (K or the chunk no multiple of `granule`: Q4_GRANULE for MXFP4, 32 for e4m3), "chunk" (above CHUNK_CAP_32ROW: kernels
+    G1q / G1q4 stage it whole), "halved" (none that 33..64 rows can stage: <= CHUNK_CAP_64ROW, or halvable by halved_chunk to whole granules), "tiles"
+    (max_rows > 64: kernels G1wq / G1wq4 take 3, 4, 6 or 8 column tiles per workgroup -- two have no form at 65..96 rows; head_cfg, which streams
+    16-bit weights on kernel G1w, any of WIDE_TILES)"""
+    bad = []
+    for name, (KC, tiles, sm) in cfg.items():
+        K_ = dims[name][1]
+        kc = min(KC, K_)
+        if K_ % granule or KC % granule:
+            bad.append((name, "granule"))
+        elif kc > CHUNK_CAP_32ROW:
+            bad.append((name, "chunk"))
+        elif halved_chunk(kc, K_, sm) > CHUNK_CAP_64ROW or halved_chunk(kc, K_, sm) % granule:
+            bad.append((name, "halved"))
+        elif max_rows > 64 and (tiles not in WIDE_TILES or tiles == 2):
+            bad.append((name, "tiles"))
+    if head_cfg is not None and max_rows > 64 and head_cfg[1] not in WIDE_TILES:
+        bad.append(("head", "tiles"))
+    return bad
 
 
 def default_shapes(dtype, g1_given, head_given, wide_hidden, gqa, compress, weights, max_rows, vocab_size):
@@ -180,10 +222,14 @@ def llamagen_row_limit(backbone):
     return WINDOW_MAX_ROWS if backbone.output.weight.dtype == torch.bfloat16 or getattr(backbone, "max_rows", 64) >= WINDOW_MAX_ROWS else Z_MAX_ROWS
 
 
+def is_llamagen(backbone):
+    return hasattr(backbone, "tok_embeddings") and hasattr(backbone, "embed_condition")
+
+
 def serves_rows(backbone, rows, window=1, head=False):
     """None when the packed `backbone` serves `rows` window rows (`window` per batch row) on the HIP path, else (why, detail): "unfused", "max_rows" / "fp16" (the
     rows it was packed for), "12-bit" (that stream's limit), "tiles" (check_set's names; head: the output head's too) or "prefill" (library GEMMs take it)"""
-    if hasattr(backbone, "tok_embeddings") and hasattr(backbone, "embed_condition"):          # LlamaGen: up to the rows its weights were packed for
+    if is_llamagen(backbone):          # LlamaGen: up to the rows its weights were packed for, whatever the stream (enable_fused(weights=...): G1wq / G1wq4 above 64)
         if getattr(backbone, "_ops", None) is None:
             return "unfused", None
         limit, fp16 = getattr(backbone, "max_rows", 64), backbone.output.weight.dtype == torch.float16 and rows > Z_MAX_ROWS

@@ -780,7 +780,8 @@ def skinny_gemm(x, w_packed, N, K, KC, waves=4, step_major=False):
     """x [M <= LS.WINDOW_MAX_ROWS, K] bf16/fp16 -> Partials([n_chunks, 32 * ceil(M / 32), N] fp32).  waves = column tiles per workgroup: 1..16 up to 64 rows,
     <= 8 up to 128 rows; above that (bf16 or fp16, uncompressed packing) kernel G1w takes LS.WIDE_TILES.  A PackedQ8 weight (bf16): up to 64 rows on kernel
     G1q (min(KC, K) <= LS.CHUNK_CAP_32ROW up to 32 rows, <= LS.CHUNK_CAP_64ROW above); 65 rows and more on kernel G1wq with LS.WIDE_TILES (not 2 at 65..96
-    rows), K and KC multiples of 32 -- the planes of the same call on pack_weight(w_packed.dequant(), KC, step_major), bit for bit."""
+    rows), K and KC multiples of 32 -- the planes of the same call on pack_weight(w_packed.dequant(), KC, step_major), bit for bit.  A PackedQ4 weight
+    (bf16) likewise: up to 64 rows on kernel G1q4 (the same chunk limits), 65 rows and more on kernel G1wq4 with the same tile counts; K and KC multiples of 128."""
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N * K
     _same_16bit_type(x, w_packed, "skinny_gemm")
@@ -934,7 +935,8 @@ def _raw_units(w_packed, gateup=False):
 
 def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_major=True):
     """G1 over the vocabulary columns [col0, col0 + n_cols) (32-aligned) of a weight packed with N_packed columns -> Partials [n_chunks, R, n_cols].
-    Row counts and `waves` per packing as skinny_gemm (PackedZ: up to LS.Z_MAX_ROWS rows; PackedQ8: up to LS.WINDOW_MAX_ROWS, kernels G1q / G1wq)."""
+    Row counts and `waves` per packing as skinny_gemm (PackedZ: up to LS.Z_MAX_ROWS rows; PackedQ8 / PackedQ4: up to LS.WINDOW_MAX_ROWS, kernels G1q / G1wq
+    and G1q4 / G1wq4)."""
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N_packed * K and col0 % 32 == 0 and n_cols % 32 == 0
     nc = (K + KC - 1) // KC
@@ -950,7 +952,7 @@ def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_m
         L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed.data), _ptr(out), M, n_cols, K, KC, waves, int(step_major),
                                              _dtype_code(x.dtype) | L.G1_W8_E4M3, N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols (e4m3 weights)")
         return Partials(out, nc, n_cols)
-    if isinstance(w_packed, PackedQ4):          # G1q4: the block scales ride behind the records of the same buffer; at most 64 rows
+    if isinstance(w_packed, PackedQ4):          # G1q4 / G1wq4: the block scales ride behind the records of the same buffer
         assert (w_packed.N, w_packed.step_major) == (N_packed, bool(step_major)) and w_packed.reads_as(KC)
         L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed.data), _ptr(out), M, n_cols, K, KC, waves, int(step_major),
                                              _dtype_code(x.dtype) | L.G1_W4_MXFP4, N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols (mxfp4 weights)")

@@ -41,8 +41,12 @@ def parse_args(argv=None):
     ap.add_argument("--window", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fused", action="store_true", help="draft windows on the hand-written HIP path (LlamaGenBackbone.enable_fused)")
+    ap.add_argument("--weights", default=None, choices=["e4m3", "mxfp4"],
+                    help="with --fused: stream the layer projections from QUANTISED weights (LOSSY, opt-in; image quality on a real checkpoint is not measured)")
     ap.add_argument("--out", default="sample.png")
     a = ap.parse_args(argv)
+    if a.weights and not a.fused:
+        ap.error("--weights packs the weights of the fused HIP path: add --fused")
     if len(a.class_id) > 1 and not a.fused:
         ap.error("several --class-id labels are decoded together on the fused HIP path: add --fused")
     if len(a.cfg_scale) not in (1, len(a.class_id)):
@@ -85,7 +89,9 @@ def main():
         # (GPT-3B's 32 heads are 100 wide: the kernels store them 128 wide with zero pad columns, which the backbone does on request only)
         # (... and several labels per forward on the padded model need its own swept launch shapes: padded_batch, no effect on the other models)
         gpt.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), pad_head_dim=gpt.head_dim == 100,
-                         padded_batch=rows > 64)
+                         padded_batch=rows > 64, weights=a.weights)
+        if a.weights:
+            print(f"--weights {a.weights}: LOSSY, rel. RMS error of the packed projections {gpt.compress_stats['rel_rms_error']:.4f}")
     one_scale = a.cfg_scale if isinstance(a.cfg_scale, float) else a.cfg_scale[0]        # (a scale per label: this one only says "CFG on")
     jac = dict(jacobi_loop_interval_l=1, jacobi_loop_interval_r=latent ** 2 - a.window - 2, max_num_new_tokens=a.window,
                guidance_scale=one_scale, seed=a.seed, multi_token_init_scheme="random", do_cfg=True, image_top_k=a.top_k,

@@ -95,7 +95,9 @@ extern "C" {
  *                         scale dwords: the kernels have no tail path).  The kernels rebuild the bf16 operand code * scale exactly, so the planes / the
  *                         16-bit output are bit for bit what the same call writes for the 16-bit packing of the dequantised weight: the format's loss
  *                         (coarser than e4m3's) is the host-side quantiser's alone.  Valid with SJD_DTYPE_BF16 only; M <= 64 with min(KC, K) <= 2560
- *                         (M <= 32) / <= 1280 (sjd_gateup_silu: M <= 32, K in {512, 1024, 2048, 4096}); there is no form for more than 64 rows.
+ *                         (M <= 32) / <= 1280 (sjd_gateup_silu: M <= 32, K in {512, 1024, 2048, 4096}); sjd_skinny_gemm / sjd_skinny_gemm_cols also take
+ *                         65 <= M <= 256 (kernel G1wq4, the 4-bit form of G1w, csrc/sjd_gemm_wide.h) with `waves` = column tiles per workgroup in
+ *                         {2, 3, 4, 6, 8} (not 2 at 65..96 rows), any KC that is a multiple of 128 -- the same packed buffer, the same bit-for-bit contract.
  *                         Everything else, and every other entry point given the bit, returns SJD_ERR_UNSUPPORTED before any launch; both weight bits
  *                         together return SJD_ERR_BAD_ARG.  SJD_VERSION did not move with it: a library without the bit returns SJD_ERR_UNSUPPORTED
  *                         for it, which is the probe. */

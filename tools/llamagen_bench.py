@@ -23,6 +23,9 @@
   --fused3b GPT-3B c2i 384px (24 layers, 32 heads of 100 stored 128 wide: enable_fused(pad_head_dim=True)), window 16, CFG, bf16: fused ms per SJD
             step over --rounds rounds (median), the packed bytes a step streams and their fraction of 8 TB/s.  No ATen leg: un-fused GPT-3B does
             not run on K1 (no head_dim-100 instantiation), so there is nothing to alternate with.
+  --quant   the lossy weight streams (enable_fused(weights="e4m3" / "mxfp4")): GPT-XL t2i 512px and GPT-3B c2i 384px at --counts (default 1,8) prompts per
+            forward, legs 16-bit / e4m3 / mxfp4 alternated over --rounds rounds (median and the rounds), then us per launch of GPT-3B's projections at
+            128 / 256 rows on kernels G1w / G1wq / G1wq4 (profiles/llamagen_quant.json).
 """
 import argparse
 import json
@@ -334,6 +337,77 @@ def batch(args):
             json.dump(out, f, indent=1)
 
 
+def quant(args):
+    """--quant: ms per SJD step from 16-bit, e4m3 and MXFP4 weights (LlamaGenBackbone.enable_fused(weights=...): LOSSY streams, synthetic weights), GPT-XL
+    t2i 512px and GPT-3B c2i 384px, --counts prompts per forward (default 1,8); one process, the legs alternated in every round, medians and the rounds.
+    Then us per launch of the GPT-3B projections at 128 / 256 rows on kernels G1w / G1wq / G1wq4 (the quantised set's shapes)."""
+    dev = torch.device("cuda:0")
+    counts = [int(c) for c in (args.counts if args.counts != "1,2,4,8" else "1,8").split(",")]
+    streams = [None, "e4m3", "mxfp4"]
+    only = args.only.split(",") if args.only else []
+    out = dict(configs=[], window=args.window, cfg=True, rounds=args.rounds, steps=args.steps, warmup=args.warmup,
+               note="synthetic weights; e4m3 / mxfp4 are LOSSY (rel_rms_error below is all there is to judge them by: image quality is NOT measured); "
+                    "the quantised launch shapes are UNTUNED (launch_shapes.LLAMAGEN_QUANT_SETS)")
+    for preset, mt, size in (CONFIGS[1], CONFIG_3B):
+        if only and preset not in only:
+            continue
+        base = _make(preset, mt, size, dev)
+        models, legs = {}, {}
+        for wt in streams:
+            for P in counts:
+                m = models[wt, P] = _make(preset, mt, size, dev)
+                m.load_state_dict(base.state_dict())
+                rows = P * 2 * args.window
+                m.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), pad_head_dim=preset == "GPT-3B",
+                               padded_batch=preset == "GPT-3B" and rows > 64, weights=wt)
+                legs[wt, P] = _Leg(m, args.window, dev) if P == 1 else _BatchLeg(m, P, args.window, dev)
+        del base
+        ms = {k: [] for k in legs}
+        for _ in range(args.rounds):
+            for P in counts:
+                for wt in streams:
+                    if P == 1:
+                        _, st, _ = legs[wt, P].decode(args.warmup, args.steps)
+                        ms[wt, P].append(1e3 * st.seconds / max(1, st.timed_nfe))
+                    else:
+                        ms[wt, P].append(legs[wt, P].decode(args.warmup, args.steps)[0])
+        for wt in streams:
+            med = {P: statistics.median(ms[wt, P]) for P in counts}
+            rec = dict(preset=preset, model_type=mt, image_size=size, weights=wt or "bf16", layers=models[wt, counts[0]].n_layers,
+                       ms_per_step={str(P): round(v, 3) for P, v in med.items()},
+                       ms_per_step_rounds={str(P): [round(x, 3) for x in ms[wt, P]] for P in counts},
+                       ms_vs_bf16={str(P): round(med[P] / statistics.median(ms[None, P]), 3) for P in counts},
+                       packed_gb_per_step={str(P): round(models[wt, P].packed_bytes() / 1e9, 3) for P in counts},
+                       rel_rms_error=models[wt, counts[0]].compress_stats.get("rel_rms_error"),
+                       g1_cfg={str(P): models[wt, P].G1_CFG for P in counts})
+            print(json.dumps(rec), flush=True)
+            out["configs"].append(rec)
+        del legs, models
+        torch.cuda.empty_cache()
+    # per launch: GPT-3B's projections (o reads heads stored 128 wide) on the quantised 256-row set, weights cycled past the Infinity Cache
+    cfg = BB.LS.LLAMAGEN_QUANT_SETS[True, 256][0]
+    shapes = BB.LS.llamagen_dims(3200, 32, 100, 8704, 128)
+    g = torch.Generator(device=dev).manual_seed(1)
+    launches = []
+    for name, (N, K) in shapes.items():
+        kc, tiles, sm = cfg[name]
+        copies = max(2, -(-768 * 2**20 // (N * K * 2)))
+        ws = [(torch.randn(N, K, generator=g, device=dev) / K ** 0.5).to(torch.bfloat16) for _ in range(copies)]
+        packs = dict(G1w=[ops.pack_weight(w, kc, sm) for w in ws], G1wq=[ops.pack_weight_q8(w, kc, sm) for w in ws], G1wq4=[ops.pack_weight_q4(w, kc, sm) for w in ws])
+        for M in (128, 256):
+            x = torch.randn(M, K, generator=g, device=dev).to(torch.bfloat16)
+            us = {kn: round(_graph_us(lambda i: ops.skinny_gemm(x, pk[i % copies], N, K, kc, tiles, sm), 2 * copies), 2) for kn, pk in packs.items()}
+            rec = dict(proj=name, N=N, K=K, rows=M, cfg=[kc, tiles, sm], us_per_launch=us)
+            print(json.dumps(rec), flush=True)
+            launches.append(rec)
+        del ws, packs
+        torch.cuda.empty_cache()
+    out["gpt_3b_launches"] = launches
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def detok(args):
     from llamagen.tokenizer.tokenizer_image.vq_model import VQ_models
     from sjd_amd.detokenizers import to_uint8
@@ -472,6 +546,7 @@ def main():
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--fused3b", action="store_true")
+    ap.add_argument("--quant", action="store_true", help="16-bit / e4m3 / mxfp4 weight streams (enable_fused(weights=...)), GPT-XL and GPT-3B, 1 and 8 prompts per forward")
     ap.add_argument("--detok", action="store_true", help="--batch: the tokens -> pixels queue (detokenizer alone, serial, overlapped) instead of the step table")
     ap.add_argument("--cfg-from", default="", help="--fused3b: a --sweep output whose `best` lines give the G1 launch shapes")
     ap.add_argument("--prompts", type=int, default=1, help="--step: prompts per forward (SJDBatchEngine above 1)")
@@ -496,6 +571,8 @@ def main():
         batch(args)
     if args.step:
         step(args)
+    if args.quant:
+        quant(args)
     if args.fused3b:
         fused3b(args)
 
