@@ -18,6 +18,7 @@ F2_ONE_HEAD = 0x1000           # F2 above 64 rows of split-K planes: one head pe
 G1_W8_E4M3 = 0x2000            # sjd_skinny_gemm / _cols / sjd_gateup_silu: w_packed is an 8-bit e4m3 stream with its column scales behind it (ops.PackedQ8)
 G1_W4_MXFP4 = 0x4000           # the same three: w_packed is an MXFP4 stream (e2m1 codes, the e8m0 block scales behind them: ops.PackedQ4)
 QKN_SHARDS_SHIFT = 16
+G1S_CHUNKS_SHIFT = 8           # sjd_gateup_silu's step_major argument: the chunks the weight was packed in above bit 8 (0: the two K halves)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("SJD_HIP_LIB") or os.path.join(_HERE, "libsjd_hip.so")      # SJD_HIP_LIB: an instrumented build (tools/phase_trace.py), or EXP_SO_PATH where a test compares against an alternative form

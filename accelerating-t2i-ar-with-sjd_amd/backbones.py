@@ -56,6 +56,10 @@ def _chk(tag, x, rows=None):
     return x
 
 
+# the same switch for the swin-norm route's K = 8192 MXFP4 form (enable_fused(weights="mxfp4", swin_quant=True)).  OFF by default: measured on the whole 30B
+# preset the fused launch is slower than G1q4 + F3 on the same copy (7.64 against 7.30 ms per step, 0.03 ms between rounds; 54.7 against 50.2 us per launch:
+# every one of its 344 workgroups stages the whole 32 x 8192 activation -- profiles/swin30b_quant.json).  `backbone.gateup_fused = True` reaches the kernel.
+_SWIN_GATEUP_FUSED_DEFAULT = False
 _GATEUP_FUSED_DEFAULT = {"0": False, "tall": "tall"}.get(_os.environ.get("SJD_GATEUP_FUSED", "1"), True)     # kernel G1s (gate|up + F3 in one launch); 0: G1 then F3; tall: also above 64 rows
 # round 3 experiment, correct, tested, OFF by default: the o / down projections of a <= 32-row window can reduce their own
 # split-K planes, add the residual and write the row statistics in their tail (sjd_skinny_gemm_reduce: device-coherent exchange between
@@ -678,7 +682,7 @@ class ChameleonBackbone(nn.Module):
                 f"the same packed copy serves windows of 33..64 rows, where kernel G1q needs chunks of <= {LS.CHUNK_CAP_64ROW} columns or a step-major packing that halved "
                 f"chunks read (_q8_chunk); {shape}"))
 
-    def enable_fused(self, ops, gemm="torch", fold_norm=True, compress=None, weights=None, max_rows=None):
+    def enable_fused(self, ops, gemm="torch", fold_norm=True, compress=None, weights=None, max_rows=None, swin_quant=False):
         """Switch to the fused HIP glue path (F1-F3): q|k|v and gate|up projections become single GEMMs whose weights are
         concatenated once; the original parameters are re-pointed at slices of the fused tensors (state-dict unchanged,
         no extra memory).  gemm="sjd": the window forward (<= 32 rows) also runs its four per-layer projections on the
@@ -715,7 +719,17 @@ class ChameleonBackbone(nn.Module):
         two stay token-identical).  Launch shapes: LS.default_shapes (UNTUNED sets) unless the caller set G1_CFG; ONE packed copy serves
         every row count, so it must pass LS.check_set -- checked here, before anything is assigned.  max_rows=256: lm_head is packed UNCOMPRESSED
         whatever `compress` says (the 12-bit stream ends at LS.Z_MAX_ROWS rows) and HEAD_CFG[1] must be one of LS.WIDE_TILES.  Whether the 8-bit
-        stream is faster than what those row counts run otherwise is a measurement, not a promise: README.md."""
+        stream is faster than what those row counts run otherwise is a measurement, not a promise: README.md.
+        swin_quant=True (with weights only): a swin-norm backbone (swin_norm=True, model_parallel_size > 1 included: the QK-norm shards live in F2, not in
+        a projection) is quantised too -- without it such a backbone raises as before.  A swin layer has no norm in front of a projection, so the quantisers
+        run on the checkpoint's own matrices; the unfolded window path streams the packed copies through ops.skinny_gemm.  LOSSY and opt-in like the rest;
+        image quality on a real checkpoint has NOT been measured.  bf16 only, max_rows None or 64, no fp8 KV cache, lm_head and the prefill keep their
+        16-bit parameters.  Launch shapes: LS.G1_CFG_30B_Q8 / LS.G1_CFG_30B_Q4 (UNTUNED) at hidden >= 8192 unless the caller set G1_CFG, which is checked
+        (LS.q4_chunk_errors; e4m3: the same rules on a granule of 32) before anything is assigned.  On "mxfp4" at hidden 8192 a window of <= 32 rows runs
+        gate|up + SiLU * up as ONE launch over the four-chunk copy when the backbone's `gateup_fused` attribute is set to True (LS.gateup_silu_chunked_ok;
+        measured slower than G1q4 + F3 with the untuned launch shapes, so the default is off: profiles/swin30b_quant.json);
+        33..64 rows, "e4m3" (which has no fused form at K = 8192: G1q + F3), the "_as_bf16" twins and other widths run G1 + F3 on the same packed copy, so a
+        twin stays token-identical to its stream.  `gateup_route` records, per row count, which of the two the last forward took."""
         if weights not in (None, "e4m3", "e4m3_as_bf16") + LS.Q4_WEIGHTS:
             raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16', 'mxfp4' or 'mxfp4_as_bf16'")
         q4 = weights in LS.Q4_WEIGHTS
@@ -728,7 +742,7 @@ class ChameleonBackbone(nn.Module):
         if weights is not None:
             if gemm != "sjd":
                 raise ValueError(f"weights={weights!r} needs gemm='sjd': the 8-bit stream is read by the hand-written projection kernels only (got gemm={gemm!r})")
-            if self.args.swin_norm or self.args.model_parallel_size > 1:
+            if (self.args.swin_norm or self.args.model_parallel_size > 1) and not swin_quant:
                 raise ValueError(f"weights={weights!r} is not served for swin-norm backbones (swin_norm=True or model_parallel_size > 1)")
             if self.lm_head.weight.dtype != torch.bfloat16:
                 raise ValueError(f"weights={weights!r} needs bf16 weights (got {self.lm_head.weight.dtype}): the dequantised values are bf16 numbers, "
@@ -739,6 +753,18 @@ class ChameleonBackbone(nn.Module):
         # the caller has not chosen launch shapes: the tuned set of the architecture, stream and row count (None: the class default as it stands)
         g1_cfg, head_cfg = LS.default_shapes(self.lm_head.weight.dtype, self.__dict__.get("G1_CFG"), self.__dict__.get("HEAD_CFG"), self.args.hidden_size >= 8192,
                                              self.n_kv_heads != self.n_heads, compress, weights, max_rows, self.vocab_size)
+        swin_q = weights is not None and (self.args.swin_norm or self.args.model_parallel_size > 1)
+        if swin_q and max_rows not in (None, 64):
+            raise ValueError(f"weights={weights!r} serves swin-norm backbones at windows of at most 64 rows (one prompt per forward): max_rows is None or 64, got {max_rows!r}")
+        if swin_q and not q4:            # (the e4m3 copy of a swin-norm backbone: the MXFP4 rules below on e4m3's granule of 32, before anything is assigned)
+            H, Hkv, D, hid, inter = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size
+            dims = dict(qkv=((H + 2 * Hkv) * D, hid), o=(hid, H * D), gate_up=(2 * inter, hid), down=(hid, inter))
+            for name, why in LS.llamagen_quant_errors(g1_cfg, dims, 64, granule=32)[:1]:
+                raise ValueError(f"weights={weights!r}: " + (
+                    "the e4m3 copy that serves 33..64 rows in halved chunks travels in whole record pairs -- K and the chunk must be multiples of 32" if why == "granule" else
+                    f"kernel G1q stages the whole activation chunk in LDS -- every G1_CFG chunk must be <= {LS.CHUNK_CAP_32ROW} columns" if why == "chunk" else
+                    f"windows of 33..64 rows need chunks of <= {LS.CHUNK_CAP_64ROW} columns, or a step-major packing whose halved chunk is a multiple of 32")
+                    + f"; G1_CFG[{name!r}] = {g1_cfg[name]} with K = {dims[name][1]}")
         if weights is not None:          # (validated before anything is assigned: a refused call leaves the backbone as it was)
             if q4:
                 H, Hkv, D, hid, inter = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size
@@ -763,6 +789,7 @@ class ChameleonBackbone(nn.Module):
         if head_cfg is not None:
             self.HEAD_CFG = head_cfg
         self.weights = weights
+        self.gateup_route = {}            # window rows -> "fused" / "g1+f3": what the last swin-norm window forward of that height ran gate|up on
         self._ops = ops
         self._gemm = gemm
         # swin-norm layers have no norm in front of a projection: nothing to fold (the unfolded window path, F1 in its post-norm form)
@@ -1001,6 +1028,10 @@ class ChameleonBackbone(nn.Module):
         pos = positions.reshape(T).contiguous()
         delta = None
         swin = self.args.swin_norm
+        fused_mlp = bool(swin and getattr(self, "gateup_fused", _SWIN_GATEUP_FUSED_DEFAULT) and isinstance(self._packed[0]["gate_up"], ops.PackedQ4)
+                         and LS.gateup_silu_chunked_ok(T, inter, hid, self._packed[0]["gate_up"].KC))
+        if swin and getattr(self, "weights", None) is not None:
+            self.gateup_route[T] = "fused" if fused_mlp else "g1+f3"
         for li, layer in enumerate(self.model.layers):
             a = layer.self_attn
             # swin-norm: the projection reads h itself; each sublayer ends in ONE F1 launch in its post-norm form (h += norm(sublayer))
@@ -1013,8 +1044,11 @@ class ChameleonBackbone(nn.Module):
                 x = ops.add_rmsnorm_post(h, attn_out, layer.input_layernorm.weight, eps)
             else:
                 x = ops.add_rmsnorm(h, attn_out, layer.post_attention_layernorm.weight, eps)
-            gu = g1(x, "gate_up", 2 * inter, hid)
-            act = ops.silu_mul(gu, rows=T, dtype=h.dtype)
+            if fused_mlp:      # (swin-norm on the MXFP4 stream at hidden 8192: the K = 8192 form of G1sq4 over the four-chunk copy; same bits as G1q4 + F3)
+                act = ops.gateup_silu(x, self._packed[li]["gate_up"], inter, hid, cfg["gate_up"][2])
+            else:
+                gu = g1(x, "gate_up", 2 * inter, hid)
+                act = ops.silu_mul(gu, rows=T, dtype=h.dtype)
             delta = g1(act, "down", hid, inter)
             if swin:
                 ops.add_rmsnorm_post(h, delta, layer.post_attention_layernorm.weight, eps)

@@ -1542,6 +1542,11 @@ extern "C" int sjd_gateup_silu(const void *x, const void *w_packed, void *y, int
     if (!x || !w_packed || !y || M < 1 || I < 64 || K < 512) return SJD_ERR_BAD_ARG;
     if (row_norm && (!row_norm->sumsq || row_norm->slices < 1 || row_norm->hidden < 1)) return SJD_ERR_BAD_ARG;
     if (row_norm && row_norm->slices > 8) return SJD_ERR_UNSUPPORTED;      // the kernel sums one batch of eight 512-column slices
+    if (const int n_chunks = step_major >> SJD_G1S_CHUNKS_SHIFT; n_chunks != 0) {      // the copy sjd_skinny_gemm streams in more than two chunks: one form
+        if ((dtype & SJD_G1_W8_E4M3) && (dtype & SJD_G1_W4_MXFP4)) return SJD_ERR_BAD_ARG;
+        if (dtype != (SJD_DTYPE_BF16 | SJD_G1_W4_MXFP4) || n_chunks != 4 || K != 8192 || M > 32 || (I % 64) != 0) return SJD_ERR_UNSUPPORTED;
+        return g1sq4k4_launch(x, w_packed, y, M, I, step_major & 1, row_norm, (hipStream_t)stream);      // w_packed = ops.pack_weight_q4([Wg; Wu], 2048, step_major)
+    }
     if (M > 128 || (I % 64) != 0 || !(K == 512 || K == 1024 || K == 2048 || K == 4096) || (M > 32 && K == 512) || (M > 64 && K != 4096)) return SJD_ERR_UNSUPPORTED;
     if ((dtype & SJD_G1_W8_E4M3) && (dtype & SJD_G1_W4_MXFP4)) return SJD_ERR_BAD_ARG;          // one weight stream per call
     if (dtype & SJD_G1_W4_MXFP4)                                           // w_packed = ops.pack_weight_q4([Wg; Wu], K / 2, step_major, gateup=True): G1sq4

@@ -20,6 +20,8 @@
 //       consecutive 128-byte groups per unit; step-major: trip 0 of every tile, trip 1 of every tile, ...).
 // bf16; M <= 64 (G1q4) / M <= 32 (G1sq4): see the launchers.  65..256 rows: kernel G1wq4, the Q && WIDE form of g1_wide (csrc/sjd_gemm_wide.h), which
 // streams the same buffer -- g1q4_launch sends those row counts there.
+// K = 8192 (30B-class hidden): g1q4_gateup_silu_k4, the form of G1sq4 over the copy G1q4 streams in FOUR chunks of 2048 (sjd_gateup_silu with
+// SJD_G1S_CHUNKS(4)): bit for bit G1q4(KC = 2048) + F3 on the same buffer.  The e4m3 stream has no such form (G1q + F3 there).
 #pragma once
 
 #define G1Q4_DEPTH 16          // k-steps a wave keeps in flight: a ring of four records, the 4 KiB per wave that G1q's ring of eight k-steps holds
@@ -292,6 +294,164 @@ __global__ __launch_bounds__(512) void g1q4_gateup_silu(const unsigned short *__
     }
 }
 
+// G1sq4 at K = 8192 (30B-class hidden): the gate|up weight is the copy G1q4 streams in FOUR chunks of 2048, so F3 would sum four planes and a wave keeps one
+// fp32 accumulator per K quarter.  Eight waves as above (two K halves x {gate, up} x two column tiles); a K half is two chunks = two units per wave, each
+// under its own pair of descriptors, and four activation phases of SP = 64 k-steps (2 x 64 KiB of LDS per phase).  The wave switches accumulator and unit
+// after two phases; the ring is never drained in between: the last trip of the first unit refills from the head of the second (still unconditional
+// loads, one per consumed record / scale dword), the last trip of the second refills past its end (no traffic).
+__global__ __launch_bounds__(512) void g1q4_gateup_silu_k4(const unsigned short *__restrict__ x, const unsigned char *__restrict__ wq,
+                                                           const unsigned char *__restrict__ scales, unsigned short *__restrict__ y, int M, int I,
+                                                           int rec_stride, const float *__restrict__ row_sumsq, int rs_slices, float rs_inv_hidden,
+                                                           float rs_eps)
+{
+    constexpr int DT = SJD_DTYPE_BF16;
+    constexpr int K = 8192, KC = 2048, SP = 64;
+    constexpr int D = G1Q4_DEPTH, DR = D / 4, HT = D / 8;
+    constexpr int NPH = K / 2 / (16 * SP);                       // phases per K half: four, two per chunk
+    static_assert(SP % D == 0 && D % 8 == 0 && NPH == 4 && KC == 2 * 16 * SP, "a phase is whole trips; a chunk is two phases");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u32x4 *xl = reinterpret_cast<u32x4 *>(smem);
+    __shared__ float rsc[32];
+    constexpr int PPS = 2 * SP;
+    constexpr int NPT = (32 * 2 * PPS) / 512;
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int kh = w >> 2, q = w & 3;
+    const int n_gate = I / 32, n_tiles = 2 * n_gate;
+    const int t_act = 2 * blockIdx.x + (q & 1);
+    const int t = (q < 2 ? 0 : n_gate) + t_act;
+    constexpr int recs = KC / 64, trips = KC / 128;              // records / scale dwords of a unit
+    const unsigned rsb = (unsigned)rec_stride * 1024u, ssb = (unsigned)rec_stride * 128u;
+    const size_t uoff = rec_stride == 1 ? (size_t)t * recs * 1024 : (size_t)t * 1024;
+    const size_t soff = rec_stride == 1 ? (size_t)t * trips * 128 : (size_t)t * 128;
+    const size_t cbytes = (size_t)KC * ((size_t)n_tiles * 16), sbytes = (size_t)KC * (size_t)n_tiles;      // a chunk's records / scales
+    const unsigned ubytes = (unsigned)(recs - 1) * rsb + 1024u, usbytes = (unsigned)(trips - 1) * ssb + 128u;      // a unit's extent under its descriptor
+    const unsigned char *cb = wq + (size_t)(2 * kh) * cbytes + uoff;                           // the wave's unit of chunk 2 kh; that of chunk 2 kh + 1 is cbytes on
+    const unsigned char *sb = scales + (size_t)(2 * kh) * sbytes + soff;
+    auto w_load = [&](const __amdgpu_buffer_rsrc_t &wr, int r) -> u32x4 {
+        return __builtin_amdgcn_raw_buffer_load_b128(wr, (unsigned)lane * 16u + (unsigned)r * rsb, 0u, G1Z_AUX); };
+    auto s_load = [&](const __amdgpu_buffer_rsrc_t &sr, int qq) -> unsigned {
+        return __builtin_amdgcn_raw_buffer_load_b32(sr, (unsigned)(lane & 31) * 4u + (unsigned)qq * ssb, 0u, G1Z_AUX); };
+    // piece v = 512 i + thread of a phase: row m = v / (2 PPS) = 2 i + m0, K half hh, 16-byte piece j of the half's SP k-steps; xp = x + the phase's
+    // first column (uniform), so a piece is one 32-bit offset from a scalar base
+    const int m0 = threadIdx.x / (2 * PPS), hh0 = (threadIdx.x / PPS) & 1, j0 = threadIdx.x % PPS;
+    static_assert(512 == 2 * (2 * PPS) && NPT == 16, "two rows per batch of 512 pieces");
+    const unsigned xo = (unsigned)(m0 * K + hh0 * (K / 2) + 8 * j0);
+    auto x_load = [&](const unsigned short *xp, int i) -> u32x4 {
+        return (2 * i + m0 < M) ? *reinterpret_cast<const u32x4 *>(xp + (xo + (unsigned)(2 * i * K))) : u32x4{0u, 0u, 0u, 0u};
+    };
+    auto x_store = [&](int i, u32x4 val) {
+        xl[(hh0 * SP + (j0 >> 1)) * 64 + g1_slot(j0 & 1, 2 * i + m0, j0 >> 1)] = val;
+    };
+    u32x4 ring[DR];
+    unsigned scr[HT];
+    u32x4 val[NPT];
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) val[i] = x_load(x, i);
+    float ssv[8];
+    {
+        const float *ssp = row_sumsq ? row_sumsq : reinterpret_cast<const float *>(x);
+#pragma unroll
+        for (int qq = 0; qq < 8; ++qq) ssv[qq] = ssp[(size_t)(row_sumsq ? min(qq, rs_slices - 1) : 0) * 32 + (threadIdx.x & 31)];
+    }
+    {
+        const __amdgpu_buffer_rsrc_t wr = g1z_unit_rsrc(cb, ubytes), sr = g1z_unit_rsrc(sb, usbytes);
+#pragma unroll
+        for (int h = 0; h < HT; ++h) {
+            ring[2 * h] = w_load(wr, 2 * h);
+            ring[2 * h + 1] = w_load(wr, 2 * h + 1);
+            scr[h] = s_load(sr, h);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) x_store(i, val[i]);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) val[i] = x_load(x + 16 * SP, i);
+    if (threadIdx.x < 32) {
+        float tsum = 0.f;
+#pragma unroll
+        for (int qq = 0; qq < 8; ++qq) tsum += (qq < rs_slices) ? ssv[qq] : 0.f;
+        rsc[threadIdx.x] = row_sumsq ? rsqrtf(__builtin_fmaf(tsum, rs_inv_hidden, rs_eps)) : 1.0f;
+    }
+    f32x16 acc[1], first[1];                                      // the chunk in flight; chunk 2 kh once it is done
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[0][r] = 0.0f; first[0][r] = 0.0f; }
+    const u32x4 *xa = xl + (size_t)kh * SP * 64;
+    // one ring trip: D k-steps staged as LDS records l0 .. of the current phase; every consumed record and scale dword is refilled from record r0 .. /
+    // dword q0 .. of (wr, sr) -- D k-steps further on in the same unit, or the head of the next one
+    auto trip = [&](int l0, const __amdgpu_buffer_rsrc_t &wr, const __amdgpu_buffer_rsrc_t &sr, int r0, int q0) {
+#pragma unroll
+        for (int h = 0; h < HT; ++h) {
+            const int lh = l0 + 8 * h;
+            g1q4_half_trip<1>(acc, ring[2 * h], ring[2 * h + 1], scr[h],
+                [&](u32x4 (&af)[1], int u) { af[0] = xa[(lh + u) * 64 + g1_slot(lane >> 5, lane & 31, u)]; });
+            ring[2 * h] = w_load(wr, r0 + 2 * h);
+            ring[2 * h + 1] = w_load(wr, r0 + 2 * h + 1);
+            scr[h] = s_load(sr, q0 + h);
+        }
+    };
+    auto restage = [&]() {          // the phase just read gives way to the one held in `val`
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) x_store(i, val[i]);
+        __syncthreads();
+    };
+    // the wave's two units, one pass each: LDS holds phase 2 u and `val` phase 2 u + 1 on entry.  The pass is a loop, not unrolled, so that the two
+    // units share their code and nothing of one is kept in registers across the other.
+#pragma nounroll
+    for (int u = 0; u < 2; ++u) {
+        const __amdgpu_buffer_rsrc_t wr = g1z_unit_rsrc(cb + (size_t)u * cbytes, ubytes), sr = g1z_unit_rsrc(sb + (size_t)u * sbytes, usbytes);
+        // what the unit's last trip refills from: the head of the next unit; behind the last one a descriptor of no bytes (an instruction, no traffic)
+        const __amdgpu_buffer_rsrc_t nwr = g1z_unit_rsrc(cb + (size_t)(u + 1) * cbytes, u == 0 ? ubytes : 0u);
+        const __amdgpu_buffer_rsrc_t nsr = g1z_unit_rsrc(sb + (size_t)(u + 1) * sbytes, u == 0 ? usbytes : 0u);
+        const unsigned short *xp = x + (size_t)u * (2 * 16 * SP);
+        for (int g = 0; g < SP / D; ++g) trip(g * D, wr, sr, g * D / 4 + DR, g * D / 8 + HT);                          // ---- the unit's k-steps 0 .. SP - 1
+        restage();
+        if (u == 0) {
+#pragma unroll
+            for (int i = 0; i < NPT; ++i) val[i] = x_load(xp + 2 * 16 * SP, i);
+        }
+        for (int g = 0; g < SP / D - 1; ++g) trip(g * D, wr, sr, (SP + g * D) / 4 + DR, (SP + g * D) / 8 + HT);        // ---- SP .. 2 SP - 1
+        trip(SP - D, nwr, nsr, 0, 0);
+        if (u == 0) {
+            restage();
+#pragma unroll
+            for (int i = 0; i < NPT; ++i) val[i] = x_load(xp + 3 * 16 * SP, i);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { first[0][r] = acc[0][r]; acc[0][r] = 0.0f; }
+        }
+    }
+    __syncthreads();
+    constexpr int RP = G1S_RP;
+    float *red = reinterpret_cast<float *>(smem);                // sixteen planes: (chunk, q), 32 rows of RP floats each
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        float *mine = red + (size_t)((2 * kh + u) * 4 + q) * 32 * RP + (lane & 31);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mine[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * RP] = u == 0 ? first[0][r] : acc[0][r];
+    }
+    __syncthreads();
+    {
+        const int a = threadIdx.x >> 8, m = (threadIdx.x >> 3) & 31, c4 = (threadIdx.x & 7) * 4;
+        auto plane = [&](int c_, int q_) { return *reinterpret_cast<const float4 *>(red + ((size_t)(c_ * 4 + q_) * 32 + m) * RP + c4); };
+        float gsum[4] = {0.f, 0.f, 0.f, 0.f}, usum[4] = {0.f, 0.f, 0.f, 0.f};      // F3: planes summed in chunk order, starting from zero
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float4 g = plane(c, a), u = plane(c, 2 + a);
+            gsum[0] += g.x; gsum[1] += g.y; gsum[2] += g.z; gsum[3] += g.w;
+            usum[0] += u.x; usum[1] += u.y; usum[2] += u.z; usum[3] += u.w;
+        }
+        const float rr = rsc[m];
+        unsigned short o16[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o16[j] = sjd_silu_mul_elem<DT>(gsum[j], usum[j], rr);
+        if (m < M) {
+            uint2 pk{(unsigned)o16[0] | ((unsigned)o16[1] << 16), (unsigned)o16[2] | ((unsigned)o16[3] << 16)};
+            *reinterpret_cast<uint2 *>(y + (size_t)m * I + 32 * (2 * blockIdx.x + a) + c4) = pk;
+        }
+    }
+}
+
 // SJD_G1_W4_MXFP4 on sjd_skinny_gemm / sjd_skinny_gemm_cols (which have checked the common arguments): K and KC multiples of 128; M <= 64 with the whole
 // activation chunk in LDS -- min(KC, K) <= 2560 up to 32 rows, <= 1280 at 33..64; 65..256 rows go to g1wq4_launch.  The scales sit behind the
 // N_packed * K / 2 code bytes.
@@ -315,4 +475,19 @@ static int g1sq4_launch(const void *x, const void *wq, void *y, int M, int I, in
         [&](auto sp, dim3 grid, dim3 block, size_t lds, const unsigned char *scales, int rec_stride, const g1s_norm_args &n) {
             return g1_launch_kernel(g1q4_gateup_silu<decltype(sp)::value>, grid, block, lds, s, x, wq, scales, y, M, I, K, rec_stride, n.ss, n.sl, n.ih,
                                     n.eps); });
+}
+
+// SJD_G1_W4_MXFP4 | SJD_G1S_CHUNKS(4) on sjd_gateup_silu (which has checked the arguments): M <= 32, K = 8192 in four chunks of 2048, the scales behind the I * K code bytes.  The
+// activation arena is one phase of two K halves x 64 k-steps = 128 KiB; the epilogue's sixteen planes (72 KiB) reuse it.
+static int g1sq4k4_launch(const void *x, const void *wq, void *y, int M, int I, int step_major, const sjd_row_norm *rn, hipStream_t s)
+{
+    constexpr int K = 8192;
+    const dim3 grid(I / 64), block(512);
+    const size_t lds_x = (size_t)2 * 64 * 1024, lds_red = 2 * g1s_epilogue_lds(1);
+    const size_t lds = lds_x > lds_red ? lds_x : lds_red;
+    static_assert((size_t)2 * 64 * 1024 <= 160 * 1024 && 2 * g1s_epilogue_lds(1) <= 160 * 1024, "the arena the launchers allow");
+    const int rec_stride = step_major ? 2 * (I / 32) : 1;
+    const unsigned char *scales = static_cast<const unsigned char *>(wq) + (size_t)(2 * (I / 32)) * 16 * K;
+    const g1s_norm_args n(rn);
+    return g1_launch_kernel(g1q4_gateup_silu_k4, grid, block, lds, s, x, wq, scales, y, M, I, rec_stride, n.ss, n.sl, n.ih, n.eps);
 }

@@ -47,9 +47,10 @@ class FlexARInferenceSolver:
     bpe_to_vq = None
 
     def __init__(self, model_path=None, precision="bf16", target_size=512, cache_dir=None, device="cpu", tokenizer=None,
-                 model: Optional[BB.ChameleonBackbone] = None, item_processor=None, fused=True, gemm="sjd", vq_model=None, bpe_to_vq=None, weights=None):
+                 model: Optional[BB.ChameleonBackbone] = None, item_processor=None, fused=True, gemm="sjd", vq_model=None, bpe_to_vq=None, weights=None, swin_quant=False):
         """weights: passed to ChameleonBackbone.enable_fused ("e4m3": the window projections streamed from 8-bit weights -- lossy; the prompt
-        prefill keeps the 16-bit parameters; see there).
+        prefill keeps the 16-bit parameters; see there).  swin_quant=True goes along: a swin-norm backbone (30B class) is quantised too -- lossy and
+        opt-in, refused without it.
         vq_model: a detokenizers.ChameleonVQ, or a state dict in `vqgan.ckpt` keys (loaded into a full-size ChameleonVQ; the encoder side is
         dropped) -- with it decode_image / decode_ids / generate_ids(decode=True) return PIL images without the reference's item processor.
         bpe_to_vq: the BPE id -> VQ code mapping of the image span, a length-V int64 table or a callable on an int64 tensor; default
@@ -63,7 +64,7 @@ class FlexARInferenceSolver:
         if self.model.attn is None and self.device.type == "cuda":
             self.model.attn = ops.HipWindowAttention()
         if fused and self.device.type == "cuda" and self.dtype != torch.float32 and getattr(self.model, "_ops", None) is None:
-            self.model.enable_fused(ops, gemm=gemm, weights=weights)
+            self.model.enable_fused(ops, gemm=gemm, weights=weights, swin_quant=swin_quant)
         if item_processor is None:
             # IS:290-293: in a maintainer's checkout of the reference (`./lumina_mgpt/` on sys.path, test_lumina_mgpt.py:3-5, tokenizer and
             # VQ-GAN files under ./ckpts/) the reference's own item processor is importable -- build it exactly as the reference does, so

@@ -68,6 +68,12 @@ Q4_MAX_ROWS = 64                  # kernels G1q4 / G1sq4 have no wide form
 # (profiles/g1_30b_sweep.jsonl), us per launch uncompressed / 12-bit: q|k|v 30.4 / 25.2, o 23.8 / 20.3, gate|up 120.5 / 98.9, down 62.9 / 50.4
 G1_CFG_30B = dict(qkv=(1536, 8, True), o=(1536, 8, False), gate_up=(2048, 8, True), down=(1536, 8, False))
 G1_CFG_30B_Z = dict(qkv=(1792, 8, True), o=(1280, 8, True), gate_up=(2048, 8, True), down=(1536, 8, True))
+# the same backbones on the quantised streams (enable_fused(weights=..., swin_quant=True)): UNTUNED -- G1_CFG_30B_Z's values, which pass q4_chunk_errors and
+# the e4m3 rules at these dimensions (every chunk a multiple of Q4_GRANULE, <= CHUNK_CAP_32ROW, step-major so that 33..64 rows read it in halved chunks;
+# G1_CFG_30B's tile-major chunks of 1536 cannot be halved); no launch-shape sweep was run on either stream.  gate|up keeps the four chunks of 2048: the
+# copy G1q / G1q4 + F3 stream, and on "mxfp4" at <= 32 rows the one the fused K = 8192 launch streams (gateup_silu_chunked_ok)
+G1_CFG_30B_Q8 = dict(G1_CFG_30B_Z)
+G1_CFG_30B_Q4 = dict(G1_CFG_30B_Z)
 HEAD_CFG = (1024, 4, True)         # G1 launch shape of the output head: (split-K chunk, column tiles per workgroup, step-major)
 # vocabularies whose image window is tens of thousands of columns (Emu3: 32768 of 184622): two K chunks, so that K2 sums two planes per
 # column instead of four, eight tiles per workgroup; Emu3 4.65 -> 4.62 ms per step (bench.py, SJD_HEAD_CFG sweep, one box)
@@ -151,6 +157,8 @@ def default_shapes(dtype, g1_given, head_given, wide_hidden, gqa, compress, weig
     """(G1_CFG, HEAD_CFG) ChameleonBackbone.enable_fused packs with; *_given: the caller's (it wins); wide_hidden: 30B class; gqa: Emu3; None: the class default stays"""
     z = compress and dtype == torch.bfloat16          # the 12-bit stream
     head = head_given or (HEAD_CFG_WIDE if vocab_size >= 131072 else None)
+    if weights is not None and wide_hidden:          # (30B class: swin-norm backbones, enable_fused(swin_quant=True); at most 64 rows)
+        return g1_given or dict(G1_CFG_30B_Q4 if weights in Q4_WEIGHTS else G1_CFG_30B_Q8), head
     if weights in Q4_WEIGHTS:
         return g1_given or dict(G1_CFG_EMU3_Q4 if gqa else G1_CFG_Q4), head
     if weights is not None:
@@ -256,6 +264,12 @@ def serves_rows(backbone, rows, window=1, head=False):
 def gateup_silu_ok(T, inter, hidden, KC, packed_z=False, packed_q8=False):
     rows_ok = T <= 32 or (not packed_q8 and ((T <= 64 and hidden >= 1024) or (T <= Z_MAX_ROWS and hidden == 4096 and not packed_z)))
     return rows_ok and hidden in (512, 1024, 2048, 4096) and 2 * KC == hidden and inter % 64 == 0
+
+
+# the one shape the fused gate|up launch serves from a copy packed in MORE than two chunks (sjd_gateup_silu with SJD_G1S_CHUNKS(4), kernel
+# g1q4_gateup_silu_k4): a <= 32-row window at hidden 8192 over the MXFP4 copy that G1q4 streams in four chunks of 2048.  The e4m3 stream has no such form.
+def gateup_silu_chunked_ok(T, inter, hidden, KC, packed_q4=True):
+    return bool(packed_q4) and T <= 32 and hidden == 8192 and KC == 2048 and inter % 64 == 0
 
 
 def packed_nbytes(w):

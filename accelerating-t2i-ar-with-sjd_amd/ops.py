@@ -8,6 +8,7 @@ from . import _lib as L
 from . import launch_shapes as LS
 
 gateup_silu_ok = LS.gateup_silu_ok          # the shapes kernels G1s / G1sz / G1sq serve
+gateup_silu_chunked_ok = LS.gateup_silu_chunked_ok          # ... and the K = 8192 form of G1sq4 over a copy packed in four chunks
 
 
 def _stream():
@@ -1246,7 +1247,9 @@ def silu_mul(gate_up, rows=None, dtype=None, row_norm=None):
 
 def gateup_silu(x, w_packed, inter, hidden, step_major=False, row_norm=None):
     """G1s: silu(r * gate(x)) * (r * up(x)) [T, inter] in ONE launch -- the gate|up projection (w_packed = pack_weight([Wg; Wu], hidden / 2,
-    step_major)) with F3 as its epilogue; bit-identical to silu_mul(skinny_gemm(x, w_packed, 2 * inter, hidden, hidden / 2), row_norm=...)."""
+    step_major)) with F3 as its epilogue; bit-identical to silu_mul(skinny_gemm(x, w_packed, 2 * inter, hidden, hidden / 2), row_norm=...).
+    A PackedQ4 at hidden 8192 packed with KC = 2048 (LS.gateup_silu_chunked_ok: <= 32 rows) runs the four-chunk form: bit-identical to
+    silu_mul(skinny_gemm(x, w_packed, 2 * inter, 8192, 2048), row_norm=...) on the same buffer.  A PackedQ8 has no such form."""
     T = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == hidden and w_packed.numel() == 2 * inter * hidden
     y = torch.empty(T, inter, dtype=x.dtype, device=x.device)
@@ -1264,8 +1267,12 @@ def gateup_silu(x, w_packed, inter, hidden, step_major=False, row_norm=None):
         return y
     if isinstance(w_packed, PackedQ4):          # G1sq4
         _same_16bit_type(x, w_packed, "gateup_silu")
-        assert (w_packed.N, w_packed.KC, w_packed.step_major) == (2 * inter, hidden // 2, bool(step_major))
-        L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed.data), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype) | L.G1_W4_MXFP4,
+        assert (w_packed.N, w_packed.step_major) == (2 * inter, bool(step_major))
+        # packed in the two K halves, or (hidden 8192: the copy skinny_gemm streams in four chunks of 2048) the chunk count goes along; the library refuses the rest
+        assert hidden % w_packed.KC == 0
+        chunks = hidden // w_packed.KC
+        sm = int(step_major) | (0 if chunks == 2 else chunks << L.G1S_CHUNKS_SHIFT)
+        L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed.data), _ptr(y), T, inter, hidden, sm, _dtype_code(x.dtype) | L.G1_W4_MXFP4,
                                         _row_norm(row_norm), _stream()), "sjd_gateup_silu (mxfp4 weights)")
         return y
     L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype),

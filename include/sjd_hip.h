@@ -95,7 +95,7 @@ extern "C" {
  *                         scale dwords: the kernels have no tail path).  The kernels rebuild the bf16 operand code * scale exactly, so the planes / the
  *                         16-bit output are bit for bit what the same call writes for the 16-bit packing of the dequantised weight: the format's loss
  *                         (coarser than e4m3's) is the host-side quantiser's alone.  Valid with SJD_DTYPE_BF16 only; M <= 64 with min(KC, K) <= 2560
- *                         (M <= 32) / <= 1280 (sjd_gateup_silu: M <= 32, K in {512, 1024, 2048, 4096}); sjd_skinny_gemm / sjd_skinny_gemm_cols also take
+ *                         (M <= 32) / <= 1280 (sjd_gateup_silu: M <= 32, K in {512, 1024, 2048, 4096}, or K == 8192 with SJD_G1S_CHUNKS(4): see there); sjd_skinny_gemm / sjd_skinny_gemm_cols also take
  *                         65 <= M <= 256 (kernel G1wq4, the 4-bit form of G1w, csrc/sjd_gemm_wide.h) with `waves` = column tiles per workgroup in
  *                         {2, 3, 4, 6, 8} (not 2 at 65..96 rows), any KC that is a multiple of 128 -- the same packed buffer, the same bit-for-bit contract.
  *                         Everything else, and every other entry point given the bit, returns SJD_ERR_UNSUPPORTED before any launch; both weight bits
@@ -388,7 +388,16 @@ int sjd_silu_mul_ex(const void *gate_up, void *y, int rows, int inter, int dtype
  * M <= 32 rows.  w_packed = the [2 I, K] weight [Wg; Wu] packed by sjd_amd.ops.pack_weight with KC = K / 2 (the copy sjd_skinny_gemm
  * streams).  The K split of G1 moves inside the workgroup (8 waves = 4 column tiles x 2 K halves, activation staged in two phases), so
  * the result is bit-identical to sjd_skinny_gemm(KC = K / 2) followed by sjd_silu_mul_ex on its two partial planes.
- * K in {512, 1024, 2048, 4096}, I % 64 == 0; SJD_ERR_UNSUPPORTED otherwise (the caller keeps G1 + F3). */
+ * K in {512, 1024, 2048, 4096}, I % 64 == 0; SJD_ERR_UNSUPPORTED otherwise (the caller keeps G1 + F3).
+ * step_major carries, above bit 0, the number of chunks the weight was packed in: SJD_G1S_CHUNKS(n) (0 = the two K halves above).  One form takes it
+ * (30B-class hidden 8192, whose gate|up is packed in four chunks of 2048 -- the launch shape of the unfused route, there is no second packing):
+ * dtype = SJD_DTYPE_BF16 | SJD_G1_W4_MXFP4, SJD_G1S_CHUNKS(4), M <= 32, K == 8192, I % 64 == 0 (kernel g1q4_gateup_silu_k4, csrc/sjd_gemm_q4.h: one fp32
+ * accumulator per chunk, the four planes summed in chunk order from zero as F3 sums them).  y is bit for bit what sjd_skinny_gemm(KC = 2048) followed
+ * by sjd_silu_mul_ex on its four planes writes for the same buffer, and so for pack_weight(the dequantised weight).  Any other chunk count, K, dtype
+ * or row count with the field set returns SJD_ERR_UNSUPPORTED before any launch (both weight bits: SJD_ERR_BAD_ARG); K == 8192 without it stays
+ * SJD_ERR_UNSUPPORTED.  The e4m3 stream has no such form: its gate|up at K = 8192 runs as G1q + F3. */
+#define SJD_G1S_CHUNKS_SHIFT 8
+#define SJD_G1S_CHUNKS(n) ((n) << SJD_G1S_CHUNKS_SHIFT)
 int sjd_gateup_silu(const void *x, const void *w_packed, void *y, int M, int I, int K, int step_major, int dtype,
                     const sjd_row_norm *row_norm, void *stream);
 

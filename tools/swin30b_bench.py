@@ -6,11 +6,18 @@
             the fastest per projection is what G1_CFG_30B / G1_CFG_30B_Z hold.
   --step    ms per SJD step of the whole preset (synthetic weights drawn on the device, window 16, CFG, bf16) on the 12-bit stream and on
             the uncompressed packing (each packed once, before its timed decode), plus the projections' algorithmic bytes per step.
+  --step --quant   the quantised streams (enable_fused(weights=..., swin_quant=True): LOSSY, opt-in) against the 12-bit stream with the protocol of
+            tools/q8_bench.py --step: one process, one device, ONE set of 16-bit parameters, the legs 12-bit / e4m3 / mxfp4 (fused gate|up) / mxfp4
+            (gate|up as G1q4 + F3, the same packed copy) alternating, --rounds timed rounds after an untimed one, the timed region at the mean KV
+            length.  Per leg: ms per step (every round, the median), packed bytes per step, the projections' launch times at 32 rows and their
+            fraction of the HBM peak on stored bytes; and whether the fused launch beats the unfused leg by more than that leg's spread.
 """
 import argparse
+import copy
 import dataclasses
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -137,10 +144,129 @@ def step(args):
             json.dump(out, f, indent=1)
 
 
+PEAK = 8.0e12          # HBM bytes per second of one MI355X
+
+
+def _spread(v):
+    return dict(median=round(statistics.median(v), 4), min=round(min(v), 4), max=round(max(v), 4), rounds=[round(t, 4) for t in v])
+
+
+def _launch_us(model, rows, dev, rounds, fused):
+    """us per launch of the four projections of `model` at `rows` window rows as its window forward runs them, over the layers' own packed copies"""
+    a = model.args
+    H, Hkv, D, hid, inter = model.n_heads, model.n_kv_heads, model.head_dim, a.hidden_size, a.intermediate_size
+    out = {}
+    for name, (N, K) in dict(qkv=((H + 2 * Hkv) * D, hid), o=(hid, H * D), gate_up=(2 * inter, hid), down=(hid, inter)).items():
+        _, waves, sm = model.G1_CFG[name]
+        KC = model._q8_chunk(name, rows, K)
+        pk = [d[name] for d in model._packed]
+        x = torch.randn(rows, K, device=dev).to(torch.bfloat16)
+        one = name == "gate_up" and fused and isinstance(pk[0], ops.PackedQ4) and ops.gateup_silu_chunked_ok(rows, inter, hid, pk[0].KC)
+        if one:
+            run = lambda i: ops.gateup_silu(x, pk[i % len(pk)], inter, hid, sm)
+        elif name == "gate_up":
+            run = lambda i: ops.silu_mul(ops.skinny_gemm(x, pk[i % len(pk)], N, K, KC, waves, sm), rows=rows, dtype=x.dtype)
+        else:
+            run = lambda i: ops.skinny_gemm(x, pk[i % len(pk)], N, K, KC, waves, sm)
+        us = [_graph_us(run, len(pk)) for _ in range(rounds)]
+        size = pk[0].nbytes() if not isinstance(pk[0], torch.Tensor) else pk[0].numel() * pk[0].element_size()
+        out[name] = dict(cfg=[KC, waves, int(sm)], launch="fused gate|up + SiLU" if one else ("projection + F3" if name == "gate_up" else "projection"),
+                         us=_spread(us), stored_bytes=size, frac_of_8TBps_on_stored_bytes=round(size / (statistics.median(us) * 1e-6) / PEAK, 4))
+    tot = sum(v["us"]["median"] for v in out.values())
+    out["sum"] = dict(us=round(tot, 2), proj_ms_per_step=round(tot * len(model._packed) / 1e3, 3),
+                      frac_of_8TBps_on_stored_bytes=round(sum(v["stored_bytes"] for v in out.values() if "stored_bytes" in v) / (tot * 1e-6) / PEAK, 4))
+    return out
+
+
+def step_quant(args):
+    from sjd_amd.engine import SJDEngine, SJDConfig
+    from sjd_amd.frontends import lumina_window_spec, lumina_prompt
+    from sjd_amd.grammar import LuminaGrammar
+    import sjd_amd.synthetic as synthetic
+    dev = torch.device("cuda:0")
+    margs = dataclasses.replace(BB.CHAMELEON_30B, num_hidden_layers=args.layers)
+    with torch.device(dev):
+        base = BB.ChameleonBackbone(margs, attn=None).to(torch.bfloat16).eval()
+    synthetic.fill_state_dict_device(base, seed=0, embed_token_scale=0.7)
+    torch.cuda.synchronize()
+    window, grid, P = 16, 48, args.prompt
+    n_img = grid * (grid + 1)
+    prompt = lumina_prompt(P, grid, grid, seed=3)
+    spec = lumina_window_spec(prompt, dev)
+    cfg = SJDConfig(jacobi_loop_interval_l=0, jacobi_loop_interval_r=grid * grid + grid - 13, max_num_new_tokens=window, guidance_scale=3.0,
+                    seed=3, max_length=P + n_img + 1, eos_token_ids=(8196,))
+    lead = int(P + n_img // 2 - (args.steps / 2.0 + args.warmup))          # the timed region sits at the mean KV length (about one token per step)
+    legs = {}
+
+    def leg(tag, src, **kw):
+        m = copy.copy(src)          # the same modules: one set of 16-bit parameters; packed copy, launch shapes, attention state and cache are the leg's own
+        m.attn = ops.HipWindowAttention()
+        m.gateup_route = {}
+        if kw is not None and "fused" not in kw:
+            m.__dict__.pop("G1_CFG", None)
+            t0 = time.time()
+            m.enable_fused(ops, gemm="sjd", **kw)
+            torch.cuda.synchronize()
+            pack_s = round(time.time() - t0, 1)
+            for other in [base] + [lg["model"] for lg in legs.values()]:
+                other._fused = m._fused          # (enable_fused re-points the shared parameters at fresh q|k|v / gate|up tensors: drop the old ones)
+        else:
+            m.gateup_fused, pack_s = kw["fused"], 0.0
+        m.setup_cache(batch=2, s_max=((P + n_img + 2 * window + 64 + 31) // 32) * 32)
+        if "fused" not in kw:
+            m.gateup_route = {}          # (enable_fused made a new one; the unfused twin leg gets its own above)
+        legs[tag] = dict(model=m, eng=SJDEngine(m, margs.vocab_size, dev, max_window=window, use_graph=True), ms=[], kv=[], tok=[], pack_s=pack_s)
+
+    leg("z12", base, compress=True)
+    leg("e4m3", base, weights="e4m3", swin_quant=True)
+    leg("mxfp4", base, weights="mxfp4", swin_quant=True)
+    legs["mxfp4"]["model"].gateup_fused = True
+    leg("mxfp4_unfused", legs["mxfp4"]["model"], fused=False)
+    tags = tuple(legs)
+    sync = torch.cuda.synchronize
+    for rnd in range(args.rounds + 1):          # round 0 is untimed practice: every hipGraph of the decode is captured in it
+        for tag in tags:
+            lg = legs[tag]
+            _, st = lg["eng"].decode(prompt, spec, LuminaGrammar(2000, 10), cfg, warmup_iters=args.warmup, timed_iters=args.steps,
+                                     on_timed_start=sync, on_timed_end=sync, lead_in_kv=lead)
+            if rnd:
+                lg["ms"].append(st.seconds / max(st.timed_nfe, 1) * 1e3)
+                lg["kv"].append([st.kv_len_start, st.kv_len])
+                lg["tok"].append(round(st.tokens / max(st.timed_nfe, 1), 3))
+    rec = dict(device=torch.cuda.get_device_name(0), peak_TBps=PEAK / 1e12,
+               workload=f"Chameleon-30B architecture (swin-norm, {args.layers} layers, synthetic weights), 1 prompt of {P} tokens, {grid}x{grid} image tokens, "
+                        "draft window 16, CFG 3.0 (32 rows per forward), bf16, 16-bit KV cache",
+               steps=args.steps, warmup=args.warmup, rounds=args.rounds, lead_in_kv=lead,
+               order="alternating " + ", ".join(tags) + " per round after one untimed round; one process, one device, one set of 16-bit parameters",
+               launch_shapes="UNTUNED: G1_CFG_30B_Q8 / G1_CFG_30B_Q4 are G1_CFG_30B_Z's values; no launch-shape sweep was run on either quantised stream",
+               per_launch_method="one hipGraph of one launch per layer's packed copy, replayed three times, the fastest taken; median / min / max over the rounds")
+    for tag, lg in legs.items():
+        m = lg["model"]
+        fused = tag == "mxfp4"
+        rec[tag] = dict(weights=m.weights, gate_up_at_32_rows=m.gateup_route.get(2 * window) if m.weights else "g1z + f3", pack_s=lg["pack_s"],
+                        G1_CFG={k: list(v) for k, v in m.G1_CFG.items()}, ms_per_step=_spread(lg["ms"]), kv_len=lg["kv"], tokens_per_step=lg["tok"],
+                        packed_bytes_per_step=m.packed_bytes(head=False), compress_stats={k: v for k, v in m.compress_stats.items() if not isinstance(v, dict)},
+                        per_launch_32_rows=_launch_us(m, 2 * window, dev, args.rounds, fused))
+    f, u, z = rec["mxfp4"]["ms_per_step"], rec["mxfp4_unfused"]["ms_per_step"], rec["z12"]["ms_per_step"]
+    rec["fused_minus_unfused_ms"] = round(f["median"] - u["median"], 4)
+    rec["unfused_leg_spread_between_rounds_ms"] = round(u["max"] - u["min"], 4)
+    rec["fused_faster_than_unfused_beyond_spread"] = bool(u["median"] - f["median"] > u["max"] - u["min"])
+    rec["largest_spread_between_rounds_ms"] = round(max(rec[t]["ms_per_step"]["max"] - rec[t]["ms_per_step"]["min"] for t in tags), 4)
+    for t in tags[1:]:
+        rec[f"{t}_minus_z12_ms"] = round(rec[t]["ms_per_step"]["median"] - z["median"], 4)
+    print(json.dumps(rec), flush=True)
+    if args.out:
+        with open(args.out, "w") as fh:
+            json.dump(rec, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--step", action="store_true")
+    ap.add_argument("--quant", action="store_true", help="--step: the quantised legs (12-bit / e4m3 / mxfp4 fused / mxfp4 unfused), alternating")
+    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--rows", type=int, default=32)
     ap.add_argument("--only", default="")
     ap.add_argument("--layers", type=int, default=BB.CHAMELEON_30B.num_hidden_layers)
@@ -151,7 +277,9 @@ def main():
     args = ap.parse_args()
     if args.sweep:
         sweep(args)
-    if args.step:
+    if args.step and args.quant:
+        step_quant(args)
+    elif args.step:
         step(args)
 
 
