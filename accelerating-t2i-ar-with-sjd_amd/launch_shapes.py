@@ -68,8 +68,8 @@ Q4_MAX_ROWS = 64                  # kernels G1q4 / G1sq4 have no wide form
 # (profiles/g1_30b_sweep.jsonl), us per launch uncompressed / 12-bit: q|k|v 30.4 / 25.2, o 23.8 / 20.3, gate|up 120.5 / 98.9, down 62.9 / 50.4
 G1_CFG_30B = dict(qkv=(1536, 8, True), o=(1536, 8, False), gate_up=(2048, 8, True), down=(1536, 8, False))
 G1_CFG_30B_Z = dict(qkv=(1792, 8, True), o=(1280, 8, True), gate_up=(2048, 8, True), down=(1536, 8, True))
-# the same backbones on the quantised streams (enable_fused(weights=..., swin_quant=True)): UNTUNED -- G1_CFG_30B_Z's values, which pass q4_chunk_errors and
-# the e4m3 rules at these dimensions (every chunk a multiple of Q4_GRANULE, <= CHUNK_CAP_32ROW, step-major so that 33..64 rows read it in halved chunks;
+# the same backbones on the quantised streams (enable_fused(weights=..., swin_quant=True)): UNTUNED -- G1_CFG_30B_Z's values, which pass quant_copy_errors on
+# either granule at these dimensions (every chunk a multiple of Q4_GRANULE, <= CHUNK_CAP_32ROW, step-major so that 33..64 rows read it in halved chunks;
 # G1_CFG_30B's tile-major chunks of 1536 cannot be halved); no launch-shape sweep was run on either stream.  gate|up keeps the four chunks of 2048: the
 # copy G1q / G1q4 + F3 stream, and on "mxfp4" at <= 32 rows the one the fused K = 8192 launch streams (gateup_silu_chunked_ok)
 G1_CFG_30B_Q8 = dict(G1_CFG_30B_Z)
@@ -110,7 +110,7 @@ LLAMAGEN_SETS = {      # (head_dim 100 stored 128 wide, max_rows) -> (G1_CFG, HE
     (True, 256): (dict(qkv=(1088, 4, False), o=(512, 4, True), gate_up=(1088, 8, True), down=(1088, 4, True)), (1600, 4, True)),
 }
 # LlamaGenBackbone.enable_fused(weights="e4m3" / "mxfp4" / their "_as_bf16" twins): the sets above with what ONE quantised copy needs to serve every row
-# count up to max_rows (llamagen_quant_errors checks it) -- every chunk a multiple of Q4_GRANULE (320 -> 384; GPT-3B's 1088 -> 1152, which keeps its plane
+# count up to max_rows (quant_copy_errors checks it) -- every chunk a multiple of Q4_GRANULE (320 -> 384; GPT-3B's 1088 -> 1152, which keeps its plane
 # counts: 3 for K = 3200, 8 for K = 8704), <= CHUNK_CAP_64ROW so that 33..64 rows stage it as it is, and above 64 rows 3, 4, 6 or 8 column tiles per
 # workgroup (two tiles have no form at 65..96 rows: o 2 -> 3, the other two-tile shapes -> 4).  One set per key serves both formats (128 is a multiple of
 # e4m3's 32).  UNTUNED: no launch-shape sweep was run on either stream.  The output head is not quantised and keeps the HEAD_CFG of LLAMAGEN_SETS.
@@ -130,27 +130,51 @@ def llamagen_dims(dim, n_head, head_dim, inter, head_pad=None):
     return dict(qkv=(3 * n_head * head_dim, dim), o=(dim, n_head * (head_pad or head_dim)), gate_up=(2 * inter, dim), down=(dim, inter))
 
 
-def llamagen_quant_errors(cfg, dims, max_rows, granule=128, head_cfg=None):
+def chameleon_dims(hidden, n_heads, n_kv_heads, head_dim, inter):
+    """the (N, K) of a Chameleon / Emu3 layer's four projections"""
+    return dict(qkv=((n_heads + 2 * n_kv_heads) * head_dim, hidden), o=(hidden, n_heads * head_dim), gate_up=(2 * inter, hidden), down=(hidden, inter))
+
+
+QUANT_REASONS = ("granule", "chunk", "halved", "tiles")
+
+
+def quant_copy_errors(cfg, dims, max_rows, granule, head_cfg=None, reasons=QUANT_REASONS):
     """[(name, why)]: what keeps ONE quantised copy packed on launch shapes `cfg` (dims: the projections' (N, K)) from serving every row count up to
-    max_rows.  why: "granule" (K or the chunk no multiple of `granule`: Q4_GRANULE for MXFP4, 32 for e4m3), "chunk" (above CHUNK_CAP_32ROW: kernels
-    G1q / G1q4 stage it whole), "halved" (none that 33..64 rows can stage: <= CHUNK_CAP_64ROW, or halvable by halved_chunk to whole granules), "tiles"
-    (max_rows > 64: kernels G1wq / G1wq4 take 3, 4, 6 or 8 column tiles per workgroup -- two have no form at 65..96 rows; head_cfg, which streams
-    16-bit weights on kernel G1w, any of WIDE_TILES)"""
+    max_rows -- the first of `reasons` that applies to each projection.  why: "granule" (K or the chunk no multiple of `granule`: Q4_GRANULE for MXFP4,
+    32 for e4m3's record pairs), "chunk" (above CHUNK_CAP_32ROW: kernels G1q / G1q4 stage it whole), "halved" (none that 33..64 rows can stage:
+    <= CHUNK_CAP_64ROW, or halvable by halved_chunk to whole granules), "tiles" (max_rows > 64: kernels G1wq / G1wq4 take 3, 4, 6 or 8 column tiles per
+    workgroup -- two have no form at 65..96 rows; head_cfg, which streams 16-bit weights on kernel G1w, any of WIDE_TILES).  The caller passes the
+    head_cfg and the reasons its call site checks when the weights are packed."""
     bad = []
     for name, (KC, tiles, sm) in cfg.items():
         K_ = dims[name][1]
         kc = min(KC, K_)
-        if K_ % granule or KC % granule:
-            bad.append((name, "granule"))
-        elif kc > CHUNK_CAP_32ROW:
-            bad.append((name, "chunk"))
-        elif halved_chunk(kc, K_, sm) > CHUNK_CAP_64ROW or halved_chunk(kc, K_, sm) % granule:
-            bad.append((name, "halved"))
-        elif max_rows > 64 and (tiles not in WIDE_TILES or tiles == 2):
-            bad.append((name, "tiles"))
+        half = halved_chunk(kc, K_, sm)
+        fault = dict(granule=K_ % granule or KC % granule, chunk=KC > CHUNK_CAP_32ROW, halved=half > CHUNK_CAP_64ROW or half % granule,
+                     tiles=max_rows > 64 and (tiles not in WIDE_TILES or tiles == 2))
+        bad += [(name, why) for why in reasons if fault[why]][:1]
     if head_cfg is not None and max_rows > 64 and head_cfg[1] not in WIDE_TILES:
         bad.append(("head", "tiles"))
     return bad
+
+
+def llamagen_quant_errors(cfg, dims, max_rows, granule=128, head_cfg=None):          # (the names the format tests call the rule by)
+    return quant_copy_errors(cfg, dims, max_rows, granule, head_cfg)
+
+
+def q4_chunk_errors(cfg, dims):
+    return quant_copy_errors(cfg, dims, Q4_MAX_ROWS, Q4_GRANULE)
+
+
+def quant_copy_refusal(name, why, granule, shape, K):
+    """the sentence enable_fused refuses with: one of quant_copy_errors' (name, why), the launch shape it names and that projection's K"""
+    if name == "head":
+        return f"the output head runs on kernel G1w at these row counts -- HEAD_CFG[1] must be one of {WIDE_TILES}; HEAD_CFG = {tuple(shape)}"
+    return dict(granule=f"K and the chunk must be multiples of {granule}",
+                chunk=f"kernels G1q / G1q4 stage the whole activation chunk in LDS -- every chunk must be <= {CHUNK_CAP_32ROW} columns",
+                halved=f"windows of 33..64 rows need a chunk of <= {CHUNK_CAP_64ROW} columns, or a step-major packing whose halved chunk is a multiple of {granule}",
+                tiles="windows of more than 64 rows take 3, 4, 6 or 8 column tiles per workgroup on the quantised streams (kernels G1wq / G1wq4 have no form of "
+                      "three row tiles x two tiles)")[why] + f"; G1_CFG[{name!r}] = {tuple(shape)} with K = {K}"
 
 
 def default_shapes(dtype, g1_given, head_given, wide_hidden, gqa, compress, weights, max_rows, vocab_size):
@@ -175,22 +199,6 @@ def halved_chunk(kc, K, step_major):
     return kc
 
 
-def q4_chunk_errors(cfg, dims):
-    """[(name, why)]: what keeps launch shapes `cfg` from the MXFP4 stream, dims = the projections' (N, K).  why: "granule" (K or the chunk no multiple of
-    Q4_GRANULE), "chunk" (above CHUNK_CAP_32ROW), "halved" (no chunk that 33..64 rows can stage: the halved chunk must itself be whole granules)"""
-    bad = []
-    for name, (KC, _, sm) in cfg.items():
-        K_ = dims[name][1]
-        kc = min(KC, K_)
-        if K_ % Q4_GRANULE or KC % Q4_GRANULE:
-            bad.append((name, "granule"))
-        elif kc > CHUNK_CAP_32ROW:
-            bad.append((name, "chunk"))
-        elif halved_chunk(kc, K_, sm) > CHUNK_CAP_64ROW or halved_chunk(kc, K_, sm) % Q4_GRANULE:
-            bad.append((name, "halved"))
-    return bad
-
-
 # Under enable_fused(weights=...) kernel G1q stages the whole activation chunk in LDS: <= CHUNK_CAP_32ROW columns up to 32 rows, <= CHUNK_CAP_64ROW at
 # 33..64.  A projection packed with a longer chunk (G1_CFG_Q8's gate|up: two K halves of 2048, the copy the fused 32-row launch streams) is read at
 # 33..64 rows in HALVED chunks until they fit: a step-major packing whose chunks are whole record pairs (K and the chunk multiples of 32) is the same
@@ -208,21 +216,11 @@ def chunk_for_rows(name, shape, T, K, weights=None, max_rows=64):
     return kc
 
 
-def check_set(cfg, head_cfg, max_rows, q8_dims=None, head_name="head"):
-    """[(name, why)]: what keeps the set from serving windows of up to max_rows (> 64) rows.  why: "tiles" (G1w / G1wq does not take the count); with q8_dims (the
-    projections' (N, K): ONE 8-bit copy serves every row count) also "pairs" (K or the chunk no multiple of 32) and "chunk" (none that 33..64 rows can stage)"""
-    bad = []
-    for name, (KC, tiles, sm) in cfg.items():
-        K_ = q8_dims[name][1] if q8_dims else 0
-        if tiles not in WIDE_TILES or (q8_dims and tiles == 2):
-            bad.append((name, "tiles"))
-        elif q8_dims and (K_ % 32 or KC % 32):
-            bad.append((name, "pairs"))
-        elif q8_dims and halved_chunk(min(KC, K_), K_, sm) > CHUNK_CAP_64ROW:
-            bad.append((name, "chunk"))
-    if head_cfg is not None and (not q8_dims or max_rows > Z_MAX_ROWS) and head_cfg[1] not in WIDE_TILES:          # (up to 128 rows the 8-bit stream's head keeps its own kernels)
-        bad.append((head_name, "tiles"))
-    return bad
+def check_set(cfg, head_cfg, head_name="head"):
+    """[(name, "tiles")]: the launch shapes of a 16-bit set (head_cfg: the output head's, or None) whose column-tile count kernel G1w does not take: what keeps
+    the set from windows of more than 64 rows (a quantised copy: quant_copy_errors)"""
+    return ([(name, "tiles") for name, (_, tiles, _) in cfg.items() if tiles not in WIDE_TILES]
+            + [(head_name, "tiles")] * (head_cfg is not None and head_cfg[1] not in WIDE_TILES))
 
 
 def llamagen_row_limit(backbone):
@@ -254,7 +252,7 @@ def serves_rows(backbone, rows, window=1, head=False):
         return None
     if isinstance(packed[0]["qkv"], backbone._ops.PackedZ):
         return "12-bit", Z_MAX_ROWS
-    bad = check_set(backbone.G1_CFG, backbone.HEAD_CFG if head and getattr(backbone, "_packed_head", None) is not None else None, rows, head_name="lm_head (HEAD_CFG)")
+    bad = check_set(backbone.G1_CFG, backbone.HEAD_CFG if head and getattr(backbone, "_packed_head", None) is not None else None, head_name="lm_head (HEAD_CFG)")
     return ("tiles", [name for name, _ in bad]) if bad else None
 
 

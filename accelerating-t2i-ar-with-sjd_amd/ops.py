@@ -512,9 +512,8 @@ def pack_weight_z(weight, KC, step_major=False, gateup=False):
     return PackedZ(data, exc, N, K, KC, step_major, total, raw_index, raw_tiles, raw_view, stats)
 
 
-class PackedQ8:
-    """A packed weight in the 8-bit (OCP e4m3fn) stream format of kernels G1q / G1sq (see pack_weight_q8): `data` uint8 [N * K + 4 * N] = the
-    records, one byte per weight, then the fp32 column scales [N] at byte offset N * K.  LOSSY: the kernels multiply by dequant(), exactly."""
+class _PackedQuant:
+    """what the quantised stream formats share: `data` uint8 = the records, then the scales; LOSSY -- the kernels multiply by dequant(), exactly"""
 
     dtype = torch.bfloat16          # the activation type the kernels take (and the type of dequant())
 
@@ -527,6 +526,18 @@ class PackedQ8:
 
     def nbytes(self):
         return self.data.numel()
+
+
+def _rel_rms_error(weight, dequantised):
+    """RMS(w - dequant) / RMS(w) (0 for an all-zero matrix): what compress_stats judges a quantised matrix by"""
+    wf = weight.float()
+    rms = float(wf.pow(2).mean().sqrt())
+    return float((wf - dequantised.float()).pow(2).mean().sqrt()) / rms if rms > 0 else 0.0
+
+
+class PackedQ8(_PackedQuant):
+    """A packed weight in the 8-bit (OCP e4m3fn) stream format of kernels G1q / G1sq (see pack_weight_q8): `data` uint8 [N * K + 4 * N] = the
+    records, one byte per weight, then the fp32 column scales [N] at byte offset N * K.  LOSSY: the kernels multiply by dequant(), exactly."""
 
     def reads_as(self, KC):
         """can a launch with split-K chunk KC stream this buffer?  The chunk it was packed with -- or, step-major with K and both chunks multiples of
@@ -613,12 +624,8 @@ def pack_weight_q8(weight, KC, step_major=False, gateup=False):
         else:
             parts.append(torch.cat([pr.reshape(T, P * 1024), hf], dim=1).reshape(-1))
     data = torch.cat(parts + [scale.contiguous().view(torch.uint8)]).contiguous()
-    wf = weight.float()
-    deq = q.view(FP8).float() * scale[:, None]
-    rms = float(wf.pow(2).mean().sqrt())
     lg = torch.log2(scale)
-    stats = dict(rel_rms_error=(float((wf - deq).pow(2).mean().sqrt()) / rms) if rms > 0 else 0.0,
-                 scale_exp_min=int(lg.min()), scale_exp_max=int(lg.max()))
+    stats = dict(rel_rms_error=_rel_rms_error(weight, q.view(FP8).float() * scale[:, None]), scale_exp_min=int(lg.min()), scale_exp_max=int(lg.max()))
     return PackedQ8(data, N, K, KC, step_major, stats)
 
 
@@ -671,21 +678,9 @@ def dequantize_mxfp4(codes, scale_exp):
     return (lut[nib].reshape(N, K // 32, 32) * scale[:, :, None]).reshape(N, K).to(torch.bfloat16)
 
 
-class PackedQ4:
+class PackedQ4(_PackedQuant):
     """A packed weight in the MXFP4 stream format of kernels G1q4 / G1sq4 (see pack_weight_q4): `data` uint8 [N * K / 2 + N * K / 32] = the code
     records, four bits per weight, then the e8m0 scale bytes at byte offset N * K / 2.  LOSSY: the kernels multiply by dequant(), exactly."""
-
-    dtype = torch.bfloat16          # the activation type the kernels take (and the type of dequant())
-
-    def __init__(self, data, N, K, KC, step_major, stats=None):
-        self.data, self.N, self.K, self.KC, self.step_major = data, int(N), int(K), int(KC), bool(step_major)
-        self.stats = stats or {}
-
-    def numel(self):
-        return self.N * self.K
-
-    def nbytes(self):
-        return self.data.numel()
 
     def reads_as(self, KC):
         """can a launch with split-K chunk KC stream this buffer?  The chunk it was packed with -- or, step-major, any other multiple of the granule:
@@ -757,11 +752,7 @@ def pack_weight_q4(weight, KC, step_major=False, gateup=False):
         sparts.append(grp.reshape(-1))
     data = torch.cat(cparts + sparts).contiguous()
     assert data.numel() == N * K // 2 + N * K // 32
-    wf = weight.float()
-    deq = dequantize_mxfp4(codes, se).float()
-    rms = float(wf.pow(2).mean().sqrt())
-    stats = dict(rel_rms_error=(float((wf - deq).pow(2).mean().sqrt()) / rms) if rms > 0 else 0.0,
-                 scale_exp_min=int(se.min()) - 127, scale_exp_max=int(se.max()) - 127)
+    stats = dict(rel_rms_error=_rel_rms_error(weight, dequantize_mxfp4(codes, se)), scale_exp_min=int(se.min()) - 127, scale_exp_max=int(se.max()) - 127)
     return PackedQ4(data, N, K, KC, step_major, stats)
 
 

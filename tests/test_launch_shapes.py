@@ -4,10 +4,12 @@ The expected values below were recorded from the code BEFORE the launch-shape ru
 whoever changes a set, a limit or a refusal text changes a literal here knowingly.  Chameleon-family backbones are built on the meta device at
 the real Lumina-7B / Emu3-8B / Chameleon-30B sizes (one layer): the choice and the chunk arithmetic need shapes, not values, and the two packers
 that look at values are replaced by stand-ins that keep their `None` rule (pack_weight_z declines fp16 and KC > 4096).  The LlamaGen backbones
-(head_dim 64, and head_dim 100 stored 128 wide) are tiny and really packed.  LlamaGen's enable_fused has no `compress` / `weights`; its axes are
-dtype x max_rows x untuned_fp16 (x padded_batch at head_dim 100)."""
+(head_dim 64, and head_dim 100 stored 128 wide) are tiny and really packed.  LlamaGen's enable_fused has no `compress`; its axes are
+dtype x max_rows x untuned_fp16 (x padded_batch at head_dim 100), and `weights`.
+
+The tables written later -- MXFP4 and swin_quant on the Chameleon families, LlamaGen's `weights`, and the refusals of a quantised copy by reason and call
+site -- were recorded the same way from the code before ITS five copies of the quantised-copy rule became one (LS.quant_copy_errors)."""
 import dataclasses
-import itertools
 import types
 
 import pytest
@@ -44,13 +46,25 @@ class _Q8(real_ops.PackedQ8):
         return self._w
 
 
+class _Q4(real_ops.PackedQ4):
+    def __init__(self, w, KC, sm):
+        super().__init__(None, w.shape[0], w.shape[1], KC, sm, dict(rel_rms_error=0.0))
+        self._w = w
+
+    def nbytes(self):
+        return self.N * self.K * 17 // 32
+
+    def dequant(self):
+        return self._w
+
+
 class _Prefill(Exception):
     pass
 
 
 class _Ops:
     """sjd_amd.ops with the two value-dependent packers replaced for meta weights, and the first kernel of the prefill path made a signal"""
-    PackedZ, PackedQ8 = real_ops.PackedZ, real_ops.PackedQ8
+    PackedZ, PackedQ8, PackedQ4 = real_ops.PackedZ, real_ops.PackedQ8, real_ops.PackedQ4
 
     def __getattr__(self, name):
         return getattr(real_ops, name)
@@ -64,6 +78,14 @@ class _Ops:
         if w.dtype != torch.bfloat16:
             raise ValueError("quantize_e4m3: bf16 weights only")
         return _Q8(w, KC, step_major)
+
+    @staticmethod
+    def pack_weight_q4(w, KC, step_major=False, gateup=False):
+        if w.dtype != torch.bfloat16:
+            raise ValueError("quantize_mxfp4: bf16 weights only")
+        if w.shape[1] % 128 or KC < 128 or KC % 128:          # (the real packer's rule, and its text)
+            raise ValueError(f"pack_weight_q4: K and KC must be multiples of 128 (whole records and scale dwords); got K = {tuple(w.shape)[-1]}, KC = {KC}")
+        return _Q4(w, KC, step_major)
 
     @staticmethod
     def add_rmsnorm(*a, **k):
@@ -104,33 +126,48 @@ def _chunks(m):
     return out
 
 
-def observe_chameleon(family, dtype, compress, weights, max_rows):
+def observe_chameleon(family, dtype, compress, weights, max_rows, swin_quant=False, g1_cfg=None, head_cfg=None):
     m = _chameleon(family, dtype)
+    given = {k: v for k, v in (("G1_CFG", g1_cfg), ("HEAD_CFG", head_cfg)) if v is not None}
+    m.__dict__.update(given)
     try:
-        m.enable_fused(OPS, gemm="sjd", compress=compress, weights=weights, max_rows=max_rows)
+        m.enable_fused(OPS, gemm="sjd", compress=compress, weights=weights, max_rows=max_rows, swin_quant=swin_quant)
     except ValueError as e:
-        assert "_packed" not in m.__dict__ and "weights" not in m.__dict__ and "G1_CFG" not in m.__dict__       # a refused call leaves the backbone as it was
+        assert "_packed" not in m.__dict__ and "weights" not in m.__dict__ and m.__dict__.get("G1_CFG") == g1_cfg       # a refused call leaves the backbone as it was
+        assert m.__dict__.get("HEAD_CFG") == head_cfg and "max_rows" not in m.__dict__
         return str(e)
     return dict(g1=tuple(m.G1_CFG[k] for k in NAMES), head=tuple(m.HEAD_CFG), max_rows=m.__dict__.get("max_rows"), given=m._max_rows_given,
                 qkv=_kind(m._packed[0]["qkv"]), head_kind=_kind(m._packed_head), chunks=_chunks(m))
 
 
 TINY_LG = {"llamagen64": dict(dim=128, n_layer=1, n_head=2, vocab_size=1024, block_size=64),
-           "llamagen100": dict(dim=800, n_layer=1, n_head=8, vocab_size=1024, block_size=64)}
+           "llamagen100": dict(dim=800, n_layer=1, n_head=8, vocab_size=1024, block_size=64),
+           "gpt_xxl": dict(dim=1536, n_layer=1, n_head=24)}          # the real widths (K = 1536, 4096 for the down projection), for refusals only
+META_LG = ("gpt_xxl",)
 
 
-def observe_llamagen(family, dtype, max_rows, untuned_fp16, padded_batch):
+def observe_llamagen(family, dtype, max_rows, untuned_fp16, padded_batch, weights=None, g1_cfg=None, head_cfg=None):
+    """weights / g1_cfg / head_cfg given: the outcome also names compress_stats' keys (a quantised copy adds its own)"""
     torch.manual_seed(0)
-    m = BB.LlamaGenBackbone(BB.LlamaGenArgs(**TINY_LG[family])).to(DTYPES[dtype])
+    with torch.device("meta" if family in META_LG else "cpu"):
+        m = BB.LlamaGenBackbone(BB.LlamaGenArgs(**TINY_LG[family])).to(DTYPES[dtype])
     kw = {} if max_rows is None else dict(max_rows=max_rows)
     if family == "llamagen100":
         kw.update(pad_head_dim=True, padded_batch=padded_batch)
+    if weights is not None:
+        kw.update(weights=weights)
+    given = {k: v for k, v in (("G1_CFG", g1_cfg), ("HEAD_CFG", head_cfg)) if v is not None}
+    m.__dict__.update(given)
     try:
         m.enable_fused(real_ops, gemm="sjd", untuned_fp16=untuned_fp16, **kw)
     except ValueError as e:
+        assert all(k not in m.__dict__ for k in ("_packed", "_ops", "weights", "max_rows")) and {k: m.__dict__.get(k) for k in given} == given
         return str(e)
-    return dict(g1=tuple(m.G1_CFG[k] for k in NAMES), head=tuple(m.HEAD_CFG), max_rows=m.max_rows, fused_rows=m._fused_rows,
-                qkv=_kind(m._packed[0]["qkv"]), head_kind=_kind(m._packed_head), head_pad=m._head_pad)
+    out = dict(g1=tuple(m.G1_CFG[k] for k in NAMES), head=tuple(m.HEAD_CFG), max_rows=m.max_rows, fused_rows=m._fused_rows,
+               qkv=_kind(m._packed[0]["qkv"]), head_kind=_kind(m._packed_head), head_pad=m._head_pad)
+    if weights is not None or given:
+        out.update(weights=m.weights, stats=tuple(sorted(m.compress_stats)))
+    return out
 
 
 # rows = n_prompts x n_batch x max_window, and the (B, n) window shapes of the same row counts
@@ -205,15 +242,6 @@ def observe_window(m, key):
         return "prefill"
     except ValueError as e:
         return str(e)
-
-
-def chameleon_cases():
-    return list(itertools.product(CHAMELEON, DTYPES, (True, False), (None, "e4m3", "e4m3_as_bf16"), MAX_ROWS))
-
-
-def llamagen_cases():
-    return ([("llamagen64", d, r, u, False) for d in DTYPES for r in MAX_ROWS for u in (False, True)] +
-            [("llamagen100", d, r, u, p) for d in DTYPES for r in MAX_ROWS for u in (False, True) for p in (False, True)])
 
 
 # ------------------------------------------------------------------------------------------ what the code did before the rule moved
@@ -299,6 +327,55 @@ def test_chameleon_enable_fused(family, dtype, compress, weights):
         assert observe_chameleon(family, dtype, compress, weights, max_rows) == want, max_rows
 
 
+# The axes added since: weights="mxfp4" and its twin on every family, and swin_quant=True on the 30B class -- recorded the same way, from the code before
+# the quantised-copy rule was gathered into one function.  (family, dtype, compress, weights, swin_quant) -> the outcome at max_rows unset, 64, 128, 256
+Q4_WIDE = {w: tuple(f"weights={w!r} serves windows of at most 64 rows (kernels G1q4 / G1sq4 have no wide form): max_rows is None or 64, got {r}" for r in (128, 256))
+           for w in ("mxfp4", "mxfp4_as_bf16")}
+SWIN_WIDE = {w: tuple(f"weights={w!r} serves swin-norm backbones at windows of at most 64 rows (one prompt per forward): max_rows is None or 64, got {r}" for r in (128, 256))
+             for w in ("e4m3", "e4m3_as_bf16")}
+NEEDS_BF16 = "weights={w!r} needs bf16 weights (got torch.float16): the dequantised values are bf16 numbers, fp16's exponent range does not hold them"
+NO_SWIN = "weights={w!r} is not served for swin-norm backbones (swin_norm=True or model_parallel_size > 1)"
+SWIN_1792, SWIN_1536 = (1792,) + (896,) * 8, (1536,) + (768,) * 8
+
+
+def narrow(served, w):
+    """max_rows unset and 64 served, 128 and 256 refused: the MXFP4 stream anywhere, either stream on a swin-norm backbone"""
+    return (served, dict(served, given=T_)) + (Q4_WIDE[w] if w in Q4_WIDE else SWIN_WIDE[w])
+
+
+def swin_q(kind, w):
+    return narrow(ok(SET_30B_Z, HEAD, 64, F_, (kind, "NoneType"), qkv=SWIN_1792, gate_up=NARROW_2048, down=SWIN_1536), w)
+
+
+EXPECTED_CHAMELEON_MORE = {}
+for _c, _head in ((True, "Z"), (False, "bfloat16")):
+    for _w, _k in (("mxfp4", "Q4"), ("mxfp4_as_bf16", "bfloat16")):
+        EXPECTED_CHAMELEON_MORE["lumina7b", "bf16", _c, _w, False] = narrow(ok(SET_Z, HEAD, 64, F_, (_k, _head), gate_up=NARROW_2048), _w)
+        EXPECTED_CHAMELEON_MORE["emu3_8b", "bf16", _c, _w, False] = narrow(ok(SET_EMU3_Q8, HEAD_WIDE, 64, F_, (_k, _head)), _w)
+        EXPECTED_CHAMELEON_MORE["lumina7b", "fp16", _c, _w, False] = EXPECTED_CHAMELEON_MORE["emu3_8b", "fp16", _c, _w, False] = \
+            EXPECTED_CHAMELEON_MORE["chameleon30b", "fp16", _c, _w, True] = (NEEDS_BF16.format(w=_w),) * 2 + Q4_WIDE[_w]
+        EXPECTED_CHAMELEON_MORE["chameleon30b", "bf16", _c, _w, False] = EXPECTED_CHAMELEON_MORE["chameleon30b", "fp16", _c, _w, False] = \
+            (NO_SWIN.format(w=_w),) * 2 + Q4_WIDE[_w]
+        EXPECTED_CHAMELEON_MORE["chameleon30b", "bf16", _c, _w, True] = swin_q(_k, _w)
+    for _w, _k in (("e4m3", "Q8"), ("e4m3_as_bf16", "bfloat16")):
+        EXPECTED_CHAMELEON_MORE["chameleon30b", "bf16", _c, _w, True] = swin_q(_k, _w)
+        EXPECTED_CHAMELEON_MORE["chameleon30b", "fp16", _c, _w, True] = (NEEDS_BF16.format(w=_w),) * 4
+    for _d in DTYPES:          # (without weights swin_quant changes nothing)
+        EXPECTED_CHAMELEON_MORE["chameleon30b", _d, _c, None, True] = EXPECTED_CHAMELEON["chameleon30b", _d, _c, None]
+
+
+def chameleon_cases():
+    """every (family, dtype, compress, weights, swin_quant) of the two tables"""
+    return [k + (False,) for k in EXPECTED_CHAMELEON] + list(EXPECTED_CHAMELEON_MORE)
+
+
+@pytest.mark.parametrize("family,dtype,compress,weights,swin_quant", sorted(EXPECTED_CHAMELEON_MORE, key=str))
+def test_chameleon_enable_fused_mxfp4_and_swin_quant(family, dtype, compress, weights, swin_quant):
+    assert len(EXPECTED_CHAMELEON_MORE) == 44 and len(set(chameleon_cases())) == 80          # 3 x 2 x 2 x 2 MXFP4 + 2 x 2 x 5 with swin_quant
+    for max_rows, want in zip(MAX_ROWS, EXPECTED_CHAMELEON_MORE[family, dtype, compress, weights, swin_quant]):
+        assert observe_chameleon(family, dtype, compress, weights, max_rows, swin_quant=swin_quant) == want, max_rows
+
+
 def lg(g1, head, rows, kind, head_pad=None):
     return dict(g1=g1, head=head, max_rows=rows, fused_rows=rows, qkv=kind, head_kind=kind, head_pad=head_pad)
 
@@ -334,6 +411,52 @@ EXPECTED_LLAMAGEN = {
 def test_llamagen_enable_fused(family, dtype, untuned_fp16, padded_batch):
     for max_rows, want in zip(MAX_ROWS, EXPECTED_LLAMAGEN[family, dtype, untuned_fp16, padded_batch]):
         assert observe_llamagen(family, dtype, max_rows, untuned_fp16, padded_batch) == want, max_rows
+
+
+# LlamaGen's `weights` axis, added since: LS.LLAMAGEN_QUANT_SETS, what the layers are packed as, and compress_stats' keys
+LGQ_64 = (((256, 2, T_), (256, 2, F_), (384, 2, F_), (512, 2, F_)), (640, 4, T_), 64)
+LGQ_128 = (((384, 4, F_), (256, 3, F_), (384, 4, T_), (512, 4, F_)), (640, 4, T_), 128)
+LGQ_256 = (((256, 4, F_), (256, 3, F_), (384, 4, T_), (512, 4, F_)), (640, 4, T_), 256)
+LGQ3B_64 = (((640, 8, T_), (512, 4, F_), (1152, 8, T_), (1152, 4, T_)), (1088, 8, T_), 64)
+LGQ3B_128 = (((1152, 4, F_), (512, 4, F_), (1152, 8, F_), (1152, 4, T_)), (1600, 4, T_), 128)
+LGQ3B_256 = (((1152, 4, F_), (512, 4, T_), (1152, 8, T_), (1152, 4, T_)), (1600, 4, T_), 256)
+LG_WEIGHTS = {"e4m3": ("PackedQ8", ("bytes_packed", "bytes_raw", "matrices", "q8_bytes_packed", "q8_matrices", "rel_rms_error")),
+              "e4m3_as_bf16": ("bfloat16", ("bytes_packed", "bytes_raw", "matrices", "q8_matrices", "rel_rms_error")),
+              "mxfp4": ("PackedQ4", ("bytes_packed", "bytes_raw", "matrices", "q4_bytes_packed", "q4_matrices", "rel_rms_error")),
+              "mxfp4_as_bf16": ("bfloat16", ("bytes_packed", "bytes_raw", "matrices", "q4_matrices", "rel_rms_error"))}
+LG_UNTUNED = "weights={w!r} packs bf16 weights: untuned_fp16=True does not go with it"
+LG_DIM_800 = "weights={w!r}: dim 800 and the intermediate size 2304 must be multiples of 128 (the MXFP4 stream travels in whole ring trips of eight k-steps)"
+
+
+def lgq(g1, head, rows, w, head_pad=None):
+    return dict(lg(g1, head, rows, "bfloat16", head_pad), qkv=LG_WEIGHTS[w][0], weights=w, stats=LG_WEIGHTS[w][1])
+
+
+# (family, dtype, weights, untuned_fp16, padded_batch) -> the outcome at max_rows unset, 64, 128, 256
+EXPECTED_LLAMAGEN_WEIGHTS = {}
+for _w in LG_WEIGHTS:
+    EXPECTED_LLAMAGEN_WEIGHTS["llamagen64", "bf16", _w, False, False] = (lgq(*LGQ_64, _w), lgq(*LGQ_64, _w), lgq(*LGQ_128, _w), lgq(*LGQ_256, _w))
+    EXPECTED_LLAMAGEN_WEIGHTS["llamagen64", "bf16", _w, True, False] = (LG_UNTUNED.format(w=_w),) * 4
+    EXPECTED_LLAMAGEN_WEIGHTS["llamagen64", "fp16", _w, False, False] = EXPECTED_LLAMAGEN_WEIGHTS["llamagen64", "fp16", _w, True, False] = (NEEDS_BF16.format(w=_w),) * 4
+    # head_dim 100 stored 128 wide at dim 800: whole e4m3 pairs (the o projection's K is 8 x 128), not whole MXFP4 trips
+    if _w in ("e4m3", "e4m3_as_bf16"):
+        EXPECTED_LLAMAGEN_WEIGHTS["llamagen100", "bf16", _w, False, False] = (lgq(*LGQ3B_64, _w, 128), lgq(*LGQ3B_64, _w, 128), LG_PAD[128], LG_PAD[256])
+        EXPECTED_LLAMAGEN_WEIGHTS["llamagen100", "bf16", _w, False, True] = (lgq(*LGQ3B_64, _w, 128), lgq(*LGQ3B_64, _w, 128), lgq(*LGQ3B_128, _w, 128), lgq(*LGQ3B_256, _w, 128))
+    else:
+        EXPECTED_LLAMAGEN_WEIGHTS["llamagen100", "bf16", _w, False, False] = (LG_DIM_800.format(w=_w),) * 2 + (LG_PAD[128], LG_PAD[256])
+        EXPECTED_LLAMAGEN_WEIGHTS["llamagen100", "bf16", _w, False, True] = (LG_DIM_800.format(w=_w),) * 4
+
+
+def llamagen_cases():
+    """every (family, dtype, weights, untuned_fp16, padded_batch) of the two tables"""
+    return [(f, d, None, u, p) for f, d, u, p in EXPECTED_LLAMAGEN] + list(EXPECTED_LLAMAGEN_WEIGHTS)
+
+
+@pytest.mark.parametrize("family,dtype,weights,untuned_fp16,padded_batch", sorted(EXPECTED_LLAMAGEN_WEIGHTS))
+def test_llamagen_enable_fused_weights(family, dtype, weights, untuned_fp16, padded_batch):
+    assert len(EXPECTED_LLAMAGEN_WEIGHTS) == 24 and len(set(llamagen_cases())) == 36
+    for max_rows, want in zip(MAX_ROWS, EXPECTED_LLAMAGEN_WEIGHTS[family, dtype, weights, untuned_fp16, padded_batch]):
+        assert observe_llamagen(family, dtype, max_rows, untuned_fp16, padded_batch, weights=weights) == want, max_rows
 
 
 # SJDBatchEngine's answers: "{rows}" is the case's row count, "{to}" the max_rows it names (128 up to 128 rows, 256 above)
@@ -415,3 +538,73 @@ def test_rows_served(name, monkeypatch):
             assert observe_window(b, key) == want.format(rows=B * n), key
     else:
         assert not isinstance(b, BB.ChameleonBackbone)
+
+
+# ------------------------------------------------------------------------------------------ refusals of a quantised copy, by reason and call site
+# Each case changes ONE projection (or the head) of a set that passes, so that exactly one reason applies; the backbones have the real dimensions
+# (Lumina-7B, Chameleon-30B, LlamaGen GPT-XXL: one layer on the meta device -- a refusal comes before anything is packed).  The full text is pinned.
+def _cham_site(family, weights, max_rows, base, swin_quant=False):
+    return lambda g1=None, head=None: observe_chameleon(family, "bf16", True, weights, max_rows, swin_quant, dict(getattr(BB.LS, base), **(g1 or {})), head)
+
+
+def _lg_site(weights, max_rows):
+    return lambda g1=None, head=None: observe_llamagen("gpt_xxl", "bf16", max_rows, False, False, weights, dict(BB.LS.LLAMAGEN_QUANT_SETS[False, max_rows][0], **(g1 or {})), head)
+
+
+REFUSAL_SITES = {
+    "chameleon e4m3": _cham_site("lumina7b", "e4m3", None, "G1_CFG_Q8"),
+    "chameleon e4m3 wide": _cham_site("lumina7b", "e4m3", 256, "G1_CFG_Q8_WIDE"),
+    "chameleon mxfp4": _cham_site("lumina7b", "mxfp4", None, "G1_CFG_Q4"),
+    "swin e4m3": _cham_site("chameleon30b", "e4m3", None, "G1_CFG_30B_Q8", True),
+    "swin mxfp4": _cham_site("chameleon30b", "mxfp4", None, "G1_CFG_30B_Q4", True),
+    "llamagen e4m3 64": _lg_site("e4m3", 64), "llamagen e4m3 256": _lg_site("e4m3", 256),
+    "llamagen mxfp4 64": _lg_site("mxfp4", 64), "llamagen mxfp4 256": _lg_site("mxfp4", 256),
+}
+# one sentence per reason, whatever the call site (the literals recorded first held four near copies of each: kernel G1q / G1q4 / "G1q / G1q4", "chunks of" / "a chunk
+# of", a lead-in naming the stream's record pairs or ring trips; Chameleon's e4m3 chunk cap printed the whole set instead of the projection and its K)
+R_GRANULE = "K and the chunk must be multiples of %d"
+R_CHUNK = "kernels G1q / G1q4 stage the whole activation chunk in LDS -- every chunk must be <= 2560 columns"
+R_HALVED = "windows of 33..64 rows need a chunk of <= 1280 columns, or a step-major packing whose halved chunk is a multiple of %d"
+R_TILES = ("windows of more than 64 rows take 3, 4, 6 or 8 column tiles per workgroup on the quantised streams (kernels G1wq / G1wq4 have no form of three row tiles x "
+           "two tiles)")
+R_HEAD = "the output head runs on kernel G1w at these row counts -- HEAD_CFG[1] must be one of (2, 3, 4, 6, 8); HEAD_CFG = (1024, 5, True)"
+LG_HEAD_TILES = "windows of more than 64 rows take (2, 3, 4, 6, 8) column tiles per workgroup; offending launch shapes: ['head']"          # (the 16-bit tile check comes first)
+E4M3, E4M3_256, MXFP4 = "weights='e4m3': ", "weights='e4m3', max_rows=256: ", "weights='mxfp4': "
+# (call site, reason) -> (the one projection changed, HEAD_CFG when it is the head that changes, the refusal)
+EXPECTED_REFUSALS = {
+    ("chameleon e4m3", "chunk"): (dict(qkv=(4096, 6, True)), None, E4M3 + R_CHUNK + "; G1_CFG['qkv'] = (4096, 6, True) with K = 4096"),
+    ("chameleon e4m3 wide", "granule"): (dict(o=(528, 3, True)), None, E4M3_256 + R_GRANULE % 32 + "; G1_CFG['o'] = (528, 3, True) with K = 4096"),
+    ("chameleon e4m3 wide", "chunk"): (dict(qkv=(4096, 4, True)), None, E4M3_256 + R_CHUNK + "; G1_CFG['qkv'] = (4096, 4, True) with K = 4096"),
+    ("chameleon e4m3 wide", "halved"): (dict(down=(1408, 4, False)), None, E4M3_256 + R_HALVED % 32 + "; G1_CFG['down'] = (1408, 4, False) with K = 11008"),
+    ("chameleon e4m3 wide", "tiles"): (dict(o=(1024, 2, True)), None, E4M3_256 + R_TILES + "; G1_CFG['o'] = (1024, 2, True) with K = 4096"),
+    ("chameleon e4m3 wide", "head tiles"): (None, (1024, 5, True), E4M3_256 + R_HEAD),
+    ("chameleon mxfp4", "granule"): (dict(qkv=(1000, 6, True)), None, MXFP4 + R_GRANULE % 128 + "; G1_CFG['qkv'] = (1000, 6, True) with K = 4096"),
+    ("chameleon mxfp4", "chunk"): (dict(qkv=(4096, 6, True)), None, MXFP4 + R_CHUNK + "; G1_CFG['qkv'] = (4096, 6, True) with K = 4096"),
+    ("chameleon mxfp4", "halved"): (dict(down=(1408, 8, True)), None, MXFP4 + R_HALVED % 128 + "; G1_CFG['down'] = (1408, 8, True) with K = 11008"),
+    ("swin e4m3", "granule"): (dict(down=(1552, 8, True)), None, E4M3 + R_GRANULE % 32 + "; G1_CFG['down'] = (1552, 8, True) with K = 22016"),
+    ("swin e4m3", "chunk"): (dict(qkv=(2688, 8, True)), None, E4M3 + R_CHUNK + "; G1_CFG['qkv'] = (2688, 8, True) with K = 8192"),
+    ("swin e4m3", "halved"): (dict(o=(1536, 8, False)), None, E4M3 + R_HALVED % 32 + "; G1_CFG['o'] = (1536, 8, False) with K = 8192"),
+    ("swin mxfp4", "granule"): (dict(down=(1552, 8, True)), None, MXFP4 + R_GRANULE % 128 + "; G1_CFG['down'] = (1552, 8, True) with K = 22016"),
+    ("swin mxfp4", "chunk"): (dict(qkv=(2688, 8, True)), None, MXFP4 + R_CHUNK + "; G1_CFG['qkv'] = (2688, 8, True) with K = 8192"),
+    ("swin mxfp4", "halved"): (dict(o=(1536, 8, False)), None, MXFP4 + R_HALVED % 128 + "; G1_CFG['o'] = (1536, 8, False) with K = 8192"),
+}
+for _w, _g in (("e4m3", 32), ("mxfp4", 128)):          # (LlamaGen's sentences are the ones kept: nothing changed here)
+    for _r in (64, 256):
+        _s, _p = f"llamagen {_w} {_r}", f"weights={_w!r}, max_rows={_r}: "
+        EXPECTED_REFUSALS[_s, "granule"] = (dict(down=(208, 4, False)), None, _p + R_GRANULE % _g + "; G1_CFG['down'] = (208, 4, False) with K = 4096")
+        EXPECTED_REFUSALS[_s, "chunk"] = (dict(down=(2688, 4, True)), None, _p + R_CHUNK + "; G1_CFG['down'] = (2688, 4, True) with K = 4096")
+        EXPECTED_REFUSALS[_s, "halved"] = (dict(down=(1408, 4, False)), None, _p + R_HALVED % _g + "; G1_CFG['down'] = (1408, 4, False) with K = 4096")
+    EXPECTED_REFUSALS[_s, "tiles"] = (dict(o=(256, 2, False)), None, _p + R_TILES + "; G1_CFG['o'] = (256, 2, False) with K = 1536")
+    EXPECTED_REFUSALS[_s, "head tiles"] = (None, (640, 5, True), LG_HEAD_TILES)
+
+
+@pytest.mark.parametrize("site,reason", sorted(EXPECTED_REFUSALS))
+def test_quantised_copy_refusals(site, reason):
+    assert len(EXPECTED_REFUSALS) == 31 and {s for s, _ in EXPECTED_REFUSALS} == set(REFUSAL_SITES)
+    g1, head, want = EXPECTED_REFUSALS[site, reason]
+    assert REFUSAL_SITES[site](g1, head) == want
+
+
+@pytest.mark.parametrize("site", [s for s in REFUSAL_SITES if not s.startswith("llamagen")])
+def test_the_sets_the_refusal_cases_start_from_are_served(site):
+    assert isinstance(REFUSAL_SITES[site](), dict)          # (LlamaGen's, at the real widths: tests/test_llamagen_quant_cfg.py)
