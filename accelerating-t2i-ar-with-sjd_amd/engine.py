@@ -27,6 +27,10 @@ reference's CPU runs) keeps the tensor path: the noise is drawn on the host and 
 When the grammar cannot name the residual rules before the launch (fast_residual_rules -> None: Anole's context-dependent processors, the
 first rows after <start>, windows that hold an end token) the iteration is launched in two stages instead -- {K5, forward}, residual
 rules computed on the host meanwhile and uploaded behind it on the same stream, {K2, K4}.
+
+Where the code lives: the host bookkeeping of one prompt (n, a', the fresh ids, the generator offsets, the read-back split, the end test) is
+window_loop.PromptLoop -- SJDEngine.decode and every slot of engine_batch.SJDBatchEngine call its plan / absorb; the launch side both
+engines share (graph cache, blob fill, rule bytes, column window, the prefill's K2 + K4) is WindowLauncher below.
 """
 import contextlib
 import ctypes
@@ -35,7 +39,7 @@ import os
 import random
 import time
 import warnings
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 from typing import List, Optional
 
 import numpy as np
@@ -43,7 +47,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .grammar import spatial_fresh_tokens
+from .window_loop import DecodeStats, PromptLoop
 
 
 # The iteration's one wait: a stream synchronize (default), or SJD_MIRROR_SPIN=1: the host spins on the sequence word K4 publishes behind the
@@ -92,25 +96,6 @@ class WindowSpec:
     # logits (llamagen_solver.sample with the prompt's own generator); first_tokens / first_positions are ignored (may be None), kv_base = T.
     cond_embeds: Optional[torch.Tensor] = None
     cond_sampling: Optional[dict] = None  # cfg_scale, temperature, top_k, top_p, sample_logits of that first draw (LlamaGenSolver.prefill)
-
-
-@dataclass
-class DecodeStats:
-    nfe: int = 0
-    tokens: int = 0
-    seconds: float = 0.0
-    wall_seconds: float = 0.0
-    timed_nfe: int = 0
-    timed_region_reached: bool = True   # False: bench mode, but the decode ended before the timed region opened (stats cover the whole decode)
-    kv_len: int = 0                # KV length at the end of the timed region (whole decode when none)
-    kv_len_start: int = 0          # ... at its start
-    total_tokens: int = 0          # whole decode (lead-in + warm-up + timed + continuation)
-    total_seconds: float = 0.0
-    timed_host_seconds: float = 0.0    # host_seconds / sync_seconds at the end of the timed region
-    timed_sync_seconds: float = 0.0
-    host_seconds: float = 0.0      # host bookkeeping + RNG launches before the window step is enqueued
-    sync_seconds: float = 0.0      # time blocked in the per-iteration state read-back
-    matched: List[int] = field(default_factory=list)
 
 
 def set_seed(seed):
@@ -172,7 +157,230 @@ def warn_no_grid(cfg, grammar):
                       "the fresh drafts stay uniformly random", stacklevel=3)
 
 
-class SJDEngine:
+def column_window(V, rule_lists):
+    """Vocabulary window [lo, hi) (32-aligned) that holds every id the non-forced rows of the given rule lists may emit, or None when it is
+    not at most half of the vocabulary (text rows, unrestricted rules)."""
+    lo, hi = V, 0
+    for rules in rule_lists:
+        for r in rules:
+            if r.forced >= 0:
+                continue
+            if r.n_ranges == 0:
+                return None
+            lo = min([lo] + [r.lo[i] for i in range(r.n_ranges)])
+            hi = max([hi] + [r.hi[i] for i in range(r.n_ranges)])
+    if hi <= lo:
+        return None
+    lo, hi = (lo // 32) * 32, min(V, ((hi + 31) // 32) * 32)
+    return (lo, hi) if 2 * (hi - lo) <= V else None
+
+
+def cached_column_window(eng, rule_lists):
+    """column_window of an engine (its V, narrow_head, _cols_cache, _rule_keep), cached by the interned rule structs' identities"""
+    if not eng.narrow_head:
+        return None
+    key = tuple(id(r) for rules in rule_lists for r in rules)
+    if key in eng._cols_cache:
+        return eng._cols_cache[key]
+    cols = column_window(eng.V, rule_lists)
+    if len(eng._cols_cache) < 4096:
+        eng._cols_cache[key] = cols
+        eng._rule_keep.append([r for rules in rule_lists for r in rules])      # the ids stay valid while the structs are alive
+    return cols
+
+
+class WindowLauncher:
+    """The launch side SJDEngine and SJDBatchEngine share.  An engine supplies _forward_body(cols) (K5 + forward), _sample_body(cur, logits,
+    cols) (K2 + K4) and _graph_key(kind, cols, cur) -- the part of a graph's key that is its own -- and has backbone, device, V, Lmax,
+    use_graph, hook, _rule_bytes, _rule_keep.  `s` below is whatever holds one prompt's buffers (params, state, probs, zero_state, scratch,
+    tokens_ptr, amax_ptr, noise, rs, noise2): the solo engine itself, or a slot of the batch engine."""
+
+    def reset_graphs(self):
+        """Call after the backbone's cache / weights were re-allocated."""
+        self._graphs, self._graph_logits, self._eager_runs = {}, {}, {}
+        self.__dict__.pop("_graph_sig", None)
+
+    def _check_graph_buffers(self):
+        """The captured graphs hold raw addresses of the K1 workspace, of the KV cache (K and V) and of the packed weights: if any was
+        re-allocated since the capture (HipWindowAttention.ws_version; the backbone's buffers_version, bumped by setup_cache /
+        enable_fused; the cache tensors' data_ptr as a belt for backbones without the counter) the graphs are dropped and captured again
+        instead of replaying into freed memory.  The G1 launch shapes are baked into the packed weights, so changing G1_CFG means
+        calling enable_fused again -- which bumps the counter."""
+        attn = getattr(self.backbone, "attn", None)
+        cache = getattr(self.backbone, "cache", None)
+        sig = (getattr(attn, "ws_version", 0), getattr(self.backbone, "buffers_version", 0),
+               cache.k.data_ptr() if cache is not None else 0, cache.v.data_ptr() if cache is not None else 0)
+        if sig != getattr(self, "_graph_sig", sig):
+            self.reset_graphs()
+        self._graph_sig = sig
+
+    def _k1_regime(self):
+        """the attention backend's launch form for this iteration (the two forms are different kernels, each forward graph owns ITS buffers)"""
+        return getattr(getattr(self.backbone, "attn", None), "regime", None)
+
+    def _run_graph(self, key, body):
+        """body() eagerly the first time `key` runs (warms up allocations / hipBLASLt), captured into a hipGraph the second time, replayed
+        from then on.  Returns what body returned (graph-owned, static across replays)."""
+        self._check_graph_buffers()
+        if key not in self._graphs:
+            if self._eager_runs.get(key, 0) < 1:
+                self._eager_runs[key] = 1
+                return body()
+            g = torch.cuda.CUDAGraph()
+            with capture_graph(g):
+                self._graph_logits[key] = body()
+            self._graphs[key] = g
+        self._graphs[key].replay()
+        return self._graph_logits[key]
+
+    def _launch_forward(self, cols=None):
+        """part 1 (K5 + transformer forward): eager, or a hipGraph captured once per output-head column window.  Returns the logits
+        tensor part 2 will read (static across replays of the same graph)."""
+        if not self.use_graph:
+            return self._forward_body(cols)
+        return self._run_graph(self._graph_key("fwd", cols), lambda: self._forward_body(cols))
+
+    def _launch_sample(self, cur, logits, cols=None):
+        """part 2 (K2 + K4) of a two-stage iteration; a hipGraph per (prob-buffer parity, column window), captured the second time that
+        combination runs on graph-owned logits."""
+        # (the K1 regime is part of the key: every regime's forward graph owns ITS static logits / head partials, and a sample graph bakes in
+        #  the buffer it was captured on -- ADVICE r4: without it the graph of one regime replayed on the other regime's stale buffer.  The
+        #  captured buffer's identity is kept beside the graph as a belt: a mismatch drops the graph and captures again.)
+        if not self.use_graph or self._graph_key("fwd", cols) not in self._graphs:
+            self._sample_body(cur, logits, cols)
+            return
+        key = self._graph_key("smp", cols, cur)
+        if key in self._graphs and self._graph_logits.get(key) is not logits:
+            del self._graphs[key]
+        if key not in self._graphs:
+            self._sample_body(cur, logits, cols)     # eager warm-up of this parity, captured below for the next use
+            g = torch.cuda.CUDAGraph()
+            with capture_graph(g):
+                self._sample_body(cur, logits, cols)
+            self._graphs[key] = g
+            self._graph_logits[key] = logits
+            return
+        self._graphs[key].replay()
+
+    def _window_body(self, cur, cols):
+        logits = self._forward_body(cols)
+        self._sample_body(cur, logits, cols)
+        return logits
+
+    def _launch_window(self, cur, cols=None):
+        """the whole iteration -- K5, forward, K2, K4 -- as ONE hipGraph per (column window, prob-buffer parity): everything it reads
+        is in the blob that was uploaded in front of it.  Returns the logits / head partials K2 read (graph-owned, static)."""
+        if not self.use_graph:
+            return self._window_body(cur, cols)
+        return self._run_graph(self._graph_key("win", cols, cur), lambda: self._window_body(cur, cols))
+
+    def captured_column_windows(self):
+        """output-head column windows for which a window graph (one- or two-stage) has been captured"""
+        return sorted({k[1] for k in self._graphs if isinstance(k, tuple) and k[0] in ("fwd", "win")}, key=lambda c: (c is None, c))
+
+    # ------------------------------------------------------------------------------------------------ blobs
+    def _write_rules(self, host_ptr, rules):
+        """rules (interned sjd_row_rule structs, ops.make_rule) -> pinned host memory, as ONE block copy: the packed bytes of a rule sequence
+        are cached by the structs' identities (an image body asks for the same two or three sequences over and over; with four slots the
+        per-element ctypes writes were ~0.1 ms of host time per forward)."""
+        key = tuple(map(id, rules))
+        blk = self._rule_bytes.get(key)
+        if blk is None:
+            blk = b"".join(bytes(r) for r in rules)
+            if len(self._rule_bytes) < 4096:
+                self._rule_bytes[key] = blk
+                self._rule_keep.append(list(rules))            # the ids stay valid while the structs are alive
+        ctypes.memmove(host_ptr, blk, len(blk))
+
+    def _fill_blob(self, blob, n, kv_len, use_cfg, scheme, fresh, rules, resid, philox):
+        """one prompt's sjd_iter_params for one iteration (host side; the caller uploads).  philox = (blocks, seed, off0, off1, off2): K2 / K4
+        generate the multinomial / rand / residual noise torch would have drawn from a device generator at that state (None: tensors)."""
+        p = blob.view
+        p.n_rows, p.kv_len, p.use_cfg, p.scheme, p.n_fresh = n, kv_len, int(use_cfg), scheme, len(fresh)
+        if philox is None:
+            p.philox_blocks = 0
+        else:
+            p.philox_blocks, p.philox_seed = philox[0], philox[1]
+            p.philox_offset[0], p.philox_offset[1], p.philox_offset[2] = philox[2], philox[3], philox[4]
+        if fresh:
+            p.fresh_tok[:len(fresh)] = fresh
+        host = blob.host.data_ptr()
+        self._write_rules(host + L.IterParams.rules.offset, rules)
+        if resid:
+            self._write_rules(host + L.IterParams.resid_rules.offset, resid)
+
+    def _upload_resid(self, blob, resid):
+        """two-stage iterations: the residual rules (read by K4 only) were computed while the forward runs; their slice of the blob goes
+        up on the SAME stream, behind the forward and in front of K2 / K4"""
+        off = L.IterParams.resid_rules.offset
+        self._write_rules(blob.host.data_ptr() + off, resid)
+        L.check(L.load().sjd_upload_async(blob.dev.data_ptr() + off, blob.host.data_ptr() + off, blob.nbytes - off, ops._stream()), "sjd_upload_async")
+
+    # ------------------------------------------------------------------------------------------------ per prompt
+    def _check_config(self, cfg, grammars):
+        if cfg.multi_token_init_scheme not in ("random", "repeat_horizon", "sample_horizon"):
+            # JL:554-560, 592: anything else (incl. the 'vertical' variants) asserts in the reference
+            raise ValueError(f"multi_token_init_scheme should be 'random', 'repeat_horizon' or 'sample_horizon', but got {cfg.multi_token_init_scheme}")
+        if cfg.prefix_token_sampler_scheme not in ("speculative_jacobi", "jacobi"):
+            raise ValueError(f"prefix_token_sampler_scheme: {cfg.prefix_token_sampler_scheme}")   # JL:1048
+        if cfg.max_num_new_tokens > self.Lmax:
+            raise ValueError("max_num_new_tokens exceeds the engine's max_window")
+        for g in grammars:
+            warn_no_grid(cfg, g)
+
+    def _calibrate_fp8(self, tokens, positions, key_start):
+        """an fp8 KV cache whose scales nobody set: calibrate them on THIS prompt, once per backbone (static calibration; round 6)"""
+        bb = self.backbone
+        cache, attn = getattr(bb, "cache", None), getattr(bb, "attn", None)
+        if (cache is None or cache.k.dtype != ops.FP8 or attn is None or getattr(attn, "layer_scales", 1) is not None
+                or getattr(attn, "kv_scale", (1.0, 1.0)) != (1.0, 1.0) or not hasattr(bb, "calibrate_kv_scales")
+                or os.environ.get("SJD_FP8_CALIBRATE", "1") == "0"):
+            return
+        bb.calibrate_kv_scales(tokens, positions, key_start)
+
+    def _k2_out(self, s=None):
+        """(tokens_out, amax_out) of K2: the draw goes into state.tokens and the mode of p into state.amax -- or, greedy (do_sample=False), the mode
+        into state.tokens, which is what K4 verifies and the host appends (the draw lands in state.amax and is ignored).
+        One documented deviation (ADVICE r5): the reference takes torch.argmax of the processed SCORES (JL:128), K2 the lowest-index mode of the
+        softmaxed p.  They differ only when two maximal scores are distinct floats whose exponentials round to the same fp32 (exp(z - zmax) == 1
+        for z < zmax): the gap must be below 2^-25, i.e. below an ulp of z unless |zmax| < 0.5 -- near-tied logits of magnitude below 0.5 at the
+        top of a row.  tests/test_oracle_golden.py::test_greedy_mode_of_p_vs_argmax_of_scores pins exactly that boundary."""
+        s = s or self
+        return (s.amax_ptr, s.tokens_ptr) if getattr(self, "_greedy", False) else (s.tokens_ptr, s.amax_ptr)
+
+    def _prefill_sample(self, s, logits, guidance, buf, n_batch, tensors=False):
+        """iteration 0: K2 over the dense logits of the prompt's last row, then K4 (its is_prefilling_phase short-circuit); the distribution
+        lands in s.probs[buf].  tensors: the kernels read s.noise / s.rs / s.noise2 instead of generating the noise.  Returns (cond, uncond) rows."""
+        lc = logits[0, -1:, :]
+        lu = logits[1, -1:, :] if n_batch > 1 else None
+        tok_out, amax_out = self._k2_out(s)
+        ops.logits_to_probs_sample(lc, lu, guidance, s.params, s.noise if tensors else None, s.probs[buf], tok_out, amax_out_ptr=amax_out)
+        s.zero_state[buf].fill_(-1)                   # (the dense-logits K2 does not keep the rows' zero state)
+        ops.verify_accept(s.params, s.state, s.probs[buf], s.probs[1 - buf], s.rs if tensors else None, s.noise2[0] if tensors else None,
+                          s.scratch, mirror=True)
+        return lc, lu
+
+    def _noise_tensors(self, s):
+        if s.noise is None:
+            dev = self.device
+            s.noise = torch.ones(self.Lmax, self.V, dtype=torch.float32, device=dev)
+            s.rs = torch.zeros(self.Lmax, self.V, dtype=torch.float32, device=dev)
+            s.noise2 = torch.ones(1, self.V, dtype=torch.float32, device=dev)
+
+    def _observer_noise(self, s, gen, ph_off, n_rows, draws_rs):
+        """what the prompt's kernels generate, drawn by torch from the same generator state -- for observers only (the parity tests' hook)"""
+        self._noise_tensors(s)
+        gen.set_offset(ph_off)
+        if getattr(self, "_greedy", False):
+            s.noise[:n_rows].fill_(1.0)
+        else:
+            s.noise[:n_rows].exponential_(generator=gen)                 # == torch.multinomial (JL:118)
+        if draws_rs:
+            s.rs[:n_rows].uniform_(0.0, 1.0, generator=gen)              # torch.rand([1,n,V]) (JL:260)
+            s.noise2.exponential_(generator=gen)                         # residual multinomial (JL:237)
+
+
+class SJDEngine(WindowLauncher):
     def __init__(self, backbone, vocab_size, device, max_window=16, n_batch=2, use_graph=False, narrow_head=True, head_partials=True):
         L.load()                                   # fail loudly if the HIP extension is missing
         if max_window > L.MAX_WINDOW:
@@ -208,73 +416,30 @@ class SJDEngine:
         self._seq = 0
         self.reset_graphs()
 
-    def reset_graphs(self):
-        """Call after the backbone's cache / weights were re-allocated."""
-        self._graphs, self._graph_logits, self._eager_runs = {}, {}, {}
-        self.__dict__.pop("_graph_sig", None)
-
-    def _check_graph_buffers(self):
-        """The captured graphs hold raw addresses of the K1 workspace, of the KV cache (K and V) and of the packed weights: if any was
-        re-allocated since the capture (HipWindowAttention.ws_version; the backbone's buffers_version, bumped by setup_cache /
-        enable_fused; the cache tensors' data_ptr as a belt for backbones without the counter) the graphs are dropped and captured again
-        instead of replaying into freed memory.  The G1 launch shapes are baked into the packed weights, so changing G1_CFG means
-        calling enable_fused again -- which bumps the counter."""
-        attn = getattr(self.backbone, "attn", None)
-        cache = getattr(self.backbone, "cache", None)
-        sig = (getattr(attn, "ws_version", 0), getattr(self.backbone, "buffers_version", 0),
-               cache.k.data_ptr() if cache is not None else 0, cache.v.data_ptr() if cache is not None else 0)
-        if sig != getattr(self, "_graph_sig", sig):
-            self.reset_graphs()
-        self._graph_sig = sig
-
-    # ------------------------------------------------------------------------------------------------
-    def _noise_tensors(self):
-        if self.noise is None:
-            dev = self.device
-            self.noise = torch.ones(self.Lmax, self.V, dtype=torch.float32, device=dev)
-            self.rs = torch.zeros(self.Lmax, self.V, dtype=torch.float32, device=dev)
-            self.noise2 = torch.ones(1, self.V, dtype=torch.float32, device=dev)
-        return self.noise, self.rs, self.noise2
-
     def _fill_params(self, n, kv_len, use_cfg, scheme, fresh, rules, resid, head_only=False, philox=None):
         """philox = (blocks, seed, off0, off1, off2): K2 / K4 generate the noise of a device generator at that state (None: tensors).
         head_only: upload everything in FRONT of resid_rules only -- the residual rules follow on the same stream once the host has
         computed them (_upload_resid), as a disjoint byte range of the blob."""
-        p = self.params.view
-        p.n_rows, p.kv_len, p.use_cfg, p.scheme, p.n_fresh = n, kv_len, int(use_cfg), scheme, len(fresh)
         self._seq = (self._seq % 0x7FFFFFF0) + 1          # K4 publishes it behind the mirrored state: what the host's spin waits for
-        p.iter_seq = self._seq
-        if philox is None:
-            p.philox_blocks = 0
-        else:
-            p.philox_blocks, p.philox_seed = philox[0], philox[1]
-            p.philox_offset[0], p.philox_offset[1], p.philox_offset[2] = philox[2], philox[3], philox[4]
-        if fresh:
-            p.fresh_tok[:len(fresh)] = fresh
-        self._write_rules(L.IterParams.rules.offset, rules)
-        if resid:
-            self._write_rules(L.IterParams.resid_rules.offset, resid)
+        self.params.view.iter_seq = self._seq
+        self._fill_blob(self.params, n, kv_len, use_cfg, scheme, fresh, rules, resid, philox)
         self.params.upload(L.IterParams.resid_rules.offset if head_only else None)
 
-    def _write_rules(self, offset, rules):
-        """rules (interned sjd_row_rule structs, ops.make_rule) -> the blob, as ONE block copy: the packed bytes of a rule sequence are
-        cached by the structs' identities (an image body asks for the same two or three sequences over and over)."""
-        key = tuple(map(id, rules))
-        blk = self._rule_bytes.get(key)
-        if blk is None:
-            blk = b"".join(bytes(r) for r in rules)
-            if len(self._rule_bytes) < 4096:
-                self._rule_bytes[key] = blk
-                self._rule_keep.append(list(rules))            # the ids stay valid while the structs are alive
-        ctypes.memmove(self.params.host.data_ptr() + offset, blk, len(blk))
+    def _graph_key(self, kind, cols, cur=None):
+        """the key of this iteration's forward ("fwd"), one-stage ("win") or two-stage sample ("smp") graph: the K1 regime, the noise source
+        and the scalar guidance are baked into the captured launches"""
+        regime = self._k1_regime()
+        if kind == "fwd":
+            return ("fwd", cols, regime)
+        own = (self.hook is not None, self._philox, regime, getattr(self, "_greedy", False))
+        return ("win", cols, cur, self._guidance) + own if kind == "win" else ("smp", cur, self._guidance, cols) + own
 
-    def _upload_resid(self, resid):
-        """two-stage iterations: the residual rules (read by K4 only) were computed while the forward runs; their slice of the blob goes
-        up on the SAME stream, behind the forward and in front of K2 / K4"""
-        off = L.IterParams.resid_rules.offset
-        self._write_rules(off, resid)
-        L.check(L.load().sjd_upload_async(self.params.dev.data_ptr() + off, self.params.host.data_ptr() + off, self.params.nbytes - off,
-                                          ops._stream()), "sjd_upload_async")
+    def logit_columns(self, rules):
+        """Vocabulary window [lo, hi) (32-aligned) that holds every id the non-forced rows of this iteration may emit, or None when
+        it is not at most half of the vocabulary (text rows, unrestricted rules).  The output head is then evaluated for these
+        columns only: the ids outside are masked by the grammar before the softmax (reference logit_processor_3dim.py:125-129,
+        jacobi_iteration_emu3.py:44-128), so not computing them changes nothing downstream."""
+        return cached_column_window(self, [rules])
 
     def _forward_body(self, cols=None):
         """Shape-static launch sequence, part 1: K5 + transformer forward (every dynamic scalar is read from device blobs).
@@ -286,25 +451,6 @@ class SJDEngine:
         if cols is None:
             return self.backbone.forward_window(self.input_ids, positions, -1, self.key_start)
         return self.backbone.forward_window(self.input_ids, positions, -1, self.key_start, cols=cols)
-
-    def _calibrate_fp8(self, tokens, positions, key_start):
-        """an fp8 KV cache whose scales nobody set: calibrate them on THIS prompt, once per backbone (static calibration; round 6)"""
-        bb = self.backbone
-        cache, attn = getattr(bb, "cache", None), getattr(bb, "attn", None)
-        if (cache is None or cache.k.dtype != ops.FP8 or attn is None or getattr(attn, "layer_scales", 1) is not None
-                or getattr(attn, "kv_scale", (1.0, 1.0)) != (1.0, 1.0) or not hasattr(bb, "calibrate_kv_scales")
-                or os.environ.get("SJD_FP8_CALIBRATE", "1") == "0"):
-            return
-        bb.calibrate_kv_scales(tokens, positions, key_start)
-
-    def _k2_out(self):
-        """(tokens_out, amax_out) of K2: the draw goes into state.tokens and the mode of p into state.amax -- or, greedy (do_sample=False), the mode
-        into state.tokens, which is what K4 verifies and the host appends (the draw lands in state.amax and is ignored).
-        One documented deviation (ADVICE r5): the reference takes torch.argmax of the processed SCORES (JL:128), K2 the lowest-index mode of the
-        softmaxed p.  They differ only when two maximal scores are distinct floats whose exponentials round to the same fp32 (exp(z - zmax) == 1
-        for z < zmax): the gap must be below 2^-25, i.e. below an ulp of z unless |zmax| < 0.5 -- near-tied logits of magnitude below 0.5 at the
-        top of a row.  tests/test_oracle_golden.py::test_greedy_mode_of_p_vs_argmax_of_scores pins exactly that boundary."""
-        return (self.amax_ptr, self.tokens_ptr) if getattr(self, "_greedy", False) else (self.tokens_ptr, self.amax_ptr)
 
     def _sample_body(self, cur, logits, cols=None):
         """part 2: K2 + K4.  In-kernel noise (self._philox): the kernels are handed NULL instead of the noise tensors."""
@@ -327,109 +473,6 @@ class SJDEngine:
             self.zero_state[cur].fill_(-1)            # (the dense-logits K2 does not keep the rows' zero state)
         ops.verify_accept(self.params, self.state, self.probs[cur], self.probs[1 - cur], rs, noise2, self.scratch, mirror=True)
 
-    def logit_columns(self, rules):
-        """Vocabulary window [lo, hi) (32-aligned) that holds every id the non-forced rows of this iteration may emit, or None when
-        it is not at most half of the vocabulary (text rows, unrestricted rules).  The output head is then evaluated for these
-        columns only: the ids outside are masked by the grammar before the softmax (reference logit_processor_3dim.py:125-129,
-        jacobi_iteration_emu3.py:44-128), so not computing them changes nothing downstream."""
-        if not self.narrow_head:
-            return None
-        key = tuple(map(id, rules))
-        if key in self._cols_cache:
-            return self._cols_cache[key]
-        cols = SJDEngine._logit_columns(self, rules)
-        if len(self._cols_cache) < 4096:
-            self._cols_cache[key] = cols
-            self._rule_keep.append(list(rules))
-        return cols
-
-    def _logit_columns(self, rules):
-        lo, hi = self.V, 0
-        for r in rules:
-            if r.forced >= 0:
-                continue
-            if r.n_ranges == 0:
-                return None
-            lo = min([lo] + [r.lo[i] for i in range(r.n_ranges)])
-            hi = max([hi] + [r.hi[i] for i in range(r.n_ranges)])
-        if hi <= lo:
-            return None
-        lo, hi = (lo // 32) * 32, min(self.V, ((hi + 31) // 32) * 32)
-        return (lo, hi) if 2 * (hi - lo) <= self.V else None
-
-    def _k1_regime(self):
-        """the attention backend's launch form for this iteration (part of every graph key: the two forms are different kernels)"""
-        return getattr(getattr(self.backbone, "attn", None), "regime", None)
-
-    def _launch_forward(self, cols=None):
-        """part 1 (K5 + transformer forward): eager, or a hipGraph captured once per output-head column window.  Returns the logits
-        tensor part 2 will read (static across replays of the same graph)."""
-        if not self.use_graph:
-            return self._forward_body(cols)
-        self._check_graph_buffers()
-        fkey = ("fwd", cols, self._k1_regime())
-        if fkey not in self._graphs:
-            if self._eager_runs.get(fkey, 0) < 1:   # one eager run warms up allocations / hipBLASLt before capture
-                self._eager_runs[fkey] = 1
-                return self._forward_body(cols)
-            g = torch.cuda.CUDAGraph()
-            with capture_graph(g):
-                self._graph_logits[fkey] = self._forward_body(cols)
-            self._graphs[fkey] = g
-        self._graphs[fkey].replay()
-        return self._graph_logits[fkey]
-
-    def _launch_sample(self, cur, logits, cols=None):
-        """part 2 (K2 + K4) of a two-stage iteration; a hipGraph per (prob-buffer parity, column window), captured the second time that
-        combination runs on graph-owned logits."""
-        # (the K1 regime is part of the key: every regime's forward graph owns ITS static logits / head partials, and a sample graph bakes in
-        #  the buffer it was captured on -- ADVICE r4: without it the graph of one regime replayed on the other regime's stale buffer.  The
-        #  captured buffer's identity is kept beside the graph as a belt: a mismatch drops the graph and captures again.)
-        regime = self._k1_regime()
-        key = ("smp", cur, self._guidance, cols, self.hook is not None, self._philox, regime, getattr(self, "_greedy", False))
-        if not self.use_graph or ("fwd", cols, regime) not in self._graphs:
-            self._sample_body(cur, logits, cols)
-            return
-        if key in self._graphs and self._graph_logits.get(key) is not logits:
-            del self._graphs[key]
-        if key not in self._graphs:
-            self._sample_body(cur, logits, cols)     # eager warm-up of this parity, captured below for the next use
-            g = torch.cuda.CUDAGraph()
-            with capture_graph(g):
-                self._sample_body(cur, logits, cols)
-            self._graphs[key] = g
-            self._graph_logits[key] = logits
-            return
-        self._graphs[key].replay()
-
-    def _launch_window(self, cur, cols=None):
-        """the whole iteration -- K5, forward, K2, K4 -- as ONE hipGraph per (column window, prob-buffer parity): everything it reads
-        is in the blob that was uploaded in front of it.  Returns the logits / head partials K2 read (graph-owned, static)."""
-        if not self.use_graph:
-            logits = self._forward_body(cols)
-            self._sample_body(cur, logits, cols)
-            return logits
-        self._check_graph_buffers()
-        key = ("win", cols, cur, self._guidance, self.hook is not None, self._philox, self._k1_regime(), getattr(self, "_greedy", False))
-        if key not in self._graphs:
-            if self._eager_runs.get(key, 0) < 1:      # one eager run warms up allocations / hipBLASLt before capture
-                self._eager_runs[key] = 1
-                logits = self._forward_body(cols)
-                self._sample_body(cur, logits, cols)
-                return logits
-            g = torch.cuda.CUDAGraph()
-            with capture_graph(g):
-                logits = self._forward_body(cols)
-                self._sample_body(cur, logits, cols)
-            self._graph_logits[key] = logits
-            self._graphs[key] = g
-        self._graphs[key].replay()
-        return self._graph_logits[key]
-
-    def captured_column_windows(self):
-        """output-head column windows for which a window graph (one- or two-stage) has been captured"""
-        return sorted({k[1] for k in self._graphs if isinstance(k, tuple) and k[0] in ("fwd", "win")}, key=lambda c: (c is None, c))
-
     def last_head_output(self, cols):
         """the logits / head partials the most recently captured window graph of `cols` hands to K2 (bench.py's scheduler leg)"""
         for k in reversed(list(self._graph_logits)):
@@ -447,32 +490,23 @@ class SJDEngine:
         decode stops after it unless continue_after (then it runs on to EOS / max_length and stats.{nfe, total_tokens,
         total_seconds} describe the whole decode).  iter_log: list receiving (kv_len before the iteration, rows, accepted,
         host clock after the iteration's sync) per iteration."""
-        if cfg.multi_token_init_scheme not in ("random", "repeat_horizon", "sample_horizon"):
-            # JL:554-560, 592: anything else (incl. the 'vertical' variants) asserts in the reference
-            raise ValueError(f"multi_token_init_scheme should be 'random', 'repeat_horizon' or 'sample_horizon', but got {cfg.multi_token_init_scheme}")
-        if cfg.prefix_token_sampler_scheme not in ("speculative_jacobi", "jacobi"):
-            raise ValueError(f"prefix_token_sampler_scheme: {cfg.prefix_token_sampler_scheme}")   # JL:1048
-        if cfg.max_num_new_tokens > self.Lmax:
-            raise ValueError("max_num_new_tokens exceeds the engine's max_window")
-        warn_no_grid(cfg, grammar)
+        self._check_config(cfg, [grammar])
         dev, B = self.device, self.B
         scheme = 0 if cfg.prefix_token_sampler_scheme == "speculative_jacobi" else 1
         do_cfg = cfg.do_cfg and (cfg.guidance_scale != 1)                          # JL:1005
-        X = [int(t) for t in prompt]
-        P = len(X)
         gen = None
         if cfg.seed is not None:                                                   # JL:1021-1023
             set_seed(cfg.seed)
             gen = torch.Generator(cfg.noise_device or dev).manual_seed(cfg.seed)
         host_noise = cfg.noise_device is not None and torch.device(cfg.noise_device).type == "cpu"
         philox = self._philox = not host_noise
+        ph_blocks, ph_seed, ph_off = None, 0, 0
         if philox:
             if gen is None:                        # no seed: the device's default generator, which exponential_(generator=None) consumes
                 gen = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
             ph_blocks, ph_seed, ph_off = ops.philox_max_blocks(gen.device), int(gen.initial_seed()), int(gen.get_offset())
-            ph_row = ops.philox_step(self.V, ph_blocks)                            # offset step of a [1, V] draw
-        l_abs, r_abs = P + cfg.jacobi_loop_interval_l, P + cfg.jacobi_loop_interval_r   # JL:1025
-        W = cfg.max_num_new_tokens
+        loop = PromptLoop(prompt, spec.kv_base, cfg, ph_seed, ph_off)
+        X, P, stats = loop.X, loop.P, loop.stats
         grammar.start(X)
         self.key_start.copy_(spec.key_start.to(device=dev, dtype=torch.int32))
         self.pos_offset.copy_(spec.pos_offset.to(device=dev, dtype=torch.int64))
@@ -480,19 +514,15 @@ class SJDEngine:
         self._greedy = greedy = not getattr(cfg, "do_sample", True)
         attn = getattr(self.backbone, "attn", None)
         st = self.state.view
-        stats = DecodeStats()
-        n, kv_len, first, cur_len, cur, n_prev, m_prev = 1, spec.kv_base, True, P, 0, 1, 1
-        carried: List[int] = []
-        carried_amax: List[int] = []
-        last_amax = None
+        cur = 0
         t0 = time.perf_counter()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
         timed_tok0, timed_nfe0 = 0, 0
         warm_nfe0, timing, timed_done = None, False, False
         t_decode0 = time.perf_counter()
-        finished = False
-        while not finished:
+        while not loop.finished:
+            first, kv_len = loop.first, loop.kv_len
             if timed_iters is not None and warm_nfe0 is None and (lead_in_kv is None or (not first and kv_len >= lead_in_kv)):
                 warm_nfe0 = stats.nfe                                            # the lead-in is over: warm-up iterations start here
             if timed_iters is not None and warm_nfe0 is not None and not timing and not timed_done and stats.nfe == warm_nfe0 + warmup_iters:
@@ -506,58 +536,28 @@ class SJDEngine:
                 ev0.record()
             # ---------------- host: integer bookkeeping only ----------------
             t_host0 = time.perf_counter()
-            win, resid = None, []
-            if first:
-                n_rows = 1
-                torch.randint(0, cfg.img_vocab_n, (1, 0))
-                rules, fresh = grammar.window_rules(1), []
-            else:
-                n_rows = n
-                a = max(0, min(n_prev - m_prev, n - 1))                              # JL:633-639, 657-662
-                fr = torch.randint(0, cfg.img_vocab_n, (1, n - 1 - a)).tolist()[0]   # GLOBAL CPU generator (JL:505)
-                fresh = [cfg.img_vocab_lo + t for t in fr]                           # img_vocab[rand] (JL:509)
-                if cfg.multi_token_init_scheme != "random":                          # spatial init (JL:516-594): copy / re-draw from the left
-                    fresh = spatial_fresh_tokens(cfg.multi_token_init_scheme, fresh, len(X) + a, carried[a - 1] if a else X[-1],
-                                                 carried_amax[a - 1] if a else last_amax, grammar.grid())
-                rules = grammar.window_rules(n_rows)
-                if scheme == 0 and n_rows > 1:
-                    # the window's ids are all known here (carried ones came with the last read-back): if the grammar can name the
-                    # residual rules without a replay, the whole iteration goes out as one graph; otherwise they are computed below,
-                    # while the forward runs (K4 is their only reader)
-                    win = [X[-1]] + carried[:a] + fresh
-                    resid = None if _TWO_STAGE else grammar.fast_residual_rules(win, rules)
+            n_rows, fresh, rules, win, resid, use_cfg, draws_rs, offs = loop.plan(cfg, grammar, None, self.V, ph_blocks, greedy, scheme, do_cfg)
+            if _TWO_STAGE and draws_rs:
+                resid = None
             two_stage = resid is None
-            use_cfg = do_cfg and not grammar.force_no_cfg()                          # JL:1086-1096
-            draws_rs = n_rows > 1 and scheme == 0
-            ph = None
-            if philox:                                  # offsets of g before the multinomial, the rand and the residual multinomial
-                ph_step = ops.philox_step(n_rows * self.V, ph_blocks)
-                k2_step = 0 if greedy else ph_step          # greedy: sampling_logits2tokens draws nothing (JL:127-129)
-                ph = (ph_blocks, ph_seed, ph_off, ph_off + k2_step, ph_off + k2_step + ph_step)
-            self._fill_params(n_rows, kv_len, use_cfg, scheme, fresh, rules, resid or [], head_only=two_stage, philox=ph)
+            self._fill_params(n_rows, kv_len, use_cfg, scheme, fresh, rules, resid or [], head_only=two_stage,
+                              philox=None if offs is None else (ph_blocks, ph_seed) + offs)
             # ---------------- noise tensors: only for host-drawn noise (the reference's CPU runs) and for observers ----------------
             e1, g_state = None, None
-            if host_noise or self.hook is not None:
-                self._noise_tensors()
+            if host_noise:                                                           # parity mode: CPU stream of the reference
+                self._noise_tensors(self)
                 e1 = self.noise[:n_rows]
-                if host_noise:                                                       # parity mode: CPU stream of the reference
-                    if greedy:
-                        e1.fill_(1.0)
-                    else:
-                        e1.copy_(torch.empty(n_rows, self.V).exponential_(generator=gen))
-                    if draws_rs:
-                        self.rs[:n_rows].copy_(torch.rand((1, n_rows, self.V), generator=gen)[0])
-                        g_state = gen.get_state()
-                        self.noise2.copy_(torch.empty(1, self.V).exponential_(generator=gen))
-                else:                           # what the kernels generate, drawn by torch from the same generator state (observers)
-                    gen.set_offset(ph_off)
-                    if greedy:
-                        e1.fill_(1.0)
-                    else:
-                        e1.exponential_(generator=gen)                               # == torch.multinomial (JL:118)
-                    if draws_rs:
-                        self.rs[:n_rows].uniform_(0.0, 1.0, generator=gen)           # torch.rand([1,n,V]) (JL:260)
-                        self.noise2.exponential_(generator=gen)                      # residual multinomial (JL:237)
+                if greedy:
+                    e1.fill_(1.0)
+                else:
+                    e1.copy_(torch.empty(n_rows, self.V).exponential_(generator=gen))
+                if draws_rs:
+                    self.rs[:n_rows].copy_(torch.rand((1, n_rows, self.V), generator=gen)[0])
+                    g_state = gen.get_state()
+                    self.noise2.copy_(torch.empty(1, self.V).exponential_(generator=gen))
+            elif self.hook is not None:
+                self._observer_noise(self, gen, loop.ph_off, n_rows, draws_rs)
+                e1 = self.noise[:n_rows]
             stats.host_seconds += time.perf_counter() - t_host0
             # ---------------- device work ----------------
             cols = None
@@ -567,15 +567,8 @@ class SJDEngine:
                 tokens, positions = spec.first_tokens.to(dev), spec.first_positions.to(dev)
                 self._calibrate_fp8(tokens, positions, self.key_start)
                 logits = self.backbone.forward_window(tokens, positions, kv_len, self.key_start)
-                lc = logits[0, -1:, :]
-                lu = logits[1, -1:, :] if B > 1 else None
                 win_len = tokens.shape[1]
-                tok_out, amax_out = self._k2_out()
-                ops.logits_to_probs_sample(lc, lu, self._guidance, self.params, None if philox else self.noise, self.probs[cur], tok_out,
-                                           amax_out_ptr=amax_out)
-                self.zero_state[cur].fill_(-1)
-                ops.verify_accept(self.params, self.state, self.probs[cur], self.probs[1 - cur], None if philox else self.rs,
-                                  None if philox else self.noise2[0], self.scratch, mirror=True)
+                lc, lu = self._prefill_sample(self, logits, self._guidance, cur, B, tensors=not philox)
                 if attn is not None and hasattr(attn, "params"):
                     attn.params = self.params                                        # windows: kv_len / n_rows from the blob
             else:
@@ -587,7 +580,7 @@ class SJDEngine:
                     logits = self._launch_forward(cols)
                     t_host0 = time.perf_counter()
                     resid = grammar.residual_rules(win)
-                    self._upload_resid(resid)
+                    self._upload_resid(self.params, resid)
                     stats.host_seconds += time.perf_counter() - t_host0
                     self._launch_sample(cur, logits, cols)
                 else:
@@ -610,41 +603,19 @@ class SJDEngine:
             t_sync0 = time.perf_counter()
             self.state.wait_mirror(None if _MIRROR_STREAM_WAIT else self._seq)     # K4 wrote the state into pinned host memory and published iter_seq: no D2H copy, no HIP call
             stats.sync_seconds += time.perf_counter() - t_sync0
-            m_dev, rejected = int(st.m), bool(st.rejected)
-            if int(st.rejected) > 1:
-                raise RuntimeError("SJD verify: the residual distribution max(p - q, 0) is empty under the residual grammar rule "
-                                   "(the reference's torch.multinomial raises on the NaN probabilities at JL:237)")
+            # ---------------- read-back: generator cursor, emitted / carried, next window length, KV rollback, end test ----------------
+            rejected = int(st.rejected)
+            tok = st.tokens
+            loop.absorb(int(st.m), rejected, tok, tok if greedy else st.amax, win_len, cfg, grammar)      # (greedy: the modes are the tokens themselves)
             if g_state is not None and not rejected:
                 gen.set_state(g_state)                 # host-drawn noise: the residual draw was speculative, rewind it
-            if philox:                                 # what torch would have consumed: multinomial [+ rand [+ residual multinomial]]
-                ph_off += k2_step + (ph_step if draws_rs else 0) + (ph_row if (draws_rs and rejected) else 0)
-                if self.hook is not None:
-                    gen.set_offset(ph_off)
-            Y = st.tokens[:n_rows]
-            A = Y if greedy else st.amax[:n_rows]              # modes of this iteration's target rows (K2 by-product; greedy: the tokens themselves)
-            if n_rows <= 1:
-                m = win_len                      # is_prefilling_phase short-circuit (JL:344-350)
-                emitted, carried, carried_amax, last_amax = [Y[0]], [], [], A[0]
-            else:
-                m = m_dev
-                emitted, carried, carried_amax, last_amax = Y[:m], Y[m:], A[m:], A[m - 1]
-            stats.matched.append(m)
+            if philox and self.hook is not None:
+                gen.set_offset(loop.ph_off)
             if iter_log is not None:
-                iter_log.append((kv_len, n_rows, m, time.perf_counter()))
-            # ---------------- next window length, append, rollback ----------------
-            n = min(W, r_abs - cur_len) if (l_abs <= cur_len < r_abs) else 1       # JL:1142-1144 (old cur_len)
-            X.extend(emitted)
-            grammar.push(emitted)
-            kv_len += m
-            n_prev, m_prev = n_rows, (1 if n_rows <= 1 else m)
+                iter_log.append((kv_len, n_rows, stats.matched[-1], time.perf_counter()))
             cur = 1 - cur
-            first = False
-            stats.nfe += 1
-            if X[-1] in cfg.eos_token_ids or len(X) >= cfg.max_length:             # JL:1200-1201
-                finished = True
-            cur_len = len(X)
             if timing and stats.nfe == timed_nfe0 + timed_iters:
-                self._close_timed(stats, ev0, ev1, t0, on_timed_end, len(X) - timed_tok0, stats.nfe - timed_nfe0, kv_len)
+                self._close_timed(stats, ev0, ev1, t0, on_timed_end, len(X) - timed_tok0, stats.nfe - timed_nfe0, loop.kv_len)
                 timing, timed_done = False, True
                 if not continue_after:
                     break
@@ -653,11 +624,11 @@ class SJDEngine:
             # its partner either (both are barriers in bench.py -- an unmatched one hangs the other ranks), and say so in the stats
             stats.timed_region_reached = timing or timed_iters is None
             self._close_timed(stats, ev0, ev1, t0, on_timed_end if timing else None,
-                              len(X) - (timed_tok0 if timing else P), stats.nfe - (timed_nfe0 if timing else 0), kv_len)
+                              len(X) - (timed_tok0 if timing else P), stats.nfe - (timed_nfe0 if timing else 0), loop.kv_len)
         torch.cuda.synchronize()
         check_reduce_timeouts()
         if philox:
-            gen.set_offset(ph_off)                     # leave the generator where the reference's draws would have left it
+            gen.set_offset(loop.ph_off)                # leave the generator where the reference's draws would have left it
         stats.total_tokens, stats.total_seconds = len(X) - P, time.perf_counter() - t_decode0
         return X, stats
 

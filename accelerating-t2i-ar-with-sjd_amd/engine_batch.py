@@ -3,9 +3,10 @@
 A draft-window forward is a pure weight stream: 13 GB of weights for 32 activation rows.  Two prompts (2 x B_cfg x L = 64 rows)
 cost the same stream, so decoding them together almost doubles the accepted tokens per second of a GPU; up to eight prompts (256 rows; the rate is flat beyond four: DESIGN.md 10b;
 G1's sub-tiled kernel) fit in one forward: 963 / 1292 tokens/s per MI355X for two / four Lumina 768px prompts against 561 for one.  Every prompt ("slot")
-keeps exactly the state machine of `SJDEngine.decode` -- its own window, accept length, KV length, grammar, device generator
-and CPU generator for the fresh ids -- so each slot takes the decisions its solo run would take on the same logits; only the
-transformer forward is shared:
+IS the state machine `SJDEngine.decode` runs (window_loop.PromptLoop: a slot is one plus its device handles) -- its own window, accept
+length, KV length, grammar, device generator and CPU generator for the fresh ids -- so each slot takes the decisions its solo run would
+take on the same logits; only the transformer forward is shared, launched through the graph cache both engines use
+(engine.WindowLauncher):
 
    host    per slot: n, fresh ids, rules, residual rules, its generator's seed / offsets -> its blob of a contiguous sjd_iter_params
            ARRAY (batch_rows = B_cfg: the kernels K1 / K3 / F2 pick the blob of a batch row, i.e. every prompt has its own kv_len and
@@ -27,8 +28,8 @@ import torch
 from . import _lib as L
 from . import launch_shapes as LS
 from . import ops
-from .engine import DecodeStats, SJDConfig, WindowSpec, warn_no_grid, capture_graph
-from .grammar import spatial_fresh_tokens
+from .engine import SJDConfig, WindowLauncher, WindowSpec, cached_column_window, check_reduce_timeouts
+from .window_loop import PromptLoop
 
 
 class _CacheView:
@@ -38,8 +39,12 @@ class _CacheView:
         self.k, self.v, self.s_max = cache.k[:, lo:hi], cache.v[:, lo:hi], cache.s_max
 
 
-class _Slot:
-    pass
+class _Slot(PromptLoop):
+    """A prompt's state machine plus the slot's device handles (params, state, probs, ...): an admission starts the machine again
+    (PromptLoop.__init__) on the same handles."""
+
+    def __init__(self):
+        pass
 
 
 # what the prompts of one decode_many may NOT differ in: the window iterations run in lock-step through one set of launches, one scheme, one noise
@@ -78,7 +83,7 @@ def per_prompt_configs(cfg, n_prompts):
     return cfgs[0], cfgs
 
 
-class SJDBatchEngine:
+class SJDBatchEngine(WindowLauncher):
     def __init__(self, backbone, vocab_size, device, n_prompts, max_window=16, n_batch=2, use_graph=True, narrow_head=True, head_partials=True):
         bargs = getattr(backbone, "args", None)
         if getattr(bargs, "swin_norm", False) or getattr(bargs, "model_parallel_size", 1) != 1:
@@ -179,79 +184,6 @@ class SJDBatchEngine:
         self._rule_bytes, self._rule_keep, self._cols_cache = {}, [], {}
         self.reset_graphs()
 
-    def reset_graphs(self):
-        """Call after the backbone's cache / weights were re-allocated."""
-        self._graphs, self._graph_logits, self._eager_runs = {}, {}, {}
-        self.__dict__.pop("_graph_sig", None)
-
-    def _check_graph_buffers(self):
-        """see SJDEngine._check_graph_buffers: never replay a graph that holds the address of a re-allocated workspace / cache"""
-        from .engine import SJDEngine
-        SJDEngine._check_graph_buffers(self)
-
-    # ------------------------------------------------------------------------------------------------
-    def _noise_tensors(self, s):
-        if s.noise is None:
-            dev = self.device
-            s.noise = torch.ones(self.Lmax, self.V, dtype=torch.float32, device=dev)
-            s.rs = torch.zeros(self.Lmax, self.V, dtype=torch.float32, device=dev)
-            s.noise2 = torch.ones(1, self.V, dtype=torch.float32, device=dev)
-
-    def _fill(self, slot, n, kv_len, use_cfg, scheme, fresh, rules, resid):
-        """the slot's blob for one iteration, incl. the state of ITS device generator: K2 / K4 generate the multinomial / rand / residual
-        noise torch would have drawn from it (SJDEngine._fill_params); slot.ph_step = what one [n, V] draw consumes"""
-        p = slot.params.view
-        p.n_rows, p.kv_len, p.use_cfg, p.scheme, p.n_fresh = n, kv_len, int(use_cfg), scheme, len(fresh)
-        slot.ph_step = ops.philox_step(n * self.V, self._ph_blocks)
-        k2_step = 0 if getattr(self, "_greedy", False) else slot.ph_step          # greedy: sampling_logits2tokens draws nothing (JL:127-129)
-        p.philox_blocks, p.philox_seed = self._ph_blocks, slot.ph_seed
-        p.philox_offset[0], p.philox_offset[1], p.philox_offset[2] = slot.ph_off, slot.ph_off + k2_step, slot.ph_off + k2_step + slot.ph_step
-        if fresh:
-            p.fresh_tok[:len(fresh)] = fresh
-        self._write_rules(slot, L.IterParams.rules.offset, rules)
-        if resid:
-            self._write_rules(slot, L.IterParams.resid_rules.offset, resid)
-
-    def _write_rules(self, slot, offset, rules):
-        """a rule sequence goes into the slot's blob as ONE block copy, its packed bytes cached by the interned structs' identities
-        (SJDEngine._write_rules: with four slots the per-element ctypes writes were ~0.1 ms of host time per forward)"""
-        key = tuple(map(id, rules))
-        blk = self._rule_bytes.get(key)
-        if blk is None:
-            blk = b"".join(bytes(r) for r in rules)
-            if len(self._rule_bytes) < 4096:
-                self._rule_bytes[key] = blk
-                self._rule_keep.append(list(rules))
-        L.ctypes.memmove(slot.params.host.data_ptr() + offset, blk, len(blk))
-
-    def _columns(self, rule_lists):
-        """union of the slots' output-head column windows (SJDEngine.logit_columns), None = all columns"""
-        if not self.narrow_head:
-            return None
-        key = tuple(id(r) for rules in rule_lists for r in rules)
-        if key in self._cols_cache:
-            return self._cols_cache[key]
-        cols = self._columns_uncached(rule_lists)
-        if len(self._cols_cache) < 4096:
-            self._cols_cache[key] = cols
-            self._rule_keep.append([r for rules in rule_lists for r in rules])
-        return cols
-
-    def _columns_uncached(self, rule_lists):
-        lo, hi = self.V, 0
-        for rules in rule_lists:
-            for r in rules:
-                if r.forced >= 0:
-                    continue
-                if r.n_ranges == 0:
-                    return None
-                lo = min([lo] + [r.lo[i] for i in range(r.n_ranges)])
-                hi = max([hi] + [r.hi[i] for i in range(r.n_ranges)])
-        if hi <= lo:
-            return None
-        lo, hi = (lo // 32) * 32, min(self.V, ((hi + 31) // 32) * 32)
-        return (lo, hi) if 2 * (hi - lo) <= self.V else None
-
     def _per_slot(self, fn):
         """fn(i, slot) for every slot, one after the other on the current stream.  (Round 6 measured the alternative -- the slots' K5 / K2 + K4
         launches as parallel branches of the iteration's hipGraph, forked onto side streams and rejoined: eight prompts 7.2 -> 8.5 ms per step,
@@ -286,8 +218,8 @@ class SJDBatchEngine:
             dbg.zero_()
         wide = part and not ops.head_slots_ok(logits)          # a head wide enough for K2a: it runs in front of every slot's own K2
         def k2_k4(i, s):
-            tok_out, amax_out = (s.amax_ptr, s.tokens_ptr) if getattr(self, "_greedy", False) else (s.tokens_ptr, s.amax_ptr)
-            if part:               # (different scales: K2a reads the slot's element of the engine's array -- a wide head, see below)
+            tok_out, amax_out = self._k2_out(s)
+            if part:              # (different scales: K2a reads the slot's element of the engine's array -- a wide head, see below)
                 g = self._guid_dev[i:i + 1] if self._mixed_guidance else self._guidance
                 ops.logits_to_probs_sample_part(logits, g, s.params, None, s.probs[cur], tok_out, amax_out_ptr=amax_out,
                                                 dbg=None if dbg is None else dbg[i * self.nb:(i + 1) * self.nb], row0=i * self.nb * self.Lmax,
@@ -319,6 +251,14 @@ class SJDBatchEngine:
         the captured K2 reads the engine's array, whatever it holds"""
         return "per-slot array" if self._mixed_guidance else self._guidance
 
+    def _graph_key(self, kind, cols, cur=None):
+        """the key of this iteration's forward ("fwd"), one-stage ("win") or two-stage sample ("smp") graph.  A sample graph bakes in the
+        forward graph's buffer it was captured on, and every K1 regime's forward owns its own: the regime is part of that key."""
+        if kind == "fwd":
+            return ("fwd", cols)
+        own = (self._guidance_key(), self.hook is not None, getattr(self, "_greedy", False))
+        return ("win", cols, cur) + own if kind == "win" else ("smp", cur, cols, self._k1_regime()) + own
+
     def _refuse_mixed_guidance_per_slot(self, why=None):
         """Different guidance scales in one batch are served by the ONE K2 launch over all slots (sjd_logits_to_probs_sample_part_slots_g) and,
         for a head window wide enough for K2a (LlamaGen's 16384 columns, Emu3), by K2a in front of every slot's K2 (sjd_head_combine_g): both read
@@ -328,81 +268,6 @@ class SJDBatchEngine:
             raise ValueError("prompts with different guidance scales need K2 as one launch over all slots or K2a in front of it, but this engine "
                              "launches K2 per slot over " + (why or "a narrow head window (SJD_SLOT_LAUNCHES=0)") + ": decode prompts of one "
                              "guidance scale per decode_many on this configuration")
-
-    def _launch_forward(self, cols):
-        if not self.use_graph:
-            return self._forward_body(cols)
-        self._check_graph_buffers()
-        fkey = ("fwd", cols)
-        if fkey not in self._graphs:
-            if self._eager_runs.get(fkey, 0) < 1:     # one eager run warms up allocations / hipBLASLt before capture
-                self._eager_runs[fkey] = 1
-                return self._forward_body(cols)
-            g = torch.cuda.CUDAGraph()
-            with capture_graph(g):
-                self._graph_logits[fkey] = self._forward_body(cols)
-            self._graphs[fkey] = g
-        self._graphs[fkey].replay()
-        return self._graph_logits[fkey]
-
-    def _launch_sample(self, cur, logits, cols):
-        key = (cur, self._guidance_key(), cols, self.hook is not None, getattr(self, "_greedy", False))
-        if not self.use_graph or ("fwd", cols) not in self._graphs:
-            self._sample_body(cur, logits, cols)
-            return
-        if key not in self._graphs:
-            self._sample_body(cur, logits, cols)
-            g = torch.cuda.CUDAGraph()
-            with capture_graph(g):
-                self._sample_body(cur, logits, cols)
-            self._graphs[key] = g
-            return
-        self._graphs[key].replay()
-
-    def _launch_window(self, cur, cols):
-        """the whole iteration of all slots as ONE hipGraph per (column window, prob-buffer parity) -- SJDEngine._launch_window"""
-        if not self.use_graph:
-            logits = self._forward_body(cols)
-            self._sample_body(cur, logits, cols)
-            return logits
-        self._check_graph_buffers()
-        key = ("win", cols, cur, self._guidance_key(), self.hook is not None, getattr(self, "_greedy", False))
-        if key not in self._graphs:
-            if self._eager_runs.get(key, 0) < 1:
-                self._eager_runs[key] = 1
-                logits = self._forward_body(cols)
-                self._sample_body(cur, logits, cols)
-                return logits
-            g = torch.cuda.CUDAGraph()
-            with capture_graph(g):
-                logits = self._forward_body(cols)
-                self._sample_body(cur, logits, cols)
-            self._graph_logits[key] = logits
-            self._graphs[key] = g
-        self._graphs[key].replay()
-        return self._graph_logits[key]
-
-    def captured_column_windows(self):
-        return sorted({k[1] for k in self._graphs if isinstance(k, tuple) and k[0] in ("fwd", "win")}, key=lambda c: (c is None, c))
-
-    def _upload_resid(self, s, resid):
-        """two-stage iterations: a slot's residual rules go up behind the forward, on the same stream (SJDEngine._upload_resid)"""
-        off = L.IterParams.resid_rules.offset
-        self._write_rules(s, off, resid)
-        L.check(L.load().sjd_upload_async(s.params.dev.data_ptr() + off, s.params.host.data_ptr() + off, s.params.nbytes - off, ops._stream()),
-                "sjd_upload_async")
-
-    def _observer_noise(self, s, n_rows, scheme):
-        """what the slot's kernels generate, drawn by torch from the same generator state -- for observers only (the parity tests' hook)"""
-        self._noise_tensors(s)
-        s.gen.set_offset(s.ph_off)
-        if getattr(self, "_greedy", False):
-            s.noise[:n_rows].fill_(1.0)
-        else:
-            s.noise[:n_rows].exponential_(generator=s.gen)
-        if n_rows > 1 and scheme == 0:
-            s.rs[:n_rows].uniform_(0.0, 1.0, generator=s.gen)
-            s.noise2.exponential_(generator=s.gen)
 
     # ------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -436,23 +301,13 @@ class SJDBatchEngine:
         if not self.head_partials:
             self._refuse_mixed_guidance_per_slot("dense logits (the backbone hands out no head partials)")
         self._greedy = greedy = not getattr(cfg, "do_sample", True)
-        k2_draws = 0 if greedy else 1
         assert len(specs) == len(grammars) == N and N >= self.P
-        if cfg.multi_token_init_scheme not in ("random", "repeat_horizon", "sample_horizon"):
-            raise ValueError(f"multi_token_init_scheme should be 'random', 'repeat_horizon' or 'sample_horizon', but got {cfg.multi_token_init_scheme}")
-        for g_ in grammars:
-            warn_no_grid(cfg, g_)
-        if cfg.prefix_token_sampler_scheme not in ("speculative_jacobi", "jacobi"):
-            raise ValueError(f"prefix_token_sampler_scheme: {cfg.prefix_token_sampler_scheme}")
-        if cfg.max_num_new_tokens > self.Lmax:
-            raise ValueError("max_num_new_tokens exceeds the engine's max_window")
+        self._check_config(cfg, grammars)
         dev, nb = self.device, self.nb
-        self._ph_blocks = ops.philox_max_blocks(dev)
-        ph_row = ops.philox_step(self.V, self._ph_blocks)                  # offset step of a [1, V] draw
+        ph_blocks = ops.philox_max_blocks(dev)
         default_gen = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
         scheme = 0 if cfg.prefix_token_sampler_scheme == "speculative_jacobi" else 1
         do_cfg = cfg.do_cfg and (cfg.guidance_scale != 1)
-        W = cfg.max_num_new_tokens
         self._guidance = float(cfg.guidance_scale)
         prompt_seed = lambda j: cfgs[j].seed if cfgs is not None else (None if cfg.seed is None else cfg.seed + j)
         attn = getattr(self.backbone, "attn", None)
@@ -504,8 +359,6 @@ class SJDBatchEngine:
                     lg = lg[0:1]
                 g0 = torch.Generator(dev).manual_seed(seed if seed is not None else pre_seeds[j])
                 first_tok = int(_lg_sample(lg, generator=g0, **sk)[0][0, 0])
-            s.X = [int(t) for t in prompts[j]] if first_tok is None else [first_tok]
-            s.P = len(s.X)
             if seed is None and pre_seeds is not None:
                 s.gen = torch.Generator(dev).manual_seed(pre_seeds[j])
             elif seed is None:
@@ -516,64 +369,44 @@ class SJDBatchEngine:
                 s.gen = torch.Generator(dev).manual_seed(slot_seed)
             else:
                 s.gen = torch.Generator(dev).manual_seed(seed)
-            s.ph_seed, s.ph_off = int(s.gen.initial_seed()), int(s.gen.get_offset())
+            PromptLoop.__init__(s, prompts[j] if first_tok is None else [first_tok], specs[j].kv_base, cfg, int(s.gen.initial_seed()), int(s.gen.get_offset()))
             s.cpu_gen = None if seed is None else torch.Generator().manual_seed(seed)     # the prompt's "global CPU generator" (JL:505)
             s.grammar = grammars[j]
             s.grammar.start(s.X)
-            s.l_abs, s.r_abs = s.P + cfg.jacobi_loop_interval_l, s.P + cfg.jacobi_loop_interval_r
-            s.n, s.kv_len, s.cur_len, s.n_prev, s.m_prev = 1, specs[j].kv_base, s.P, 1, 1
-            s.carried, s.carried_amax, s.last_amax, s.finished, s.harvested, s.stats = [], [], None, False, False, DecodeStats()
-            s.t_admit = time.perf_counter()
+            s.harvested, s.t_admit = False, time.perf_counter()
             self.pos_offset[i * nb:(i + 1) * nb].copy_(specs[j].pos_offset.to(device=dev, dtype=torch.int64))
-            if s.cpu_gen is not None:
-                torch.randint(0, cfg.img_vocab_n, (1, 0), generator=s.cpu_gen)
-            rules = s.grammar.window_rules(1)
-            use_cfg = do_cfg and not s.grammar.force_no_cfg()
-            self._fill(s, 1, s.kv_len, use_cfg, scheme, [], rules, [])
+            _, _, rules, _, _, use_cfg, _, offs = s.plan(cfg, s.grammar, s.cpu_gen, self.V, ph_blocks, greedy, scheme, do_cfg)
+            self._fill_blob(s.params, 1, s.kv_len, use_cfg, scheme, [], rules, [], (ph_blocks, s.ph_seed) + offs)
             s.params.upload()
             if self.hook is not None:
-                self._observer_noise(s, 1, scheme)
+                self._observer_noise(s, s.gen, s.ph_off, 1, False)
             if first_tok is None:
                 tokens, positions = specs[j].first_tokens.to(dev), specs[j].first_positions.to(dev)
             else:                                # the window starts as the solo path's: the first image token at position T
                 tokens = torch.full((nb, 1), first_tok, dtype=torch.long, device=dev)
                 positions = torch.full((nb, 1), specs[j].kv_base, dtype=torch.long, device=dev)
-            from .engine import SJDEngine
-            SJDEngine._calibrate_fp8(self, tokens, positions, self.key_start[i * nb:(i + 1) * nb])      # (an fp8 cache nobody calibrated: once per backbone)
+            self._calibrate_fp8(tokens, positions, self.key_start[i * nb:(i + 1) * nb])      # (an fp8 cache nobody calibrated: once per backbone)
             self.backbone.cache = _CacheView(full_cache, i * nb, (i + 1) * nb)
             try:
                 logits = self.backbone.forward_window(tokens, positions, s.kv_len, self.key_start[i * nb:(i + 1) * nb])
             finally:
                 self.backbone.cache = full_cache
-            lc = logits[0, -1:, :]
-            lu = logits[1, -1:, :] if nb > 1 else None
-            tok_out, amax_out = (s.amax_ptr, s.tokens_ptr) if greedy else (s.tokens_ptr, s.amax_ptr)
-            ops.logits_to_probs_sample(lc, lu, guidance, s.params, None, s.probs[buf], tok_out, amax_out_ptr=amax_out)
-            s.zero_state[buf].fill_(-1)
-            ops.verify_accept(s.params, s.state, s.probs[buf], s.probs[1 - buf], None, None, s.scratch, mirror=True)
-            s.ph_off += s.ph_step * k2_draws                       # the [1, V] multinomial of iteration 0 (greedy: none)
+            lc, lu = self._prefill_sample(s, logits, guidance, buf, nb)
             if self.hook is not None:
                 self.hook(j, dict(first=True, n_rows=1, logits_c=lc, logits_u=lu, use_cfg=use_cfg, rules=rules, resid=[],
                                   noise=s.noise[:1], rs=s.rs[:1], noise2=s.noise2[0], probs=s.probs[buf], prev_probs=s.probs[1 - buf],
                                   ctx=list(s.X), scheme=scheme))
-                s.gen.set_offset(s.ph_off)
             s.win_len = tokens.shape[1]
 
-        def after_prefill(s):
-            """host bookkeeping of iteration 0 (after the state download)"""
+        def read_back(s, win_len):
+            """a slot's host bookkeeping after the state download (iteration 0: win_len = the rows of its prefill)"""
             nonlocal emitted_total
-            y0 = int(s.state.view.tokens[0])
-            s.last_amax = y0 if greedy else int(s.state.view.amax[0])
-            s.stats.matched.append(s.win_len)
-            s.n = min(W, s.r_abs - s.cur_len) if (s.l_abs <= s.cur_len < s.r_abs) else 1
-            s.X.append(y0)
-            emitted_total += 1
-            s.grammar.push([y0])
-            s.kv_len += s.win_len
-            s.n_prev, s.m_prev, s.carried, s.carried_amax = 1, 1, [], []
-            s.stats.nfe += 1
-            s.finished = s.X[-1] in cfg.eos_token_ids or len(s.X) >= cfg.max_length
-            s.cur_len = len(s.X)
+            st = s.state.view
+            tok = st.tokens
+            k = s.absorb(int(st.m), int(st.rejected), tok, tok if greedy else st.amax, win_len, cfg, s.grammar)
+            emitted_total += k
+            if k and self.hook is not None:
+                s.gen.set_offset(s.ph_off)
 
         images, self.detok_events = [None] * N, [None] * N
         if detokenize is not None and getattr(self, "detok_stream", None) is None:
@@ -607,7 +440,7 @@ class SJDBatchEngine:
             admit(i, cur)
         self.state.wait_mirror()
         for s in self.slots:
-            after_prefill(s)
+            read_back(s, s.win_len)
         cur = 1 - cur
         if attn is not None and hasattr(attn, "params"):
             attn.params = self.params                          # windows: kv_len / n_rows of every prompt from its blob
@@ -632,7 +465,7 @@ class SJDBatchEngine:
                             attn.params = None
                         admit(i, 1 - cur)
                         self.state.wait_mirror()
-                        after_prefill(s)
+                        read_back(s, s.win_len)
                         if attn is not None and hasattr(attn, "params"):
                             attn.params = self.params
             if all(s.finished for s in self.slots):
@@ -650,40 +483,26 @@ class SJDBatchEngine:
             t_h = time.perf_counter()
             rule_lists, metas, slow = [], [], []
             for s in self.slots:
-                resid, win = [], None
-                if s.finished:                                 # dummy one-row window: a forced row (K2 reads no logits), result ignored
-                    n_rows, fresh, a = 1, [], 0
-                    rules, use_cfg = [ops.make_rule(forced=0)], False
-                else:
-                    n_rows = s.n
-                    a = max(0, min(s.n_prev - s.m_prev, s.n - 1))
-                    fr = torch.randint(0, cfg.img_vocab_n, (1, s.n - 1 - a), generator=s.cpu_gen)[0].tolist()
-                    fresh = [cfg.img_vocab_lo + t for t in fr]
-                    if cfg.multi_token_init_scheme != "random":                      # spatial init (JL:516-594), as in SJDEngine.decode
-                        fresh = spatial_fresh_tokens(cfg.multi_token_init_scheme, fresh, len(s.X) + a, s.carried[a - 1] if a else s.X[-1],
-                                                     s.carried_amax[a - 1] if a else s.last_amax, s.grammar.grid())
-                    rules = s.grammar.window_rules(n_rows)
-                    use_cfg = do_cfg and not s.grammar.force_no_cfg()
+                # (a finished slot rides along with a dummy one-row window: PromptLoop.plan)
+                n_rows, fresh, rules, win, resid, use_cfg, _, offs = s.plan(cfg, s.grammar, s.cpu_gen, self.V, ph_blocks, greedy, scheme, do_cfg)
+                if not s.finished:
                     rule_lists.append(rules)
-                    if scheme == 0 and n_rows > 1:             # residual rules before the launch when the grammar can name them
-                        win = [s.X[-1]] + s.carried[:a] + fresh
-                        resid = s.grammar.fast_residual_rules(win, rules)
-                        if resid is None:
-                            slow.append((s, win, len(metas)))
-                self._fill(s, n_rows, s.kv_len, use_cfg, scheme, fresh, rules, resid or [])
+                    if resid is None:                          # the grammar cannot name the residual rules before the launch
+                        slow.append((s, win, len(metas)))
+                self._fill_blob(s.params, n_rows, s.kv_len, use_cfg, scheme, fresh, rules, resid or [], (ph_blocks, s.ph_seed) + offs)
                 metas.append([n_rows, rules, resid, use_cfg])
             self.params.upload()
-            cols = self._columns(rule_lists) if rule_lists else None
+            cols = cached_column_window(self, rule_lists) if rule_lists else None      # the union of the slots' output-head column windows
             if self.hook is not None:
-                for s, mt in zip(self.slots, metas):
-                    self._observer_noise(s, mt[0], scheme)
+                for s in self.slots:
+                    self._observer_noise(s, s.gen, s.ph_off, s.n_rows, s.draws_rs)
             host_s += time.perf_counter() - t_h
             if slow:                                            # two stages: the missing residual rules are computed under the forward
                 logits = self._launch_forward(cols)
                 t_h = time.perf_counter()
                 for s, win, k in slow:
                     metas[k][2] = s.grammar.residual_rules(win)
-                    self._upload_resid(s, metas[k][2])
+                    self._upload_resid(s.params, metas[k][2])
                 host_s += time.perf_counter() - t_h
                 self._launch_sample(cur, logits, cols)
             else:
@@ -709,35 +528,8 @@ class SJDBatchEngine:
             t_s = time.perf_counter()
             self.state.wait_mirror()                              # the single sync of the iteration
             sync_s += time.perf_counter() - t_s
-            for s, (n_rows, _, _, _) in zip(self.slots, metas):
-                if s.finished:
-                    s.ph_off += s.ph_step * k2_draws           # (the dummy row's draw: keeps blob and generator consistent; never observed)
-                    continue
-                st = s.state.view
-                m_dev, rejected = int(st.m), bool(st.rejected)
-                if int(st.rejected) > 1:
-                    raise RuntimeError("SJD verify: the residual distribution max(p - q, 0) is empty under the residual grammar rule")
-                draws_rs = n_rows > 1 and scheme == 0          # what torch would have consumed: multinomial [+ rand [+ residual multinomial]]
-                s.ph_off += s.ph_step * (k2_draws + (1 if draws_rs else 0)) + (ph_row if (draws_rs and rejected) else 0)
-                if self.hook is not None:
-                    s.gen.set_offset(s.ph_off)
-                Y = st.tokens[:n_rows]
-                A = Y if greedy else st.amax[:n_rows]          # modes of this iteration's target rows (K2 by-product; greedy: the tokens themselves)
-                if n_rows <= 1:
-                    m, emitted, s.carried, s.carried_amax, s.last_amax = 1, [Y[0]], [], [], A[0]
-                else:
-                    m, emitted, s.carried, s.carried_amax, s.last_amax = m_dev, Y[:m_dev], Y[m_dev:], A[m_dev:], A[m_dev - 1]
-                s.stats.matched.append(m)
-                s.n = min(W, s.r_abs - s.cur_len) if (s.l_abs <= s.cur_len < s.r_abs) else 1      # JL:1142-1144 (old cur_len)
-                s.X.extend(emitted)
-                emitted_total += len(emitted)
-                s.grammar.push(emitted)
-                s.kv_len += m
-                s.n_prev, s.m_prev = n_rows, (1 if n_rows <= 1 else m)
-                s.stats.nfe += 1
-                if s.X[-1] in cfg.eos_token_ids or len(s.X) >= cfg.max_length:
-                    s.finished = True
-                s.cur_len = len(s.X)
+            for s, mt in zip(self.slots, metas):
+                read_back(s, mt[0])
             cur = 1 - cur
             it += 1
             if timed_iters is not None and it == warmup_iters + timed_iters:
@@ -746,7 +538,6 @@ class SJDBatchEngine:
         if detokenize is not None:
             self.detok_stream.synchronize()                    # the one wait for the side stream
         torch.cuda.synchronize()
-        from .engine import check_reduce_timeouts
         check_reduce_timeouts()                    # (a reducing projection that gave up a wait: wrong numbers must not become tokens -- ADVICE r3)
         if on_timed_end is not None and (timed_started or timed_iters is None):      # never an unmatched barrier (SJDEngine.decode)
             on_timed_end()
