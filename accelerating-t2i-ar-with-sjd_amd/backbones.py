@@ -34,14 +34,30 @@ import logging as _logging
 import os as _os
 _log = _logging.getLogger("sjd_amd.backbones")
 
-# K1F (F2 + K1 + combine in one launch, 64 workgroups) is correct and tested but NOT faster on MI355X: a CU streams ~30 GB/s at most, so
-# 64 workgroups cap at ~1.9 TB/s where the 256-workgroup split kernel reaches 2.8 TB/s, and the dependent round trips (partials -> q/K/V
-# -> tiles -> merge) remain inside the fused kernel (profiles/r2_attention_block.jsonl: 17.3 / 23.2 / 32.5 / 47.6 us against 17.7 / 21.6 /
-# 27.0 / 33.7 us at kv_len 64 / 448 / 1216 / 2368).  Default off; SJD_K1_FUSED=1 or model.k1_fused = True selects it.
+# The opt-in experiments of the folded window forward -- K1F / K1Fs, the reducing o / down tail, the one-launch MLP, the side-stream weight prefetch and
+# `gateup_fused = "tall"` -- live in backbones_exp.py with their measurements; every one is OFF by default and calls libsjd_hip_exp.so.  This module only
+# reads their switches (environment, or the instance attribute of the same name: _experiments_on) and imports backbones_exp when one is set.
 _K1_FUSED_DEFAULT = _os.environ.get("SJD_K1_FUSED", "0") == "1"
-_K1_FUSED_SPLIT_DEFAULT = _os.environ.get("SJD_K1_FUSED_SPLIT", "1") != "0"   # with k1_fused: the split form K1Fs (0: one workgroup per (batch, head))
-_MLP_PAIR_DEFAULT = _os.environ.get("SJD_MLP_PAIR", "0") == "1"          # sjd_mlp_pair_z: the MLP as one launch (round-4 experiment)
+_REDUCE_FUSED_DEFAULT = _os.environ.get("SJD_REDUCE_FUSED", "0") == "1"
+_MLP_PAIR_DEFAULT = _os.environ.get("SJD_MLP_PAIR", "0") == "1"
+_GATEUP_FUSED_DEFAULT = {"0": False, "tall": "tall"}.get(_os.environ.get("SJD_GATEUP_FUSED", "1"), True)     # kernel G1s (gate|up + F3 in one launch); 0: G1 then F3; tall: also above 64 rows (an experiment)
+# the same switch for the swin-norm route's K = 8192 MXFP4 form (enable_fused(weights="mxfp4", swin_quant=True)).  OFF by default: measured on the whole 30B
+# preset the fused launch is slower than G1q4 + F3 on the same copy (7.64 against 7.30 ms per step, 0.03 ms between rounds; 54.7 against 50.2 us per launch:
+# every one of its 344 workgroups stages the whole 32 x 8192 activation -- profiles/swin30b_quant.json).  `backbone.gateup_fused = True` reaches the kernel.
+_SWIN_GATEUP_FUSED_DEFAULT = False
 _NAN_CHECK = _os.environ.get("SJD_NAN_CHECK", "0") == "1"                    # debug aid: name the first kernel whose output is not finite
+
+
+def _experiments_on(m):
+    """is one of backbones_exp's experiments switched on for backbone `m`?"""
+    return bool(getattr(m, "k1_fused", _K1_FUSED_DEFAULT) or getattr(m, "reduce_fused", _REDUCE_FUSED_DEFAULT) or getattr(m, "mlp_pair", _MLP_PAIR_DEFAULT)
+                or getattr(m, "gateup_fused", _GATEUP_FUSED_DEFAULT) == "tall"
+                or getattr(m, "_pf_on", _os.environ.get("SJD_PREFETCH") or any(b > 0 for b, _ in m.PREFETCH.values())))          # (the plan, once backbones_exp resolved it)
+
+
+def _exp():
+    from . import backbones_exp
+    return backbones_exp
 
 
 def _chk(tag, x, rows=None):
@@ -56,20 +72,6 @@ def _chk(tag, x, rows=None):
     return x
 
 
-# the same switch for the swin-norm route's K = 8192 MXFP4 form (enable_fused(weights="mxfp4", swin_quant=True)).  OFF by default: measured on the whole 30B
-# preset the fused launch is slower than G1q4 + F3 on the same copy (7.64 against 7.30 ms per step, 0.03 ms between rounds; 54.7 against 50.2 us per launch:
-# every one of its 344 workgroups stages the whole 32 x 8192 activation -- profiles/swin30b_quant.json).  `backbone.gateup_fused = True` reaches the kernel.
-_SWIN_GATEUP_FUSED_DEFAULT = False
-_GATEUP_FUSED_DEFAULT = {"0": False, "tall": "tall"}.get(_os.environ.get("SJD_GATEUP_FUSED", "1"), True)     # kernel G1s (gate|up + F3 in one launch); 0: G1 then F3; tall: also above 64 rows
-# round 3 experiment, correct, tested, OFF by default: the o / down projections of a <= 32-row window can reduce their own
-# split-K planes, add the residual and write the row statistics in their tail (sjd_skinny_gemm_reduce: device-coherent exchange between
-# the workgroups of a 512-column slice, bit-identical h and statistics), so that stage F1r -- two graph nodes per layer -- disappears.
-# Measured on one box against G1 + F1r: by kernel time o 13.55 -> 12.79 us, down 23.13 -> 22.05 us, but 3.512 against 3.416 ms/step end
-# to end once F1r itself was repaired (it had lost 1 us to serialised loads; 2.9 us now): three dependent device-scope round trips
-# (store acknowledgement, ticket, plane loads) cost more than a graph-node boundary plus ONE round trip.  SJD_REDUCE_FUSED=1 selects it.
-_REDUCE_FUSED_DEFAULT = _os.environ.get("SJD_REDUCE_FUSED", "0") == "1"
-
-
 def _head_logits(linear, x, cols):
     """fp32 logits of the output head, optionally only for the vocabulary columns [cols[0], cols[1]) -- the rows of the weight the
     grammar can give probability mass to in this iteration (Lumina image body: 8192 of 65536 ids).  K2 never reads a masked column,
@@ -79,19 +81,6 @@ def _head_logits(linear, x, cols):
     w = linear.weight[cols[0]:cols[1]]
     b = linear.bias[cols[0]:cols[1]] if linear.bias is not None else None
     return F.linear(x, w, b).float()
-
-
-def _head_partials(model, h, delta, cols, n, hid, eps, sumsq=None):
-    """final residual add + the output head of a fused backbone as G1 split-K partials over the column window `cols` -> ops.HeadOut (K2 applies
-    the folded final RMSNorm as a row scale while it reads them).  sumsq: the statistics of h when the residual add is already done."""
-    ops = model._ops
-    if sumsq is None:
-        sumsq = ops.residual_sumsq(h, delta)
-    lo, hi = cols if cols is not None else (0, model.vocab_size)
-    lo32, hi32 = (lo // 32) * 32, min(model._head_cols, ((hi + 31) // 32) * 32)
-    kc, tiles, sm = model.HEAD_CFG
-    part = ops.skinny_gemm_cols(h, model._packed_head, model._head_cols, hid, kc, lo32, hi32 - lo32, tiles, sm)
-    return ops.HeadOut(part, lo32, n if h.shape[0] > n else 0, h.dtype, row_norm=(sumsq, hid, eps))
 
 
 def _packer(ops, weights, compress, st):
@@ -141,6 +130,125 @@ def _refuse_quant_copy(prefix, g1_cfg, head_cfg, dims, max_rows, granule, reason
     """ValueError for the first thing LS.quant_copy_errors finds: enable_fused calls it before anything is assigned"""
     for name, why in LS.quant_copy_errors(g1_cfg, dims, max_rows, granule, head_cfg, reasons)[:1]:
         raise ValueError(prefix + LS.quant_copy_refusal(name, why, granule, head_cfg if name == "head" else g1_cfg[name], dims.get(name, (0, 0))[1]))
+
+
+def _pack_fused(m, ops, layers, pack, head=None, pack_head=None):
+    """The packing loop of both enable_fused, after their validation.  layers: per layer (q|k|v Linears, o matrix, gate Linear, up Linear, down matrix,
+    norm gain in front of q|k|v, norm gain in front of gate|up); a gain of None folds nothing.  Several q|k|v Linears and gate | up are concatenated ONCE and
+    the parameters re-pointed at the slices (state dict unchanged, no extra memory): m._fused.  pack (None: no packed copy) packs the four projections
+    on m.G1_CFG with the gains folded in: m._packed.  head = (matrix, final norm gain): the output head on G1, ONE packed copy with the
+    gain folded in -- a launch covers only the vocabulary columns the grammar allows and K2 reads its split-K partials: m._packed_head, m._head_cols."""
+    fold = lambda w, g: w if g is None else (w.float() * g.float()[None, :]).to(w.dtype)      # W' = W diag(gamma): the norm becomes a row scale (F2 / F3 / K2)
+
+    def joined(linears):
+        if len(linears) == 1:
+            return linears[0].weight
+        w, r0 = torch.cat([lin.weight for lin in linears], dim=0).contiguous(), 0
+        for lin in linears:
+            lin.weight.data, r0 = w[r0:r0 + lin.weight.shape[0]], r0 + lin.weight.shape[0]
+        return w
+
+    c = m.G1_CFG
+    m._packed, m._fused, m._packed_head = [], [], None
+    with torch.no_grad():
+        for qkv_lin, wo, gate, up, wd, g_qkv, g_gu in layers:
+            qkv, gu = joined(qkv_lin), joined([gate, up])           # gate | up: F3 / G1s read the gate half first
+            m._fused.append((qkv, gu) if len(qkv_lin) > 1 else gu)
+            if pack is not None:
+                m._packed.append(dict(qkv=pack(fold(qkv, g_qkv), c["qkv"][0], c["qkv"][2]),
+                                      o=pack(wo, c["o"][0], c["o"][2]),
+                                      gate_up=pack(fold(gu, g_gu), c["gate_up"][0], c["gate_up"][2], gateup=2 * c["gate_up"][0] == gu.shape[1]),
+                                      down=pack(wd, c["down"][0], c["down"][2])))
+        if head is not None:
+            wf = fold(*head)
+            pad = (-wf.shape[0]) % 32
+            if pad:
+                # the columns past the vocabulary are never read (K2's rules end at V); they are copies of the last real row, not zeros:
+                # a tile that is half zeros has no eight-exponent window, and the 12-bit packer declined Emu3's whole 184622-row head for
+                # that ONE tile (round 5: 14 real rows x 2048 weights "out of window" in the last tile, every other unit <= 60)
+                wf = torch.cat([wf, wf[-1:].expand(pad, -1)], dim=0)
+            m._head_cols = wf.shape[0]
+            m._packed_head = pack_head(wf, m.HEAD_CFG[0], m.HEAD_CFG[2])
+
+
+@dataclass
+class _WindowPath:
+    """what the shared window forwards read where the two backbones differ, gathered once by enable_fused (the packed copies stay in m._packed)"""
+    heads: tuple                  # (H, H_kv, D, DS); DS: the storage head dim of q, the cache rows and K1's output (128 for a padded head_dim 100)
+    hid: int
+    inter: int
+    eps: float
+    qk_norms: list                # per layer (q gain, q bias, k gain, k bias) of the QK-norm, or (None,) * 4
+    inv_freq: Optional[torch.Tensor]          # F2's rotary frequencies (None: it reads a table, see the F2 keywords)
+    attend_kw: dict               # K1's keyword arguments (a padded head_dim 100: the true head dim)
+    embed: nn.Module
+    norm: nn.Module               # the final norm
+    head: nn.Module               # the output head
+
+
+def _chunk(m, name, T, K_):
+    """split-K chunk of projection `name` for a T-row window of K_ columns (LS.chunk_for_rows); ValueError where none exists"""
+    return LS.chunk_for_rows(name, m.G1_CFG[name], T, K_, getattr(m, "weights", None), getattr(m, "max_rows", 64))
+
+
+def _g1_of(m, T):
+    """g1(x, li, name, N, K): kernel G1 over layer li's packed projection `name` on its launch shape, for a T-row window"""
+    def g1(x_, li, name, N_, K_):
+        cfg = m.G1_CFG[name]
+        return m._ops.skinny_gemm(x_, m._packed[li][name], N_, K_, _chunk(m, name, T, K_), cfg[1], cfg[2])
+    return g1
+
+
+def _window_rows(w, tokens, positions):
+    T = tokens.shape[0] * tokens.shape[1]
+    return T, w.embed(tokens).view(T, -1).contiguous(), positions.reshape(T).contiguous()
+
+
+def _window_head(m, h, delta, sumsq, B, n, cols, head_partials):
+    """The end of a window forward.  head_partials (and a packed head): the final residual add + the output head as G1 split-K partials over the column
+    window `cols` -> ops.HeadOut (K2 applies the folded final RMSNorm as a row scale and the 16-bit rounding of the head's output while it reads them);
+    else F1 and the library head -> fp32 logits.  sumsq: the statistics of h when the last residual add is already done."""
+    ops, w = m._ops, m._window
+    if not (head_partials and m._packed_head is not None):
+        x = ops.add_rmsnorm(h, None if sumsq is not None else delta, w.norm.weight, w.eps)
+        return _head_logits(w.head, x, cols).view(B, n, -1)
+    if sumsq is None:
+        sumsq = ops.residual_sumsq(h, delta)
+    lo, hi = cols if cols is not None else (0, m.vocab_size)
+    lo32, hi32 = (lo // 32) * 32, min(m._head_cols, ((hi + 31) // 32) * 32)
+    kc, tiles, sm = m.HEAD_CFG
+    part = ops.skinny_gemm_cols(h, m._packed_head, m._head_cols, w.hid, kc, lo32, hi32 - lo32, tiles, sm)
+    return ops.HeadOut(part, lo32, n if h.shape[0] > n else 0, h.dtype, row_norm=(sumsq, w.hid, w.eps))
+
+
+def _forward_folded(m, tokens, positions, kv_len, key_start, cols, head_partials, *, f2_kw, fuse_rows):
+    """The window forward with the RMSNorms folded away, for both backbones: the projections run on the residual stream h itself (norm gain inside the
+    packed weight), F1r does the residual add and the per-slice sums of h^2, F2 / F3 / K2 apply the row scale on the partials.  Per layer
+      F1r, G1 q|k|v, F2, K1, G1 o, F1r, G1s (up to fuse_rows rows, where ops.gateup_silu_ok allows) or G1 gate|up + F3, G1 down
+    then the head (_window_head).  f2_kw: F2's keyword arguments per layer."""
+    ops, w, cfg = m._ops, m._window, m.G1_CFG
+    (H, Hkv, D, DS), hid, inter, eps, (B, n) = w.heads, w.hid, w.inter, w.eps, tokens.shape
+    T, h, pos = _window_rows(w, tokens, positions)
+    params = getattr(m.attn, "params", None)
+    g1 = _g1_of(m, T)
+    fuse_mlp = T <= fuse_rows and ops.gateup_silu_ok(T, inter, hid, cfg["gate_up"][0], isinstance(m._packed[0]["gate_up"], ops.PackedZ),
+                                                     getattr(m, "weights", None) is not None)          # (a quantised copy's bf16 twin takes the 8-bit route)
+    delta = None                        # the down projection's split-K planes, summed by the next F1r
+    for li, qn in enumerate(w.qk_norms):
+        rn = (ops.residual_sumsq(h, delta), hid, eps)
+        _chk(f"L{li} sumsq", rn[0][:, :T] if rn[0].dim() == 2 and rn[0].shape[1] >= T else rn[0])
+        qkv = _chk(f"L{li} qkv", g1(h, li, "qkv", (H + 2 * Hkv) * D, hid), T)
+        q = ops.qknorm_rope_append(qkv, m.cache.k[li], m.cache.v[li], *qn, w.inv_freq, pos, B, n, H, Hkv, D, params, kv_len if params is None else 0,
+                                   row_norm=rn, **f2_kw[li])
+        o = _chk(f"L{li} attention", m.attn.attend(li, q, m.cache, kv_len, key_start, **w.attend_kw))
+        rn = (ops.residual_sumsq(h, g1(o.view(T, H * DS), li, "o", hid, H * DS)), hid, eps)
+        if fuse_mlp:       # G1s: gate|up with SiLU * up as its epilogue (one launch, no partial planes, bit-identical to G1 + F3)
+            act = ops.gateup_silu(h, m._packed[li]["gate_up"], inter, hid, cfg["gate_up"][2], row_norm=rn)
+        else:
+            act = ops.silu_mul(g1(h, li, "gate_up", 2 * inter, hid), rows=T, dtype=h.dtype, row_norm=rn)
+        delta = _chk(f"L{li} down", g1(_chk(f"L{li} act", act), li, "down", hid, inter), T)
+        _chk(f"L{li} h", h)
+    return _window_head(m, h, delta, None, B, n, cols, head_partials)
 
 
 class StaticKVCache:
@@ -429,38 +537,24 @@ class LlamaGenBackbone(nn.Module):
                                  + ("(the MXFP4 stream travels in whole ring trips of eight k-steps)" if q4 else "(the e4m3 stream travels in whole record pairs)"))
             dims = LS.llamagen_dims(self.args.dim, self.n_heads, self.head_dim, inter, self.HEAD_PAD if pad100 else None)
             _refuse_quant_copy(f"weights={weights!r}, max_rows={max_rows}: ", g1_cfg, head_cfg or self.HEAD_CFG, dims, max_rows, gran)
-        c = self.G1_CFG = g1_cfg
+        self.G1_CFG = g1_cfg
         if head_cfg is not None:
             self.HEAD_CFG = tuple(head_cfg)
         self.weights = weights
         self._max_rows_given = weights is not None          # (SJDBatchEngine: a quantised copy serves the rows it was packed for)
         self.compress_stats = dict(matrices=0, bytes_raw=0, bytes_packed=0)
-        pack = _packer(ops, weights, False, self.compress_stats)
-        fold = lambda w, g: (w.float() * g.float()[None, :]).to(w.dtype)      # W' = W diag(gamma)
         wo_of = (lambda w: self._pad_o_weight(w, self.n_heads, self.head_dim, self.HEAD_PAD)) if pad100 else (lambda w: w)
-        self._packed, self._fused = [], []
-        with torch.no_grad():
-            for layer in self.layers:
-                a, f = layer.attention, layer.feed_forward
-                gu = torch.cat([f.w1.weight, f.w3.weight], dim=0).contiguous()           # gate | up: F3 / G1s read the gate half first
-                ni = f.w1.weight.shape[0]
-                f.w1.weight.data, f.w3.weight.data = gu[:ni], gu[ni:]
-                self._fused.append(gu)
-                self._packed.append(dict(qkv=pack(fold(a.wqkv.weight, layer.attention_norm.weight), c["qkv"][0], c["qkv"][2]),
-                                         o=pack(wo_of(a.wo.weight), c["o"][0], c["o"][2]),
-                                         gate_up=pack(fold(gu, layer.ffn_norm.weight), c["gate_up"][0], c["gate_up"][2], gateup=2 * c["gate_up"][0] == gu.shape[1]),
-                                         down=pack(f.w2.weight, c["down"][0], c["down"][2])))
-            wf = fold(self.output.weight, self.norm.weight)
-            pad = (-wf.shape[0]) % 32
-            if pad:          # (columns past the vocabulary are never read: K2's rules end at V)
-                wf = torch.cat([wf, wf[-1:].expand(pad, -1)], dim=0)
-            self._head_cols = wf.shape[0]
-            self._packed_head = ops.pack_weight(wf, self.HEAD_CFG[0], self.HEAD_CFG[2])
-            del wf
+        layers = (([b.attention.wqkv], wo_of(b.attention.wo.weight), b.feed_forward.w1, b.feed_forward.w3, b.feed_forward.w2.weight,
+                   b.attention_norm.weight, b.ffn_norm.weight) for b in self.layers)          # (a generator: one padded wo at a time)
+        _pack_fused(self, ops, layers, _packer(ops, weights, False, self.compress_stats), (self.output.weight, self.norm.weight),
+                    lambda w, kc, sm: ops.pack_weight(w, kc, sm))          # (the head is neither quantised nor counted in compress_stats)
         self._ops = ops
         self._fused_rows = self.max_rows = int(max_rows)
         self.supports_head_partials = True
         self._head_pad = self.HEAD_PAD if pad100 else None
+        self._window = _WindowPath((self.n_heads, self.n_kv_heads, self.head_dim, self._head_pad or self.head_dim), self.args.dim, self._fused[0].shape[0] // 2,
+                                   self.args.norm_eps, [(None,) * 4] * self.n_layers, None, dict(head_dim=self.head_dim) if pad100 else {}, self.tok_embeddings,
+                                   self.norm, self.output)
         if pad100 and self.cache is not None and self.cache.k.shape[-1] != self.HEAD_PAD:
             # (a cache set up before this call is head_dim wide: the same cache at the storage width, empty -- either order of the two calls ends 128 wide)
             ck = self.cache.k
@@ -473,38 +567,9 @@ class LlamaGenBackbone(nn.Module):
         return sum(LS.packed_nbytes(w) for d in self._packed for w in d.values()) + LS.packed_nbytes(self._packed_head)
 
     def _forward_window_g1(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
-        ops, B, n = self._ops, tokens.shape[0], tokens.shape[1]
-        T, eps, cfg = B * n, self.args.norm_eps, self.G1_CFG
-        H, Hkv, D, hid = self.n_heads, self.n_kv_heads, self.head_dim, self.args.dim
-        DS = self._head_pad or D                # storage head dim of q, the cache rows and K1's output (128 for a padded head_dim 100)
-        akw = dict(head_dim=D) if DS != D else {}
-        inter = self._fused[0].shape[0] // 2
-        params = getattr(self.attn, "params", None)
-        kv_arg = kv_len if params is None else 0
-        wts = getattr(self, "weights", None)          # (a quantised copy and its twin: 33..64 rows read a chunk G1q / G1q4 can stage, LS.chunk_for_rows)
-        g1 = lambda x_, li, name, N_, K_: ops.skinny_gemm(x_, self._packed[li][name], N_, K_, LS.chunk_for_rows(name, cfg[name], T, K_, wts, self.max_rows),
-                                                          cfg[name][1], cfg[name][2])
-        fuse_mlp = ops.gateup_silu_ok(T, inter, hid, cfg["gate_up"][0], packed_q8=wts is not None)
-        h = self.tok_embeddings(tokens).view(T, -1).contiguous()
-        pos = positions.reshape(T).contiguous()
-        delta = None                        # the down projection's split-K planes, summed by the next F1r
-        for li in range(self.n_layers):
-            kc, vc = self.cache.k[li], self.cache.v[li]
-            rn = (ops.residual_sumsq(h, delta), hid, eps)
-            qkv = g1(h, li, "qkv", (H + 2 * Hkv) * D, hid)
-            q = ops.qknorm_rope_append(qkv, kc, vc, None, None, None, None, None, pos, B, n, H, Hkv, D, params, kv_arg, dtype=h.dtype,
-                                       row_norm=rn, rope_table=self._rope_ext, head_pad=self._head_pad)
-            o = self.attn.attend(li, q, self.cache, kv_len, key_start, **akw)
-            rn = (ops.residual_sumsq(h, g1(o.view(T, H * DS), li, "o", hid, H * DS)), hid, eps)
-            if fuse_mlp:
-                act = ops.gateup_silu(h, self._packed[li]["gate_up"], inter, hid, cfg["gate_up"][2], row_norm=rn)
-            else:
-                act = ops.silu_mul(g1(h, li, "gate_up", 2 * inter, hid), rows=T, dtype=h.dtype, row_norm=rn)
-            delta = g1(act, li, "down", hid, inter)
-        if head_partials:
-            return _head_partials(self, h, delta, cols, n, hid, eps)
-        x = ops.add_rmsnorm(h, delta, self.norm.weight, eps)
-        return _head_logits(self.output, x, cols).view(B, n, -1)
+        """the folded window forward (_forward_folded) with F2's interleaved rotary from the table and, for a padded head_dim 100, K1 told the true head dim"""
+        f2 = dict(dtype=self.tok_embeddings.weight.dtype, rope_table=self._rope_ext, head_pad=self._head_pad)
+        return _forward_folded(self, tokens, positions, kv_len, key_start, cols, head_partials, f2_kw=[f2] * self.n_layers, fuse_rows=LS.WINDOW_MAX_ROWS)
 
 
 # ------------------------------------------------------------------------------------------ Chameleon / Llama
@@ -643,53 +708,10 @@ class ChameleonBackbone(nn.Module):
     G1_CFG_Q4, G1_CFG_EMU3_Q4 = LS.G1_CFG_Q4, LS.G1_CFG_EMU3_Q4
     HEAD_CFG, HEAD_CFG_WIDE, G1_WIDE_TILES = LS.HEAD_CFG, LS.HEAD_CFG_WIDE, LS.WIDE_TILES
 
-    # Weight prefetch plan of the G1 window forward: projection -> (workgroups of the prefetch kernel, when it is issued).  The packed
-    # weights of projection j+1 are read into the Infinity Cache on a side stream (a parallel branch of the forward hipGraph)
-    # "g1": from the moment G1(j) is launched, "after": from the moment G1(j) has finished (i.e. under the latency-bound kernels that
-    # follow it).  0 workgroups = no prefetch.  Tuned end to end on MI355X ("Idle HBM"); override with
-    # SJD_PREFETCH="o:128:after,gate_up:0,..." or model.PREFETCH = {...} before the first forward.
+    # Weight prefetch plan of the G1 window forward (an experiment: backbones_exp.py), projection -> (workgroups of the prefetch kernel, when it is issued).
+    # 0 workgroups = no prefetch; override with SJD_PREFETCH="o:128:after,gate_up:0,..." or model.PREFETCH = {...} before the first forward.
     PREFETCH = dict(qkv=(0, "after"), o=(0, "after"), gate_up=(0, "after"), down=(0, "after"))
-    _PF_NEXT = dict(qkv=("o", 0), o=("gate_up", 0), gate_up=("down", 0), down=("qkv", 1))
-
-    def _prefetch_plan(self):
-        plan = getattr(self, "_pf_plan", None)
-        if plan is None:
-            import os
-            plan = dict(self.PREFETCH)
-            for item in filter(None, os.environ.get("SJD_PREFETCH", "").split(",")):
-                f = item.split(":")
-                plan[f[0]] = (int(f[1]), f[2] if len(f) > 2 else "after")
-            self._pf_plan = plan
-            self._pf_on = any(b > 0 for b, _ in plan.values())
-            self._pf_stream = torch.cuda.Stream(device=self.lm_head.weight.device) if self._pf_on else None
-        return plan
-
-    def _prefetch(self, li, name, when):
-        """issue the prefetch of the projection that FOLLOWS (li, name), if the plan asks for it at this point"""
-        if not self._pf_on:
-            return
-        nxt, dl = self._PF_NEXT[name]
-        blocks, w = self._pf_plan[nxt]
-        if blocks <= 0 or w != when or li + dl >= len(self._packed):
-            return
-        self._pf_stream.wait_stream(torch.cuda.current_stream())          # gate: not before the main branch got here
-        with torch.cuda.stream(self._pf_stream):
-            self._ops.weight_prefetch(self._packed[li + dl][nxt], blocks)
-
-    def _q8_chunk(self, name, T, K_):
-        """split-K chunk of projection `name` for a T-row window of K_ columns (LS.chunk_for_rows); ValueError where none exists"""
-        return LS.chunk_for_rows(name, self.G1_CFG[name], T, K_, getattr(self, "weights", None), getattr(self, "max_rows", 64))
-
-    def _g1(self, li, x_, name, N_, K_):
-        cfg = self.G1_CFG[name]
-        self._prefetch(li, name, "g1")
-        out = self._ops.skinny_gemm(x_, self._packed[li][name], N_, K_, self._q8_chunk(name, x_.shape[0], K_), cfg[1], cfg[2])
-        self._prefetch(li, name, "after")
-        return out
-
-    def _prefetch_join(self):
-        if self._pf_on:
-            torch.cuda.current_stream().wait_stream(self._pf_stream)       # every forked branch rejoins (hipGraph capture needs it)
+    _q8_chunk = _chunk
 
     def _dims(self):
         return LS.chameleon_dims(self.args.hidden_size, self.n_heads, self.n_kv_heads, self.head_dim, self.args.intermediate_size)
@@ -802,45 +824,15 @@ class ChameleonBackbone(nn.Module):
             pack = _packer(ops, weights, compress, self.compress_stats)          # the layer projections: the quantised copy or its twin
             if self.max_rows > 128:          # 129..256 rows: the head runs on kernel G1w, which streams the uncompressed packing
                 pack_head = lambda w, kc, sm: ops.pack_weight(w, kc, sm)
-        self._packed = []
-        self._fused = []
-        with torch.no_grad():
-            for layer in self.model.layers:
-                a, m = layer.self_attn, layer.mlp
-                qkv = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], dim=0).contiguous()
-                nq, nk = a.q_proj.weight.shape[0], a.k_proj.weight.shape[0]
-                a.q_proj.weight.data, a.k_proj.weight.data, a.v_proj.weight.data = qkv[:nq], qkv[nq:nq + nk], qkv[nq + nk:]
-                gu = torch.cat([m.gate_proj.weight, m.up_proj.weight], dim=0).contiguous()
-                ni = m.gate_proj.weight.shape[0]
-                m.gate_proj.weight.data, m.up_proj.weight.data = gu[:ni], gu[ni:]
-                self._fused.append((qkv, gu))
-                if gemm == "sjd":
-                    c = self.G1_CFG
-                    if self._fold_norm:       # W' = W diag(gamma): the norm gain of the projection's input lives in the packed copy
-                        fold = lambda w, g: (w.float() * g.float()[None, :]).to(w.dtype)
-                        qkv_p, gu_p = fold(qkv, layer.input_layernorm.weight), fold(gu, layer.post_attention_layernorm.weight)
-                    else:
-                        qkv_p, gu_p = qkv, gu
-                    self._packed.append(dict(qkv=pack(qkv_p, c["qkv"][0], c["qkv"][2]),
-                                             o=pack(a.o_proj.weight, c["o"][0], c["o"][2]),
-                                             gate_up=pack(gu_p, c["gate_up"][0], c["gate_up"][2], gateup=2 * c["gate_up"][0] == gu_p.shape[1]),
-                                             down=pack(m.down_proj.weight, c["down"][0], c["down"][2])))
-            self._packed_head = None
-            if gemm == "sjd" and self._fold_norm and self.lm_head.bias is None:
-                # output head on G1: ONE packed copy of lm_head with the final norm gain folded in; a launch covers only
-                # the vocabulary columns the grammar allows and K2 reads its split-K partials directly (no fp32 logits tensor)
-                w = self.lm_head.weight
-                wf = (w.float() * self.model.norm.weight.float()[None, :]).to(w.dtype)
-                V, pad = w.shape[0], (-w.shape[0]) % 32
-                if pad:
-                    # the columns past the vocabulary are never read (K2's rules end at V); they are copies of the last real row, not zeros:
-                    # a tile that is half zeros has no eight-exponent window, and the 12-bit packer declined Emu3's whole 184622-row head for
-                    # that ONE tile (round 5: 14 real rows x 2048 weights "out of window" in the last tile, every other unit <= 60)
-                    wf = torch.cat([wf, wf[-1:].expand(pad, -1)], dim=0)
-                self._head_cols = V + pad
-                self._packed_head = pack_head(wf, self.HEAD_CFG[0], self.HEAD_CFG[2])
-                del wf
+        fold, L_ = self._fold_norm, self.model.layers          # (swin-norm, fold_norm=False: the packed copy holds the matrices as they are)
+        layers = (([b.self_attn.q_proj, b.self_attn.k_proj, b.self_attn.v_proj], b.self_attn.o_proj.weight, b.mlp.gate_proj, b.mlp.up_proj, b.mlp.down_proj.weight,
+                   b.input_layernorm.weight if fold else None, b.post_attention_layernorm.weight if fold else None) for b in L_)
+        with_head = gemm == "sjd" and fold and self.lm_head.bias is None
+        _pack_fused(self, ops, layers, pack if gemm == "sjd" else None, (self.lm_head.weight, self.model.norm.weight) if with_head else None, pack_head)
         self._inv_freq32 = self.inv_freq.float().contiguous()
+        qn = [(a.q_norm.weight, a.q_norm.bias, a.k_norm.weight, a.k_norm.bias) if self.args.qk_norm else (None,) * 4 for a in (b.self_attn for b in L_)]
+        self._window = _WindowPath((self.n_heads, self.n_kv_heads, self.head_dim, self.head_dim), self.args.hidden_size, self.args.intermediate_size,
+                                   self.args.rms_norm_eps, qn, self._inv_freq32, {}, self.model.embed_tokens, self.model.norm, self.lm_head)
         self.buffers_version = getattr(self, "buffers_version", 0) + 1          # ... and the packed weights' (engine._check_graph_buffers)
         return self
 
@@ -850,12 +842,6 @@ class ChameleonBackbone(nn.Module):
         return per + (LS.packed_nbytes(self._packed_head) if head and self._packed_head is not None else 0)
 
     supports_head_partials = True
-
-    def _head_partials(self, h, delta, cols, n, sumsq=None):
-        """final residual add + the output head as G1 split-K partials over the column window `cols` -> ops.HeadOut (K2 applies the folded
-        final RMSNorm as a row scale and the 16-bit rounding of the lm_head output while it reads them).  sumsq: the statistics of h when the
-        last down projection already did the residual add (its reducing tail)"""
-        return _head_partials(self, h, delta, cols, n, self.args.hidden_size, self.args.rms_norm_eps, sumsq)
 
     @torch.no_grad()
     def calibrate_kv_scales(self, tokens, positions, key_start, headroom=4.0):
@@ -885,136 +871,76 @@ class ChameleonBackbone(nn.Module):
         self.buffers_version = getattr(self, "buffers_version", 0) + 1      # (captured graphs hold the old scales as kernel arguments)
         return scales
 
-    def _f2(self, qkv, li, qn, pos, B, n, params, kv_len, row_norm=None):
-        """F2 (QK-norm + RoPE + KV append); an fp8 cache gets its rows quantised in the same launch."""
-        ops, H, Hkv, D = self._ops, self.n_heads, self.n_kv_heads, self.head_dim
-        return ops.qknorm_rope_append(qkv, self.cache.k[li], self.cache.v[li], *qn, self._inv_freq32, pos, B, n, H, Hkv, D, params,
-                                      kv_len if params is None else 0, kv_scale=self.attn.scale_of(li) if hasattr(self.attn, "scale_of") else (1.0, 1.0),
-                                      dtype=self.lm_head.weight.dtype, row_norm=row_norm, qk_shards=self.args.model_parallel_size)
+    def _f2_kw(self, li):
+        """F2's keyword arguments for layer li: an fp8 cache gets its rows quantised in the same launch (that layer's scales); the QK-norm shards"""
+        return dict(kv_scale=self.attn.scale_of(li) if hasattr(self.attn, "scale_of") else (1.0, 1.0), dtype=self.lm_head.weight.dtype,
+                    qk_shards=self.args.model_parallel_size)
 
-    def _attention_block(self, qkv_part, li, qn, pos, B, n, params, kv_len, key_start, row_norm=None):
-        """QK-norm + RoPE + KV append + draft-window attention of one layer on the G1 partials of the q|k|v projection: kernel K1F (one
-        launch) for the multi-head 16-row window, F2 then K1 (+ combine) otherwise."""
-        ops, H, Hkv, D = self._ops, self.n_heads, self.n_kv_heads, self.head_dim
-        ks_ok = isinstance(key_start, torch.Tensor) and key_start.is_cuda and key_start.dtype == torch.int32
-        if getattr(self, "k1_fused", _K1_FUSED_DEFAULT) and ks_ok and not self.args.swin_norm and self.args.model_parallel_size == 1 and ops.fused_attention_ok(B, n, H, Hkv, D, self.cache.k.dtype):
-            ns, ws = 1, None
-            if getattr(self, "k1_fused_split", _K1_FUSED_SPLIT_DEFAULT):       # K1Fs: the split form (F2 + k1_partial in one launch, then k1_combine)
-                ns = self.attn._resolve_split(B, Hkv, n, H)
-                ws = self.attn._workspace(B, H, n, D, self.cache.k.device) if ns > 1 else None
-            return ops.qkv_attention_fused(qkv_part, self.cache.k[li], self.cache.v[li], *qn, self._inv_freq32, pos, B, n, H, D, params,
-                                           kv_len if params is None else 0, key_start, row_norm=row_norm, dtype=self.lm_head.weight.dtype,
-                                           n_split=ns, workspace=ws)
-        q = self._f2(qkv_part, li, qn, pos, B, n, params, kv_len, row_norm=row_norm)
-        return self.attn.attend(li, q, self.cache, kv_len, key_start)
+    def _f2(self, qkv, li, qn, pos, B, n, params, kv_len, row_norm=None):
+        """F2 (QK-norm + RoPE + KV append) of the unfolded paths"""
+        return self._ops.qknorm_rope_append(qkv, self.cache.k[li], self.cache.v[li], *qn, self._inv_freq32, pos, B, n, self.n_heads, self.n_kv_heads, self.head_dim,
+                                            params, kv_len if params is None else 0, row_norm=row_norm, **self._f2_kw(li))
+
+    def _f2_k1(self, qkv, li, qn, pos, B, n, params, kv_len, key_start, tag=None):
+        """F2 then K1 (+ combine) of one layer on the q|k|v projection's output"""
+        q = self._f2(qkv, li, qn, pos, B, n, params, kv_len)
+        return self.attn.attend(li, _chk(f"{tag} L{li} q", q) if tag else q, self.cache, kv_len, key_start)
 
     def _forward_window_g1_folded(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
-        """_forward_window_g1 with the RMSNorm folded away: the projections run on the residual stream h itself (norm gain inside
-        the packed weight), F1r does the residual add and the per-slice sums of h^2, F2 / F3 apply the row scale on the partials:
-          F1r, qkv GEMM, F2, K1 partial, K1 combine, o GEMM, F1r, gate|up GEMM, F3, down GEMM   (F1r 3.5 us against F1's 6.1)."""
-        ops, B, n = self._ops, tokens.shape[0], tokens.shape[1]
-        T, eps, cfg = B * n, self.args.rms_norm_eps, self.G1_CFG
-        self._prefetch_plan()
-        g1 = lambda x_, name, N_, K_: self._g1(li, x_, name, N_, K_)
-        H, Hkv, D, hid, inter = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size
+        """the folded window forward (_forward_folded): F2 with the QK-norm and this layer's cache scales, G1s up to 64 rows unless `gateup_fused` is off
+        (65..128-row windows: the four-row-tile G1s is served -- ops.gateup_silu_ok -- but the eight-wave 8-step G1 + F3 measured faster, 4.89 against
+        5.06 ms per step with four prompts, profiles/r3_g1_tiled8.txt).  With an experiment switched on: backbones_exp's forward."""
+        if _experiments_on(self):
+            return _exp().forward_folded(self, tokens, positions, kv_len, key_start, cols, head_partials)
+        return _forward_folded(self, tokens, positions, kv_len, key_start, cols, head_partials, f2_kw=[self._f2_kw(li) for li in range(self.n_layers)],
+                               fuse_rows=64 if getattr(self, "gateup_fused", _GATEUP_FUSED_DEFAULT) else 0)
+
+    def _forward_unfolded(self, tokens, positions, kv_len, key_start, cols, mm, attention, fused_mlp=False, tag=None):
+        """A forward with the norms as launches of their own, the multiplier mm(x, li, name, N, K) given: kernel G1 over the packed copies (split-K partials
+        flow straight into the consuming glue kernel) or the library GEMM.  Pre-norm layers: F1, q|k|v, F2, K1, o, F1, gate|up, F3, down.  Swin-norm: the
+        projection reads h itself and each sublayer ends in ONE F1 launch in its post-norm form (h += norm(sublayer)).  attention: F2 + K1 (_f2_k1);
+        fused_mlp: gate|up + F3 as one launch over the packed copy; tag: the path's name in its SJD_NAN_CHECK stages (None: it has none)."""
+        ops, w, swin = self._ops, self._window, self.args.swin_norm
+        (H, Hkv, D, _), hid, inter, eps, (B, n) = w.heads, w.hid, w.inter, w.eps, tokens.shape
+        T, h, pos = _window_rows(w, tokens, positions)
         params = getattr(self.attn, "params", None)
-        # (65..128-row windows: the four-row-tile G1s is served -- ops.gateup_silu_ok -- but the eight-wave 8-step G1 + F3 measured faster,
-        #  4.89 against 5.06 ms per step with four prompts, profiles/r3_g1_tiled8.txt; `gateup_fused = "tall"` forces the fused kernel there)
-        want_fused = getattr(self, "gateup_fused", _GATEUP_FUSED_DEFAULT)
-        fuse_mlp = want_fused and (T <= 64 or want_fused == "tall") and not self._pf_on and ops.gateup_silu_ok(T, inter, hid, cfg["gate_up"][0],
-                                                                                                                   isinstance(self._packed[0]["gate_up"], ops.PackedZ),
-                                                                                                                   getattr(self, "weights", None) is not None)      # (the bf16 twin takes the 8-bit route)
-        # o / down with F1r as their tail (one launch each; the reducing kernel wants whole 512-column slices per workgroup pair: 8 waves)
-        red = getattr(self, "reduce_fused", _REDUCE_FUSED_DEFAULT) and not self._pf_on
-        raw = lambda name: not isinstance(self._packed[0][name], (ops.PackedZ, ops.PackedQ8, ops.PackedQ4)) and getattr(self, "weights", None) is None        # (the reducing kernel streams the uncompressed packing)
-        h_dev = self.lm_head.weight.device
-        red_o = red and raw("o") and ops.skinny_gemm_reduce_ok(T, hid, H * D, cfg["o"][0], 8, h_dev)
-        red_d = red and raw("down") and ops.skinny_gemm_reduce_ok(T, hid, inter, cfg["down"][0], 8, h_dev)
-        pair_mlp = (getattr(self, "mlp_pair", _MLP_PAIR_DEFAULT) and fuse_mlp and not red_d and h_dev.type == "cuda" and
-                    ops.mlp_pair_ok(T, inter, hid, self._packed[0]["gate_up"], self._packed[0]["down"], cfg["down"][0], cfg["down"][1], h_dev))
-        h = self.model.embed_tokens(tokens).view(T, -1).contiguous()
-        pos = positions.reshape(T).contiguous()
-        delta, ss_next = None, None         # the down projection's split-K planes (summed by the next F1r), or the statistics its tail already wrote
-        for li, layer in enumerate(self.model.layers):
-            a = layer.self_attn
-            rn = (ss_next if ss_next is not None else ops.residual_sumsq(h, delta), hid, eps)
-            qn = (a.q_norm.weight, a.q_norm.bias, a.k_norm.weight, a.k_norm.bias) if self.args.qk_norm else (None,) * 4
-            _chk(f"L{li} sumsq", rn[0][:, :T] if rn[0].dim() == 2 and rn[0].shape[1] >= T else rn[0])
-            o = self._attention_block(_chk(f"L{li} qkv", g1(h, "qkv", (H + 2 * Hkv) * D, hid), T), li, qn, pos, B, n, params, kv_len, key_start, row_norm=rn)
-            _chk(f"L{li} attention", o)
-            if red_o:
-                rn = (ops.skinny_gemm_reduce(o.view(T, H * D), self._packed[li]["o"], hid, H * D, cfg["o"][0], h, 8, cfg["o"][2]), hid, eps)
+        delta = None
+        chk = (lambda stage, x: _chk(f"{tag} L{li} {stage}", x)) if tag else (lambda stage, x: x)
+        for li, (layer, qn) in enumerate(zip(self.model.layers, w.qk_norms)):
+            n1, n2 = layer.input_layernorm.weight, layer.post_attention_layernorm.weight
+            x = h if swin else ops.add_rmsnorm(h, delta, n1, eps)
+            qkv = chk("qkv", mm(x, li, "qkv", (H + 2 * Hkv) * D, hid))
+            o = chk("attention", attention(qkv, li, qn, pos, B, n, params, kv_len, key_start, tag=tag))
+            attn_out = mm(o.view(T, H * D), li, "o", hid, H * D)
+            if swin:           # (the swin-norm order: the norms sit behind the sublayers, h is the next projection's input)
+                x = chk("norm1", ops.add_rmsnorm_post(h, attn_out, n1, eps))
             else:
-                rn = (ops.residual_sumsq(h, g1(o.view(T, H * D), "o", hid, H * D)), hid, eps)
-            if pair_mlp:       # round 4 experiment (SJD_MLP_PAIR=1): gate|up + SiLU * up AND the down projection in one launch
-                if getattr(self, "_pair_ready", None) is None or self._pair_ready.device != h.device:       # this backbone's own arrival counters
-                    self._pair_ready = torch.zeros(max(64, (inter + cfg["down"][0] - 1) // cfg["down"][0] + 1), dtype=torch.int32, device=h.device)
-                _, delta = ops.mlp_pair(h, self._packed[li]["gate_up"], self._packed[li]["down"], inter, hid, cfg["down"][0], row_norm=rn,
-                                        ready=self._pair_ready)
-                ss_next = None
-                continue
-            if fuse_mlp:       # G1s: gate|up with SiLU * up as its epilogue (one launch, no partial planes, bit-identical to G1 + F3)
-                act = ops.gateup_silu(h, self._packed[li]["gate_up"], inter, hid, cfg["gate_up"][2], row_norm=rn)
+                x = chk("norm2", ops.add_rmsnorm(h, attn_out, n2, eps))
+            if fused_mlp:      # (swin-norm on the MXFP4 stream at hidden 8192: the K = 8192 form of G1sq4 over the four-chunk copy; same bits as G1q4 + F3)
+                act = ops.gateup_silu(x, self._packed[li]["gate_up"], inter, hid, self.G1_CFG["gate_up"][2])
             else:
-                act = ops.silu_mul(g1(h, "gate_up", 2 * inter, hid), rows=T, dtype=h.dtype, row_norm=rn)
-            _chk(f"L{li} act", act)
-            if red_d:
-                delta, ss_next = None, ops.skinny_gemm_reduce(act, self._packed[li]["down"], hid, inter, cfg["down"][0], h, 8, cfg["down"][2])
-            else:
-                delta, ss_next = g1(act, "down", hid, inter), None
-            _chk(f"L{li} down", delta, T)
-            _chk(f"L{li} h", h)
-        self._prefetch_join()
-        if head_partials and self._packed_head is not None:
-            return self._head_partials(h, delta, cols, n, sumsq=ss_next)
-        if ss_next is not None:             # (h already holds the last residual add)
-            x = ops.add_rmsnorm(h, None, self.model.norm.weight, eps)
-        else:
-            x = ops.add_rmsnorm(h, delta, self.model.norm.weight, eps)
-        return _head_logits(self.lm_head, x, cols).view(B, n, -1)
+                gu = mm(x, li, "gate_up", 2 * inter, hid)
+                act = ops.silu_mul(gu) if isinstance(gu, torch.Tensor) else ops.silu_mul(gu, rows=T, dtype=h.dtype)          # (split-K planes carry neither)
+            delta = chk("mlp", mm(act, li, "down", hid, inter))
+            if swin:
+                ops.add_rmsnorm_post(h, delta, n2, eps)
+                delta = None
+        return _window_head(self, h, delta, None, B, n, cols, False)
 
     def _forward_window_g1(self, tokens, positions, kv_len, key_start, cols=None):
-        """Window forward (B*n <= 32 rows) with the four per-layer projections on kernel G1; split-K partials flow straight
-        into the consuming glue kernel (F2 / F1 / F3 / F1)."""
-        ops, B, n = self._ops, tokens.shape[0], tokens.shape[1]
-        T, eps, cfg = B * n, self.args.rms_norm_eps, self.G1_CFG
+        """Window forward with the norms unfolded (fold_norm=False, swin-norm backbones) and the four per-layer projections on kernel G1"""
+        ops, T, cfg = self._ops, tokens.shape[0] * tokens.shape[1], self.G1_CFG
         cap = LS.CHUNK_CAP_32ROW if T <= 32 else 1 << 30     # the staged activation chunk of a 32-row window must fit in LDS; taller windows are sub-tiled when it does not
         if any(c[0] > cap for c in cfg.values()):
             raise ValueError(f"G1_CFG chunk sizes must be <= {cap} for a {T}-row window")
-        g1 = lambda x_, name, N_, K_: ops.skinny_gemm(x_, self._packed[li][name], N_, K_, self._q8_chunk(name, T, K_), cfg[name][1], cfg[name][2])
-        H, Hkv, D, hid, inter = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size
-        params = getattr(self.attn, "params", None)
-        h = self.model.embed_tokens(tokens).view(T, -1).contiguous()
-        pos = positions.reshape(T).contiguous()
-        delta = None
-        swin = self.args.swin_norm
-        fused_mlp = bool(swin and getattr(self, "gateup_fused", _SWIN_GATEUP_FUSED_DEFAULT) and isinstance(self._packed[0]["gate_up"], ops.PackedQ4)
-                         and LS.gateup_silu_chunked_ok(T, inter, hid, self._packed[0]["gate_up"].KC))
+        swin, gu = self.args.swin_norm, self._packed[0]["gate_up"]
+        fused_mlp = bool(swin and getattr(self, "gateup_fused", _SWIN_GATEUP_FUSED_DEFAULT) and isinstance(gu, ops.PackedQ4)
+                         and LS.gateup_silu_chunked_ok(T, self.args.intermediate_size, self.args.hidden_size, gu.KC))
         if swin and getattr(self, "weights", None) is not None:
             self.gateup_route[T] = "fused" if fused_mlp else "g1+f3"
-        for li, layer in enumerate(self.model.layers):
-            a = layer.self_attn
-            # swin-norm: the projection reads h itself; each sublayer ends in ONE F1 launch in its post-norm form (h += norm(sublayer))
-            x = h if swin else ops.add_rmsnorm(h, delta, layer.input_layernorm.weight, eps)
-            qkv = g1(x, "qkv", (H + 2 * Hkv) * D, hid)
-            qn = (a.q_norm.weight, a.q_norm.bias, a.k_norm.weight, a.k_norm.bias) if self.args.qk_norm else (None,) * 4
-            o = self._attention_block(qkv, li, qn, pos, B, n, params, kv_len, key_start)
-            attn_out = g1(o.view(T, H * D), "o", hid, H * D)
-            if swin:
-                x = ops.add_rmsnorm_post(h, attn_out, layer.input_layernorm.weight, eps)
-            else:
-                x = ops.add_rmsnorm(h, attn_out, layer.post_attention_layernorm.weight, eps)
-            if fused_mlp:      # (swin-norm on the MXFP4 stream at hidden 8192: the K = 8192 form of G1sq4 over the four-chunk copy; same bits as G1q4 + F3)
-                act = ops.gateup_silu(x, self._packed[li]["gate_up"], inter, hid, cfg["gate_up"][2])
-            else:
-                gu = g1(x, "gate_up", 2 * inter, hid)
-                act = ops.silu_mul(gu, rows=T, dtype=h.dtype)
-            delta = g1(act, "down", hid, inter)
-            if swin:
-                ops.add_rmsnorm_post(h, delta, layer.post_attention_layernorm.weight, eps)
-                delta = None
-        x = ops.add_rmsnorm(h, delta, self.model.norm.weight, eps)
-        return _head_logits(self.lm_head, x, cols).view(B, n, -1)
+        k1f = getattr(self, "k1_fused", _K1_FUSED_DEFAULT)          # (an experiment: one launch for F2 + K1 where kernel K1F serves the shape)
+        attention = (lambda *a, **k: _exp().attention_block(self, *a, **k)) if k1f else self._f2_k1
+        return self._forward_unfolded(tokens, positions, kv_len, key_start, cols, _g1_of(self, T), attention, fused_mlp)
 
     def _forward_window_fused(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
         T_ = tokens.shape[0] * tokens.shape[1]
@@ -1026,8 +952,7 @@ class ChameleonBackbone(nn.Module):
                 raise ValueError(f"weights='e4m3' serves draft windows of at most {no[1]} rows (max_rows={no[1]}); got {T_} rows")
             raise ValueError(f"weights='e4m3' serves draft windows of at most 64 rows (one prompt per forward); got {T_} rows")
         if getattr(self, "weights", None) is not None and self._gemm == "sjd" and 32 < T_ <= 64:          # (refuse before the first launch, not in the middle of a layer)
-            H_, Hkv_, D_, hid_, inter_ = self.n_heads, self.n_kv_heads, self.head_dim, self.args.hidden_size, self.args.intermediate_size
-            for name_, K_ in (("qkv", hid_), ("o", H_ * D_), ("gate_up", hid_), ("down", inter_)):
+            for name_, (_, K_) in self._dims().items():
                 self._q8_chunk(name_, T_, K_)
         # G1 serves windows: <= 64 rows, or <= 256 rows of up to eight prompts' draft windows (n <= 32 rows per batch row; 129..256 rows: round 5, the
         # uncompressed packing on kernel G1w -- G1_CFG_256ROW); longer inputs are prefill
@@ -1035,32 +960,10 @@ class ChameleonBackbone(nn.Module):
             if self._fold_norm:
                 return self._forward_window_g1_folded(tokens, positions, kv_len, key_start, cols, head_partials)
             return self._forward_window_g1(tokens, positions, kv_len, key_start, cols)     # (swin-norm backbones: always here)
-        ops, B, n = self._ops, tokens.shape[0], tokens.shape[1]
-        T, eps = B * n, self.args.rms_norm_eps
-        H, Hkv, D = self.n_heads, self.n_kv_heads, self.head_dim
-        params = getattr(self.attn, "params", None)
-        h = self.model.embed_tokens(tokens).view(T, -1).contiguous()
-        pos = positions.reshape(T).contiguous()
-        delta = None
-        swin = self.args.swin_norm
-        for li, layer in enumerate(self.model.layers):
-            a = layer.self_attn
-            qkv_w, gu_w = self._fused[li]
-            x = h if swin else ops.add_rmsnorm(h, delta, layer.input_layernorm.weight, eps)
-            qkv = F.linear(x, qkv_w)
-            qn = (a.q_norm.weight, a.q_norm.bias, a.k_norm.weight, a.k_norm.bias) if self.args.qk_norm else (None,) * 4
-            q = _chk(f"prefill L{li} q", self._f2(_chk(f"prefill L{li} qkv", qkv), li, qn, pos, B, n, params, kv_len))
-            o = _chk(f"prefill L{li} attention", self.attn.attend(li, q, self.cache, kv_len, key_start))
-            attn_out = F.linear(o.view(T, H * D), a.o_proj.weight)
-            if swin:           # (the swin-norm order: the norms sit behind the sublayers, h is the next projection's input)
-                x = _chk(f"prefill L{li} norm1", ops.add_rmsnorm_post(h, attn_out, layer.input_layernorm.weight, eps))
-                ops.add_rmsnorm_post(h, _chk(f"prefill L{li} mlp", F.linear(ops.silu_mul(F.linear(x, gu_w)), layer.mlp.down_proj.weight)),
-                                     layer.post_attention_layernorm.weight, eps)
-                continue
-            x = _chk(f"prefill L{li} norm2", ops.add_rmsnorm(h, attn_out, layer.post_attention_layernorm.weight, eps))
-            delta = _chk(f"prefill L{li} mlp", F.linear(ops.silu_mul(F.linear(x, gu_w)), layer.mlp.down_proj.weight))
-        x = ops.add_rmsnorm(h, delta, self.model.norm.weight, eps)
-        return _head_logits(self.lm_head, x, cols).view(B, n, -1)
+        def linear(x, li, name, N_, K_):          # the library GEMM over the concatenated matrices and the o / down parameters
+            layer, (qkv_w, gu_w) = self.model.layers[li], self._fused[li]
+            return F.linear(x, dict(qkv=qkv_w, o=layer.self_attn.o_proj.weight, gate_up=gu_w, down=layer.mlp.down_proj.weight)[name])
+        return self._forward_unfolded(tokens, positions, kv_len, key_start, cols, linear, self._f2_k1, tag="prefill")
 
     def forward_window(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
         """cols = (lo, hi): compute the logits of vocabulary columns [lo, hi) only (returned compact, [B, n, hi - lo]).
