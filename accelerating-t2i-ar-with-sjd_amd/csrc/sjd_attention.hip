@@ -1017,14 +1017,22 @@ __global__ __launch_bounds__(64 * K1F_WAVES) void k1f_qkv_attention(
             const float d0 = x0 - mean, d1 = x1 - mean;
             const float var = k1f_wave_sum(d0 * d0 + d1 * d1) / (float)D;
             const float inv = rsqrtf(var + 1e-5f);
-            const float n0 = k1f_round<DT>(d0 * inv), n1 = k1f_round<DT>(d1 * inv);
-            x0 = k1f_round<DT>(k1f_round<DT>(n0 * (x == 0 ? qw0 : kw0)) + (x == 0 ? qb0 : kb0));
-            x1 = k1f_round<DT>(k1f_round<DT>(n1 * (x == 0 ? qw1 : kw1)) + (x == 0 ? qb1 : kb1));
+            {
+#pragma clang fp contract(off)
+                // (as F2, sjd_glue.hip: in fp16 the compiler otherwise demotes dtype(n * gain) + bias to ONE half-precision FMA and the rounding of
+                // the product is gone)
+                const float n0 = k1f_round<DT>(d0 * inv), n1 = k1f_round<DT>(d1 * inv);
+                x0 = k1f_round<DT>(k1f_round<DT>(n0 * (x == 0 ? qw0 : kw0)) + (x == 0 ? qb0 : kb0));
+                x1 = k1f_round<DT>(k1f_round<DT>(n1 * (x == 0 ? qw1 : kw1)) + (x == 0 ? qb1 : kb1));
+            }
         }
-        const float a0 = k1f_round<DT>(x0 * csr[r]), b0 = k1f_round<DT>(-x1 * snr[r]);
-        const float a1 = k1f_round<DT>(x1 * csr[r]), b1 = k1f_round<DT>(x0 * snr[r]);
-        o0 = k1f_bits<DT>(k1f_round<DT>(a0 + b0));
-        o1 = k1f_bits<DT>(k1f_round<DT>(a1 + b1));
+        {
+#pragma clang fp contract(off)
+            const float a0 = k1f_round<DT>(x0 * csr[r]), b0 = k1f_round<DT>(-x1 * snr[r]);
+            const float a1 = k1f_round<DT>(x1 * csr[r]), b1 = k1f_round<DT>(x0 * snr[r]);
+            o0 = k1f_bits<DT>(k1f_round<DT>(a0 + b0));
+            o1 = k1f_bits<DT>(k1f_round<DT>(a1 + b1));
+        }
     };
     if (does_kv && !few) plane_loads(1, kv0, kv1);                               // (more than four planes: k under the q math, v under the k math)
 #pragma unroll

@@ -153,6 +153,9 @@ __global__ __launch_bounds__(256) void f1_add_rmsnorm(unsigned short *__restrict
     const float inv = rsqrtf(tot / (float)hidden + eps);
     nv = 0;
     for (int c = threadIdx.x * 8; c < hidden && nv < MAXV; c += 256 * 8, ++nv) {
+#pragma clang fp contract(off)
+        // (fp16: the compiler otherwise demotes dtype(a * b) + c to ONE half-precision FMA and the documented rounding of the product is gone --
+        // tests/test_gpu_glue_bounds.py)
         float wv[8], o[8];
         unpack8<DT>(*reinterpret_cast<const u32x4 *>(w + c), wv);
 #pragma unroll
@@ -231,6 +234,9 @@ __global__ __launch_bounds__(1024) void f1p_add_rmsnorm(unsigned short *__restri
     const float inv = rsqrtf(tot / (float)hidden + eps);
     ns = 0;
     for (int c = threadIdx.x * 4; c < hidden && ns < MAXS; c += 4096, ++ns) {
+#pragma clang fp contract(off)
+        // (fp16: the compiler otherwise demotes dtype(a * b) + c to ONE half-precision FMA and the documented rounding of the product is gone --
+        // tests/test_gpu_glue_bounds.py)
         const uint2 wv = *reinterpret_cast<const uint2 *>(w + c);
         const float ww[4] = {Cvt<DT>::to_f((unsigned short)(wv.x & 0xffffu)), Cvt<DT>::to_f((unsigned short)(wv.x >> 16)),
                              Cvt<DT>::to_f((unsigned short)(wv.y & 0xffffu)), Cvt<DT>::to_f((unsigned short)(wv.y >> 16))};
@@ -542,7 +548,9 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
         const float var = wave_sum(active ? d0 * d0 + d1 * d1 : 0.f) / (float)D;
         const float inv = rsqrtf(var + 1e-5f);
         if (active) {
-            // F.layer_norm output and the gamma/beta affine both round to the activation dtype in the reference
+#pragma clang fp contract(off)
+            // F.layer_norm output and the gamma/beta affine both round to the activation dtype in the reference (contraction off: in fp16 the
+            // compiler otherwise demotes dtype(n * gain) + bias to ONE half-precision FMA and the rounding of the product is gone)
             const float n0 = Cvt<DT>::to_f(Cvt<DT>::from_f(d0 * inv)), n1 = Cvt<DT>::to_f(Cvt<DT>::from_f(d1 * inv));
             x0 = Cvt<DT>::to_f(Cvt<DT>::from_f(n0 * Cvt<DT>::to_f(nw0))) + Cvt<DT>::to_f(nb0);
             x1 = Cvt<DT>::to_f(Cvt<DT>::from_f(n1 * Cvt<DT>::to_f(nw1))) + Cvt<DT>::to_f(nb1);
@@ -565,6 +573,8 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append(
             if (!active) { dst[2 * lane] = 0; dst[2 * lane + 1] = 0; }      // pad columns D..DS-1 of the q / k row
         }
     } else if (active) {
+#pragma clang fp contract(off)
+        // (each product rounds before the sum: no half-precision FMA in fp16)
         const float ang = (float)posv * ifr;
         float sn, cs;
         sincosf(ang, &sn, &cs);
@@ -733,6 +743,8 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
             const float var = wave_sum(active ? d0 * d0 + d1 * d1 : 0.f) / (float)D;
             const float inv = rsqrtf(var + 1e-5f);
             if (active) {
+#pragma clang fp contract(off)
+                // (as in the one-head kernel: no half-precision FMA over the rounded product)
                 const float n0 = Cvt<DT>::to_f(Cvt<DT>::from_f(d0 * inv)), n1 = Cvt<DT>::to_f(Cvt<DT>::from_f(d1 * inv));
                 float y0 = Cvt<DT>::to_f(Cvt<DT>::from_f(n0 * w0)) + b0;
                 float y1 = Cvt<DT>::to_f(Cvt<DT>::from_f(n1 * w1)) + b1;
@@ -767,6 +779,8 @@ __global__ __launch_bounds__(256) void f2_qknorm_rope_append_rows(
             }
         }
     } else if (active) {
+#pragma clang fp contract(off)
+        // (each product rounds before the sum: no half-precision FMA in fp16)
         const float ang = (float)posv * ifr;
         float sn, cs;
         sincosf(ang, &sn, &cs);
