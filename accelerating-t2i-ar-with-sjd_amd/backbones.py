@@ -721,7 +721,9 @@ class ChameleonBackbone(nn.Module):
         (N, K) -- this backbone's by default.  ValueError names what cannot; nothing is assigned.  (Up to LS.Z_MAX_ROWS rows the head keeps its own kernels.)"""
         _refuse_quant_copy(f"max_rows={max_rows}: ", cfg, head_cfg if max_rows > LS.Z_MAX_ROWS else None, dims or self._dims(), max_rows, 32)
 
-    def enable_fused(self, ops, gemm="torch", fold_norm=True, compress=None, weights=None, max_rows=None, swin_quant=False):
+    released_16bit = False        # enable_fused(..., release_16bit=True) has dropped the 16-bit layer matrices: the packed quantised copy is the only one
+
+    def enable_fused(self, ops, gemm="torch", fold_norm=True, compress=None, weights=None, max_rows=None, swin_quant=False, release_16bit=False):
         """Switch to the fused HIP glue path (F1-F3): q|k|v and gate|up projections become single GEMMs whose weights are
         concatenated once; the original parameters are re-pointed at slices of the fused tensors (state-dict unchanged,
         no extra memory).  gemm="sjd": the window forward (<= 32 rows) also runs its four per-layer projections on the
@@ -768,7 +770,28 @@ class ChameleonBackbone(nn.Module):
         gate|up + SiLU * up as ONE launch over the four-chunk copy when the backbone's `gateup_fused` attribute is set to True (LS.gateup_silu_chunked_ok;
         measured slower than G1q4 + F3 with the untuned launch shapes, so the default is off: profiles/swin30b_quant.json);
         33..64 rows, "e4m3" (which has no fused form at K = 8192: G1q + F3), the "_as_bf16" twins and other widths run G1 + F3 on the same packed copy, so a
-        twin stays token-identical to its stream.  `gateup_route` records, per row count, which of the two the last forward took."""
+        twin stays token-identical to its stream.  `gateup_route` records, per row count, which of the two the last forward took.
+        release_16bit=True (with weights only; opt-in, default False changes nothing): the PREFILL reads the packed copy too -- every input LS.serves_rows calls
+        "prefill", and every input above 64 rows the window kernels were not packed for ("max_rows"), runs the per-layer sequence with kernel G1p
+        (ops.prefill_gemm, any row count) as its multiplier: _forward_prefill_packed.  Prompt rows and window rows then come from ONE model, the quantised
+        one, and after packing the data of every layer's q / k / v / o / gate / up / down parameters is released (the parameters are re-pointed at empty
+        tensors, `_fused` goes; embed_tokens, the norms, the QK-norm gains and lm_head stay): compress_stats["bytes_released"] counts the bytes,
+        `released_16bit` is True.  The "_as_bf16" twins run G1p over the plain packing, bit for bit their stream.  A released backbone refuses, with
+        ValueError: a second enable_fused, the un-fused forward (`_ops` set to None) and state_dict() -- the checkpoint's matrices are gone.  Refused before
+        anything is assigned: release_16bit without weights (the lossless 12-bit stream has no G1p form), gemm != "sjd", a non-bf16 backbone, K or a chunk that
+        is no multiple of 32 (e4m3) / LS.Q4_GRANULE.  G1p's launch shape is UNTUNED and whether it is faster than the library GEMM at a row count is a
+        measurement: README.md."""
+        if self.released_16bit:
+            raise ValueError("enable_fused: this backbone was packed with release_16bit=True -- its 16-bit layer matrices are gone, there is nothing to pack "
+                             "again; load the checkpoint into a new backbone")
+        if release_16bit:
+            if weights is None:
+                raise ValueError("release_16bit=True needs weights='e4m3' / 'mxfp4' (or an '_as_bf16' twin): kernel G1p reads those packed copies; the lossless "
+                                 "12-bit stream has no G1p form, so its prefill keeps the 16-bit matrices")
+            if gemm != "sjd":
+                raise ValueError(f"release_16bit=True needs gemm='sjd' (the packed copies are read by the hand-written projection kernels only), got gemm={gemm!r}")
+            if self.lm_head.weight.dtype != torch.bfloat16:
+                raise ValueError(f"release_16bit=True needs a bf16 backbone (got {self.lm_head.weight.dtype}): the quantised streams and kernel G1p are bf16 only")
         if weights not in (None, "e4m3", "e4m3_as_bf16") + LS.Q4_WEIGHTS:
             raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16', 'mxfp4' or 'mxfp4_as_bf16'")
         q4 = weights in LS.Q4_WEIGHTS
@@ -799,7 +822,7 @@ class ChameleonBackbone(nn.Module):
             # ONE copy serves every row count it is packed for.  A plain e4m3 copy for <= 64 rows is held only to what 32 rows stage: it packs, and a 33..64-row
             # window it cannot read in halved chunks is refused at the forward (_q8_chunk); MXFP4, swin-norm and max_rows > 64 are held to the whole rule
             rows = max_rows or 64
-            reasons = LS.QUANT_REASONS if q4 or swin_q or rows > 64 else ("chunk",)
+            reasons = LS.QUANT_REASONS if q4 or swin_q or rows > 64 else ("granule", "chunk") if release_16bit else ("chunk",)          # (G1p: whole record pairs)
             _refuse_quant_copy(f"weights={weights!r}: " if rows <= 64 else f"weights={weights!r}, max_rows={max_rows}: ", g1_cfg,
                                (head_cfg or self.HEAD_CFG) if rows > LS.Z_MAX_ROWS else None, self._dims(), rows, LS.Q4_GRANULE if q4 else 32, reasons=reasons)
             self.max_rows, self._max_rows_given = int(max_rows) if max_rows is not None else 64, max_rows is not None
@@ -833,8 +856,33 @@ class ChameleonBackbone(nn.Module):
         qn = [(a.q_norm.weight, a.q_norm.bias, a.k_norm.weight, a.k_norm.bias) if self.args.qk_norm else (None,) * 4 for a in (b.self_attn for b in L_)]
         self._window = _WindowPath((self.n_heads, self.n_kv_heads, self.head_dim, self.head_dim), self.args.hidden_size, self.args.intermediate_size,
                                    self.args.rms_norm_eps, qn, self._inv_freq32, {}, self.model.embed_tokens, self.model.norm, self.lm_head)
+        if release_16bit:
+            self._release_16bit()
         self.buffers_version = getattr(self, "buffers_version", 0) + 1          # ... and the packed weights' (engine._check_graph_buffers)
         return self
+
+    def _layer_projections(self):
+        """the seven projection parameters of every layer: what release_16bit=True releases"""
+        for b in self.model.layers:
+            a, m = b.self_attn, b.mlp
+            yield from (a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.o_proj.weight, m.gate_proj.weight, m.up_proj.weight, m.down_proj.weight)
+
+    def _release_16bit(self):
+        """drop the 16-bit layer matrices behind the packed quantised copy: the parameters keep their names and point at empty tensors, `_fused` (the
+        concatenated q|k|v and gate|up matrices they were views of) goes with them"""
+        released = 0
+        for p in self._layer_projections():
+            released += p.numel() * p.element_size()
+            p.data = torch.empty(0, dtype=p.dtype, device=p.device)
+        del self._fused
+        self.compress_stats["bytes_released"] = released
+        self.released_16bit = True
+
+    def state_dict(self, *args, **kwargs):
+        if self.released_16bit:
+            raise ValueError("state_dict(): this backbone was packed with release_16bit=True -- the 16-bit layer matrices are gone and the quantised copy is "
+                             "lossy, so there is no checkpoint to save; save from a backbone that still holds them")
+        return super().state_dict(*args, **kwargs)
 
     def packed_bytes(self, head=True):
         """bytes of packed weights one window forward streams: the four projections of every layer and (head=True) the whole output head"""
@@ -942,9 +990,39 @@ class ChameleonBackbone(nn.Module):
         attention = (lambda *a, **k: _exp().attention_block(self, *a, **k)) if k1f else self._f2_k1
         return self._forward_unfolded(tokens, positions, kv_len, key_start, cols, _g1_of(self, T), attention, fused_mlp)
 
+    def _forward_prefill_packed(self, tokens, positions, kv_len, key_start, cols=None):
+        """The prefill of a backbone packed with release_16bit=True, at any row count: the per-layer sequence F1, q|k|v, F2, K1, o, F1, gate|up, F3, down with
+        kernel G1p (ops.prefill_gemm over self._packed[li], read as packed) as its multiplier -> fp32 logits.  Swin-norm (and fold_norm=False): the copies
+        hold the matrices as they are, the sequence is _forward_unfolded's with its norm launches.  Pre-norm with folded gains: the copies hold W diag(gamma),
+        so the projection runs on the residual stream itself and G1p applies rsqrt(mean h^2 + eps) as its row scale to the fp32 sums -- the window
+        forward's definition (_forward_folded: F2 / F3), so prompt rows and window rows come from the same model."""
+        ops, w = self._ops, self._window
+
+        def g1p(x, li, name, N_, K_, row_scale=None):
+            kc, _, sm = self.G1_CFG[name]
+            return ops.prefill_gemm(x, self._packed[li][name], N_, K_, row_scale, KC=kc, step_major=sm)
+        if not self._fold_norm:
+            return self._forward_unfolded(tokens, positions, kv_len, key_start, cols, g1p, self._f2_k1, tag="prefill")
+        (H, Hkv, D, _), hid, inter, eps, (B, n) = w.heads, w.hid, w.inter, w.eps, tokens.shape
+        T, h, pos = _window_rows(w, tokens, positions)
+        params = getattr(self.attn, "params", None)
+        row_scale = lambda: torch.rsqrt(h.float().square().mean(dim=1) + eps)          # fp32 [T]: the un-gained RMSNorm of the residual stream
+        delta = None
+        for li, qn in enumerate(w.qk_norms):
+            if delta is not None:
+                h += delta
+            qkv = _chk(f"prefill L{li} qkv", g1p(h, li, "qkv", (H + 2 * Hkv) * D, hid, row_scale()))
+            o = _chk(f"prefill L{li} attention", self._f2_k1(qkv, li, qn, pos, B, n, params, kv_len, key_start, tag="prefill"))
+            h += g1p(o.view(T, H * D), li, "o", hid, H * D)
+            act = ops.silu_mul(_chk(f"prefill L{li} gate_up", g1p(h, li, "gate_up", 2 * inter, hid, row_scale())))
+            delta = _chk(f"prefill L{li} down", g1p(act, li, "down", hid, inter))
+        return _window_head(self, h, delta, None, B, n, cols, False)
+
     def _forward_window_fused(self, tokens, positions, kv_len, key_start, cols=None, head_partials=False):
         T_ = tokens.shape[0] * tokens.shape[1]
         no = LS.serves_rows(self, T_, tokens.shape[1])
+        if self.released_16bit and no is not None and (no[0] == "prefill" or T_ > 64):          # (a released copy serves every row count: G1p)
+            return self._forward_prefill_packed(tokens, positions, kv_len, key_start, cols)
         if no is not None and no[0] == "max_rows":          # (an 8-bit copy packed for fewer rows: there is no 16-bit copy to fall back on)
             if getattr(self, "weights", None) in LS.Q4_WEIGHTS:
                 raise ValueError(f"weights={self.weights!r} serves draft windows of at most 64 rows (kernels G1q4 / G1sq4 have no wide form); got {T_} rows")
@@ -971,6 +1049,9 @@ class ChameleonBackbone(nn.Module):
         materialised fp32 logits; paths that cannot (library GEMMs, prefill shapes) return logits as usual."""
         if getattr(self, "_ops", None) is not None:
             return self._forward_window_fused(tokens, positions, kv_len, key_start, cols, head_partials)
+        if self.released_16bit:
+            raise ValueError("the un-fused forward reads the 16-bit layer matrices, which release_16bit=True released: a released backbone runs on the "
+                             "fused HIP path only (`_ops` must stay set)")
         B, n = tokens.shape
         h = self.model.embed_tokens(tokens)
         cos, sin = self._rope(positions, h.dtype)

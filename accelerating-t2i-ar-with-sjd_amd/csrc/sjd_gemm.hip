@@ -1127,6 +1127,7 @@ __device__ __forceinline__ g1z_pair g1z_load(__amdgpu_buffer_rsrc_t wr, unsigned
 #include "sjd_gemm_wide.h"          // (kernel G1w: behind the declarations of the 12-bit decode it shares with G1z)
 #include "sjd_gemm_q8.h"            // (kernels G1q / G1sq: the 8-bit e4m3 stream, SJD_G1_W8_E4M3)
 #include "sjd_gemm_q4.h"            // (kernels G1q4 / G1sq4: the MXFP4 stream, SJD_G1_W4_MXFP4)
+#include "sjd_gemm_prefill.h"       // (kernel G1p: the prefill projection over the same packed copies, any row count)
 
 template <int SP, bool WIDE>
 __global__ __launch_bounds__(512) void g1z_gateup_silu(const unsigned short *__restrict__ x, const unsigned char *__restrict__ wz,
@@ -1964,7 +1965,13 @@ extern "C" int sjd_skinny_gemm_z(const void *x, const void *wz, const void *exc,
 #undef SJD_G1Z_LAUNCH_W
 }
 
-extern "C" int sjd_gemm_num_chunks(int K, int KC) { return (K + KC - 1) / KC; }
+// G1p (csrc/sjd_gemm_prefill.h): y [M, N] = round16(row_scale[m] * x [M, K] @ W^T) over a packed copy, any M >= 1; see include/sjd_hip.h
+extern "C" int sjd_prefill_gemm(const void *x, const void *w_packed, void *y, int M, int N, int K, int KC, int step_major, int dtype,
+                                const float *row_scale, void *stream)
+{
+    if (!x || !w_packed || !y || M < 1) return SJD_ERR_BAD_ARG;
+    return g1p_launch(x, w_packed, y, M, N, K, KC, step_major, dtype, row_scale, (hipStream_t)stream);
+}
 
 // out: fp32 [n_chunks, 32, N] partial products; the consumer sums the chunks.
 template <int DT, int MT>

@@ -47,9 +47,11 @@ class FlexARInferenceSolver:
     bpe_to_vq = None
 
     def __init__(self, model_path=None, precision="bf16", target_size=512, cache_dir=None, device="cpu", tokenizer=None,
-                 model: Optional[BB.ChameleonBackbone] = None, item_processor=None, fused=True, gemm="sjd", vq_model=None, bpe_to_vq=None, weights=None, swin_quant=False):
+                 model: Optional[BB.ChameleonBackbone] = None, item_processor=None, fused=True, gemm="sjd", vq_model=None, bpe_to_vq=None, weights=None, swin_quant=False,
+                 release_16bit=False):
         """weights: passed to ChameleonBackbone.enable_fused ("e4m3": the window projections streamed from 8-bit weights -- lossy; the prompt
-        prefill keeps the 16-bit parameters; see there).  swin_quant=True goes along: a swin-norm backbone (30B class) is quantised too -- lossy and
+        prefill keeps the 16-bit parameters unless release_16bit=True goes along, which runs the prefill on the packed copy as well and releases the 16-bit
+        layer matrices; see there).  swin_quant=True goes along: a swin-norm backbone (30B class) is quantised too -- lossy and
         opt-in, refused without it.
         vq_model: a detokenizers.ChameleonVQ, or a state dict in `vqgan.ckpt` keys (loaded into a full-size ChameleonVQ; the encoder side is
         dropped) -- with it decode_image / decode_ids / generate_ids(decode=True) return PIL images without the reference's item processor.
@@ -64,7 +66,7 @@ class FlexARInferenceSolver:
         if self.model.attn is None and self.device.type == "cuda":
             self.model.attn = ops.HipWindowAttention()
         if fused and self.device.type == "cuda" and self.dtype != torch.float32 and getattr(self.model, "_ops", None) is None:
-            self.model.enable_fused(ops, gemm=gemm, weights=weights, swin_quant=swin_quant)
+            self.model.enable_fused(ops, gemm=gemm, weights=weights, swin_quant=swin_quant, release_16bit=release_16bit)
         if item_processor is None:
             # IS:290-293: in a maintainer's checkout of the reference (`./lumina_mgpt/` on sys.path, test_lumina_mgpt.py:3-5, tokenizer and
             # VQ-GAN files under ./ckpts/) the reference's own item processor is importable -- build it exactly as the reference does, so

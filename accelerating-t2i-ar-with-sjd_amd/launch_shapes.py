@@ -8,6 +8,7 @@ CHUNK_CAP_32ROW = 2560            # columns of an activation chunk a <= 32-row w
 CHUNK_CAP_64ROW = 1280            # the same at 33..64 rows: the staged chunk is twice as tall
 Z_MAX_ROWS = 128                  # the 12-bit stream (G1z / G1sz) serves windows of up to 128 rows
 WINDOW_MAX_ROWS = 256             # the window path (G1, F1-F3) as a whole; above 64 rows a batch row holds at most 32 of them (longer inputs are prefill)
+PREFILL_ROW_BLOCK = 128           # rows of a workgroup of kernel G1p (csrc/sjd_gemm_prefill.h: G1P_ROWS), the prefill projection over the packed copies
 Z_MAX_KC = 4096                   # the 12-bit packer: the k-step of an exception is 7 + 1 bits of its position
 
 # ------------------------------------------------------------------------------------------ Chameleon / Lumina-mGPT / Emu3

@@ -785,6 +785,30 @@ def skinny_gemm(x, w_packed, N, K, KC, waves=4, step_major=False):
     return Partials(out, nc, N)
 
 
+def prefill_gemm(x, w_packed, N, K, row_scale=None, KC=None, step_major=None):
+    """G1p: x [M, K] bf16 (any M >= 1) -> y [M, N] bf16 = round16(row_scale[m] * x @ W^T) over a packed copy as it is packed -- a PackedQ8 / PackedQ4
+    (the chunk and record order they carry) or the plain pack_weight tensor (which carries neither: pass KC and step_major).  row_scale: fp32 [M] or None;
+    it multiplies the finished fp32 sum in front of the one rounding (the folded RMSNorm of F2 / F3).  A workgroup runs LS.PREFILL_ROW_BLOCK rows x the whole
+    of K: no split-K planes.  A quantised copy gives the bits of prefill_gemm on pack_weight(w_packed.dequant(), KC, step_major); a row's output does not
+    depend on M or on its position.  K and KC multiples of LS.Q4_GRANULE (PackedQ4) / 32, N a multiple of 32, bf16: the library refuses the rest before
+    any launch ("unsupported configuration")."""
+    M = x.shape[0]
+    assert x.dim() == 2 and x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N * K
+    flag, data = 0, w_packed
+    if isinstance(w_packed, (PackedQ8, PackedQ4)):
+        assert (w_packed.N, w_packed.K) == (N, K) and KC in (None, w_packed.KC) and step_major in (None, w_packed.step_major)
+        flag, data, KC, step_major = (L.G1_W4_MXFP4 if isinstance(w_packed, PackedQ4) else L.G1_W8_E4M3), w_packed.data, w_packed.KC, w_packed.step_major
+    else:
+        assert isinstance(w_packed, torch.Tensor) and KC is not None and step_major is not None, "a plain packing carries neither its chunk nor its record order"
+    _same_16bit_type(x, w_packed, "prefill_gemm")
+    if row_scale is not None:
+        assert row_scale.dtype == torch.float32 and row_scale.is_contiguous() and row_scale.shape == (M,) and row_scale.device == x.device
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device)
+    L.check(L.load().sjd_prefill_gemm(_ptr(x), _ptr(data), _ptr(y), M, N, K, int(KC), int(step_major), _dtype_code(x.dtype) | flag, _ptr(row_scale), _stream()),
+            "sjd_prefill_gemm")
+    return y
+
+
 _REDUCE_TICKETS = {}
 
 

@@ -417,7 +417,22 @@ int sjd_gateup_silu(const void *x, const void *w_packed, void *y, int M, int I, 
  * SJD_ERR_BAD_ARG otherwise): no limit on KC.  fp16 at 64 < M <= 128 stays on the sub-tiled kernels.  Same
  * chunking and accumulation order as the kernels above: the planes do not depend on which kernel ran (tests/test_gpu_glue.py::test_g1w_*,
  * test_g1_skinny_gemm_*_row_tiles). */
-int sjd_gemm_num_chunks(int K, int KC);
+/* n_chunks of the planes above.  This used to be an exported symbol of libsjd_hip.so; it is now this inline function (the product library holds at
+ * most 45 exports and sjd_prefill_gemm took the slot): code that includes this header compiles and behaves as before, a binary linked against the old
+ * symbol must be rebuilt.  SJD_VERSION did not move with it (as for the SJD_G1_W* bits): a library that has sjd_prefill_gemm is the one without the symbol. */
+static inline int sjd_gemm_num_chunks(int K, int KC) { return (K + KC - 1) / KC; }
+
+/* G1p -- the PREFILL projection over the packed copies of the window kernels, at any row count (csrc/sjd_gemm_prefill.h):
+ *   y[m, n] = round16(row_scale[m] * sum_k x[m, k] * W[n, k])     x [M, K] bf16 contiguous, y [M, N] bf16, M >= 1
+ * w_packed: what sjd_amd.ops.pack_weight (dtype = SJD_DTYPE_BF16), pack_weight_q8 (| SJD_G1_W8_E4M3) or pack_weight_q4 (| SJD_G1_W4_MXFP4) wrote
+ * with the chunk KC and record order step_major -- read as packed (a gate|up copy is KC = K / 2), no second packing.  row_scale: fp32 [M] or NULL
+ * (= 1): it multiplies the finished fp32 sum in front of the one 16-bit rounding, the definition F2 / F3 give the folded RMSNorm.  One workgroup
+ * per block of 128 rows x 4 column tiles runs the whole of K: no split-K planes, no workspace.  Every output element is one fp32 MFMA accumulator
+ * chain over the k-steps in k order from zero: it does not depend on M, on the row's position or on the weight form -- a quantised copy gives the
+ * bits of the plain packing of its dequantised matrix.  bf16 only; N % 32 == 0; K and KC multiples of 128 (MXFP4) / 32 (the other two): anything
+ * else returns SJD_ERR_UNSUPPORTED before any launch (both weight bits, a NULL pointer or M < 1: SJD_ERR_BAD_ARG). */
+int sjd_prefill_gemm(const void *x, const void *w_packed, void *y, int M, int N, int K, int KC, int step_major, int dtype,
+                     const float *row_scale, void *stream);
 
 /* the same over the N = 32 n columns [32 * tile0, 32 * tile0 + N) of a weight packed with N_packed columns (the output head evaluated on
  * the grammar's column window out of ONE packed copy of lm_head): out [n_chunks, R, N] */

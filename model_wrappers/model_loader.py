@@ -32,11 +32,12 @@ def _backbone_from_dir(path, kind):
 
 
 def load_lumina_mgpt(cache_dir="./ckpts", model_name="Alpha-VLLM/Lumina-mGPT-7B-768", target_size=768, seed=1, max_num_new_tokens=16,
-                     multi_token_init_scheme='random', guidance_scale=7.0, device="cpu", model=None, item_processor=None, weights=None, **kwargs):
-    """reference ML:25-60.  weights: ChameleonBackbone.enable_fused's option ("e4m3": the window projections streamed from 8-bit weights)."""
+                     multi_token_init_scheme='random', guidance_scale=7.0, device="cpu", model=None, item_processor=None, weights=None, release_16bit=False, **kwargs):
+    """reference ML:25-60.  weights, release_16bit: ChameleonBackbone.enable_fused's options ("e4m3": the window projections streamed from 8-bit weights;
+    release_16bit=True: the prefill reads that copy too and the 16-bit layer matrices are released)."""
     path = model_name if os.path.isdir(model_name) else os.path.join(cache_dir, model_name)
     inference_solver = FlexARInferenceSolver(model_path=path, precision="bf16", target_size=target_size, cache_dir=cache_dir, device=device,
-                                             model=model, item_processor=item_processor, weights=weights)
+                                             model=model, item_processor=item_processor, weights=weights, release_16bit=release_16bit)
     return renew_pipeline_sampler(inference_solver, jacobi_loop_interval_l=1,
                                   jacobi_loop_interval_r=(target_size // 16) ** 2 + target_size // 16 - 10,
                                   max_num_new_tokens=max_num_new_tokens, guidance_scale=guidance_scale, seed=seed,
@@ -45,8 +46,8 @@ def load_lumina_mgpt(cache_dir="./ckpts", model_name="Alpha-VLLM/Lumina-mGPT-7B-
 
 def load_anole(cache_dir="./ckpts", model_name="leloy/Anole-7b-v0.1-hf", target_size=512, seed=1, max_num_new_tokens=16,
                multi_token_init_scheme='random', guidance_scale=7.0, device="cpu", dtype=torch.bfloat16, image_top_k=2000, text_top_k=10,
-               prefix_token_sampler_scheme='speculative_jacobi', model=None, processor=None, weights=None, **kwargs):
-    """reference ML:62-110 -> dict(processor, model).  `model`: a ChameleonBackbone (HF Chameleon state-dict keys).  weights: enable_fused's option."""
+               prefix_token_sampler_scheme='speculative_jacobi', model=None, processor=None, weights=None, release_16bit=False, **kwargs):
+    """reference ML:62-110 -> dict(processor, model).  `model`: a ChameleonBackbone (HF Chameleon state-dict keys).  weights, release_16bit: enable_fused's options."""
     import sjd_amd.ops as ops
     if model is None:
         path = model_name if os.path.isdir(model_name) else os.path.join(cache_dir, model_name)
@@ -54,7 +55,7 @@ def load_anole(cache_dir="./ckpts", model_name="leloy/Anole-7b-v0.1-hf", target_
     model = model.to(device=device, dtype=dtype).eval()
     if model.attn is None and torch.device(device).type == "cuda":
         model.attn = ops.HipWindowAttention()
-        model.enable_fused(ops, gemm="sjd", weights=weights)
+        model.enable_fused(ops, gemm="sjd", weights=weights, release_16bit=release_16bit)
     if not hasattr(model.model, "image_seq_length"):
         model.model.image_seq_length = getattr(processor, "image_seq_length", (target_size // 16) ** 2)
     model = renew_pipeline_sampler_anhole(model, processor, jacobi_loop_interval_l=1,
@@ -67,8 +68,8 @@ def load_anole(cache_dir="./ckpts", model_name="leloy/Anole-7b-v0.1-hf", target_
 
 def load_emu3(cache_dir="./ckpts", model_name="BAAI/Emu3-Gen", target_size=720, seed=1, max_num_new_tokens=16, multi_token_init_scheme='random',
               guidance_scale=7.0, device="cpu", dtype=torch.bfloat16, image_top_k=2048, text_top_k=10,
-              prefix_token_sampler_scheme='speculative_jacobi', model=None, processor=None, weights=None, **kwargs):
-    """(weights: ChameleonBackbone.enable_fused's option)  reference ML:112-192 -> dict(processor, model, GENERATION_CONFIG, logits_processor).  `processor`: an
+              prefix_token_sampler_scheme='speculative_jacobi', model=None, processor=None, weights=None, release_16bit=False, **kwargs):
+    """(weights, release_16bit: ChameleonBackbone.enable_fused's options)  reference ML:112-192 -> dict(processor, model, GENERATION_CONFIG, logits_processor).  `processor`: an
     emu3.mllm.processing_emu3.Emu3Processor (or anything with build_prefix_constrained_fn(h, w))."""
     from transformers.generation.configuration_utils import GenerationConfig
     import sjd_amd.ops as ops
@@ -80,7 +81,7 @@ def load_emu3(cache_dir="./ckpts", model_name="BAAI/Emu3-Gen", target_size=720, 
     model = model.to(device=device, dtype=dtype).eval()
     if model.attn is None and torch.device(device).type == "cuda":
         model.attn = ops.HipWindowAttention()
-        model.enable_fused(ops, gemm="sjd", weights=weights)
+        model.enable_fused(ops, gemm="sjd", weights=weights, release_16bit=release_16bit)
     cfg = getattr(model, "config", None)
     eos = getattr(cfg, "eos_token_id", None) or processor.build_prefix_constrained_fn(1, 1).eos_token
     pad = getattr(cfg, "pad_token_id", None) or processor.build_prefix_constrained_fn(1, 1).pad_token
