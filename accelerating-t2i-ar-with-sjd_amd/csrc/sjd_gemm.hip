@@ -805,11 +805,7 @@ __global__ __launch_bounds__(512) void g1_gateup_silu(const unsigned short *__re
     // eight slices).  Every thread issues the eight loads -- unconditional, so the waits around them stay exact -- BEHIND the activation
     // and ahead of the weights: they are cache hits and cost the staging nothing (first version: threads 0..31 did this first, +0.7 us).
     float ssv[8];
-    {
-        const float *ssp = row_sumsq ? row_sumsq : reinterpret_cast<const float *>(x);
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) ssv[qq] = ssp[(size_t)(row_sumsq ? min(qq, rs_slices - 1) : 0) * 32 + (threadIdx.x & 31)];
-    }
+    g1s_row_sumsq_load<32>(ssv, x, row_sumsq, rs_slices, 32);
 #pragma unroll
     for (int u = 0; u < G1_UNROLL; ++u) cur[u] = __builtin_nontemporal_load(wu + (size_t)u * rs);      // first weight group right behind
 #pragma unroll
@@ -821,12 +817,7 @@ __global__ __launch_bounds__(512) void g1_gateup_silu(const unsigned short *__re
     // of the restaging barrier, which then took ~4 us with one weight group per wave in flight)
 #pragma unroll
     for (int i = 0; i < NPT; ++i) val[i] = x_load(1, i);
-    if (threadIdx.x < 32) {
-        float tsum = 0.f;                          // sjd_glue.hip row_sumsq_total: one batch of eight in slice order, missing slices add zero
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) tsum += (qq < rs_slices) ? ssv[qq] : 0.f;
-        rsc[threadIdx.x] = row_sumsq ? rsqrtf(__builtin_fmaf(tsum, rs_inv_hidden, rs_eps)) : 1.0f;
-    }
+    g1s_row_scale<32>(rsc, ssv, row_sumsq, rs_slices, rs_inv_hidden, rs_eps);
     __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): nothing pending when the loop is entered (see g1_skinny_gemm)
     SJD_TR(3);
     f32x16 acc;
@@ -874,34 +865,10 @@ __global__ __launch_bounds__(512) void g1_gateup_silu(const unsigned short *__re
     // every thread finishes FOUR outputs: one (activation tile, row, four columns) each -- first version: the two gate waves of K half 0 did
     // all sixteen IEEE divisions per lane and 2-byte stores, 3.6 us.
     __syncthreads();                                              // the activation arena is free
-    constexpr int RP = G1S_RP;
-    float *red = reinterpret_cast<float *>(smem);                 // [8 planes][32 rows][RP]
-    {
-        float *mine = red + (size_t)(kh * 4 + q) * 32 * RP + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mine[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * RP] = acc[r];
-    }
+    float *red = reinterpret_cast<float *>(smem);                 // [8 planes][32 rows][G1S_RP]
+    g1s_plane_store<1>(red, kh * 4 + q, &acc);
     __syncthreads();
-    {
-        const int a = threadIdx.x >> 8, m = (threadIdx.x >> 3) & 31, c4 = (threadIdx.x & 7) * 4;
-        auto plane = [&](int kh_, int q_) { return *reinterpret_cast<const float4 *>(red + ((size_t)(kh_ * 4 + q_) * 32 + m) * RP + c4); };
-        const float4 g0 = plane(0, a), g1 = plane(1, a), u0 = plane(0, 2 + a), u1 = plane(1, 2 + a);
-        const float gs[4] = {g0.x, g0.y, g0.z, g0.w}, gt[4] = {g1.x, g1.y, g1.z, g1.w};
-        const float us_[4] = {u0.x, u0.y, u0.z, u0.w}, ut[4] = {u1.x, u1.y, u1.z, u1.w};
-        const float rr = rsc[m];
-        unsigned short o16[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gsum = 0.f, usum = 0.f;                          // F3: planes summed in chunk order, starting from zero
-            gsum += gs[j]; gsum += gt[j];
-            usum += us_[j]; usum += ut[j];
-            o16[j] = sjd_silu_mul_elem<DT>(gsum, usum, rr);         // sjd_mlp_epilogue.h: the element arithmetic F3 uses, same bits
-        }
-        if (m < M) {
-            uint2 pk{(unsigned)o16[0] | ((unsigned)o16[1] << 16), (unsigned)o16[2] | ((unsigned)o16[3] << 16)};
-            *reinterpret_cast<uint2 *>(y + (size_t)m * I + 32 * (2 * blockIdx.x + a) + c4) = pk;
-        }
-    }
+    g1s_finish<DT, 1, 2>(red, rsc, y, M, I);
     SJD_TR(6);
 }
 
@@ -965,12 +932,7 @@ __global__ __launch_bounds__(512) void g1_gateup_silu_tall(const unsigned short 
     // eight slices).  Every thread issues the eight loads -- unconditional, so the waits around them stay exact -- BEHIND the activation
     // and ahead of the weights: they are cache hits and cost the staging nothing (first version: threads 0..31 did this first, +0.7 us).
     float ssv[8];
-    {
-        const int rs_rows = ((M + 31) / 32) * 32;                 // F1r's slices are [rows padded to 32]: 96 for a 65..96-row window on the four-tile kernel
-        const float *ssp = row_sumsq ? row_sumsq : reinterpret_cast<const float *>(x);
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) ssv[qq] = ssp[(size_t)(row_sumsq ? min(qq, rs_slices - 1) : 0) * rs_rows + min((int)(threadIdx.x & (R - 1)), rs_rows - 1)];
-    }
+    g1s_row_sumsq_load<R>(ssv, x, row_sumsq, rs_slices, ((M + 31) / 32) * 32);      // F1r's slices are [rows padded to 32]: 96 for a 65..96-row window on the four-tile kernel
 #pragma unroll
     for (int u = 0; u < G1_UNROLL; ++u) cur[u] = __builtin_nontemporal_load(wu + (size_t)u * rs);      // first weight group right behind
 #pragma unroll
@@ -981,12 +943,7 @@ __global__ __launch_bounds__(512) void g1_gateup_silu_tall(const unsigned short 
     // the activation of the next phase is requested NOW and travels under the whole of this one
 #pragma unroll
     for (int i = 0; i < NPT; ++i) val[i] = x_load(1, i);
-    if (threadIdx.x < R) {
-        float tsum = 0.f;                          // sjd_glue.hip row_sumsq_total: one batch of eight in slice order, missing slices add zero
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) tsum += (qq < rs_slices) ? ssv[qq] : 0.f;
-        rsc[threadIdx.x] = row_sumsq ? rsqrtf(__builtin_fmaf(tsum, rs_inv_hidden, rs_eps)) : 1.0f;
-    }
+    g1s_row_scale<R>(rsc, ssv, row_sumsq, rs_slices, rs_inv_hidden, rs_eps);
     SJD_TR(3);
     f32x16 acc[MT];
 #pragma unroll
@@ -1029,38 +986,10 @@ __global__ __launch_bounds__(512) void g1_gateup_silu_tall(const unsigned short 
     // ---- epilogue: the eight planes (tile q x K half) go through LDS (row-major, rows padded to 36 floats: conflict-free both ways), then
     // every thread finishes FOUR outputs per row tile: one (activation tile, row, four columns) each -- first version: the two gate waves
     // of K half 0 did all sixteen IEEE divisions per lane and 2-byte stores, 3.6 us.  (the last barrier of the loop freed the arena)
-    constexpr int RP = G1S_RP;
-    float *red = reinterpret_cast<float *>(smem);                 // [8 planes][R rows][RP]
-    {
-        float *mine = red + (size_t)(kh * 4 + q) * R * RP + (lane & 31);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mine[(32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * RP] = acc[mt][r];
-    }
+    float *red = reinterpret_cast<float *>(smem);                 // [8 planes][R rows][G1S_RP]
+    g1s_plane_store<MT>(red, kh * 4 + q, acc);
     __syncthreads();
-#pragma unroll
-    for (int it = 0; it < MT; ++it) {
-        const int idx = it * 512 + (int)threadIdx.x;
-        const int a = idx / (8 * R), m = (idx >> 3) % R, c4 = (idx & 7) * 4;
-        auto plane = [&](int kh_, int q_) { return *reinterpret_cast<const float4 *>(red + ((size_t)(kh_ * 4 + q_) * R + m) * RP + c4); };
-        const float4 g0 = plane(0, a), g1 = plane(1, a), u0 = plane(0, 2 + a), u1 = plane(1, 2 + a);
-        const float gs[4] = {g0.x, g0.y, g0.z, g0.w}, gt[4] = {g1.x, g1.y, g1.z, g1.w};
-        const float us_[4] = {u0.x, u0.y, u0.z, u0.w}, ut[4] = {u1.x, u1.y, u1.z, u1.w};
-        const float rr = rsc[m];
-        unsigned short o16[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gsum = 0.f, usum = 0.f;                          // F3: planes summed in chunk order, starting from zero
-            gsum += gs[j]; gsum += gt[j];
-            usum += us_[j]; usum += ut[j];
-            o16[j] = sjd_silu_mul_elem<DT>(gsum, usum, rr);         // sjd_mlp_epilogue.h: the element arithmetic F3 uses, same bits
-        }
-        if (m < M) {
-            uint2 pk{(unsigned)o16[0] | ((unsigned)o16[1] << 16), (unsigned)o16[2] | ((unsigned)o16[3] << 16)};
-            *reinterpret_cast<uint2 *>(y + (size_t)m * I + 32 * (2 * blockIdx.x + a) + c4) = pk;
-        }
-    }
+    g1s_finish<DT, MT, 2>(red, rsc, y, M, I);
     SJD_TR(6);
 }
 
@@ -1129,6 +1058,7 @@ __device__ __forceinline__ g1z_pair g1z_load(__amdgpu_buffer_rsrc_t wr, unsigned
 #include "sjd_gemm_q4.h"            // (kernels G1q4 / G1sq4: the MXFP4 stream, SJD_G1_W4_MXFP4)
 #include "sjd_gemm_prefill.h"       // (kernel G1p: the prefill projection over the same packed copies, any row count)
 
+// (keeps its own copy of the gate|up tail: with the helpers of sjd_gemm_parts.h the headline decode, whose MLP runs this kernel, missed its timing rule -- DESIGN.md 4.2f)
 template <int SP, bool WIDE>
 __global__ __launch_bounds__(512) void g1z_gateup_silu(const unsigned short *__restrict__ x, const unsigned char *__restrict__ wz,
                                                        const u32x2 *__restrict__ exc, unsigned short *__restrict__ y, int M, int I, int K,
@@ -1343,11 +1273,7 @@ __global__ __launch_bounds__(512) void g1z_gateup_silu_tall(const unsigned short
 #pragma unroll
     for (int i = 0; i < NPT; ++i) val[i] = x_load(0, i);
     float ssv[8];
-    {
-        const float *ssp = row_sumsq ? row_sumsq : reinterpret_cast<const float *>(x);
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) ssv[qq] = ssp[(size_t)(row_sumsq ? min(qq, rs_slices - 1) : 0) * R + (threadIdx.x & (R - 1))];
-    }
+    g1s_row_sumsq_load<R>(ssv, x, row_sumsq, rs_slices, R);
     G1Z_XFIRST_BARRIER();
     const g1z_hraw hraw = g1z_header_load<WIDE>(exc, (size_t)kh * n_tiles + t, lane, exc_cap);
 #pragma unroll
@@ -1359,12 +1285,7 @@ __global__ __launch_bounds__(512) void g1z_gateup_silu_tall(const unsigned short
     SJD_TR(2);
 #pragma unroll
     for (int i = 0; i < NPT; ++i) val[i] = x_load(1, i);
-    if (threadIdx.x < R) {
-        float tsum = 0.f;
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) tsum += (qq < rs_slices) ? ssv[qq] : 0.f;
-        rsc[threadIdx.x] = row_sumsq ? rsqrtf(__builtin_fmaf(tsum, rs_inv_hidden, rs_eps)) : 1.0f;
-    }
+    g1s_row_scale<R>(rsc, ssv, row_sumsq, rs_slices, rs_inv_hidden, rs_eps);
     SJD_TR(3);
     const g1z_hdr hd = g1z_header<WIDE>(hraw, lane, exc_cap);
     f32x16 acc[MT];
@@ -1432,38 +1353,10 @@ __global__ __launch_bounds__(512) void g1z_gateup_silu_tall(const unsigned short
     if constexpr (RAW_HERE) { if (z_raw) { SJD_G1SZ_PHASES(trip_raw) } else { SJD_G1SZ_PHASES(trip) } } else { SJD_G1SZ_PHASES(trip) }
 #undef SJD_G1SZ_PHASES
     SJD_TR(5);
-    constexpr int RP = G1S_RP;
     float *red = reinterpret_cast<float *>(smem);
-    {
-        float *mine = red + (size_t)(kh * 4 + q) * R * RP + (lane & 31);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mine[(32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * RP] = acc[mt][r];
-    }
+    g1s_plane_store<MT>(red, kh * 4 + q, acc);
     __syncthreads();
-#pragma unroll
-    for (int it = 0; it < MT; ++it) {
-        const int idx = it * 512 + (int)threadIdx.x;
-        const int a = idx / (8 * R), m = (idx >> 3) % R, c4 = (idx & 7) * 4;
-        auto plane = [&](int kh_, int q_) { return *reinterpret_cast<const float4 *>(red + ((size_t)(kh_ * 4 + q_) * R + m) * RP + c4); };
-        const float4 g0 = plane(0, a), g1 = plane(1, a), u0 = plane(0, 2 + a), u1 = plane(1, 2 + a);
-        const float gs[4] = {g0.x, g0.y, g0.z, g0.w}, gt[4] = {g1.x, g1.y, g1.z, g1.w};
-        const float us_[4] = {u0.x, u0.y, u0.z, u0.w}, ut[4] = {u1.x, u1.y, u1.z, u1.w};
-        const float rr = rsc[m];
-        unsigned short o16[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gsum = 0.f, usum = 0.f;
-            gsum += gs[j]; gsum += gt[j];
-            usum += us_[j]; usum += ut[j];
-            o16[j] = sjd_silu_mul_elem<DT>(gsum, usum, rr);
-        }
-        if (m < M) {
-            uint2 pk{(unsigned)o16[0] | ((unsigned)o16[1] << 16), (unsigned)o16[2] | ((unsigned)o16[3] << 16)};
-            *reinterpret_cast<uint2 *>(y + (size_t)m * I + 32 * (2 * blockIdx.x + a) + c4) = pk;
-        }
-    }
+    g1s_finish<DT, MT, 2>(red, rsc, y, M, I);
     SJD_TR(6);
 }
 

@@ -218,11 +218,7 @@ __global__ __launch_bounds__(512) void g1q4_gateup_silu(const unsigned short *__
 #pragma unroll
     for (int i = 0; i < NPT; ++i) val[i] = x_load(0, i);
     float ssv[8];
-    {
-        const float *ssp = row_sumsq ? row_sumsq : reinterpret_cast<const float *>(x);
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) ssv[qq] = ssp[(size_t)(row_sumsq ? min(qq, rs_slices - 1) : 0) * 32 + (threadIdx.x & 31)];
-    }
+    g1s_row_sumsq_load<32>(ssv, x, row_sumsq, rs_slices, 32);
 #pragma unroll
     for (int h = 0; h < HT; ++h) {
         ring[2 * h] = w_load(2 * h);
@@ -234,12 +230,7 @@ __global__ __launch_bounds__(512) void g1q4_gateup_silu(const unsigned short *__
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NPT; ++i) val[i] = x_load(1, i);
-    if (threadIdx.x < 32) {
-        float tsum = 0.f;
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) tsum += (qq < rs_slices) ? ssv[qq] : 0.f;
-        rsc[threadIdx.x] = row_sumsq ? rsqrtf(__builtin_fmaf(tsum, rs_inv_hidden, rs_eps)) : 1.0f;
-    }
+    g1s_row_scale<32>(rsc, ssv, row_sumsq, rs_slices, rs_inv_hidden, rs_eps);
     f32x16 acc[1];
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[0][r] = 0.0f;
@@ -264,34 +255,10 @@ __global__ __launch_bounds__(512) void g1q4_gateup_silu(const unsigned short *__
     __syncthreads();
     for (int g = 0; g < SP / D; ++g) trip(g * D, SP + g * D);                 // ---- phase 1
     __syncthreads();
-    constexpr int RP = G1S_RP;
     float *red = reinterpret_cast<float *>(smem);
-    {
-        float *mine = red + (size_t)(kh * 4 + q) * 32 * RP + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mine[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * RP] = acc[0][r];
-    }
+    g1s_plane_store<1>(red, kh * 4 + q, acc);
     __syncthreads();
-    {
-        const int a = threadIdx.x >> 8, m = (threadIdx.x >> 3) & 31, c4 = (threadIdx.x & 7) * 4;
-        auto plane = [&](int kh_, int q_) { return *reinterpret_cast<const float4 *>(red + ((size_t)(kh_ * 4 + q_) * 32 + m) * RP + c4); };
-        const float4 g0 = plane(0, a), g1 = plane(1, a), u0 = plane(0, 2 + a), u1 = plane(1, 2 + a);
-        const float gs[4] = {g0.x, g0.y, g0.z, g0.w}, gt[4] = {g1.x, g1.y, g1.z, g1.w};
-        const float us_[4] = {u0.x, u0.y, u0.z, u0.w}, ut[4] = {u1.x, u1.y, u1.z, u1.w};
-        const float rr = rsc[m];
-        unsigned short o16[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gsum = 0.f, usum = 0.f;                          // F3: planes summed in chunk order, starting from zero
-            gsum += gs[j]; gsum += gt[j];
-            usum += us_[j]; usum += ut[j];
-            o16[j] = sjd_silu_mul_elem<DT>(gsum, usum, rr);
-        }
-        if (m < M) {
-            uint2 pk{(unsigned)o16[0] | ((unsigned)o16[1] << 16), (unsigned)o16[2] | ((unsigned)o16[3] << 16)};
-            *reinterpret_cast<uint2 *>(y + (size_t)m * I + 32 * (2 * blockIdx.x + a) + c4) = pk;
-        }
-    }
+    g1s_finish<DT, 1, 2>(red, rsc, y, M, I);
 }
 
 // G1sq4 at K = 8192 (30B-class hidden): the gate|up weight is the copy G1q4 streams in FOUR chunks of 2048, so F3 would sum four planes and a wave keeps one
@@ -348,11 +315,7 @@ __global__ __launch_bounds__(512) void g1q4_gateup_silu_k4(const unsigned short 
 #pragma unroll
     for (int i = 0; i < NPT; ++i) val[i] = x_load(x, i);
     float ssv[8];
-    {
-        const float *ssp = row_sumsq ? row_sumsq : reinterpret_cast<const float *>(x);
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) ssv[qq] = ssp[(size_t)(row_sumsq ? min(qq, rs_slices - 1) : 0) * 32 + (threadIdx.x & 31)];
-    }
+    g1s_row_sumsq_load<32>(ssv, x, row_sumsq, rs_slices, 32);
     {
         const __amdgpu_buffer_rsrc_t wr = g1z_unit_rsrc(cb, ubytes), sr = g1z_unit_rsrc(sb, usbytes);
 #pragma unroll
@@ -367,12 +330,7 @@ __global__ __launch_bounds__(512) void g1q4_gateup_silu_k4(const unsigned short 
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NPT; ++i) val[i] = x_load(x + 16 * SP, i);
-    if (threadIdx.x < 32) {
-        float tsum = 0.f;
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) tsum += (qq < rs_slices) ? ssv[qq] : 0.f;
-        rsc[threadIdx.x] = row_sumsq ? rsqrtf(__builtin_fmaf(tsum, rs_inv_hidden, rs_eps)) : 1.0f;
-    }
+    g1s_row_scale<32>(rsc, ssv, row_sumsq, rs_slices, rs_inv_hidden, rs_eps);
     f32x16 acc[1], first[1];                                      // the chunk in flight; chunk 2 kh once it is done
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.0f; first[0][r] = 0.0f; }
@@ -422,34 +380,11 @@ __global__ __launch_bounds__(512) void g1q4_gateup_silu_k4(const unsigned short 
         }
     }
     __syncthreads();
-    constexpr int RP = G1S_RP;
-    float *red = reinterpret_cast<float *>(smem);                // sixteen planes: (chunk, q), 32 rows of RP floats each
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        float *mine = red + (size_t)((2 * kh + u) * 4 + q) * 32 * RP + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mine[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * RP] = u == 0 ? first[0][r] : acc[0][r];
-    }
+    float *red = reinterpret_cast<float *>(smem);                // sixteen planes: (chunk, q), 32 rows of G1S_RP floats each
+    g1s_plane_store<1>(red, (2 * kh) * 4 + q, first);
+    g1s_plane_store<1>(red, (2 * kh + 1) * 4 + q, acc);
     __syncthreads();
-    {
-        const int a = threadIdx.x >> 8, m = (threadIdx.x >> 3) & 31, c4 = (threadIdx.x & 7) * 4;
-        auto plane = [&](int c_, int q_) { return *reinterpret_cast<const float4 *>(red + ((size_t)(c_ * 4 + q_) * 32 + m) * RP + c4); };
-        float gsum[4] = {0.f, 0.f, 0.f, 0.f}, usum[4] = {0.f, 0.f, 0.f, 0.f};      // F3: planes summed in chunk order, starting from zero
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float4 g = plane(c, a), u = plane(c, 2 + a);
-            gsum[0] += g.x; gsum[1] += g.y; gsum[2] += g.z; gsum[3] += g.w;
-            usum[0] += u.x; usum[1] += u.y; usum[2] += u.z; usum[3] += u.w;
-        }
-        const float rr = rsc[m];
-        unsigned short o16[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o16[j] = sjd_silu_mul_elem<DT>(gsum[j], usum[j], rr);
-        if (m < M) {
-            uint2 pk{(unsigned)o16[0] | ((unsigned)o16[1] << 16), (unsigned)o16[2] | ((unsigned)o16[3] << 16)};
-            *reinterpret_cast<uint2 *>(y + (size_t)m * I + 32 * (2 * blockIdx.x + a) + c4) = pk;
-        }
-    }
+    g1s_finish<DT, 1, 4>(red, rsc, y, M, I);
 }
 
 // SJD_G1_W4_MXFP4 on sjd_skinny_gemm / sjd_skinny_gemm_cols (which have checked the common arguments): K and KC multiples of 128; M <= 64 with the whole

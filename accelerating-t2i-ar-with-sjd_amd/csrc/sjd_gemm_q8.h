@@ -201,11 +201,7 @@ __global__ __launch_bounds__(512) void g1q_gateup_silu(const unsigned short *__r
 #pragma unroll
     for (int i = 0; i < NPT; ++i) val[i] = x_load(0, i);
     float ssv[8];
-    {
-        const float *ssp = row_sumsq ? row_sumsq : reinterpret_cast<const float *>(x);
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) ssv[qq] = ssp[(size_t)(row_sumsq ? min(qq, rs_slices - 1) : 0) * 32 + (threadIdx.x & 31)];
-    }
+    g1s_row_sumsq_load<32>(ssv, x, row_sumsq, rs_slices, 32);
     const float sc = scales[32 * t + (lane & 31)];
 #pragma unroll
     for (int u = 0; u < DP; ++u) ring[u] = w_load(u);
@@ -214,12 +210,7 @@ __global__ __launch_bounds__(512) void g1q_gateup_silu(const unsigned short *__r
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NPT; ++i) val[i] = x_load(1, i);
-    if (threadIdx.x < 32) {
-        float tsum = 0.f;
-#pragma unroll
-        for (int qq = 0; qq < 8; ++qq) tsum += (qq < rs_slices) ? ssv[qq] : 0.f;
-        rsc[threadIdx.x] = row_sumsq ? rsqrtf(__builtin_fmaf(tsum, rs_inv_hidden, rs_eps)) : 1.0f;
-    }
+    g1s_row_scale<32>(rsc, ssv, row_sumsq, rs_slices, rs_inv_hidden, rs_eps);
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
@@ -248,34 +239,10 @@ __global__ __launch_bounds__(512) void g1q_gateup_silu(const unsigned short *__r
     __syncthreads();
     for (int g = 0; g < SP / TL; ++g) trip(g * TL, SP + g * TL);              // ---- phase 1
     __syncthreads();
-    constexpr int RP = G1S_RP;
     float *red = reinterpret_cast<float *>(smem);
-    {
-        float *mine = red + (size_t)(kh * 4 + q) * 32 * RP + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mine[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * RP] = acc[r];
-    }
+    g1s_plane_store<1>(red, kh * 4 + q, &acc);
     __syncthreads();
-    {
-        const int a = threadIdx.x >> 8, m = (threadIdx.x >> 3) & 31, c4 = (threadIdx.x & 7) * 4;
-        auto plane = [&](int kh_, int q_) { return *reinterpret_cast<const float4 *>(red + ((size_t)(kh_ * 4 + q_) * 32 + m) * RP + c4); };
-        const float4 g0 = plane(0, a), g1 = plane(1, a), u0 = plane(0, 2 + a), u1 = plane(1, 2 + a);
-        const float gs[4] = {g0.x, g0.y, g0.z, g0.w}, gt[4] = {g1.x, g1.y, g1.z, g1.w};
-        const float us_[4] = {u0.x, u0.y, u0.z, u0.w}, ut[4] = {u1.x, u1.y, u1.z, u1.w};
-        const float rr = rsc[m];
-        unsigned short o16[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gsum = 0.f, usum = 0.f;                          // F3: planes summed in chunk order, starting from zero
-            gsum += gs[j]; gsum += gt[j];
-            usum += us_[j]; usum += ut[j];
-            o16[j] = sjd_silu_mul_elem<DT>(gsum, usum, rr);
-        }
-        if (m < M) {
-            uint2 pk{(unsigned)o16[0] | ((unsigned)o16[1] << 16), (unsigned)o16[2] | ((unsigned)o16[3] << 16)};
-            *reinterpret_cast<uint2 *>(y + (size_t)m * I + 32 * (2 * blockIdx.x + a) + c4) = pk;
-        }
-    }
+    g1s_finish<DT, 1, 2>(red, rsc, y, M, I);
 }
 
 // SJD_G1_W8_E4M3 on sjd_skinny_gemm / sjd_skinny_gemm_cols (which have checked the common arguments): M <= 64 with the whole activation chunk in
