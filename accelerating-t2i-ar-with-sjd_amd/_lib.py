@@ -17,6 +17,7 @@ K1_HEAD_DIM_100 = 0x800        # the 16-bit K1 entry points: D = 128 storage wit
 F2_ONE_HEAD = 0x1000           # F2 above 64 rows of split-K planes: one head per wave in place of four (same bits; the parity tests compare them)
 G1_W8_E4M3 = 0x2000            # sjd_skinny_gemm / _cols / sjd_gateup_silu: w_packed is an 8-bit e4m3 stream with its column scales behind it (ops.PackedQ8)
 G1_W4_MXFP4 = 0x4000           # the same three: w_packed is an MXFP4 stream (e2m1 codes, the e8m0 block scales behind them: ops.PackedQ4)
+G1_W6_E2M3 = 0x8000            # the same three: w_packed is a 6-bit stream (e2m3 codes, the e8m0 block scales behind them: ops.PackedQ6)
 QKN_SHARDS_SHIFT = 16
 G1S_CHUNKS_SHIFT = 8           # sjd_gateup_silu's step_major argument: the chunks the weight was packed in above bit 8 (0: the two K halves)
 

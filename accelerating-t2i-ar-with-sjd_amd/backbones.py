@@ -85,15 +85,16 @@ def _head_logits(linear, x, cols):
 
 def _packer(ops, weights, compress, st):
     """pack(w, kc, step_major, gateup=False) of either backbone's enable_fused, counting into its compress_stats `st`.  Under `weights` the quantised copy
-    (ops.pack_weight_q8 / pack_weight_q4) or, for an "_as_bf16" twin, its dequantised values packed uncompressed; else the lossless 12-bit stream where
+    (ops.pack_weight_q8 / pack_weight_q4 / pack_weight_q6) or, for an "_as_bf16" twin, its dequantised values packed uncompressed; else the lossless 12-bit stream where
     `compress` asks for it and ops.pack_weight_z takes the matrix (a declined one is counted, and logged once per reason); else the plain packing."""
-    tag = "q4" if weights in LS.Q4_WEIGHTS else "q8"
+    tag = "q4" if weights in LS.Q4_WEIGHTS else "q6" if weights in LS.Q6_WEIGHTS else "q8"
+    quantise = getattr(ops, "pack_weight_" + tag)
 
     def pack(w, kc, sm, gateup=False):          # gateup: [Wg; Wu] in the two K halves the fused gate|up launch streams
         st["matrices"] += 1
         st["bytes_raw"] += w.numel() * w.element_size()
         if weights is not None:
-            z = (ops.pack_weight_q4 if tag == "q4" else ops.pack_weight_q8)(w, kc, sm, gateup=gateup)
+            z = quantise(w, kc, sm, gateup=gateup)
             st[tag + "_matrices"] = st.get(tag + "_matrices", 0) + 1
             st["rel_rms_error"] = max(st.get("rel_rms_error", 0.0), z.stats["rel_rms_error"])
             if weights.endswith("_as_bf16"):
@@ -749,6 +750,15 @@ class ChameleonBackbone(nn.Module):
                           must be multiples of LS.Q4_GRANULE.  At most 64 window rows: max_rows is None or 64 (there is no wide form).  compress_stats
                           gains q4_matrices, q4_bytes_packed and the format's rel_rms_error.
           "mxfp4_as_bf16" its verification twin: the dequantised values packed uncompressed, the same chunks and the same fused / unfused route.
+          "e2m3"          the same four projections QUANTISED to 6-bit OCP e2m3 codes (three mantissa bits, as e4m3) with one power-of-two (e8m0) scale per
+                          block of 32 weights (ops.quantize_e2m3: the block is an output column x 64-k record x MFMA lane half, NOT 32 consecutive k -- a
+                          private stream format) and streamed at 6.25 bits per weight by kernels G1q6 / G1sq6 (ops.pack_weight_q6).  LOSSY, e4m3's error
+                          class at 78 % of its bytes; what it does to image quality on a real checkpoint has NOT been measured.  Launch shapes: the MXFP4
+                          sets G1_CFG_Q4 / G1_CFG_EMU3_Q4 (UNTUNED for this stream) unless the caller set G1_CFG; K and every chunk must be multiples of
+                          LS.Q4_GRANULE.  At most 64 window rows: max_rows is None or 64.  No swin-norm / model_parallel_size > 1 (with or without
+                          swin_quant) and no release_16bit: the stream has no K = 8192 gate|up form and no prefill kernel -- ValueError before anything is
+                          assigned.  compress_stats gains q6_matrices, q6_bytes_packed and the format's rel_rms_error.
+          "e2m3_as_bf16"  its verification twin: the dequantised values packed uncompressed, the same chunks and the same fused / unfused route.
         Only the window forward (inputs of at most 64 rows) reads the 8-bit copy: the prompt prefill (hipBLASLt on the 16-bit parameters) is
         NOT quantised.  SJD's draft and verify both run the window forward, so the sampler stays exact with respect to ITS model -- and that
         model is the quantised one.  8-bit weights serve bf16 backbones with gemm="sjd", no swin-norm / model_parallel_size > 1, at most 64
@@ -792,11 +802,19 @@ class ChameleonBackbone(nn.Module):
                 raise ValueError(f"release_16bit=True needs gemm='sjd' (the packed copies are read by the hand-written projection kernels only), got gemm={gemm!r}")
             if self.lm_head.weight.dtype != torch.bfloat16:
                 raise ValueError(f"release_16bit=True needs a bf16 backbone (got {self.lm_head.weight.dtype}): the quantised streams and kernel G1p are bf16 only")
-        if weights not in (None, "e4m3", "e4m3_as_bf16") + LS.Q4_WEIGHTS:
-            raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16', 'mxfp4' or 'mxfp4_as_bf16'")
-        q4 = weights in LS.Q4_WEIGHTS
+        if weights not in (None, "e4m3", "e4m3_as_bf16") + LS.Q4_WEIGHTS + LS.Q6_WEIGHTS:
+            raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16', 'mxfp4' or 'mxfp4_as_bf16', 'e2m3' or 'e2m3_as_bf16'")
+        q4, q6 = weights in LS.Q4_WEIGHTS, weights in LS.Q6_WEIGHTS
         if q4 and max_rows not in (None, 64):
             raise ValueError(f"weights={weights!r} serves windows of at most 64 rows (kernels G1q4 / G1sq4 have no wide form): max_rows is None or 64, got {max_rows!r}")
+        if q6:          # (the 6-bit stream: window rows only, folded-norm backbones only)
+            if max_rows not in (None, LS.Q6_MAX_ROWS):
+                raise ValueError(f"weights={weights!r} serves windows of at most {LS.Q6_MAX_ROWS} rows (kernels G1q6 / G1sq6 have no wide form): max_rows is None or "
+                                 f"{LS.Q6_MAX_ROWS}, got {max_rows!r}")
+            if self.args.swin_norm or self.args.model_parallel_size > 1:
+                raise ValueError(f"weights={weights!r} is not served for swin-norm backbones (swin_norm=True or model_parallel_size > 1), with or without swin_quant")
+            if release_16bit:
+                raise ValueError(f"weights={weights!r} has no prefill kernel (G1p reads the e4m3 / MXFP4 copies): release_16bit=True does not go with it")
         if max_rows is not None and weights is None:
             raise ValueError(f"max_rows={max_rows!r} goes with weights='e4m3' / 'e4m3_as_bf16' (without it the packed copy serves the row counts of its G1_CFG)")
         if max_rows not in (None, 64, 128, 256):
@@ -822,9 +840,9 @@ class ChameleonBackbone(nn.Module):
             # ONE copy serves every row count it is packed for.  A plain e4m3 copy for <= 64 rows is held only to what 32 rows stage: it packs, and a 33..64-row
             # window it cannot read in halved chunks is refused at the forward (_q8_chunk); MXFP4, swin-norm and max_rows > 64 are held to the whole rule
             rows = max_rows or 64
-            reasons = LS.QUANT_REASONS if q4 or swin_q or rows > 64 else ("granule", "chunk") if release_16bit else ("chunk",)          # (G1p: whole record pairs)
+            reasons = LS.QUANT_REASONS if q4 or q6 or swin_q or rows > 64 else ("granule", "chunk") if release_16bit else ("chunk",)          # (G1p: whole record pairs)
             _refuse_quant_copy(f"weights={weights!r}: " if rows <= 64 else f"weights={weights!r}, max_rows={max_rows}: ", g1_cfg,
-                               (head_cfg or self.HEAD_CFG) if rows > LS.Z_MAX_ROWS else None, self._dims(), rows, LS.Q4_GRANULE if q4 else 32, reasons=reasons)
+                               (head_cfg or self.HEAD_CFG) if rows > LS.Z_MAX_ROWS else None, self._dims(), rows, LS.Q4_GRANULE if q4 or q6 else 32, reasons=reasons)
             self.max_rows, self._max_rows_given = int(max_rows) if max_rows is not None else 64, max_rows is not None
         else:
             self.__dict__.pop("max_rows", None)
@@ -1026,6 +1044,8 @@ class ChameleonBackbone(nn.Module):
         if no is not None and no[0] == "max_rows":          # (an 8-bit copy packed for fewer rows: there is no 16-bit copy to fall back on)
             if getattr(self, "weights", None) in LS.Q4_WEIGHTS:
                 raise ValueError(f"weights={self.weights!r} serves draft windows of at most 64 rows (kernels G1q4 / G1sq4 have no wide form); got {T_} rows")
+            if getattr(self, "weights", None) in LS.Q6_WEIGHTS:
+                raise ValueError(f"weights={self.weights!r} serves draft windows of at most {LS.Q6_MAX_ROWS} rows (kernels G1q6 / G1sq6 have no wide form); got {T_} rows")
             if no[1] > 64:
                 raise ValueError(f"weights='e4m3' serves draft windows of at most {no[1]} rows (max_rows={no[1]}); got {T_} rows")
             raise ValueError(f"weights='e4m3' serves draft windows of at most 64 rows (one prompt per forward); got {T_} rows")

@@ -1056,6 +1056,14 @@ __device__ __forceinline__ g1z_pair g1z_load(__amdgpu_buffer_rsrc_t wr, unsigned
 #include "sjd_gemm_wide.h"          // (kernel G1w: behind the declarations of the 12-bit decode it shares with G1z)
 #include "sjd_gemm_q8.h"            // (kernels G1q / G1sq: the 8-bit e4m3 stream, SJD_G1_W8_E4M3)
 #include "sjd_gemm_q4.h"            // (kernels G1q4 / G1sq4: the MXFP4 stream, SJD_G1_W4_MXFP4)
+#include "sjd_gemm_q6.h"            // (kernels G1q6 / G1sq6: the 6-bit e2m3 stream, SJD_G1_W6_E2M3)
+
+// more than one weight-stream bit in a call's dtype
+static inline bool g1_two_streams(int dtype)
+{
+    const int b = dtype & (SJD_G1_W8_E4M3 | SJD_G1_W4_MXFP4 | SJD_G1_W6_E2M3);
+    return (b & (b - 1)) != 0;
+}
 #include "sjd_gemm_prefill.h"       // (kernel G1p: the prefill projection over the same packed copies, any row count)
 
 // (keeps its own copy of the gate|up tail: with the helpers of sjd_gemm_parts.h the headline decode, whose MLP runs this kernel, missed its timing rule -- DESIGN.md 4.2f)
@@ -1437,12 +1445,14 @@ extern "C" int sjd_gateup_silu(const void *x, const void *w_packed, void *y, int
     if (row_norm && (!row_norm->sumsq || row_norm->slices < 1 || row_norm->hidden < 1)) return SJD_ERR_BAD_ARG;
     if (row_norm && row_norm->slices > 8) return SJD_ERR_UNSUPPORTED;      // the kernel sums one batch of eight 512-column slices
     if (const int n_chunks = step_major >> SJD_G1S_CHUNKS_SHIFT; n_chunks != 0) {      // the copy sjd_skinny_gemm streams in more than two chunks: one form
-        if ((dtype & SJD_G1_W8_E4M3) && (dtype & SJD_G1_W4_MXFP4)) return SJD_ERR_BAD_ARG;
+        if (g1_two_streams(dtype)) return SJD_ERR_BAD_ARG;
         if (dtype != (SJD_DTYPE_BF16 | SJD_G1_W4_MXFP4) || n_chunks != 4 || K != 8192 || M > 32 || (I % 64) != 0) return SJD_ERR_UNSUPPORTED;
         return g1sq4k4_launch(x, w_packed, y, M, I, step_major & 1, row_norm, (hipStream_t)stream);      // w_packed = ops.pack_weight_q4([Wg; Wu], 2048, step_major)
     }
     if (M > 128 || (I % 64) != 0 || !(K == 512 || K == 1024 || K == 2048 || K == 4096) || (M > 32 && K == 512) || (M > 64 && K != 4096)) return SJD_ERR_UNSUPPORTED;
-    if ((dtype & SJD_G1_W8_E4M3) && (dtype & SJD_G1_W4_MXFP4)) return SJD_ERR_BAD_ARG;          // one weight stream per call
+    if (g1_two_streams(dtype)) return SJD_ERR_BAD_ARG;          // one weight stream per call
+    if (dtype & SJD_G1_W6_E2M3)                                            // w_packed = ops.pack_weight_q6([Wg; Wu], K / 2, step_major, gateup=True): G1sq6
+        return dtype == (SJD_DTYPE_BF16 | SJD_G1_W6_E2M3) ? g1sq6_launch(x, w_packed, y, M, I, K, step_major, row_norm, (hipStream_t)stream) : SJD_ERR_UNSUPPORTED;
     if (dtype & SJD_G1_W4_MXFP4)                                           // w_packed = ops.pack_weight_q4([Wg; Wu], K / 2, step_major, gateup=True): G1sq4
         return dtype == (SJD_DTYPE_BF16 | SJD_G1_W4_MXFP4) ? g1sq4_launch(x, w_packed, y, M, I, K, step_major, row_norm, (hipStream_t)stream) : SJD_ERR_UNSUPPORTED;
     if (dtype & SJD_G1_W8_E4M3)                                            // w_packed = ops.pack_weight_q8([Wg; Wu], K / 2, step_major, gateup=True): G1sq
@@ -1942,7 +1952,10 @@ extern "C" int sjd_skinny_gemm_cols(const void *x, const void *w_packed, float *
     if (!x || !w_packed || !out || M < 1 || M > 256 || N < 32 || (N % 32) != 0 || (N_packed % 32) != 0 || (K % 16) != 0 || KC < 16 || (KC % 16) != 0)
         return SJD_ERR_BAD_ARG;
     if (waves < 1 || waves > 16) return SJD_ERR_BAD_ARG;
-    if ((dtype & SJD_G1_W8_E4M3) && (dtype & SJD_G1_W4_MXFP4)) return SJD_ERR_BAD_ARG;          // one weight stream per call
+    if (g1_two_streams(dtype)) return SJD_ERR_BAD_ARG;          // one weight stream per call
+    if (dtype & SJD_G1_W6_E2M3)                                            // w_packed = ops.pack_weight_q6: G1q6 (csrc/sjd_gemm_q6.h)
+        return dtype == (SJD_DTYPE_BF16 | SJD_G1_W6_E2M3) ? g1q6_launch(x, w_packed, out, M, N, K, KC, waves, step_major, N_packed / 32, tile0, (hipStream_t)stream)
+                                                          : SJD_ERR_UNSUPPORTED;
     if (dtype & SJD_G1_W4_MXFP4)                                           // w_packed = ops.pack_weight_q4: G1q4 (csrc/sjd_gemm_q4.h)
         return dtype == (SJD_DTYPE_BF16 | SJD_G1_W4_MXFP4) ? g1q4_launch(x, w_packed, out, M, N, K, KC, waves, step_major, N_packed / 32, tile0, (hipStream_t)stream)
                                                            : SJD_ERR_UNSUPPORTED;
@@ -1958,7 +1971,10 @@ extern "C" int sjd_skinny_gemm(const void *x, const void *w_packed, float *out, 
 {
     if (!x || !w_packed || !out || M < 1 || M > 256 || (N % 32) != 0 || (K % 16) != 0 || KC < 16 || (KC % 16) != 0) return SJD_ERR_BAD_ARG;
     if (waves < 1 || waves > 16) return SJD_ERR_BAD_ARG;       // (the staged activation chunk must fit in LDS: min(KC, K) <= 2560 / 1280)
-    if ((dtype & SJD_G1_W8_E4M3) && (dtype & SJD_G1_W4_MXFP4)) return SJD_ERR_BAD_ARG;
+    if (g1_two_streams(dtype)) return SJD_ERR_BAD_ARG;
+    if (dtype & SJD_G1_W6_E2M3)
+        return dtype == (SJD_DTYPE_BF16 | SJD_G1_W6_E2M3) ? g1q6_launch(x, w_packed, out, M, N, K, KC, waves, step_major, N / 32, 0, (hipStream_t)stream)
+                                                          : SJD_ERR_UNSUPPORTED;
     if (dtype & SJD_G1_W4_MXFP4)
         return dtype == (SJD_DTYPE_BF16 | SJD_G1_W4_MXFP4) ? g1q4_launch(x, w_packed, out, M, N, K, KC, waves, step_major, N / 32, 0, (hipStream_t)stream)
                                                            : SJD_ERR_UNSUPPORTED;

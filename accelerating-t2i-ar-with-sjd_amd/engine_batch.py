@@ -105,6 +105,11 @@ class SJDBatchEngine(WindowLauncher):
             raise ValueError(f"a backbone packed with enable_fused(weights={backbone.weights!r}) serves at most {LS.Q4_MAX_ROWS} window rows per forward (kernels "
                              f"G1q4 / G1sq4 have no wide form), but n_prompts * n_batch * max_window = {rows}: use fewer prompts per forward, or weights='e4m3' "
                              "with max_rows=128 / 256")
+        # enable_fused(weights="e2m3" / "e2m3_as_bf16"): the 6-bit copy is packed for 64 rows, always (Chameleon-family backbones only)
+        if getattr(backbone, "weights", None) in LS.Q6_WEIGHTS and rows > LS.Q6_MAX_ROWS:
+            raise ValueError(f"a backbone packed with enable_fused(weights={backbone.weights!r}) serves at most {LS.Q6_MAX_ROWS} window rows per forward (kernels "
+                             f"G1q6 / G1sq6 have no wide form), but n_prompts * n_batch * max_window = {rows}: use fewer prompts per forward, or weights='e4m3' "
+                             "with max_rows=128 / 256")
         L.load()                                   # fail loudly if the HIP extension is missing
         if max_window > L.MAX_WINDOW:
             raise ValueError(f"max_window {max_window} > {L.MAX_WINDOW}")

@@ -64,6 +64,10 @@ G1_CFG_EMU3_Q4 = dict(G1_CFG_EMU3_Q8)
 Q4_GRANULE = 128                  # K granule of the MXFP4 stream (ops.pack_weight_q4): K and every chunk are multiples of it
 Q4_WEIGHTS = ("mxfp4", "mxfp4_as_bf16")
 Q4_MAX_ROWS = 64                  # kernels G1q4 / G1sq4 have no wide form
+# the 6-bit e2m3 stream (enable_fused(weights="e2m3"), kernels G1q6 / G1sq6, ops.pack_weight_q6): the MXFP4 stream's granule and its launch-shape sets
+# G1_CFG_Q4 / G1_CFG_EMU3_Q4 -- UNTUNED for this stream too: no launch-shape sweep was run.  Deliberately NOT part of QUANT_WEIGHTS / Q4_WEIGHTS.
+Q6_WEIGHTS = ("e2m3", "e2m3_as_bf16")
+Q6_MAX_ROWS = 64                  # kernels G1q6 / G1sq6 have no wide form
 # 30B-class Chameleon (hidden 8192, intermediate 22016, GQA 64 / 8: q|k|v 10240 columns, gate|up 44032, down K 22016); chunks <= 2560 so that
 # the 32-row window stages its chunk in LDS.  The fastest shapes of `tools/swin30b_bench.py --sweep` at 32 rows on one MI355X
 # (profiles/g1_30b_sweep.jsonl), us per launch uncompressed / 12-bit: q|k|v 30.4 / 25.2, o 23.8 / 20.3, gate|up 120.5 / 98.9, down 62.9 / 50.4
@@ -184,7 +188,7 @@ def default_shapes(dtype, g1_given, head_given, wide_hidden, gqa, compress, weig
     head = head_given or (HEAD_CFG_WIDE if vocab_size >= 131072 else None)
     if weights is not None and wide_hidden:          # (30B class: swin-norm backbones, enable_fused(swin_quant=True); at most 64 rows)
         return g1_given or dict(G1_CFG_30B_Q4 if weights in Q4_WEIGHTS else G1_CFG_30B_Q8), head
-    if weights in Q4_WEIGHTS:
+    if weights in Q4_WEIGHTS + Q6_WEIGHTS:          # (the 6-bit stream runs on the MXFP4 sets)
         return g1_given or dict(G1_CFG_EMU3_Q4 if gqa else G1_CFG_Q4), head
     if weights is not None:
         wide = (G1_CFG_EMU3_Q8_WIDE if gqa else G1_CFG_Q8_WIDE) if (max_rows or 64) > 64 else None
@@ -245,7 +249,7 @@ def serves_rows(backbone, rows, window=1, head=False):
     limit = getattr(backbone, "max_rows", 64) if weights is not None else 64
     if weights == "e4m3" and limit < rows <= WINDOW_MAX_ROWS and window <= 32:
         return "max_rows", limit
-    if weights in Q4_WEIGHTS and rows > Q4_MAX_ROWS:          # (neither the 4-bit copy nor its twin was packed for more: there is no other copy to serve them)
+    if weights in Q4_WEIGHTS + Q6_WEIGHTS and rows > Q4_MAX_ROWS:          # (neither the 4- / 6-bit copy nor its twin was packed for more: there is no other copy to serve them)
         return ("max_rows", Q4_MAX_ROWS) if rows <= WINDOW_MAX_ROWS and window <= 32 else ("prefill", None)
     if getattr(backbone, "_gemm", None) != "sjd" or rows > WINDOW_MAX_ROWS or (rows > 64 and window > 32) or (rows > Z_MAX_ROWS and not packed):
         return "prefill", None

@@ -756,6 +756,162 @@ def pack_weight_q4(weight, KC, step_major=False, gateup=False):
     return PackedQ4(data, N, K, KC, step_major, stats)
 
 
+Q6_MIN_SCALE_EXP = -123     # 0.125 (the smallest non-zero e2m3 magnitude) * 2^-123 = 2^-126: every dequantised value is a NORMAL bf16 number or zero
+Q6_MAX_SCALE_EXP = 125      # 7.5 (the largest) * 2^125 is a finite bf16 number; 7.5 * 2^126 would not be
+
+
+def _q6_block_view(t, K):
+    """[N, K] -> [N, K / 64, 2, 32]: the e2m3 stream's scale blocks (n, record R, lane half h) x element e = 8 u + j, k = 64 R + 16 u + 8 h + j"""
+    return t.reshape(t.shape[0], K // 64, 4, 2, 8).permute(0, 1, 3, 2, 4).reshape(t.shape[0], K // 64, 2, 32)
+
+
+def quantize_e2m3(weight):
+    """[N, K] bf16 weight (K % 64 == 0) -> (codes uint8 [N, K], one 6-bit code per byte in the weight's own order; scale_exp uint8 [N, K / 32]): OCP e2m3
+    elements under one e8m0 scale per block of 32 weights.  THE BLOCK IS NOT 32 CONSECUTIVE k: block (n, R, h) -- scale_exp[n, 2 R + h] -- holds the
+    weights at k = 64 R + 16 u + 8 h + j, u = 0..3, j = 0..7: the 32 values ONE v_cvt_scalef32_pk32_bf16_fp6 of MFMA lane 32 h + r decodes into its B
+    operands of the four k-steps of record R (csrc/sjd_gemm_q6.h).  A private stream format of this library, not an interchange format (not OCP MXFP6).
+    Code: sign << 5 | 2 exponent bits (bias 1) | 3 mantissa bits = sign << 5 | index into {0, 0.125, .., 0.875 (subnormals), 1 .. 1.875 in steps of 0.125,
+    2 .. 3.75 in steps of 0.25, 4 .. 7.5 in steps of 0.5}; no infinity, no NaN.  scale = 2^ceil(log2(amax_block / 7.5)) (1 for an all-zero block; never
+    below 2^-123, so that 0.125 * scale is a normal bf16 number), stored as the byte log2(scale) + 127.  Codes are those of w / scale, round to nearest
+    even.  amax <= 7.5 * scale by construction: nothing saturates.  code * scale is exactly a bf16 number, and |w - code * scale| <= max(scale, |w|) / 16
+    for every element (half a grid step is scale / 16 below 2 and at most |w| / 16 above).  fp16 raises; so does a block whose scale would exceed 2^125."""
+    if weight.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_e2m3: bf16 weights only (got {weight.dtype}): the dequantised values are bf16 numbers, fp16's exponent range does not hold them")
+    if weight.dim() != 2 or weight.shape[1] % 64:
+        raise ValueError("quantize_e2m3: a [N, K] matrix with K a multiple of 64 (a scale block spans the four k-steps of a 64-k record)")
+    w = weight.float()
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("quantize_e2m3: the weight has non-finite values")
+    N, K = w.shape
+    blk = _q6_block_view(w, K)                                    # [n, R, h, e]
+    amax = blk.abs().amax(dim=3)
+    m, e = torch.frexp(amax)                                      # amax = m * 2^e, m in [0.5, 1); 7.5 = 0.9375 * 2^3
+    exp = (e - 3 + (m > 0.9375).to(e.dtype)).clamp(min=Q6_MIN_SCALE_EXP)
+    exp = torch.where(amax > 0, exp, torch.zeros_like(exp))
+    if int(exp.max()) > Q6_MAX_SCALE_EXP:
+        raise ValueError(f"quantize_e2m3: a block needs a scale above 2^{Q6_MAX_SCALE_EXP} (|w| > 7.5 * 2^{Q6_MAX_SCALE_EXP}): code * scale would not be a bf16 number")
+    inv = ((127 - exp).to(torch.int32) << 23).view(torch.float32)          # 1 / scale, built from its exponent bits: exact on every device
+    v = blk.abs() * inv[..., None]                                # exact: a power of two; <= 7.5
+    # the grid's step is 2^-3 below 2, 2^-2 below 4, 2^-1 above; v / step has the parity of the code index on all three, so torch.round's ties-to-even
+    # are the format's (a v just under 2 or 4 rounds up onto the next binade's first code, which both steps hit)
+    sh = (v >= 2).to(torch.float32) + (v >= 4).to(torch.float32)
+    n = torch.round(v * torch.ldexp(torch.full_like(v, 8.0), -sh.to(torch.int32)))          # 0..16 at sh = 0, 8..16 above
+    up = ((n == 16) & (sh < 2)).to(torch.float32)                 # onto the next binade: (16, sh) = (8, sh + 1)
+    n, sh = torch.where(up > 0, torch.full_like(n, 8.0), n), sh + up
+    idx = torch.where(sh == 0, n, n + 8 * sh).to(torch.uint8)     # sh = 1: 16 + (n - 8); sh = 2: 24 + (n - 8)
+    code = idx | (torch.signbit(blk).to(torch.uint8) << 5)
+    codes = code.reshape(N, K // 64, 2, 4, 8).permute(0, 1, 3, 2, 4).reshape(N, K).contiguous()
+    return codes, (exp + 127).to(torch.uint8).reshape(N, K // 32)
+
+
+def dequantize_e2m3(codes, scale_exp):
+    """(codes uint8 [N, K], scale_exp uint8 [N, K / 32]: quantize_e2m3's) -> bf16 [N, K]: code * scale, exactly (a -0 code stays -0)"""
+    N, K = codes.shape
+    i = (codes & 31).long()
+    mag = torch.where(i < 16, i * 0.125, torch.where(i < 24, 2.0 + (i - 16) * 0.25, 4.0 + (i - 24) * 0.5)).to(torch.float32)
+    val = torch.where((codes & 32) != 0, -mag, mag)
+    scale = (scale_exp.to(torch.int32) << 23).view(torch.float32).reshape(N, K // 64, 2)          # the e8m0 byte is the float's exponent field: what the kernels do
+    deq = _q6_block_view(val, K) * scale[..., None]
+    return deq.reshape(N, K // 64, 2, 4, 8).permute(0, 1, 3, 2, 4).reshape(N, K).to(torch.bfloat16)
+
+
+def _q6_pack_bits(c):
+    """uint8 [..., 32] codes of a lane (element e = 8 u + j) -> uint8 [..., 24]: code e in bits [6 e, 6 e + 6) of the 192, little-endian -- the operand
+    order of v_cvt_scalef32_pk32_bf16_fp6 (tests/test_gpu_q6.py's one-hot probe holds the kernels to it)"""
+    g = c.reshape(*c.shape[:-1], 8, 4).to(torch.int32)
+    w24 = g[..., 0] | (g[..., 1] << 6) | (g[..., 2] << 12) | (g[..., 3] << 18)
+    return torch.stack([w24 & 0xFF, (w24 >> 8) & 0xFF, w24 >> 16], dim=-1).to(torch.uint8).reshape(*c.shape[:-1], 24)
+
+
+def _q6_unpack_bits(b):
+    """the inverse of _q6_pack_bits: uint8 [..., 24] -> uint8 [..., 32]"""
+    g = b.reshape(*b.shape[:-1], 8, 3).to(torch.int32)
+    w24 = g[..., 0] | (g[..., 1] << 8) | (g[..., 2] << 16)
+    return torch.stack([w24 & 63, (w24 >> 6) & 63, (w24 >> 12) & 63, w24 >> 18], dim=-1).to(torch.uint8).reshape(*b.shape[:-1], 32)
+
+
+class PackedQ6(_PackedQuant):
+    """A packed weight in the 6-bit (e2m3) stream format of kernels G1q6 / G1sq6 (see pack_weight_q6): `data` uint8 [N * K * 3 / 4 + N * K / 32] = the code
+    records, six bits per weight, then the e8m0 scale bytes at byte offset N * K * 3 / 4.  LOSSY: the kernels multiply by dequant(), exactly."""
+
+    def reads_as(self, KC):
+        """can a launch with split-K chunk KC stream this buffer?  The chunk it was packed with -- or, step-major, any other multiple of the granule:
+        every chunk is then whole records and whole scale groups and the buffer is [record][tile], then [trip][tile], throughout, whatever the chunking"""
+        return KC == self.KC or (self.step_major and self.KC % Q4_GRANULE == 0 and KC % Q4_GRANULE == 0)
+
+    def _chunks(self):
+        return [(k0, min(self.KC, self.K - k0)) for k0 in range(0, self.K, self.KC)]
+
+    def codes(self):
+        """uint8 [N, K]: the e2m3 codes, one per byte as quantize_e2m3 returns them, read back from the packed records (the inverse of pack_weight_q6's
+        permutation)"""
+        N, T = self.N, self.N // 32
+        cols, off = [], 0
+        for _, kc in self._chunks():
+            R = kc // 64
+            blk = self.data[off:off + N * kc * 3 // 4]
+            off += N * kc * 3 // 4
+            rec = blk.reshape(R, T, 1536).permute(1, 0, 2) if self.step_major else blk.reshape(T, R, 1536)
+            lane = torch.cat([rec[..., :1024].reshape(T, R, 64, 16), rec[..., 1024:].reshape(T, R, 64, 8)], dim=-1)      # [t, R, lane = 32 h + r, 24]
+            c = _q6_unpack_bits(lane).reshape(T, R, 2, 32, 4, 8)                                                          # [t, R, h, r, u, j]
+            cols.append(c.permute(0, 3, 1, 4, 2, 5).reshape(N, kc))                                                       # [t, r, R, u, h, j]
+        return torch.cat(cols, dim=1).contiguous()
+
+    def scale_exp(self):
+        """uint8 [N, K / 32]: the e8m0 scale bytes (column 2 R + h: quantize_e2m3's) read back from behind the records"""
+        N, T = self.N, self.N // 32
+        cols, off = [], self.N * self.K * 3 // 4
+        for _, kc in self._chunks():
+            Q = kc // 128
+            blk = self.data[off:off + N * kc // 32]
+            off += N * kc // 32
+            grp = blk.reshape(Q, T, 128).permute(1, 0, 2) if self.step_major else blk.reshape(T, Q, 128)
+            cols.append(grp.reshape(T, Q, 32, 4).permute(0, 2, 1, 3).reshape(N, kc // 32))
+        return torch.cat(cols, dim=1).contiguous()
+
+    def dequant(self):
+        """bf16 [N, K]: the weight the kernels multiply by, read back from the packed buffer (exact: three mantissa bits times a power of two)"""
+        return dequantize_e2m3(self.codes(), self.scale_exp())
+
+
+def pack_weight_q6(weight, KC, step_major=False, gateup=False):
+    """[N, K] bf16 weight -> PackedQ6: quantize_e2m3(weight) in pack_weight(weight, KC, step_major)'s (k-chunk, 32-column tile, k-step, lane, element)
+    order at SIX BITS per weight, then the e8m0 scale bytes at byte offset N * K * 3 / 4 of the same buffer -- what sjd_skinny_gemm /
+    sjd_skinny_gemm_cols / sjd_gateup_silu stream under SJD_G1_W6_E2M3 (kernels G1q6 / G1sq6, csrc/sjd_gemm_q6.h).  N * K * 3 / 4 + N * K / 32 bytes.
+    K granule Q4_GRANULE = 128 (the MXFP4 stream's): K and KC must be multiples of 128 (ValueError otherwise) -- a unit is then whole records and whole
+    scale dwords.  The scale blocks are quantize_e2m3's (column, 64-k record, lane half): a private stream format, not an interchange format.
+    Byte layout: the k-steps of a unit (chunk c, tile t) travel in RECORDS of four -- record R (1536 B) = 64 lanes x 16 B, then 64 lanes x 8 B: bytes
+    0..15 and 16..23 of the lane's 24, which hold its 32 codes (lane l = 32 h + r, element e = 8 u + j = the code of q[32 t + r][k0 + 64 R + 16 u + 8 h + j])
+    in bits [6 e, 6 e + 6), little-endian.  Tile-major: a unit is S * 384 contiguous bytes; step_major: a chunk holds record 0 of every tile, record 1 of
+    every tile, ...  A chunk starts at byte k0 * N * 3 / 4.  Scales: per unit and trip q of two records 128 bytes = 32 columns x 4 bytes (byte 2 i + h: record
+    2 q + i, lane half h), the trips laid out like the records; a chunk's scales start at scale byte k0 * N / 32.
+    gateup=True: `weight` is [Wg; Wu] packed with KC = K / 2 for sjd_gateup_silu.
+    stats: rel_rms_error (RMS of w - dequant over RMS of w), scale_exp_min / scale_exp_max (log2 of the smallest / largest block scale)."""
+    if weight.dim() != 2 or weight.shape[1] % Q4_GRANULE or KC < Q4_GRANULE or KC % Q4_GRANULE:
+        raise ValueError(f"pack_weight_q6: K and KC must be multiples of {Q4_GRANULE} (whole records and scale dwords); got K = {tuple(weight.shape)[-1]}, KC = {KC}")
+    codes, se = quantize_e2m3(weight)
+    N, K = weight.shape
+    assert N % 32 == 0
+    T = N // 32
+    assert not gateup or (2 * KC == K and T % 2 == 0)
+    cparts, sparts = [], []
+    for k0 in range(0, K, KC):
+        kc = min(KC, K - k0)
+        R, Q = kc // 64, kc // 128
+        c = codes[:, k0:k0 + kc].reshape(T, 32, R, 4, 2, 8).permute(0, 2, 4, 1, 3, 5).reshape(T, R, 64, 32)      # [t, r, R, u, h, j] -> [t, R, lane = 32 h + r, e = 8 u + j]
+        b = _q6_pack_bits(c)                                                                                     # [t, R, lane, 24]
+        rec = torch.cat([b[..., :16].reshape(T, R, 1024), b[..., 16:].reshape(T, R, 512)], dim=-1)
+        grp = se[:, k0 // 32:(k0 + kc) // 32].reshape(T, 32, Q, 4).permute(0, 2, 1, 3).reshape(T, Q, 128)
+        if step_major:
+            rec, grp = rec.permute(1, 0, 2), grp.permute(1, 0, 2)
+        cparts.append(rec.reshape(-1))
+        sparts.append(grp.reshape(-1))
+    data = torch.cat(cparts + sparts).contiguous()
+    assert data.numel() == N * K * 3 // 4 + N * K // 32
+    stats = dict(rel_rms_error=_rel_rms_error(weight, dequantize_e2m3(codes, se)), scale_exp_min=int(se.min()) - 127, scale_exp_max=int(se.max()) - 127)
+    return PackedQ6(data, N, K, KC, step_major, stats)
+
+
 def _same_16bit_type(x, w_packed, what):
     """the kernels read the packed records as the activation's type: bf16 rows against fp16 records (or the reverse) would multiply garbage"""
     wd = getattr(w_packed, "dtype", None)
@@ -773,11 +929,12 @@ def skinny_gemm(x, w_packed, N, K, KC, waves=4, step_major=False):
     <= 8 up to 128 rows; above that (bf16 or fp16, uncompressed packing) kernel G1w takes LS.WIDE_TILES.  A PackedQ8 weight (bf16): up to 64 rows on kernel
     G1q (min(KC, K) <= LS.CHUNK_CAP_32ROW up to 32 rows, <= LS.CHUNK_CAP_64ROW above); 65 rows and more on kernel G1wq with LS.WIDE_TILES (not 2 at 65..96
     rows), K and KC multiples of 32 -- the planes of the same call on pack_weight(w_packed.dequant(), KC, step_major), bit for bit.  A PackedQ4 weight
-    (bf16) likewise: up to 64 rows on kernel G1q4 (the same chunk limits), 65 rows and more on kernel G1wq4 with the same tile counts; K and KC multiples of 128."""
+    (bf16) likewise: up to 64 rows on kernel G1q4 (the same chunk limits), 65 rows and more on kernel G1wq4 with the same tile counts; K and KC multiples of 128.
+    A PackedQ6 weight (bf16): up to LS.Q6_MAX_ROWS = 64 rows on kernel G1q6 (the same chunk limits; K and KC multiples of 128), no form for more rows."""
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N * K
     _same_16bit_type(x, w_packed, "skinny_gemm")
-    if isinstance(w_packed, (PackedZ, PackedQ8, PackedQ4)):
+    if isinstance(w_packed, (PackedZ, PackedQ8, PackedQ4, PackedQ6)):
         return skinny_gemm_cols(x, w_packed, N, K, KC, 0, N, waves, step_major)
     nc = (K + KC - 1) // KC
     out = torch.empty(nc, _prows(M), N, dtype=torch.float32, device=x.device)
@@ -793,6 +950,8 @@ def prefill_gemm(x, w_packed, N, K, row_scale=None, KC=None, step_major=None):
     depend on M or on its position.  K and KC multiples of LS.Q4_GRANULE (PackedQ4) / 32, N a multiple of 32, bf16: the library refuses the rest before
     any launch ("unsupported configuration")."""
     M = x.shape[0]
+    if isinstance(w_packed, PackedQ6):
+        raise ValueError("prefill_gemm: the e2m3 stream (PackedQ6) has no prefill kernel; prefill from the 16-bit weights")
     assert x.dim() == 2 and x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N * K
     flag, data = 0, w_packed
     if isinstance(w_packed, (PackedQ8, PackedQ4)):
@@ -853,7 +1012,7 @@ _PREFETCH_SINK = {}
 def weight_prefetch(w_packed, blocks=128, nbytes=None):
     """Read `w_packed` (a G1 packed weight) on the CURRENT stream and discard it: pulls the lines into the Infinity Cache ahead of
     the G1 launch that streams them (call it on a side stream forked from the forward, see ChameleonBackbone._prefetch)."""
-    if isinstance(w_packed, (PackedZ, PackedQ8, PackedQ4)):
+    if isinstance(w_packed, (PackedZ, PackedQ8, PackedQ4, PackedQ6)):
         w_packed = w_packed.data
     dev = w_packed.device
     sink = _PREFETCH_SINK.get(dev)
@@ -952,7 +1111,7 @@ def _raw_units(w_packed, gateup=False):
 def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_major=True):
     """G1 over the vocabulary columns [col0, col0 + n_cols) (32-aligned) of a weight packed with N_packed columns -> Partials [n_chunks, R, n_cols].
     Row counts and `waves` per packing as skinny_gemm (PackedZ: up to LS.Z_MAX_ROWS rows; PackedQ8 / PackedQ4: up to LS.WINDOW_MAX_ROWS, kernels G1q / G1wq
-    and G1q4 / G1wq4)."""
+    and G1q4 / G1wq4; PackedQ6: up to LS.Q6_MAX_ROWS, kernel G1q6)."""
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N_packed * K and col0 % 32 == 0 and n_cols % 32 == 0
     nc = (K + KC - 1) // KC
@@ -972,6 +1131,11 @@ def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_m
         assert (w_packed.N, w_packed.step_major) == (N_packed, bool(step_major)) and w_packed.reads_as(KC)
         L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed.data), _ptr(out), M, n_cols, K, KC, waves, int(step_major),
                                              _dtype_code(x.dtype) | L.G1_W4_MXFP4, N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols (mxfp4 weights)")
+        return Partials(out, nc, n_cols)
+    if isinstance(w_packed, PackedQ6):          # G1q6: the block scales ride behind the records of the same buffer
+        assert (w_packed.N, w_packed.step_major) == (N_packed, bool(step_major)) and w_packed.reads_as(KC)
+        L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed.data), _ptr(out), M, n_cols, K, KC, waves, int(step_major),
+                                             _dtype_code(x.dtype) | L.G1_W6_E2M3, N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols (e2m3 weights)")
         return Partials(out, nc, n_cols)
     L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed), _ptr(out), M, n_cols, K, KC, waves, int(step_major), _dtype_code(x.dtype),
                                          N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols")
@@ -1264,7 +1428,7 @@ def gateup_silu(x, w_packed, inter, hidden, step_major=False, row_norm=None):
     """G1s: silu(r * gate(x)) * (r * up(x)) [T, inter] in ONE launch -- the gate|up projection (w_packed = pack_weight([Wg; Wu], hidden / 2,
     step_major)) with F3 as its epilogue; bit-identical to silu_mul(skinny_gemm(x, w_packed, 2 * inter, hidden, hidden / 2), row_norm=...).
     A PackedQ4 at hidden 8192 packed with KC = 2048 (LS.gateup_silu_chunked_ok: <= 32 rows) runs the four-chunk form: bit-identical to
-    silu_mul(skinny_gemm(x, w_packed, 2 * inter, 8192, 2048), row_norm=...) on the same buffer.  A PackedQ8 has no such form."""
+    silu_mul(skinny_gemm(x, w_packed, 2 * inter, 8192, 2048), row_norm=...) on the same buffer.  A PackedQ8 / PackedQ6 has no such form (PackedQ6: kernel G1sq6, <= 32 rows, hidden in {512, 1024, 2048, 4096})."""
     T = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == hidden and w_packed.numel() == 2 * inter * hidden
     y = torch.empty(T, inter, dtype=x.dtype, device=x.device)
@@ -1289,6 +1453,12 @@ def gateup_silu(x, w_packed, inter, hidden, step_major=False, row_norm=None):
         sm = int(step_major) | (0 if chunks == 2 else chunks << L.G1S_CHUNKS_SHIFT)
         L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed.data), _ptr(y), T, inter, hidden, sm, _dtype_code(x.dtype) | L.G1_W4_MXFP4,
                                         _row_norm(row_norm), _stream()), "sjd_gateup_silu (mxfp4 weights)")
+        return y
+    if isinstance(w_packed, PackedQ6):          # G1sq6
+        _same_16bit_type(x, w_packed, "gateup_silu")
+        assert (w_packed.N, w_packed.KC, w_packed.step_major) == (2 * inter, hidden // 2, bool(step_major))
+        L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed.data), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype) | L.G1_W6_E2M3,
+                                        _row_norm(row_norm), _stream()), "sjd_gateup_silu (e2m3 weights)")
         return y
     L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype),
                                     _row_norm(row_norm), _stream()), "sjd_gateup_silu")

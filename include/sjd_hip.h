@@ -100,7 +100,22 @@ extern "C" {
  *                         {2, 3, 4, 6, 8} (not 2 at 65..96 rows), any KC that is a multiple of 128 -- the same packed buffer, the same bit-for-bit contract.
  *                         Everything else, and every other entry point given the bit, returns SJD_ERR_UNSUPPORTED before any launch; both weight bits
  *                         together return SJD_ERR_BAD_ARG.  SJD_VERSION did not move with it: a library without the bit returns SJD_ERR_UNSUPPORTED
- *                         for it, which is the probe. */
+ *                         for it, which is the probe.
+ *   SJD_G1_W6_E2M3        `w_packed` points at a 6-bit weight stream (sjd_amd.ops.pack_weight_q6; kernels G1q6 / G1sq6, csrc/sjd_gemm_q6.h): N_packed * K * 3 / 4
+ *                         bytes of OCP e2m3 codes (sign, 2 exponent bits of bias 1, 3 mantissa bits: 0 .. 7.5, no infinity, no NaN), then N_packed * K / 32 e8m0
+ *                         scale bytes (scale = 2^(byte - 127)) at byte offset N_packed * K * 3 / 4.  A scale BLOCK is (output column, 64-k record R, lane half
+ *                         h): the 32 weights at k = 64 R + 16 u + 8 h + j, u = 0..3, j = 0..7 -- what ONE v_cvt_scalef32_pk32_bf16_fp6 of a lane decodes into its
+ *                         B operands of four k-steps.  It is NOT 32 consecutive k: a private stream format, not OCP MXFP6 interchange data.  The k-steps of a
+ *                         (k-chunk, 32-column tile) unit travel in 1536-byte records of FOUR k-steps: 64 lanes x 16 bytes (the lane's code dwords 0..3), then
+ *                         64 lanes x 8 bytes (dwords 4, 5); code e = 8 u + j of a lane is bits [6 e, 6 e + 6) of its 192, little-endian; a chunk starts at byte
+ *                         k0 * N_packed * 3 / 4.  Scales: per unit and two records 128 bytes = 32 columns x {record 2q half 0, half 1, record 2q + 1 half 0,
+ *                         half 1}, laid out like MXFP4's.  K granule 128: K and KC must be multiples of 128.  The kernels rebuild the bf16 operand
+ *                         code * scale exactly, so the planes / the 16-bit output are bit for bit what the same call writes for the 16-bit packing of the
+ *                         dequantised weight: the format's loss (e4m3's class: three mantissa bits) is the host-side quantiser's alone.  Valid with
+ *                         SJD_DTYPE_BF16 only; M <= 64 with min(KC, K) <= 2560 (M <= 32) / <= 1280 (sjd_gateup_silu: M <= 32, K in {512, 1024, 2048, 4096}, no
+ *                         SJD_G1S_CHUNKS form).  No 65..256-row form and no prefill form: everything else, and every other entry point given the bit
+ *                         (sjd_prefill_gemm among them), returns SJD_ERR_UNSUPPORTED before any launch; two weight-stream bits together return
+ *                         SJD_ERR_BAD_ARG.  SJD_VERSION did not move with it: a library without the bit returns SJD_ERR_UNSUPPORTED for it, which is the probe. */
 #define SJD_DTYPE_MASK 0xff
 #define SJD_F1_POST_NORM 0x100
 #define SJD_F2_ROPE_TABLE 0x200
@@ -109,6 +124,7 @@ extern "C" {
 #define SJD_F2_ONE_HEAD 0x1000
 #define SJD_G1_W8_E4M3 0x2000
 #define SJD_G1_W4_MXFP4 0x4000
+#define SJD_G1_W6_E2M3 0x8000
 #define SJD_QKN_SHARDS_SHIFT 16
 #define SJD_QKN_SHARDS_MASK (0xff << SJD_QKN_SHARDS_SHIFT)
 #define SJD_QKN_SHARDS(mp) ((int)(mp) << SJD_QKN_SHARDS_SHIFT)

@@ -34,7 +34,7 @@ def _backbone_from_dir(path, kind):
 def load_lumina_mgpt(cache_dir="./ckpts", model_name="Alpha-VLLM/Lumina-mGPT-7B-768", target_size=768, seed=1, max_num_new_tokens=16,
                      multi_token_init_scheme='random', guidance_scale=7.0, device="cpu", model=None, item_processor=None, weights=None, release_16bit=False, **kwargs):
     """reference ML:25-60.  weights, release_16bit: ChameleonBackbone.enable_fused's options ("e4m3": the window projections streamed from 8-bit weights;
-    release_16bit=True: the prefill reads that copy too and the 16-bit layer matrices are released)."""
+    "mxfp4" / "e2m3": from 4.25- / 6.25-bit ones; release_16bit=True (not with "e2m3"): the prefill reads that copy too and the 16-bit layer matrices are released)."""
     path = model_name if os.path.isdir(model_name) else os.path.join(cache_dir, model_name)
     inference_solver = FlexARInferenceSolver(model_path=path, precision="bf16", target_size=target_size, cache_dir=cache_dir, device=device,
                                              model=model, item_processor=item_processor, weights=weights, release_16bit=release_16bit)

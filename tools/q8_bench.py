@@ -19,6 +19,8 @@ median and spread (min .. max over the rounds) per leg.
 
   --mxfp4   adds an MXFP4 leg ("q4": enable_fused(weights="mxfp4"), kernels G1q4 / G1sq4, launch shapes G1_CFG_Q4 / G1_CFG_EMU3_Q4) to --launch and --step:
             the legs then alternate 12-bit / e4m3 / mxfp4 (per launch: bf16 first), and the record compares the mxfp4 leg with the e4m3 leg of the same run.
+  --e2m3    adds a 6-bit e2m3 leg ("q6": enable_fused(weights="e2m3"), kernels G1q6 / G1sq6, the MXFP4 launch shapes -- untuned for this stream) to --launch and
+            --step, between the e4m3 and the mxfp4 leg: 12-bit / e4m3 / e2m3 / mxfp4; the record compares the e2m3 leg with the e4m3 leg of the same run.
 
 One JSON document on stdout (and in --out)."""
 import argparse
@@ -50,7 +52,7 @@ def launch_legs(a, dev, lib):
     C = BB.ChameleonBackbone
     arch = [("lumina7b", 32, dict(qkv=(12288, 4096), o=(4096, 4096), gate_up=(22016, 4096), down=(4096, 11008)), (C.G1_CFG, C.G1_CFG_Z, C.G1_CFG_Q8, C.G1_CFG_Q4)),
             ("emu3_8b", 64, dict(qkv=(6144, 4096), o=(4096, 4096), gate_up=(28672, 4096), down=(4096, 14336)), (C.G1_CFG_EMU3, C.G1_CFG_EMU3_Z, C.G1_CFG_EMU3_Q8, C.G1_CFG_EMU3_Q4))]
-    tags = ("bf16", "z12", "q8") + (("q4",) if a.mxfp4 else ())
+    tags = ("bf16", "z12", "q8") + (("q6",) if a.e2m3 else ()) + (("q4",) if a.mxfp4 else ())
     out = []
     for model, rows, shapes, cfgs in arch:
         for name, (N, K) in shapes.items():
@@ -59,8 +61,8 @@ def launch_legs(a, dev, lib):
             x = torch.randn(rows, K, device=dev).to(torch.bfloat16)
             ws = [(torch.randn(N, K, device=dev) / K ** 0.5).to(torch.bfloat16) for _ in range(a.copies)]
             legs = {}
-            for tag, cfg in zip(tags, cfgs):
-                KC, waves, sm = cfg[name]
+            for tag in tags:
+                KC, waves, sm = cfgs[dict(bf16=0, z12=1, q8=2, q6=3, q4=3)[tag]][name]          # (the 6-bit stream runs on the MXFP4 sets)
                 gu = name == "gate_up" and 2 * KC == K
                 if tag == "bf16":
                     pk = [ops.pack_weight(w, KC, sm) for w in ws]
@@ -72,9 +74,9 @@ def launch_legs(a, dev, lib):
                     pk = [ops.pack_weight_q8(w, KC, sm, gateup=gu) for w in ws]
                     stored = pk[0].nbytes()
                 else:
-                    pk = [ops.pack_weight_q4(w, KC, sm, gateup=gu) for w in ws]
+                    pk = [(ops.pack_weight_q6 if tag == "q6" else ops.pack_weight_q4)(w, KC, sm, gateup=gu) for w in ws]
                     stored = pk[0].nbytes()
-                fused = gu and ops.gateup_silu_ok(rows, N // 2, K, KC, tag == "z12", tag in ("q8", "q4"))
+                fused = gu and ops.gateup_silu_ok(rows, N // 2, K, KC, tag == "z12", tag in ("q8", "q6", "q4"))
                 if fused:
                     run = lambda i, pk=pk, sm=sm: ops.gateup_silu(x, pk[i % a.copies], N // 2, K, sm)
                 elif name == "gate_up":
@@ -97,6 +99,8 @@ def launch_legs(a, dev, lib):
             rec["q8_over_bf16"] = round(rec["q8"]["us"]["median"] / rec["bf16"]["us"]["median"], 4)
             if a.mxfp4:
                 rec["q4_over_q8"] = round(rec["q4"]["us"]["median"] / rec["q8"]["us"]["median"], 4)
+            if a.e2m3:
+                rec["q6_over_q8"] = round(rec["q6"]["us"]["median"] / rec["q8"]["us"]["median"], 4)
             print(json.dumps(rec), flush=True)
             out.append(rec)
             del legs
@@ -110,13 +114,13 @@ def step_legs(a, dev):
     base = bench.parse(["--gpus", "1", "--steps", str(a.steps), "--warmup", str(a.warmup)])
     base.model, base.window, base.prompts_per_gpu, base.n_split = "lumina7b", 16, 1, 0
     legs = {}
-    tags = ("z12", "q8") + (("q4",) if a.mxfp4 else ())
+    tags = ("z12", "q8") + (("q6",) if a.e2m3 else ()) + (("q4",) if a.mxfp4 else ())
     for tag in tags:
         b = copy.copy(base)
         b.no_fused = tag != "z12"                         # (the q8 / q4 legs call enable_fused themselves, on the same synthetic weights)
         model, margs, attn = bench.build_model(b, dev)
         if tag != "z12":
-            model.enable_fused(ops, gemm="sjd", weights="e4m3" if tag == "q8" else "mxfp4")
+            model.enable_fused(ops, gemm="sjd", weights=dict(q8="e4m3", q6="e2m3", q4="mxfp4")[tag])
         w = bench.workload_of(b, margs, 0, dev)
         P, n_img = w["P"], w["n_img"]
         model.setup_cache(batch=2, s_max=((P + n_img + 2 * 16 + 64 + 31) // 32) * 32)
@@ -156,6 +160,15 @@ def step_legs(a, dev):
         rec["q4_minus_q8_ms"] = round(q4["median"] - q["median"], 4)
         rec["largest_spread_between_rounds_ms"] = round(max(rec["largest_spread_between_rounds_ms"], q4["max"] - q4["min"]), 4)
         rec["q4_faster_than_q8_beyond_spread"] = bool(q["median"] - q4["median"] > rec["largest_spread_between_rounds_ms"])
+    if a.e2m3:           # the 6-bit leg against the 8-bit leg of the SAME run, by the same rule
+        q6 = rec["q6"]["ms_per_step"]
+        rec["q6_minus_q8_ms"] = round(q6["median"] - q["median"], 4)
+        rec["largest_spread_between_rounds_ms"] = round(max(rec["largest_spread_between_rounds_ms"], q6["max"] - q6["min"]), 4)
+        rec["q6_faster_than_q8_beyond_spread"] = bool(q["median"] - q6["median"] > rec["largest_spread_between_rounds_ms"])
+        if a.mxfp4:
+            rec["q4_faster_than_q8_beyond_spread"] = bool(q["median"] - rec["q4"]["ms_per_step"]["median"] > rec["largest_spread_between_rounds_ms"])
+    for tag in tags:     # stored layer bytes per step against the HBM peak
+        rec[tag]["frac_of_8TBps_on_layer_bytes"] = round(rec[tag]["layer_bytes_per_step"] / (rec[tag]["ms_per_step"]["median"] * 1e-3) / PEAK, 4)
     print(json.dumps(rec), flush=True)
     return rec
 
@@ -250,6 +263,7 @@ def main():
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--mxfp4", action="store_true", help="--launch / --step: add the MXFP4 leg (q4)")
+    ap.add_argument("--e2m3", action="store_true", help="--launch / --step: add the 6-bit e2m3 leg (q6)")
     ap.add_argument("--prompts", default="2,4,8", help="--batch: prompts per forward, comma separated")
     ap.add_argument("--launches", type=int, default=48)
     ap.add_argument("--copies", type=int, default=8)
@@ -265,7 +279,7 @@ def main():
     if a.launch:
         doc["per_launch"] = launch_legs(a, dev, lib)
         doc["per_launch_method"] = (f"{a.launches} launches per hipGraph over {a.copies} weight sets, the graph replayed three times and the middle time taken; "
-                                    f"{a.rounds} rounds alternating bf16 / 12-bit / 8-bit{' / mxfp4' if a.mxfp4 else ''}; us per launch: median, min, max over the rounds")
+                                    f"{a.rounds} rounds alternating bf16 / 12-bit / 8-bit{' / e2m3' if a.e2m3 else ''}{' / mxfp4' if a.mxfp4 else ''}; us per launch: median, min, max over the rounds")
     if a.step:
         doc["per_step"] = step_legs(a, dev)
     if a.batch:
