@@ -464,7 +464,7 @@ class LlamaGenBackbone(nn.Module):
         w[:, :, :head_dim] = wo.view(wo.shape[0], n_heads, head_dim)
         return w.view(wo.shape[0], n_heads * head_pad)
 
-    def enable_fused(self, ops, gemm="sjd", max_rows=64, untuned_fp16=False, pad_head_dim=False, padded_batch=False, weights=None):
+    def enable_fused(self, ops, gemm="sjd", max_rows=64, untuned_fp16=False, pad_head_dim=False, padded_batch=False, weights=None, compress=False):
         """Switch draft windows of <= max_rows rows (64, 128 or 256: rows = prompts per forward x CFG batch x window; fp16 weights take 256
         with untuned_fp16=True only: kernel G1w serves them on the launch shapes swept in bf16) to the hand-written HIP path: per layer F1r, G1 q|k|v, F2 (the interleaved rotary from a
         table, SJD_F2_ROPE_TABLE), K1, G1 o, F1r, G1 gate|up (+ F3, or G1s where ops.gateup_silu_ok allows), G1 down; then the output head
@@ -488,6 +488,14 @@ class LlamaGenBackbone(nn.Module):
         compress_stats carries rel_rms_error (the largest over the matrices of RMS(w - dequant) / RMS(w)) and the packed bytes.  What either format does to
         image quality on a real checkpoint has NOT been measured.  bf16 only; not with untuned_fp16; dim and the intermediate size multiples of 128
         (mxfp4) / 32 (e4m3).
+        compress (default False: nothing changes) -- LOSSLESS, opt-in: the packed copies of the four projections AND of the output head are kept in the 12-bit
+        stream of ops.pack_weight_z (kernels G1z / G1sz, as ChameleonBackbone.enable_fused(compress=True)): about 0.78 of the bytes, the same split-K planes
+        bit for bit, so every logit and token is that of compress=False on the same launch shapes.  Launch shapes: LS.LLAMAGEN_Z_SETS (UNTUNED: the 16-bit
+        sets) unless the caller set G1_CFG / HEAD_CFG; either way they must pass LS.z_copy_errors.  ONE copy serves every row count up to max_rows = 64 or 128
+        (the stream ends at LS.Z_MAX_ROWS rows).  gate|up stays G1z + F3 at LlamaGen's widths (LS.gateup_silu_ok).  GPT-3B's padded wo packs too: a unit of
+        zero pad columns travels as exceptions or verbatim (a raw unit), never as a declined matrix.  compress_stats carries ChameleonBackbone's keys
+        (compressed, exceptions, raw_units, declined, declined_reasons, ...).  Refused: fp16 weights (the format encodes bf16), together with `weights`
+        (one stream per copy), max_rows=256, a chunk above LS.Z_MAX_KC.
         `ops` is sjd_amd.ops.  Raises ValueError for what the kernels do not serve -- a refused call leaves the backbone as it was."""
         if weights not in (None,) + LS.QUANT_WEIGHTS:
             raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16', 'mxfp4' or 'mxfp4_as_bf16'")
@@ -500,6 +508,12 @@ class LlamaGenBackbone(nn.Module):
             raise ValueError(f"weights={weights!r} needs bf16 weights (got {dt}): the dequantised values are bf16 numbers, fp16's exponent range does not hold them")
         if weights is not None and untuned_fp16:
             raise ValueError(f"weights={weights!r} packs bf16 weights: untuned_fp16=True does not go with it")
+        if compress and dt != torch.bfloat16:          # (asked for by name: refused, not packed uncompressed behind the caller's back)
+            raise ValueError(f"LlamaGenBackbone.enable_fused: compress=True needs bf16 weights (got {dt}): the 12-bit form encodes bf16, fp16's high byte "
+                             "does not concentrate")
+        if compress and weights is not None:
+            raise ValueError(f"LlamaGenBackbone.enable_fused: compress=True does not go with weights={weights!r}: one stream per copy (the 12-bit stream "
+                             "is lossless, a quantised copy is not)")
         pad100 = bool(pad_head_dim) and self.head_dim == 100
         if self.head_dim not in (64, 128) and not pad100:
             raise ValueError(f"LlamaGenBackbone.enable_fused: head_dim {self.head_dim} is not served (F2's table rotary takes head_dim 64 or 128; "
@@ -521,8 +535,11 @@ class LlamaGenBackbone(nn.Module):
             # (the plain call keeps what it did before fp16 was served at 129..256 rows: nobody gets launch shapes that were never swept for fp16 unasked)
             raise ValueError("LlamaGenBackbone.enable_fused: max_rows=256 packs bf16 weights; it keeps fp16 windows of at most 128 rows unless "
                              "untuned_fp16=True (kernel G1 serves fp16 at 129..256 rows on the launch shapes swept in bf16)")
+        if compress and max_rows > LS.Z_MAX_ROWS:
+            raise ValueError(f"LlamaGenBackbone.enable_fused: compress=True serves windows of at most {LS.Z_MAX_ROWS} rows (the 12-bit stream's kernels end "
+                             f"there, and one copy serves every row count up to max_rows), got max_rows={max_rows!r}: max_rows=64 or {LS.Z_MAX_ROWS}, or compress=False")
         # (a G1_CFG / HEAD_CFG set by the caller still wins)
-        g1_cfg, head_cfg = (LS.LLAMAGEN_SETS if weights is None else LS.LLAMAGEN_QUANT_SETS)[pad100, max_rows]
+        g1_cfg, head_cfg = (LS.LLAMAGEN_Z_SETS if compress else LS.LLAMAGEN_SETS if weights is None else LS.LLAMAGEN_QUANT_SETS)[pad100, max_rows]
         g1_cfg = self.__dict__.get("G1_CFG") or dict(g1_cfg)          # (the default keeps packing exactly what it packed before: the class's HEAD_CFG)
         head_cfg = self.__dict__.get("HEAD_CFG") or (head_cfg if max_rows > 64 or pad100 else None)
         if max_rows > 64:
@@ -538,17 +555,27 @@ class LlamaGenBackbone(nn.Module):
                                  + ("(the MXFP4 stream travels in whole ring trips of eight k-steps)" if q4 else "(the e4m3 stream travels in whole record pairs)"))
             dims = LS.llamagen_dims(self.args.dim, self.n_heads, self.head_dim, inter, self.HEAD_PAD if pad100 else None)
             _refuse_quant_copy(f"weights={weights!r}, max_rows={max_rows}: ", g1_cfg, head_cfg or self.HEAD_CFG, dims, max_rows, gran)
+        if compress:          # (one 12-bit copy, the head's included: validated by shape before anything is assigned)
+            inter = self.layers[0].feed_forward.w1.weight.shape[0]
+            dims = dict(LS.llamagen_dims(self.args.dim, self.n_heads, self.head_dim, inter, self.HEAD_PAD if pad100 else None),
+                        head=(self.output.weight.shape[0], self.args.dim))
+            for name, why in LS.z_copy_errors(g1_cfg, dims, max_rows, head_cfg or self.HEAD_CFG)[:1]:
+                raise ValueError(f"compress=True, max_rows={max_rows}: "
+                                 + LS.z_copy_refusal(name, why, (head_cfg or self.HEAD_CFG) if name == "head" else g1_cfg[name], dims))
         self.G1_CFG = g1_cfg
         if head_cfg is not None:
             self.HEAD_CFG = tuple(head_cfg)
         self.weights = weights
+        self.compress = bool(compress)
         self._max_rows_given = weights is not None          # (SJDBatchEngine: a quantised copy serves the rows it was packed for)
-        self.compress_stats = dict(matrices=0, bytes_raw=0, bytes_packed=0)
+        self.compress_stats = (dict(matrices=0, compressed=0, bytes_raw=0, bytes_packed=0, exceptions=0, raw_units=0, declined=0, declined_reasons={})
+                               if compress else dict(matrices=0, bytes_raw=0, bytes_packed=0))
         wo_of = (lambda w: self._pad_o_weight(w, self.n_heads, self.head_dim, self.HEAD_PAD)) if pad100 else (lambda w: w)
         layers = (([b.attention.wqkv], wo_of(b.attention.wo.weight), b.feed_forward.w1, b.feed_forward.w3, b.feed_forward.w2.weight,
                    b.attention_norm.weight, b.ffn_norm.weight) for b in self.layers)          # (a generator: one padded wo at a time)
-        _pack_fused(self, ops, layers, _packer(ops, weights, False, self.compress_stats), (self.output.weight, self.norm.weight),
-                    lambda w, kc, sm: ops.pack_weight(w, kc, sm))          # (the head is neither quantised nor counted in compress_stats)
+        pack = _packer(ops, weights, bool(compress), self.compress_stats)
+        _pack_fused(self, ops, layers, pack, (self.output.weight, self.norm.weight),          # (the 12-bit stream takes the head too, counted like a layer matrix;
+                    pack if compress else lambda w, kc, sm: ops.pack_weight(w, kc, sm))          #  else it is neither quantised nor counted in compress_stats)
         self._ops = ops
         self._fused_rows = self.max_rows = int(max_rows)
         self.supports_head_partials = True

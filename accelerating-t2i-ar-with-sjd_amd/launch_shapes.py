@@ -128,6 +128,38 @@ LLAMAGEN_QUANT_SETS = {
     (True, 256): (dict(qkv=(1152, 4, False), o=(512, 4, True), gate_up=(1152, 8, True), down=(1152, 4, True)), (1600, 4, True)),
 }
 QUANT_WEIGHTS = ("e4m3", "e4m3_as_bf16") + Q4_WEIGHTS
+# LlamaGenBackbone.enable_fused(compress=True): the LOSSLESS 12-bit stream (ops.pack_weight_z, kernels G1z / G1sz) for the four projections and the output
+# head, up to Z_MAX_ROWS rows -- there is no key for 256.  UNTUNED: the 16-bit sets above with every chunk capped at Z_MAX_KC (none of them reaches it, so
+# today these ARE the 16-bit shapes, which makes the two streams comparable launch for launch); no launch-shape sweep was run on the 12-bit kernels at
+# LlamaGen's widths.  z_copy_errors is the rule they pass.
+LLAMAGEN_Z_SETS = {(pad, rows): ({name: (min(kc, Z_MAX_KC), tiles, sm) for name, (kc, tiles, sm) in cfg.items()}, (min(head[0], Z_MAX_KC),) + tuple(head[1:]))
+                   for (pad, rows), (cfg, head) in LLAMAGEN_SETS.items() if rows <= Z_MAX_ROWS}
+Z_REASONS = ("rows", "granule", "chunk", "tiles")
+
+
+def z_copy_errors(cfg, dims, max_rows, head_cfg=None):
+    """[(name, why)]: what keeps a set of launch shapes `cfg` (dims: the projections' (N, K); head_cfg: the output head's shape, its (N, K) in dims["head"])
+    from being packed as ONE 12-bit copy that serves every row count up to max_rows -- the first of Z_REASONS that applies to each matrix.  why: "rows"
+    (max_rows above Z_MAX_ROWS: kernels G1z / G1sz end there), "granule" (N no multiple of 32, K or the chunk no multiple of 16: whole MFMA tiles and
+    k-steps), "chunk" (above Z_MAX_KC: an exception's k-step is 7 + 1 bits of its position -- ops.pack_weight_z would decline the matrix), "tiles" (column
+    tiles per workgroup outside 1..16, or above 8 where max_rows > 64: the sub-tiled kernel of 65..128 rows runs at most eight waves)."""
+    bad = []
+    for name, (KC, tiles, _) in list(cfg.items()) + ([("head", tuple(head_cfg))] if head_cfg is not None else []):
+        N_, K_ = dims[name]
+        fault = dict(rows=max_rows > Z_MAX_ROWS, granule=bool(N_ % 32 or K_ % 16 or KC % 16 or KC < 16), chunk=KC > Z_MAX_KC,
+                     tiles=not 1 <= tiles <= (8 if max_rows > 64 else 16))
+        bad += [(name, why) for why in Z_REASONS if fault[why]][:1]
+    return bad
+
+
+def z_copy_refusal(name, why, shape, dims):
+    """the sentence enable_fused(compress=True) refuses with: one of z_copy_errors' (name, why), the launch shape it names and that matrix's (N, K)"""
+    what = "HEAD_CFG" if name == "head" else f"G1_CFG[{name!r}]"
+    return dict(rows=f"the 12-bit stream serves windows of at most {Z_MAX_ROWS} rows (kernels G1z / G1sz)",
+                granule="the 12-bit stream travels in whole 32-column tiles and 16-wide k-steps (N a multiple of 32, K and the chunk multiples of 16)",
+                chunk=f"the 12-bit stream takes chunks of at most {Z_MAX_KC} columns (an exception's k-step is 7 + 1 bits of its position)",
+                tiles="kernel G1z takes 1..16 column tiles per workgroup, at most 8 where the copy serves more than 64 rows")[why] \
+        + f"; {what} = {tuple(shape)} with (N, K) = {tuple(dims[name])}"
 
 
 def llamagen_dims(dim, n_head, head_dim, inter, head_pad=None):

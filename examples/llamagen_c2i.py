@@ -43,10 +43,19 @@ def parse_args(argv=None):
     ap.add_argument("--fused", action="store_true", help="draft windows on the hand-written HIP path (LlamaGenBackbone.enable_fused)")
     ap.add_argument("--weights", default=None, choices=["e4m3", "mxfp4"],
                     help="with --fused: stream the layer projections from QUANTISED weights (LOSSY, opt-in; image quality on a real checkpoint is not measured)")
+    ap.add_argument("--compress", action="store_true",
+                    help="with --fused: stream the layer projections and the output head from the LOSSLESS 12-bit copy (about 0.78 of the bytes, the same tokens; "
+                         "at most 128 window rows per forward)")
     ap.add_argument("--out", default="sample.png")
     a = ap.parse_args(argv)
     if a.weights and not a.fused:
         ap.error("--weights packs the weights of the fused HIP path: add --fused")
+    if a.compress and not a.fused:
+        ap.error("--compress packs the weights of the fused HIP path: add --fused")
+    if a.compress and a.weights:
+        ap.error("--compress (lossless 12-bit) and --weights (a quantised copy) are two streams: one per packed copy")
+    if a.compress and (a.prompts_per_forward or len(a.class_id)) * 2 * a.window > 128:
+        ap.error(f"--compress serves at most 128 window rows per forward: --prompts-per-forward {max(1, 128 // (2 * a.window))} or fewer at --window {a.window}")
     if len(a.class_id) > 1 and not a.fused:
         ap.error("several --class-id labels are decoded together on the fused HIP path: add --fused")
     if len(a.cfg_scale) not in (1, len(a.class_id)):
@@ -89,7 +98,10 @@ def main():
         # (GPT-3B's 32 heads are 100 wide: the kernels store them 128 wide with zero pad columns, which the backbone does on request only)
         # (... and several labels per forward on the padded model need its own swept launch shapes: padded_batch, no effect on the other models)
         gpt.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else (128 if rows <= 128 else 256), pad_head_dim=gpt.head_dim == 100,
-                         padded_batch=rows > 64, weights=a.weights)
+                         padded_batch=rows > 64, weights=a.weights, compress=a.compress)
+        if a.compress:
+            st = gpt.compress_stats
+            print(f"--compress: lossless 12-bit copy, {st['bytes_packed'] / st['bytes_raw']:.3f} of the 16-bit bytes ({st['raw_units']} of {st.get('units', 0)} units verbatim)")
         if a.weights:
             print(f"--weights {a.weights}: LOSSY, rel. RMS error of the packed projections {gpt.compress_stats['rel_rms_error']:.4f}")
     one_scale = a.cfg_scale if isinstance(a.cfg_scale, float) else a.cfg_scale[0]        # (a scale per label: this one only says "CFG on")

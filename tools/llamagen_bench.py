@@ -26,6 +26,10 @@
   --quant   the lossy weight streams (enable_fused(weights="e4m3" / "mxfp4")): GPT-XL t2i 512px and GPT-3B c2i 384px at --counts (default 1,8) prompts per
             forward, legs 16-bit / e4m3 / mxfp4 alternated over --rounds rounds (median and the rounds), then us per launch of GPT-3B's projections at
             128 / 256 rows on kernels G1w / G1wq / G1wq4 (profiles/llamagen_quant.json).
+  --z       the LOSSLESS 12-bit stream (enable_fused(compress=True)): GPT-B c2i 256px, GPT-XL t2i 512px and GPT-3B c2i 384px at --counts (default 1,4)
+            prompts per forward, legs 16-bit / 12-bit on the same weights and launch shapes alternated over --rounds rounds (median, min / max, the
+            verdict against the larger round-to-round spread, the 16-bit leg against the recorded rounds), then us per launch of G1 against G1z at
+            GPT-3B's four shapes, 32 and 128 rows (profiles/llamagen_z.json).
 """
 import argparse
 import json
@@ -408,6 +412,103 @@ def quant(args):
             json.dump(out, f, indent=1)
 
 
+def _recorded_16bit(preset, P):
+    """(min, max) ms per step of the 16-bit leg's recorded rounds at P prompts per forward (profiles/llamagen_batch.json, llamagen_3b_batch.json), or None"""
+    name = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "llamagen_3b_batch.json" if preset == "GPT-3B" else "llamagen_batch.json")
+    try:
+        rec = next(c for c in json.load(open(name))["configs"] if c["preset"] == preset)
+        return min(rec["ms_per_step_rounds"][str(P)]), max(rec["ms_per_step_rounds"][str(P)])
+    except (OSError, KeyError, StopIteration):
+        return None
+
+
+def zstream(args):
+    """--z: ms per SJD step from 16-bit weights and from the LOSSLESS 12-bit stream (LlamaGenBackbone.enable_fused(compress=True)) on the same synthetic
+    weights and the same launch shapes: GPT-B c2i 256px, GPT-XL t2i 512px and GPT-3B c2i 384px at --counts (default 1,4) prompts per forward; one
+    process, the two legs alternated in every round, medians with min / max.  The 12-bit leg counts as faster (or slower) only where the gap exceeds the
+    larger of the two legs' round-to-round spreads; the 16-bit leg is held against the rounds recorded in profiles/llamagen_batch.json /
+    llamagen_3b_batch.json.  Then us per launch of G1 against G1z at GPT-3B's four shapes (o with the zero pad columns of heads stored 128 wide)."""
+    dev = torch.device("cuda:0")
+    counts = [int(c) for c in (args.counts if args.counts != "1,2,4,8" else "1,4").split(",")]
+    only = args.only.split(",") if args.only else []
+    out = dict(configs=[], window=args.window, cfg=True, rounds=args.rounds, steps=args.steps, warmup=args.warmup,
+               note="synthetic weights; the 12-bit stream is lossless (bit-identical planes), its launch shapes are the 16-bit ones (UNTUNED: launch_shapes.LLAMAGEN_Z_SETS)")
+    for preset, mt, size in (CONFIGS[0], CONFIGS[1], CONFIG_3B):
+        if only and preset not in only:
+            continue
+        base = _make(preset, mt, size, dev)
+        models, legs = {}, {}
+        for z in (False, True):
+            for P in counts:
+                m = models[z, P] = _make(preset, mt, size, dev)
+                m.load_state_dict(base.state_dict())
+                rows = P * 2 * args.window
+                m.enable_fused(ops, gemm="sjd", max_rows=64 if rows <= 64 else 128, pad_head_dim=preset == "GPT-3B", padded_batch=preset == "GPT-3B" and rows > 64,
+                               compress=z)
+                legs[z, P] = _Leg(m, args.window, dev) if P == 1 else _BatchLeg(m, P, args.window, dev)
+        del base
+        ms = {k: [] for k in legs}
+        for _ in range(args.rounds):
+            for P in counts:
+                for z in (False, True):
+                    if P == 1:
+                        _, st, _ = legs[z, P].decode(args.warmup, args.steps)
+                        ms[z, P].append(1e3 * st.seconds / max(1, st.timed_nfe))
+                    else:
+                        ms[z, P].append(legs[z, P].decode(args.warmup, args.steps)[0])
+        rec = dict(preset=preset, model_type=mt, image_size=size, layers=models[False, counts[0]].n_layers, prompts_per_forward={})
+        for P in counts:
+            med = {z: statistics.median(ms[z, P]) for z in (False, True)}
+            spread = max(max(ms[z, P]) - min(ms[z, P]) for z in (False, True))
+            gain = med[False] - med[True]
+            was = _recorded_16bit(preset, P)
+            st = models[True, P].compress_stats
+            rec["prompts_per_forward"][str(P)] = dict(
+                ms_per_step={n: dict(median=round(med[z], 3), min=round(min(ms[z, P]), 3), max=round(max(ms[z, P]), 3), rounds=[round(x, 3) for x in ms[z, P]])
+                             for n, z in (("bf16", False), ("z12", True))},
+                gain_ms=round(gain, 3), larger_round_spread_ms=round(spread, 3),
+                verdict="12-bit faster" if gain > spread else "12-bit slower" if -gain > spread else "no difference beyond the round-to-round spread",
+                z12_vs_bf16=round(med[True] / med[False], 3),
+                packed_gb_per_step=dict(bf16=round(models[False, P].packed_bytes() / 1e9, 3), z12=round(models[True, P].packed_bytes() / 1e9, 3)),
+                bytes_packed_over_raw=round(st["bytes_packed"] / st["bytes_raw"], 4), raw_units=st["raw_units"], units=st.get("units"),
+                recorded_bf16_rounds_min_max=was,
+                bf16_inside_recorded_spread=None if was is None else bool(was[0] <= med[False] <= was[1]),
+                g1_cfg=models[True, P].G1_CFG, head_cfg=list(models[True, P].HEAD_CFG))
+            if was is not None and not was[0] <= med[False] <= was[1]:
+                rec["prompts_per_forward"][str(P)]["box_note"] = (f"the 16-bit leg ({med[False]:.3f} ms) lies outside the recorded rounds {was[0]:.3f}..{was[1]:.3f} ms: "
+                                                                  "this box (or its software) is not the one of the recorded profile; compare the two legs of this run only")
+        print(json.dumps(rec), flush=True)
+        out["configs"].append(rec)
+        del legs, models
+        torch.cuda.empty_cache()
+    # per launch: GPT-3B's projections on the 12-bit set's shapes, 32 and 128 rows, weights cycled past the Infinity Cache
+    shapes = BB.LS.llamagen_dims(3200, 32, 100, 8704, 128)
+    g = torch.Generator(device=dev).manual_seed(1)
+    launches = []
+    for name, (N, K) in shapes.items():
+        copies = max(2, -(-768 * 2**20 // (N * K * 2)))
+        ws = [(torch.randn(N, K, generator=g, device=dev) / K ** 0.5).to(torch.bfloat16) for _ in range(copies)]
+        if name == "o":          # heads of 100 stored 128 wide: zero columns at the pad positions (every unit of the 12-bit copy then travels verbatim)
+            for w in ws:
+                w.view(N, 32, 128)[:, :, 100:] = 0
+        for M, pad_rows in ((32, 64), (128, 128)):
+            kc, tiles, sm = BB.LS.LLAMAGEN_Z_SETS[True, pad_rows][0][name]
+            packs = dict(G1=[ops.pack_weight(w, kc, sm) for w in ws], G1z=[ops.pack_weight_z(w, kc, sm) for w in ws])
+            x = torch.randn(M, K, generator=g, device=dev).to(torch.bfloat16)
+            us = {kn: round(_graph_us(lambda i: ops.skinny_gemm(x, pk[i % copies], N, K, kc, tiles, sm), 2 * copies), 2) for kn, pk in packs.items()}
+            rec = dict(proj=name, N=N, K=K, rows=M, cfg=[kc, tiles, sm], us_per_launch=us, raw_units=packs["G1z"][0].n_raw, units=packs["G1z"][0].stats["units"],
+                       bytes_z_over_16bit=round(packs["G1z"][0].nbytes() / (N * K * 2), 4))
+            print(json.dumps(rec), flush=True)
+            launches.append(rec)
+            del packs
+        del ws
+        torch.cuda.empty_cache()
+    out["gpt_3b_launches"] = launches
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def detok(args):
     from llamagen.tokenizer.tokenizer_image.vq_model import VQ_models
     from sjd_amd.detokenizers import to_uint8
@@ -547,6 +648,8 @@ def main():
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--fused3b", action="store_true")
     ap.add_argument("--quant", action="store_true", help="16-bit / e4m3 / mxfp4 weight streams (enable_fused(weights=...)), GPT-XL and GPT-3B, 1 and 8 prompts per forward")
+    ap.add_argument("--z", action="store_true", help="16-bit against the lossless 12-bit stream (enable_fused(compress=True)): GPT-B, GPT-XL and GPT-3B at 1 and 4 prompts per forward, "
+                                                     "then G1 against G1z per launch at GPT-3B's shapes")
     ap.add_argument("--detok", action="store_true", help="--batch: the tokens -> pixels queue (detokenizer alone, serial, overlapped) instead of the step table")
     ap.add_argument("--cfg-from", default="", help="--fused3b: a --sweep output whose `best` lines give the G1 launch shapes")
     ap.add_argument("--prompts", type=int, default=1, help="--step: prompts per forward (SJDBatchEngine above 1)")
@@ -573,6 +676,8 @@ def main():
         step(args)
     if args.quant:
         quant(args)
+    if args.z:
+        zstream(args)
     if args.fused3b:
         fused3b(args)
 
