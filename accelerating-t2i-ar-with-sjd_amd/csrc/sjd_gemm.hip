@@ -1055,6 +1055,7 @@ __device__ __forceinline__ g1z_pair g1z_load(__amdgpu_buffer_rsrc_t wr, unsigned
 
 #include "sjd_gemm_wide.h"          // (kernel G1w: behind the declarations of the 12-bit decode it shares with G1z)
 #include "sjd_gemm_q8.h"            // (kernels G1q / G1sq: the 8-bit e4m3 stream, SJD_G1_W8_E4M3)
+#include "sjd_gemm_qblock.h"        // (the kernel templates of the two block-scaled streams below)
 #include "sjd_gemm_q4.h"            // (kernels G1q4 / G1sq4: the MXFP4 stream, SJD_G1_W4_MXFP4)
 #include "sjd_gemm_q6.h"            // (kernels G1q6 / G1sq6: the 6-bit e2m3 stream, SJD_G1_W6_E2M3)
 

@@ -5,16 +5,20 @@
 //   g1s_row_sumsq_load, g1s_row_scale   the folded RMSNorm's row scale of the gate|up kernels: the eight loads every thread issues, and the finish
 //   g1s_plane_store, g1s_finish         the gate|up epilogue: a wave's accumulators as a plane in LDS; planes summed in chunk order, SiLU * up, store
 //   g1s_norm_args             sjd_row_norm unpacked into the four kernel arguments of the folded RMSNorm
-//   g1_stream_launch           the launcher body of a quantised stream's whole-chunk kernel (G1q, G1q4)
-//   g1s_stream_launch          ... and of its 32-row gate|up kernel (G1sq, G1sq4)
+//   g1_stream_launch           the launcher body of a quantised stream's whole-chunk kernel (G1q, G1q4, G1q6)
+//   g1s_stream_launch          ... and of its 32-row gate|up kernel (G1sq, G1sq4, G1sq6)
 // A new quantised stream supplies its kernels, its bytes per weight and its own refusals; the argument checks, the LDS limit, the grid and the
 // (row tiles, threads) / phase-length ladders are here.
+// Shared elsewhere, by TEMPLATE PARAMETER: the kernels of the two block-scaled streams (MXFP4, e2m3) are one whole-chunk and one gate|up template
+// over a stream-traits struct (csrc/sjd_gemm_qblock.h).  The body stands in place, once; only the record type, its sizes, its load and its half
+// trip come from the parameter, so an instantiation is the machine code of the copy it replaced.
 // Of the DEVICE bodies the kernels repeat, the gate|up kernels' tail (row scale, plane store, finish) is here: it runs behind the weight stream or
 // on cache hits, its 31 instantiations compile to other machine code than the copies did and were timed against them (DESIGN.md 4.2f;
 // g1z_gateup_silu, the headline's kernel, keeps its copy).  The
 // bodies ON the streaming path (whole-chunk staging, phase staging, g1_wide's plane store) are NOT gathered: as force-inlined functions they
 // changed the machine code of every kernel that called them -- the optimiser simplifies a callee on its own before it inlines it, so operand
-// orders and what is known about `lane` differ from the code written in place -- and each needs a timing of its own.
+// orders and what is known about `lane` differ from the code written in place -- and each needs a timing of its own.  (A template over types
+// and constants is not such a function: nothing is simplified apart from its caller.  That is how sjd_gemm_qblock.h shares whole kernels.)
 // Not on the helpers: the raw gate|up fix-up (csrc/sjd_gemm_raw.h: planes [4][32][33], row scale read per thread, one tile pair per workgroup) and
 // the MLP pair's gate|up phase (csrc/sjd_gemm_pair.h: workgroup index `bid`, write-through 8-byte stores) -- their indexing differs.
 #pragma once
@@ -110,7 +114,7 @@ struct g1s_norm_args {
         : ss(rn ? rn->sumsq : nullptr), sl(rn ? rn->slices : 0), ih(rn ? 1.0f / (float)rn->hidden : 0.f), eps(rn ? rn->eps : 0.f) {}
 };
 
-// The launcher of a quantised stream's whole-chunk kernel (G1q, G1q4) behind sjd_skinny_gemm / sjd_skinny_gemm_cols, which have checked the common
+// The launcher of a quantised stream's whole-chunk kernel (G1q, G1q4, G1q6) behind sjd_skinny_gemm / sjd_skinny_gemm_cols, which have checked the common
 // arguments: M <= 64 with the activation chunk in LDS -- min(KC, K) <= 2560 up to 32 rows, <= 1280 at 33..64.
 //   tile_k_bytes   the stream's record bytes per 32-column tile and column of K (32 at one byte per weight); the scales sit behind n_tiles * K of them
 //   other_form()   the stream's own refusals (its K granule) and its forms for more rows: an SJD_* code, or G1_STREAM_GO for this launcher's shapes
@@ -137,7 +141,7 @@ static int g1_stream_launch(const void *wq, int M, int N, int K, int KC, int wav
     return waves <= 8 ? launch(two{}, t512{}, grid, block, lds, scales, rs) : launch(two{}, t1024{}, grid, block, lds, scales, rs);
 }
 
-// ... and of its 32-row gate|up kernel (G1sq, G1sq4) behind sjd_gateup_silu: M <= 32; the packed weight is [Wg; Wu], 2 I / 32 tiles.
+// ... and of its 32-row gate|up kernel (G1sq, G1sq4, G1sq6) behind sjd_gateup_silu: M <= 32; the packed weight is [Wg; Wu], 2 I / 32 tiles.
 //   launch(SP, grid, block, lds, scales, rec_stride, norm)   names the kernel (SP = K / 64 k-steps per phase: std::integral_constant)
 template <typename Launch>
 static int g1s_stream_launch(const void *wq, int M, int I, int K, int step_major, int tile_k_bytes, const sjd_row_norm *rn, Launch launch)

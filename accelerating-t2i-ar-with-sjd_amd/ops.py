@@ -678,9 +678,10 @@ def dequantize_mxfp4(codes, scale_exp):
     return (lut[nib].reshape(N, K // 32, 32) * scale[:, :, None]).reshape(N, K).to(torch.bfloat16)
 
 
-class PackedQ4(_PackedQuant):
-    """A packed weight in the MXFP4 stream format of kernels G1q4 / G1sq4 (see pack_weight_q4): `data` uint8 [N * K / 2 + N * K / 32] = the code
-    records, four bits per weight, then the e8m0 scale bytes at byte offset N * K / 2.  LOSSY: the kernels multiply by dequant(), exactly."""
+class _PackedBlockQuant(_PackedQuant):
+    """what the block-scaled stream formats (MXFP4, e2m3) share: 64-k records of REC code bytes per 32-column tile, tile- or step-major per chunk, then
+    one e8m0 scale byte per 32 weights in groups of 128 bytes per tile and trip of two records, laid out like the records.  A subclass supplies REC and
+    its record permutation both ways: _to_records (a chunk's columns of the quantiser's codes -> [T, R, REC]) and _from_records."""
 
     def reads_as(self, KC):
         """can a launch with split-K chunk KC stream this buffer?  The chunk it was packed with -- or, step-major, any other multiple of the granule:
@@ -690,30 +691,67 @@ class PackedQ4(_PackedQuant):
     def _chunks(self):
         return [(k0, min(self.KC, self.K - k0)) for k0 in range(0, self.K, self.KC)]
 
-    def codes(self):
-        """uint8 [N, K / 2]: the e2m1 codes, two per byte, read back from the packed records (the inverse of pack_weight_q4's permutation)"""
-        N, T = self.N, self.N // 32
-        cols, off = [], 0
+    def _groups(self, off, width, k_per):
+        """the chunk walk: per chunk its groups [T, kc / k_per, width] (records: 64 k each; a trip's scales: 128 k) from byte `off` of `data` on"""
+        T = self.N // 32
         for _, kc in self._chunks():
-            S = kc // 16
-            blk = self.data[off:off + N * kc // 2]
-            off += N * kc // 2
-            rec = blk.reshape(S // 4, T, 1024).permute(1, 0, 2) if self.step_major else blk.reshape(T, S // 4, 1024)
-            st = rec.reshape(T, S // 4, 64, 4, 4).permute(0, 1, 3, 2, 4).reshape(T, S, 2, 32, 4)         # [t, R, lane, i, b] -> [t, s, h, r, b]
-            cols.append(st.permute(0, 3, 1, 2, 4).reshape(N, kc // 2))
-        return torch.cat(cols, dim=1).contiguous()
+            G = kc // k_per
+            blk = self.data[off:off + T * G * width]
+            off += T * G * width
+            yield blk.reshape(G, T, width).permute(1, 0, 2) if self.step_major else blk.reshape(T, G, width)
+
+    def codes(self):
+        """uint8, the codes as the stream's quantiser returns them (MXFP4: [N, K / 2], the e2m1 codes, two per byte; e2m3: [N, K], one per byte), read
+        back from the packed records (the inverse of the packer's permutation)"""
+        return torch.cat([self._from_records(rec) for rec in self._groups(0, self.REC, 64)], dim=1).contiguous()
 
     def scale_exp(self):
-        """uint8 [N, K / 32]: the e8m0 scale bytes read back from behind the records"""
-        N, T = self.N, self.N // 32
-        cols, off = [], self.N * self.K // 2
-        for _, kc in self._chunks():
-            Q = kc // 128
-            blk = self.data[off:off + N * kc // 32]
-            off += N * kc // 32
-            grp = blk.reshape(Q, T, 128).permute(1, 0, 2) if self.step_major else blk.reshape(T, Q, 128)
-            cols.append(grp.reshape(T, Q, 32, 4).permute(0, 2, 1, 3).reshape(N, kc // 32))
+        """uint8 [N, K / 32]: the e8m0 scale bytes (e2m3: column 2 R + h, quantize_e2m3's) read back from behind the records"""
+        T = self.N // 32
+        cols = [grp.reshape(T, -1, 32, 4).permute(0, 2, 1, 3).reshape(self.N, -1) for grp in self._groups(T * (self.K // 64) * self.REC, 128, 128)]
         return torch.cat(cols, dim=1).contiguous()
+
+
+def _pack_block_quant(cls, name, quantize, dequantize, weight, KC, step_major, gateup):
+    """the packer of a block-scaled stream: `quantize`'s codes as cls's records chunk by chunk, then its scale bytes in groups of 128 (see cls)"""
+    if weight.dim() != 2 or weight.shape[1] % Q4_GRANULE or KC < Q4_GRANULE or KC % Q4_GRANULE:
+        raise ValueError(f"{name}: K and KC must be multiples of {Q4_GRANULE} (whole records and scale dwords); got K = {tuple(weight.shape)[-1]}, KC = {KC}")
+    codes, se = quantize(weight)
+    N, K = weight.shape
+    assert N % 32 == 0
+    T, W = N // 32, codes.shape[1]
+    assert not gateup or (2 * KC == K and T % 2 == 0)
+    cparts, sparts = [], []
+    for k0 in range(0, K, KC):
+        kc = min(KC, K - k0)
+        rec = cls._to_records(codes[:, k0 * W // K:(k0 + kc) * W // K], T)
+        grp = se[:, k0 // 32:(k0 + kc) // 32].reshape(T, 32, kc // 128, 4).permute(0, 2, 1, 3).reshape(T, kc // 128, 128)
+        if step_major:
+            rec, grp = rec.permute(1, 0, 2), grp.permute(1, 0, 2)
+        cparts.append(rec.reshape(-1))
+        sparts.append(grp.reshape(-1))
+    data = torch.cat(cparts + sparts).contiguous()
+    assert data.numel() == T * (K // 64) * cls.REC + N * K // 32
+    stats = dict(rel_rms_error=_rel_rms_error(weight, dequantize(codes, se)), scale_exp_min=int(se.min()) - 127, scale_exp_max=int(se.max()) - 127)
+    return cls(data, N, K, KC, step_major, stats)
+
+
+class PackedQ4(_PackedBlockQuant):
+    """A packed weight in the MXFP4 stream format of kernels G1q4 / G1sq4 (see pack_weight_q4): `data` uint8 [N * K / 2 + N * K / 32] = the code
+    records, four bits per weight, then the e8m0 scale bytes at byte offset N * K / 2.  LOSSY: the kernels multiply by dequant(), exactly."""
+
+    REC = 1024
+
+    @staticmethod
+    def _to_records(c, T):
+        b = c.reshape(T, 32, -1, 2, 4).permute(0, 2, 3, 1, 4).reshape(T, -1, 4, 64, 4)      # [t, r, s, h, b] -> [t, R, i, lane = 32 h + r, b]
+        return b.permute(0, 1, 3, 2, 4).reshape(T, -1, 1024)
+
+    @staticmethod
+    def _from_records(rec):
+        T, R = rec.shape[:2]
+        st = rec.reshape(T, R, 64, 4, 4).permute(0, 1, 3, 2, 4).reshape(T, 4 * R, 2, 32, 4)         # [t, R, lane, i, b] -> [t, s, h, r, b]
+        return st.permute(0, 3, 1, 2, 4).reshape(32 * T, 32 * R)
 
     def dequant(self):
         """bf16 [N, K]: the weight the kernels multiply by, read back from the packed buffer (exact: one mantissa bit times a power of two)"""
@@ -732,28 +770,7 @@ def pack_weight_q4(weight, KC, step_major=False, gateup=False):
     out like the records; a chunk's scales start at scale byte k0 * N / 32.
     gateup=True: `weight` is [Wg; Wu] packed with KC = K / 2 for sjd_gateup_silu.
     stats: rel_rms_error (RMS of w - dequant over RMS of w), scale_exp_min / scale_exp_max (log2 of the smallest / largest block scale)."""
-    if weight.dim() != 2 or weight.shape[1] % Q4_GRANULE or KC < Q4_GRANULE or KC % Q4_GRANULE:
-        raise ValueError(f"pack_weight_q4: K and KC must be multiples of {Q4_GRANULE} (whole records and scale dwords); got K = {tuple(weight.shape)[-1]}, KC = {KC}")
-    codes, se = quantize_mxfp4(weight)
-    N, K = weight.shape
-    assert N % 32 == 0
-    T = N // 32
-    assert not gateup or (2 * KC == K and T % 2 == 0)
-    cparts, sparts = [], []
-    for k0 in range(0, K, KC):
-        kc = min(KC, K - k0)
-        S, Q = kc // 16, kc // 128
-        b = codes[:, k0 // 2:(k0 + kc) // 2].reshape(T, 32, S, 2, 4).permute(0, 2, 3, 1, 4).reshape(T, S // 4, 4, 64, 4)      # [t, R, i, lane = 32 h + r, b]
-        rec = b.permute(0, 1, 3, 2, 4).reshape(T, S // 4, 1024)
-        grp = se[:, k0 // 32:(k0 + kc) // 32].reshape(T, 32, Q, 4).permute(0, 2, 1, 3).reshape(T, Q, 128)
-        if step_major:
-            rec, grp = rec.permute(1, 0, 2), grp.permute(1, 0, 2)
-        cparts.append(rec.reshape(-1))
-        sparts.append(grp.reshape(-1))
-    data = torch.cat(cparts + sparts).contiguous()
-    assert data.numel() == N * K // 2 + N * K // 32
-    stats = dict(rel_rms_error=_rel_rms_error(weight, dequantize_mxfp4(codes, se)), scale_exp_min=int(se.min()) - 127, scale_exp_max=int(se.max()) - 127)
-    return PackedQ4(data, N, K, KC, step_major, stats)
+    return _pack_block_quant(PackedQ4, "pack_weight_q4", quantize_mxfp4, dequantize_mxfp4, weight, KC, step_major, gateup)
 
 
 Q6_MIN_SCALE_EXP = -123     # 0.125 (the smallest non-zero e2m3 magnitude) * 2^-123 = 2^-126: every dequantised value is a NORMAL bf16 number or zero
@@ -830,44 +847,24 @@ def _q6_unpack_bits(b):
     return torch.stack([w24 & 63, (w24 >> 6) & 63, (w24 >> 12) & 63, w24 >> 18], dim=-1).to(torch.uint8).reshape(*b.shape[:-1], 32)
 
 
-class PackedQ6(_PackedQuant):
+class PackedQ6(_PackedBlockQuant):
     """A packed weight in the 6-bit (e2m3) stream format of kernels G1q6 / G1sq6 (see pack_weight_q6): `data` uint8 [N * K * 3 / 4 + N * K / 32] = the code
     records, six bits per weight, then the e8m0 scale bytes at byte offset N * K * 3 / 4.  LOSSY: the kernels multiply by dequant(), exactly."""
 
-    def reads_as(self, KC):
-        """can a launch with split-K chunk KC stream this buffer?  The chunk it was packed with -- or, step-major, any other multiple of the granule:
-        every chunk is then whole records and whole scale groups and the buffer is [record][tile], then [trip][tile], throughout, whatever the chunking"""
-        return KC == self.KC or (self.step_major and self.KC % Q4_GRANULE == 0 and KC % Q4_GRANULE == 0)
+    REC = 1536
 
-    def _chunks(self):
-        return [(k0, min(self.KC, self.K - k0)) for k0 in range(0, self.K, self.KC)]
+    @staticmethod
+    def _to_records(c, T):
+        c = c.reshape(T, 32, -1, 4, 2, 8).permute(0, 2, 4, 1, 3, 5).reshape(T, -1, 64, 32)          # [t, r, R, u, h, j] -> [t, R, lane = 32 h + r, e = 8 u + j]
+        b = _q6_pack_bits(c)                                                                        # [t, R, lane, 24]
+        return torch.cat([b[..., :16].reshape(T, -1, 1024), b[..., 16:].reshape(T, -1, 512)], dim=-1)
 
-    def codes(self):
-        """uint8 [N, K]: the e2m3 codes, one per byte as quantize_e2m3 returns them, read back from the packed records (the inverse of pack_weight_q6's
-        permutation)"""
-        N, T = self.N, self.N // 32
-        cols, off = [], 0
-        for _, kc in self._chunks():
-            R = kc // 64
-            blk = self.data[off:off + N * kc * 3 // 4]
-            off += N * kc * 3 // 4
-            rec = blk.reshape(R, T, 1536).permute(1, 0, 2) if self.step_major else blk.reshape(T, R, 1536)
-            lane = torch.cat([rec[..., :1024].reshape(T, R, 64, 16), rec[..., 1024:].reshape(T, R, 64, 8)], dim=-1)      # [t, R, lane = 32 h + r, 24]
-            c = _q6_unpack_bits(lane).reshape(T, R, 2, 32, 4, 8)                                                          # [t, R, h, r, u, j]
-            cols.append(c.permute(0, 3, 1, 4, 2, 5).reshape(N, kc))                                                       # [t, r, R, u, h, j]
-        return torch.cat(cols, dim=1).contiguous()
-
-    def scale_exp(self):
-        """uint8 [N, K / 32]: the e8m0 scale bytes (column 2 R + h: quantize_e2m3's) read back from behind the records"""
-        N, T = self.N, self.N // 32
-        cols, off = [], self.N * self.K * 3 // 4
-        for _, kc in self._chunks():
-            Q = kc // 128
-            blk = self.data[off:off + N * kc // 32]
-            off += N * kc // 32
-            grp = blk.reshape(Q, T, 128).permute(1, 0, 2) if self.step_major else blk.reshape(T, Q, 128)
-            cols.append(grp.reshape(T, Q, 32, 4).permute(0, 2, 1, 3).reshape(N, kc // 32))
-        return torch.cat(cols, dim=1).contiguous()
+    @staticmethod
+    def _from_records(rec):
+        T, R = rec.shape[:2]
+        lane = torch.cat([rec[..., :1024].reshape(T, R, 64, 16), rec[..., 1024:].reshape(T, R, 64, 8)], dim=-1)      # [t, R, lane = 32 h + r, 24]
+        c = _q6_unpack_bits(lane).reshape(T, R, 2, 32, 4, 8)                                                          # [t, R, h, r, u, j]
+        return c.permute(0, 3, 1, 4, 2, 5).reshape(32 * T, 64 * R)                                                    # [t, r, R, u, h, j]
 
     def dequant(self):
         """bf16 [N, K]: the weight the kernels multiply by, read back from the packed buffer (exact: three mantissa bits times a power of two)"""
@@ -887,29 +884,7 @@ def pack_weight_q6(weight, KC, step_major=False, gateup=False):
     2 q + i, lane half h), the trips laid out like the records; a chunk's scales start at scale byte k0 * N / 32.
     gateup=True: `weight` is [Wg; Wu] packed with KC = K / 2 for sjd_gateup_silu.
     stats: rel_rms_error (RMS of w - dequant over RMS of w), scale_exp_min / scale_exp_max (log2 of the smallest / largest block scale)."""
-    if weight.dim() != 2 or weight.shape[1] % Q4_GRANULE or KC < Q4_GRANULE or KC % Q4_GRANULE:
-        raise ValueError(f"pack_weight_q6: K and KC must be multiples of {Q4_GRANULE} (whole records and scale dwords); got K = {tuple(weight.shape)[-1]}, KC = {KC}")
-    codes, se = quantize_e2m3(weight)
-    N, K = weight.shape
-    assert N % 32 == 0
-    T = N // 32
-    assert not gateup or (2 * KC == K and T % 2 == 0)
-    cparts, sparts = [], []
-    for k0 in range(0, K, KC):
-        kc = min(KC, K - k0)
-        R, Q = kc // 64, kc // 128
-        c = codes[:, k0:k0 + kc].reshape(T, 32, R, 4, 2, 8).permute(0, 2, 4, 1, 3, 5).reshape(T, R, 64, 32)      # [t, r, R, u, h, j] -> [t, R, lane = 32 h + r, e = 8 u + j]
-        b = _q6_pack_bits(c)                                                                                     # [t, R, lane, 24]
-        rec = torch.cat([b[..., :16].reshape(T, R, 1024), b[..., 16:].reshape(T, R, 512)], dim=-1)
-        grp = se[:, k0 // 32:(k0 + kc) // 32].reshape(T, 32, Q, 4).permute(0, 2, 1, 3).reshape(T, Q, 128)
-        if step_major:
-            rec, grp = rec.permute(1, 0, 2), grp.permute(1, 0, 2)
-        cparts.append(rec.reshape(-1))
-        sparts.append(grp.reshape(-1))
-    data = torch.cat(cparts + sparts).contiguous()
-    assert data.numel() == N * K * 3 // 4 + N * K // 32
-    stats = dict(rel_rms_error=_rel_rms_error(weight, dequantize_e2m3(codes, se)), scale_exp_min=int(se.min()) - 127, scale_exp_max=int(se.max()) - 127)
-    return PackedQ6(data, N, K, KC, step_major, stats)
+    return _pack_block_quant(PackedQ6, "pack_weight_q6", quantize_e2m3, dequantize_e2m3, weight, KC, step_major, gateup)
 
 
 def _same_16bit_type(x, w_packed, what):

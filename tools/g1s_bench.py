@@ -18,7 +18,7 @@ import torch
 
 import sjd_amd.ops as ops
 
-KERNEL = {"plain": "g1_gateup_silu", "z": "g1z_gateup_silu", "q8": "g1q_gateup_silu", "q4": "g1q4_gateup_silu"}
+KERNEL = {"plain": "g1_gateup_silu", "z": "g1z_gateup_silu", "q8": "g1q_gateup_silu", "q4": "g1q4_gateup_silu"}          # (q4: g1qb_gateup_silu<G1Q4Stream>, under the label profiles/ knows it by)
 BITS = {"plain": 16, "z": 12, "q8": 8, "q4": 4.25}          # stored bits per weight (z: without the unit headers)
 
 

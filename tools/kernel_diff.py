@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Per-kernel machine-code comparison of two builds (CPU only):  tools/kernel_diff.py OLD NEW [--arch gfx950] [--list]
+r"""Per-kernel machine-code comparison of two builds (CPU only):  tools/kernel_diff.py OLD NEW [--arch gfx950] [--list] [--rename REGEX=REPL]...
 
 OLD / NEW are either two shared libraries (every gfx950 code object in their offload bundles is disassembled with llvm-objdump) or two
 `hipcc --cuda-device-only -S` outputs of the same translation unit.  For every kernel symbol: identical, differs, or only in one side.  The
 instruction text of WHOLE kernels is compared, local block labels renumbered in order of appearance; for a kernel that differs the VGPR / SGPR /
-scratch / LDS figures of both sides are printed from the code-object metadata.  Exit status 1 if anything differs or is only in one side."""
+scratch / LDS figures of both sides are printed from the code-object metadata.  Exit status 1 if anything differs or is only in one side.
+--rename pairs kernels whose (mangled) names changed: re.sub(REGEX, REPL) on NEW's names, e.g. for kernels that became instantiations of one template
+  --rename 'g1qb_(\w+?)I10G1Q(\d)Stream(\w+?)S4_=g1q\2_\1I\3S3_'"""
 import argparse
 import os
 import re
@@ -82,8 +84,11 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--arch", default="gfx950")
     ap.add_argument("--list", action="store_true", help="print the identical kernels too")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL", help="re.sub on NEW's kernel names before pairing")
     a = ap.parse_args()
     (co, mo), (cn, mn) = load(a.old, a.arch), load(a.new, a.arch)
+    for pat, repl in (r.split("=", 1) for r in a.rename):
+        cn, mn = ({re.sub(pat, repl, k): v for k, v in d.items()} for d in (cn, mn))
     same = [k for k in co if k in cn and co[k] == cn[k]]
     diff = [k for k in co if k in cn and co[k] != cn[k]]
     only = [(k, "old") for k in co if k not in cn] + [(k, "new") for k in cn if k not in co]
