@@ -591,8 +591,13 @@ def quantize_e4m3(weight):
     amax = w.abs().amax(dim=1)
     m, e = torch.frexp(amax)                                      # amax = m * 2^e, m in [0.5, 1); 448 = 0.875 * 2^9
     exp = (e - 9 + (m > 0.875).to(e.dtype)).clamp(min=Q8_MIN_SCALE_EXP)
-    scale = torch.where(amax > 0, torch.ldexp(torch.ones_like(amax), exp), torch.ones_like(amax))
-    q = (w / scale[:, None]).to(FP8).view(torch.uint8)
+    exp = torch.where(amax > 0, exp, torch.zeros_like(exp)).to(torch.int32)
+    # scale and 1 / scale built from their exponent bits: exact on every device.  torch.ldexp(1, e) is NOT on the GPU (a pow() underneath: one ulp below
+    # 2^e at e = 16..20, 22, ... on the MI355X), and the kernels take the scale's EXPONENT FIELD (v_cvt_scalef32_pk_bf16_fp8): such a column was
+    # multiplied by half its scale, while dequant(), a float product rounded to bf16, still gave the right weight (tests/test_gpu_gemm_exact.py)
+    scale = ((127 + exp) << 23).view(torch.float32)
+    inv = ((127 - exp) << 23).view(torch.float32)
+    q = (w * inv[:, None]).to(FP8).view(torch.uint8)               # exact: a power of two
     return q, scale
 
 
@@ -624,7 +629,7 @@ def pack_weight_q8(weight, KC, step_major=False, gateup=False):
         else:
             parts.append(torch.cat([pr.reshape(T, P * 1024), hf], dim=1).reshape(-1))
     data = torch.cat(parts + [scale.contiguous().view(torch.uint8)]).contiguous()
-    lg = torch.log2(scale)
+    lg = (scale.view(torch.int32) >> 23) - 127                     # (the exponent field: a log2() need not be exact on every device either)
     stats = dict(rel_rms_error=_rel_rms_error(weight, q.view(FP8).float() * scale[:, None]), scale_exp_min=int(lg.min()), scale_exp_max=int(lg.max()))
     return PackedQ8(data, N, K, KC, step_major, stats)
 

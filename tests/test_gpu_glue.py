@@ -111,7 +111,8 @@ def test_fused_forward_matches_unfused(dev):
                                         (64, 6144, 4096, 1024), (47, 4096, 14336, 1280), (64, 64, 96, 32)])
 @pytest.mark.parametrize("waves,step_major", [(4, False), (8, True), (11, True), (3, False)])
 def test_g1_skinny_gemm(dev, dtype, M, N, K, KC, waves, step_major):
-    """G1 weight-streaming projection (split-K partials) against an fp32 matmul of the same bf16/fp16 operands."""
+    """G1 weight-streaming projection (split-K partials) against an fp32 matmul of the same bf16/fp16 operands.
+    (The per-plane anchor of this family is tests/test_gpu_gemm_exact.py: exact fp64 chunk sums, zero tolerance; this test checks sum(0) only.)"""
     import sjd_amd.ops as ops
     g = torch.Generator().manual_seed(N + K)
     x = torch.randn(M, K, generator=g).to(dtype).to(dev)
@@ -130,7 +131,8 @@ def test_g1_skinny_gemm(dev, dtype, M, N, K, KC, waves, step_major):
 def test_g1_row_tile_ladder(dev, dtype):
     """every boundary the (dtype, row tiles, column tiles) dispatch of sjd_skinny_gemm decides on: each side of every multiple of 32 rows, the tile
     counts kernel G1w takes and one it does not (5: the sub-tiled kernels up to 128 rows, SJD_ERR_BAD_ARG above), both packings -- against
-    test_g1_skinny_gemm's reference and tolerance."""
+    test_g1_skinny_gemm's reference and tolerance.
+    (The per-plane anchor of this family is tests/test_gpu_gemm_exact.py: exact fp64 chunk sums, zero tolerance; this test checks sum(0) only.)"""
     import sjd_amd._lib as L
     import sjd_amd.ops as ops
     N, K, KC = 256, 512, 256
@@ -159,7 +161,8 @@ def test_g1_row_tile_ladder(dev, dtype):
 def test_g1_skinny_gemm_three_and_four_row_tiles(dev, dtype, M, N, K, KC, waves, step_major):
     """65..128-row windows (three / four prompts per forward), and 64-row windows whose chunk does not fit in LDS (KC > 1280): the
     sub-tiled G1 (activation double-buffered through LDS 256 columns at a time) against an fp32 matmul; chunk lengths that are not whole
-    sub-tiles / whole 8-step groups included."""
+    sub-tiles / whole 8-step groups included.
+    (The per-plane anchor of this family is tests/test_gpu_gemm_exact.py: exact fp64 chunk sums, zero tolerance; this test checks sum(0) only.)"""
     import sjd_amd.ops as ops
     g = torch.Generator().manual_seed(N + K + M)
     x = torch.randn(M, K, generator=g).to(dtype).to(dev)
@@ -185,7 +188,8 @@ def test_g1_skinny_gemm_three_and_four_row_tiles(dev, dtype, M, N, K, KC, waves,
 def test_g1w_two_row_tiles(dev, dtype, M, N, K, KC, tiles, step_major):
     """late round 6: 33..64-row windows on the uncompressed stream (Emu3's window of 32 with CFG in fp16; two prompts per forward) run on kernel G1w with
     two row tiles, bf16 AND fp16 -- against an fp32 matmul and plane for plane against the 32-row kernel fed 32 rows at a time (bit-identical); Emu3's
-    shapes, ragged chunks, column counts that leave waves without a tile, one K chunk, rows that are not whole tiles; poisoned planes."""
+    shapes, ragged chunks, column counts that leave waves without a tile, one K chunk, rows that are not whole tiles; poisoned planes.
+    (The per-plane anchor of this family is tests/test_gpu_gemm_exact.py: exact fp64 chunk sums, zero tolerance; this test checks sum(0) only.)"""
     import sjd_amd.ops as ops
     g = torch.Generator().manual_seed(N + K + M)
     x = torch.randn(M, K, generator=g).to(dtype).to(dev)
@@ -212,7 +216,8 @@ def test_g1_skinny_gemm_five_to_eight_row_tiles(dev, M, N, K, KC, tiles, step_ma
     """129..256-row windows (five to eight prompts per forward): kernel G1w (round 6: activation stages by LDS-DMA, hand-counted vmcnt, one or two
     column tiles per wave) -- against an fp32 matmul, and plane for plane against the 32-row kernel fed 32 rows at a time (same chunking, same
     accumulation order: bit-identical); every column-tile count the launcher serves, ragged chunks, column counts that leave waves without a tile,
-    rows that are not whole tiles.  The planes are POISONED first: every element must be written."""
+    rows that are not whole tiles.  The planes are POISONED first: every element must be written.
+    (The per-plane anchor of this family is tests/test_gpu_gemm_exact.py: exact fp64 chunk sums, zero tolerance; this test checks sum(0) only.)"""
     import sjd_amd.ops as ops
     g = torch.Generator().manual_seed(N + K + M)
     x = torch.randn(M, K, generator=g).to(torch.bfloat16).to(dev)
