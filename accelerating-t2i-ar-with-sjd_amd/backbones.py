@@ -85,19 +85,18 @@ def _head_logits(linear, x, cols):
 
 def _packer(ops, weights, compress, st):
     """pack(w, kc, step_major, gateup=False) of either backbone's enable_fused, counting into its compress_stats `st`.  Under `weights` the quantised copy
-    (ops.pack_weight_q8 / pack_weight_q4 / pack_weight_q6) or, for an "_as_bf16" twin, its dequantised values packed uncompressed; else the lossless 12-bit stream where
-    `compress` asks for it and ops.pack_weight_z takes the matrix (a declined one is counted, and logged once per reason); else the plain packing."""
-    tag = "q4" if weights in LS.Q4_WEIGHTS else "q6" if weights in LS.Q6_WEIGHTS else "q8"
-    quantise = getattr(ops, "pack_weight_" + tag)
+    (its stream's packer, ops.pack_weight_<tag> of LS.STREAMS) or, for an "_as_bf16" twin, its dequantised values packed uncompressed; else the lossless 12-bit
+    stream where `compress` asks for it and ops.pack_weight_z takes the matrix (a declined one is counted, and logged once per reason); else the plain packing."""
+    stream, twin = LS.stream_of(weights)
 
     def pack(w, kc, sm, gateup=False):          # gateup: [Wg; Wu] in the two K halves the fused gate|up launch streams
         st["matrices"] += 1
         st["bytes_raw"] += w.numel() * w.element_size()
-        if weights is not None:
-            z = quantise(w, kc, sm, gateup=gateup)
+        if stream is not None:
+            tag, z = stream.tag, getattr(ops, "pack_weight_" + stream.tag)(w, kc, sm, gateup=gateup)
             st[tag + "_matrices"] = st.get(tag + "_matrices", 0) + 1
             st["rel_rms_error"] = max(st.get("rel_rms_error", 0.0), z.stats["rel_rms_error"])
-            if weights.endswith("_as_bf16"):
+            if twin:
                 st["bytes_packed"] += w.numel() * w.element_size()
                 return ops.pack_weight(z.dequant(), kc, sm)
             st["bytes_packed"] += z.nbytes()
@@ -497,8 +496,9 @@ class LlamaGenBackbone(nn.Module):
         (compressed, exceptions, raw_units, declined, declined_reasons, ...).  Refused: fp16 weights (the format encodes bf16), together with `weights`
         (one stream per copy), max_rows=256, a chunk above LS.Z_MAX_KC.
         `ops` is sjd_amd.ops.  Raises ValueError for what the kernels do not serve -- a refused call leaves the backbone as it was."""
-        if weights not in (None,) + LS.QUANT_WEIGHTS:
-            raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16', 'mxfp4' or 'mxfp4_as_bf16'")
+        stream = LS.stream_of(weights)[0]
+        if weights is not None and not (stream is not None and "llamagen" in stream.has):
+            raise ValueError(f"weights={weights!r}: " + ", ".join(["None"] + ["%r or %r" % s.names for s in LS.STREAMS if "llamagen" in s.has]))
         if gemm != "sjd":
             raise ValueError(f"LlamaGenBackbone.enable_fused serves gemm='sjd' only (the G1 weight-streaming kernels), got gemm={gemm!r}")
         dt = self.output.weight.dtype
@@ -548,13 +548,11 @@ class LlamaGenBackbone(nn.Module):
                 raise ValueError(f"windows of more than 64 rows take {LS.WIDE_TILES} column tiles per workgroup; offending launch shapes: {bad}")
         if weights is not None:          # (one quantised copy for every row count: validated before anything is assigned)
             inter = self.layers[0].feed_forward.w1.weight.shape[0]
-            q4 = weights in LS.Q4_WEIGHTS
-            gran = LS.Q4_GRANULE if q4 else 32
-            if self.args.dim % gran or inter % gran:
-                raise ValueError(f"weights={weights!r}: dim {self.args.dim} and the intermediate size {inter} must be multiples of {gran} "
-                                 + ("(the MXFP4 stream travels in whole ring trips of eight k-steps)" if q4 else "(the e4m3 stream travels in whole record pairs)"))
+            if self.args.dim % stream.granule or inter % stream.granule:
+                raise ValueError(f"weights={weights!r}: dim {self.args.dim} and the intermediate size {inter} must be multiples of {stream.granule} "
+                                 + ("(the MXFP4 stream travels in whole ring trips of eight k-steps)" if stream.tag == "q4" else "(the e4m3 stream travels in whole record pairs)"))
             dims = LS.llamagen_dims(self.args.dim, self.n_heads, self.head_dim, inter, self.HEAD_PAD if pad100 else None)
-            _refuse_quant_copy(f"weights={weights!r}, max_rows={max_rows}: ", g1_cfg, head_cfg or self.HEAD_CFG, dims, max_rows, gran)
+            _refuse_quant_copy(f"weights={weights!r}, max_rows={max_rows}: ", g1_cfg, head_cfg or self.HEAD_CFG, dims, max_rows, stream.granule)
         if compress:          # (one 12-bit copy, the head's included: validated by shape before anything is assigned)
             inter = self.layers[0].feed_forward.w1.weight.shape[0]
             dims = dict(LS.llamagen_dims(self.args.dim, self.n_heads, self.head_dim, inter, self.HEAD_PAD if pad100 else None),
@@ -747,7 +745,7 @@ class ChameleonBackbone(nn.Module):
     def _q8_wide_check(self, cfg, head_cfg, max_rows, dims=None):
         """enable_fused(weights=..., max_rows > 64): can ONE e4m3 copy with launch shapes `cfg` serve every row count up to max_rows?  dims: the projections'
         (N, K) -- this backbone's by default.  ValueError names what cannot; nothing is assigned.  (Up to LS.Z_MAX_ROWS rows the head keeps its own kernels.)"""
-        _refuse_quant_copy(f"max_rows={max_rows}: ", cfg, head_cfg if max_rows > LS.Z_MAX_ROWS else None, dims or self._dims(), max_rows, 32)
+        _refuse_quant_copy(f"max_rows={max_rows}: ", cfg, head_cfg if max_rows > LS.Z_MAX_ROWS else None, dims or self._dims(), max_rows, LS.STREAMS[0].granule)
 
     released_16bit = False        # enable_fused(..., release_16bit=True) has dropped the 16-bit layer matrices: the packed quantised copy is the only one
 
@@ -829,18 +827,16 @@ class ChameleonBackbone(nn.Module):
                 raise ValueError(f"release_16bit=True needs gemm='sjd' (the packed copies are read by the hand-written projection kernels only), got gemm={gemm!r}")
             if self.lm_head.weight.dtype != torch.bfloat16:
                 raise ValueError(f"release_16bit=True needs a bf16 backbone (got {self.lm_head.weight.dtype}): the quantised streams and kernel G1p are bf16 only")
-        if weights not in (None, "e4m3", "e4m3_as_bf16") + LS.Q4_WEIGHTS + LS.Q6_WEIGHTS:
-            raise ValueError(f"weights={weights!r}: None, 'e4m3' or 'e4m3_as_bf16', 'mxfp4' or 'mxfp4_as_bf16', 'e2m3' or 'e2m3_as_bf16'")
-        q4, q6 = weights in LS.Q4_WEIGHTS, weights in LS.Q6_WEIGHTS
-        if q4 and max_rows not in (None, 64):
-            raise ValueError(f"weights={weights!r} serves windows of at most 64 rows (kernels G1q4 / G1sq4 have no wide form): max_rows is None or 64, got {max_rows!r}")
-        if q6:          # (the 6-bit stream: window rows only, folded-norm backbones only)
-            if max_rows not in (None, LS.Q6_MAX_ROWS):
-                raise ValueError(f"weights={weights!r} serves windows of at most {LS.Q6_MAX_ROWS} rows (kernels G1q6 / G1sq6 have no wide form): max_rows is None or "
-                                 f"{LS.Q6_MAX_ROWS}, got {max_rows!r}")
-            if self.args.swin_norm or self.args.model_parallel_size > 1:
+        stream = LS.stream_of(weights)[0]
+        if weights is not None and stream is None:
+            raise ValueError(f"weights={weights!r}: " + ", ".join(["None"] + ["%r or %r" % s.names for s in LS.STREAMS]))
+        if stream is not None:          # (what the stream has no kernel for: a wide form, the swin-norm route, the prefill)
+            if stream.max_rows <= 64 and max_rows not in (None, stream.max_rows):
+                raise ValueError(f"weights={weights!r} serves windows of at most {stream.max_rows} rows (kernels {stream.kernels} have no wide form): max_rows is None or "
+                                 f"{stream.max_rows}, got {max_rows!r}")
+            if "swin" not in stream.has and (self.args.swin_norm or self.args.model_parallel_size > 1):
                 raise ValueError(f"weights={weights!r} is not served for swin-norm backbones (swin_norm=True or model_parallel_size > 1), with or without swin_quant")
-            if release_16bit:
+            if "prefill" not in stream.has and release_16bit:
                 raise ValueError(f"weights={weights!r} has no prefill kernel (G1p reads the e4m3 / MXFP4 copies): release_16bit=True does not go with it")
         if max_rows is not None and weights is None:
             raise ValueError(f"max_rows={max_rows!r} goes with weights='e4m3' / 'e4m3_as_bf16' (without it the packed copy serves the row counts of its G1_CFG)")
@@ -865,11 +861,11 @@ class ChameleonBackbone(nn.Module):
             raise ValueError(f"weights={weights!r} serves swin-norm backbones at windows of at most 64 rows (one prompt per forward): max_rows is None or 64, got {max_rows!r}")
         if weights is not None:          # (validated before anything is assigned: a refused call leaves the backbone as it was)
             # ONE copy serves every row count it is packed for.  A plain e4m3 copy for <= 64 rows is held only to what 32 rows stage: it packs, and a 33..64-row
-            # window it cannot read in halved chunks is refused at the forward (_q8_chunk); MXFP4, swin-norm and max_rows > 64 are held to the whole rule
+            # window it cannot read in halved chunks is refused at the forward (_q8_chunk); a stream without a wide form, swin-norm and max_rows > 64 are held to the whole rule
             rows = max_rows or 64
-            reasons = LS.QUANT_REASONS if q4 or q6 or swin_q or rows > 64 else ("granule", "chunk") if release_16bit else ("chunk",)          # (G1p: whole record pairs)
+            reasons = LS.QUANT_REASONS if stream.max_rows <= 64 or swin_q or rows > 64 else ("granule", "chunk") if release_16bit else ("chunk",)          # (G1p: whole record pairs)
             _refuse_quant_copy(f"weights={weights!r}: " if rows <= 64 else f"weights={weights!r}, max_rows={max_rows}: ", g1_cfg,
-                               (head_cfg or self.HEAD_CFG) if rows > LS.Z_MAX_ROWS else None, self._dims(), rows, LS.Q4_GRANULE if q4 or q6 else 32, reasons=reasons)
+                               (head_cfg or self.HEAD_CFG) if rows > LS.Z_MAX_ROWS else None, self._dims(), rows, stream.granule, reasons=reasons)
             self.max_rows, self._max_rows_given = int(max_rows) if max_rows is not None else 64, max_rows is not None
         else:
             self.__dict__.pop("max_rows", None)
@@ -1027,7 +1023,8 @@ class ChameleonBackbone(nn.Module):
         if any(c[0] > cap for c in cfg.values()):
             raise ValueError(f"G1_CFG chunk sizes must be <= {cap} for a {T}-row window")
         swin, gu = self.args.swin_norm, self._packed[0]["gate_up"]
-        fused_mlp = bool(swin and getattr(self, "gateup_fused", _SWIN_GATEUP_FUSED_DEFAULT) and isinstance(gu, ops.PackedQ4)
+        stream = ops.streamed(gu)[0]          # (a copy whose stream has the four-chunk form of the fused launch: MXFP4)
+        fused_mlp = bool(swin and getattr(self, "gateup_fused", _SWIN_GATEUP_FUSED_DEFAULT) and stream is not None and "gateup_k4" in stream.has
                          and LS.gateup_silu_chunked_ok(T, self.args.intermediate_size, self.args.hidden_size, gu.KC))
         if swin and getattr(self, "weights", None) is not None:
             self.gateup_route[T] = "fused" if fused_mlp else "g1+f3"
@@ -1069,10 +1066,9 @@ class ChameleonBackbone(nn.Module):
         if self.released_16bit and no is not None and (no[0] == "prefill" or T_ > 64):          # (a released copy serves every row count: G1p)
             return self._forward_prefill_packed(tokens, positions, kv_len, key_start, cols)
         if no is not None and no[0] == "max_rows":          # (an 8-bit copy packed for fewer rows: there is no 16-bit copy to fall back on)
-            if getattr(self, "weights", None) in LS.Q4_WEIGHTS:
-                raise ValueError(f"weights={self.weights!r} serves draft windows of at most 64 rows (kernels G1q4 / G1sq4 have no wide form); got {T_} rows")
-            if getattr(self, "weights", None) in LS.Q6_WEIGHTS:
-                raise ValueError(f"weights={self.weights!r} serves draft windows of at most {LS.Q6_MAX_ROWS} rows (kernels G1q6 / G1sq6 have no wide form); got {T_} rows")
+            stream = LS.stream_of(self.weights)[0]
+            if stream.max_rows <= 64:
+                raise ValueError(f"weights={self.weights!r} serves draft windows of at most {stream.max_rows} rows (kernels {stream.kernels} have no wide form); got {T_} rows")
             if no[1] > 64:
                 raise ValueError(f"weights='e4m3' serves draft windows of at most {no[1]} rows (max_rows={no[1]}); got {T_} rows")
             raise ValueError(f"weights='e4m3' serves draft windows of at most 64 rows (one prompt per forward); got {T_} rows")

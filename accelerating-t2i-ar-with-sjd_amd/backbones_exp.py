@@ -92,7 +92,7 @@ def forward_folded(m, tokens, positions, kv_len, key_start, cols=None, head_part
                                                                                                         getattr(m, "weights", None) is not None)
     # o / down with F1r as their tail (one launch each; the reducing kernel wants whole 512-column slices per workgroup pair: 8 waves)
     red = getattr(m, "reduce_fused", BB._REDUCE_FUSED_DEFAULT) and not m._pf_on
-    raw = lambda name: not isinstance(m._packed[0][name], (ops.PackedZ, ops.PackedQ8, ops.PackedQ4)) and getattr(m, "weights", None) is None        # (the reducing kernel streams the uncompressed packing)
+    raw = lambda name: not isinstance(m._packed[0][name], ops.Packed) and getattr(m, "weights", None) is None        # (the reducing kernel streams the uncompressed packing)
     h_dev = m.lm_head.weight.device
     red_o = red and raw("o") and ops.skinny_gemm_reduce_ok(T, hid, H * D, cfg["o"][0], 8, h_dev)
     red_d = red and raw("down") and ops.skinny_gemm_reduce_ok(T, hid, inter, cfg["down"][0], 8, h_dev)

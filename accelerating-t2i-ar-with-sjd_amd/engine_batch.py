@@ -99,16 +99,12 @@ class SJDBatchEngine(WindowLauncher):
             if why == "max_rows":
                 raise ValueError(f"the backbone was packed for windows of at most max_rows={detail} rows, but n_prompts * n_batch * max_window = "
                                  f"{rows}: call enable_fused(ops, gemm='sjd', weights='e4m3', max_rows={to}), or use fewer prompts per forward")
-        # enable_fused(weights="mxfp4" / "mxfp4_as_bf16") on a Chameleon-family backbone: packed for 64 rows, always.  (A LlamaGen backbone's 4-bit copy serves
-        # the max_rows it was packed for -- kernel G1wq4 above 64 -- and is refused below like any other LlamaGen backbone.)
-        if getattr(backbone, "weights", None) in LS.Q4_WEIGHTS and rows > LS.Q4_MAX_ROWS and not LS.is_llamagen(backbone):
-            raise ValueError(f"a backbone packed with enable_fused(weights={backbone.weights!r}) serves at most {LS.Q4_MAX_ROWS} window rows per forward (kernels "
-                             f"G1q4 / G1sq4 have no wide form), but n_prompts * n_batch * max_window = {rows}: use fewer prompts per forward, or weights='e4m3' "
-                             "with max_rows=128 / 256")
-        # enable_fused(weights="e2m3" / "e2m3_as_bf16"): the 6-bit copy is packed for 64 rows, always (Chameleon-family backbones only)
-        if getattr(backbone, "weights", None) in LS.Q6_WEIGHTS and rows > LS.Q6_MAX_ROWS:
-            raise ValueError(f"a backbone packed with enable_fused(weights={backbone.weights!r}) serves at most {LS.Q6_MAX_ROWS} window rows per forward (kernels "
-                             f"G1q6 / G1sq6 have no wide form), but n_prompts * n_batch * max_window = {rows}: use fewer prompts per forward, or weights='e4m3' "
+        # a stream without a wide form on a Chameleon-family backbone ("mxfp4", "e2m3" and their twins): packed for 64 rows, always.  (A LlamaGen backbone's
+        # 4-bit copy serves the max_rows it was packed for -- kernel G1wq4 above 64 -- and is refused below like any other LlamaGen backbone.)
+        stream = LS.stream_of(getattr(backbone, "weights", None))[0]
+        if stream is not None and rows > stream.max_rows <= 64 and not ("llamagen" in stream.has and LS.is_llamagen(backbone)):
+            raise ValueError(f"a backbone packed with enable_fused(weights={backbone.weights!r}) serves at most {stream.max_rows} window rows per forward (kernels "
+                             f"{stream.kernels} have no wide form), but n_prompts * n_batch * max_window = {rows}: use fewer prompts per forward, or weights='e4m3' "
                              "with max_rows=128 / 256")
         L.load()                                   # fail loudly if the HIP extension is missing
         if max_window > L.MAX_WINDOW:

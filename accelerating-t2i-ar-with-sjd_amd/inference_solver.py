@@ -49,8 +49,8 @@ class FlexARInferenceSolver:
     def __init__(self, model_path=None, precision="bf16", target_size=512, cache_dir=None, device="cpu", tokenizer=None,
                  model: Optional[BB.ChameleonBackbone] = None, item_processor=None, fused=True, gemm="sjd", vq_model=None, bpe_to_vq=None, weights=None, swin_quant=False,
                  release_16bit=False):
-        """weights: passed to ChameleonBackbone.enable_fused ("e4m3": the window projections streamed from 8-bit weights, "mxfp4": from 4.25-bit, "e2m3":
-        from 6.25-bit ones (that one without release_16bit or swin_quant) -- lossy; the prompt
+        """weights: passed to ChameleonBackbone.enable_fused: the name of a row of launch_shapes.STREAMS or its "_as_bf16" twin -- the window projections
+        streamed from quantised weights, lossy; the table says which streams go with release_16bit and swin_quant; the prompt
         prefill keeps the 16-bit parameters unless release_16bit=True goes along, which runs the prefill on the packed copy as well and releases the 16-bit
         layer matrices; see there).  swin_quant=True goes along: a swin-norm backbone (30B class) is quantised too -- lossy and
         opt-in, refused without it.

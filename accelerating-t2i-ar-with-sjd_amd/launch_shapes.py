@@ -1,5 +1,7 @@
 """Launch shapes (split-K chunk, column tiles per workgroup, step-major packing) of the window projections: the tuned sets, the kernels' limits, and
-what serves which rows.  The packed layout depends on the chunk, so a set is chosen when the weights are packed (enable_fused)."""
+what serves which rows.  The packed layout depends on the chunk, so a set is chosen when the weights are packed (enable_fused).  STREAMS: the lossy streams."""
+from typing import NamedTuple
+
 import torch
 
 # ------------------------------------------------------------------------------------------ the kernels' limits
@@ -61,13 +63,6 @@ G1_CFG_EMU3_Q8_WIDE = dict(qkv=(1024, 4, True), o=(512, 4, True), gate_up=(2048,
 # that halves to <= 1280 for 33..64 rows); no launch-shape sweep was run for this format
 G1_CFG_Q4 = dict(G1_CFG_Q8)
 G1_CFG_EMU3_Q4 = dict(G1_CFG_EMU3_Q8)
-Q4_GRANULE = 128                  # K granule of the MXFP4 stream (ops.pack_weight_q4): K and every chunk are multiples of it
-Q4_WEIGHTS = ("mxfp4", "mxfp4_as_bf16")
-Q4_MAX_ROWS = 64                  # kernels G1q4 / G1sq4 have no wide form
-# the 6-bit e2m3 stream (enable_fused(weights="e2m3"), kernels G1q6 / G1sq6, ops.pack_weight_q6): the MXFP4 stream's granule and its launch-shape sets
-# G1_CFG_Q4 / G1_CFG_EMU3_Q4 -- UNTUNED for this stream too: no launch-shape sweep was run.  Deliberately NOT part of QUANT_WEIGHTS / Q4_WEIGHTS.
-Q6_WEIGHTS = ("e2m3", "e2m3_as_bf16")
-Q6_MAX_ROWS = 64                  # kernels G1q6 / G1sq6 have no wide form
 # 30B-class Chameleon (hidden 8192, intermediate 22016, GQA 64 / 8: q|k|v 10240 columns, gate|up 44032, down K 22016); chunks <= 2560 so that
 # the 32-row window stages its chunk in LDS.  The fastest shapes of `tools/swin30b_bench.py --sweep` at 32 rows on one MI355X
 # (profiles/g1_30b_sweep.jsonl), us per launch uncompressed / 12-bit: q|k|v 30.4 / 25.2, o 23.8 / 20.3, gate|up 120.5 / 98.9, down 62.9 / 50.4
@@ -79,6 +74,39 @@ G1_CFG_30B_Z = dict(qkv=(1792, 8, True), o=(1280, 8, True), gate_up=(2048, 8, Tr
 # copy G1q / G1q4 + F3 stream, and on "mxfp4" at <= 32 rows the one the fused K = 8192 launch streams (gateup_silu_chunked_ok)
 G1_CFG_30B_Q8 = dict(G1_CFG_30B_Z)
 G1_CFG_30B_Q4 = dict(G1_CFG_30B_Z)
+
+
+class WeightStream(NamedTuple):
+    """A LOSSY weight stream of the window projections, stated once (plain data: no import of ops or _lib); ops.PackedZ and the plain packing are not rows"""
+    names: tuple                  # enable_fused(weights=...): the stream, and its verification twin (the dequantised values, packed uncompressed)
+    tag: str                      # compress_stats' "<tag>_matrices" / "<tag>_bytes_packed"; the packer is ops.pack_weight_<tag>, its class ops.Packed<TAG>
+    flag: str                     # the _lib constant the C entry points take beside the dtype code
+    granule: int                  # K and every chunk are multiples of it
+    max_rows: int                 # window rows a Chameleon-family backbone serves from it (above 64: packed with enable_fused(max_rows=128 / 256))
+    kernels: str                  # the kernels a row-limit refusal names
+    has: frozenset                # of "prefill" (G1p, release_16bit), "swin" (swin_quant), "llamagen" (there up to 256 rows), "gateup_k4" (gateup_silu_chunked_ok)
+    sets: tuple                   # default_shapes: the plain set, Emu3's, the 30B class's, and the plain and Emu3's for max_rows > 64 (None: no wide form)
+
+
+STREAMS = (
+    WeightStream(("e4m3", "e4m3_as_bf16"), "q8", "G1_W8_E4M3", 32, 256, "G1q / G1sq", frozenset({"prefill", "swin", "llamagen"}),
+                 (G1_CFG_Q8, G1_CFG_EMU3_Q8, G1_CFG_30B_Q8, G1_CFG_Q8_WIDE, G1_CFG_EMU3_Q8_WIDE)),
+    WeightStream(("mxfp4", "mxfp4_as_bf16"), "q4", "G1_W4_MXFP4", 128, 64, "G1q4 / G1sq4", frozenset({"prefill", "swin", "llamagen", "gateup_k4"}),
+                 (G1_CFG_Q4, G1_CFG_EMU3_Q4, G1_CFG_30B_Q4, None, None)),
+    # (window rows of folded-norm Chameleon-family backbones only, on the MXFP4 sets -- UNTUNED for it too; no swin route, so the 30B set is never reached)
+    WeightStream(("e2m3", "e2m3_as_bf16"), "q6", "G1_W6_E2M3", 128, 64, "G1q6 / G1sq6", frozenset(), (G1_CFG_Q4, G1_CFG_EMU3_Q4, G1_CFG_30B_Q4, None, None)),
+)
+
+
+def stream_of(weights):
+    """(stream, is_twin) of a `weights=` name; (None, False) for None and for a name no stream has"""
+    return next(((s, weights == s.names[1]) for s in STREAMS if weights in s.names), (None, False))
+
+
+Q4_WEIGHTS, Q6_WEIGHTS = STREAMS[1].names, STREAMS[2].names
+QUANT_WEIGHTS = tuple(n for s in STREAMS if "llamagen" in s.has for n in s.names)          # the streams with a LlamaGen route: without the e2m3 names
+Q4_GRANULE = STREAMS[1].granule   # K granule of the MXFP4 stream (ops.pack_weight_q4), and of the e2m3 stream
+Q4_MAX_ROWS, Q6_MAX_ROWS = STREAMS[1].max_rows, STREAMS[2].max_rows          # kernels G1q4 / G1sq4 and G1q6 / G1sq6 have no wide form
 HEAD_CFG = (1024, 4, True)         # G1 launch shape of the output head: (split-K chunk, column tiles per workgroup, step-major)
 # vocabularies whose image window is tens of thousands of columns (Emu3: 32768 of 184622): two K chunks, so that K2 sums two planes per
 # column instead of four, eight tiles per workgroup; Emu3 4.65 -> 4.62 ms per step (bench.py, SJD_HEAD_CFG sweep, one box)
@@ -127,7 +155,6 @@ LLAMAGEN_QUANT_SETS = {
     (True, 128): (dict(qkv=(1152, 4, False), o=(512, 4, False), gate_up=(1152, 8, False), down=(1152, 4, True)), (1600, 4, True)),
     (True, 256): (dict(qkv=(1152, 4, False), o=(512, 4, True), gate_up=(1152, 8, True), down=(1152, 4, True)), (1600, 4, True)),
 }
-QUANT_WEIGHTS = ("e4m3", "e4m3_as_bf16") + Q4_WEIGHTS
 # LlamaGenBackbone.enable_fused(compress=True): the LOSSLESS 12-bit stream (ops.pack_weight_z, kernels G1z / G1sz) for the four projections and the output
 # head, up to Z_MAX_ROWS rows -- there is no key for 256.  UNTUNED: the 16-bit sets above with every chunk capped at Z_MAX_KC (none of them reaches it, so
 # today these ARE the 16-bit shapes, which makes the two streams comparable launch for launch); no launch-shape sweep was run on the 12-bit kernels at
@@ -218,13 +245,11 @@ def default_shapes(dtype, g1_given, head_given, wide_hidden, gqa, compress, weig
     """(G1_CFG, HEAD_CFG) ChameleonBackbone.enable_fused packs with; *_given: the caller's (it wins); wide_hidden: 30B class; gqa: Emu3; None: the class default stays"""
     z = compress and dtype == torch.bfloat16          # the 12-bit stream
     head = head_given or (HEAD_CFG_WIDE if vocab_size >= 131072 else None)
-    if weights is not None and wide_hidden:          # (30B class: swin-norm backbones, enable_fused(swin_quant=True); at most 64 rows)
-        return g1_given or dict(G1_CFG_30B_Q4 if weights in Q4_WEIGHTS else G1_CFG_30B_Q8), head
-    if weights in Q4_WEIGHTS + Q6_WEIGHTS:          # (the 6-bit stream runs on the MXFP4 sets)
-        return g1_given or dict(G1_CFG_EMU3_Q4 if gqa else G1_CFG_Q4), head
-    if weights is not None:
-        wide = (G1_CFG_EMU3_Q8_WIDE if gqa else G1_CFG_Q8_WIDE) if (max_rows or 64) > 64 else None
-        return g1_given or dict(wide or (G1_CFG_EMU3_Q8 if gqa else G1_CFG_Q8)), head
+    s = stream_of(weights)[0]          # (None also for a name no stream has: enable_fused has refused it by now, so the 16-bit sets below are never reached with one)
+    if s is not None:          # (e2m3 at the 30B class takes the Q4 copy of G1_CFG_30B_Z where the Q8 copy used to be named: equal values, and no swin route reaches it; 30B class: swin-norm backbones, enable_fused(swin_quant=True), at most 64 rows; a stream without a wide form keeps its sets)
+        plain, emu3, big, wide, emu3_wide = s.sets
+        wide = (emu3_wide if gqa else wide) if (max_rows or 64) > 64 else None
+        return g1_given or dict(big if wide_hidden else wide or (emu3 if gqa else plain)), head
     g1 = g1_given or (dict(G1_CFG_30B_Z if z else G1_CFG_30B) if wide_hidden else dict(G1_CFG_EMU3) if gqa else dict(G1_CFG_Z) if z else None)
     return (dict(G1_CFG_EMU3_Z) if z and g1 == G1_CFG_EMU3 else g1), head          # (also when the caller named Emu3's set: the packing follows the stream)
 
@@ -278,11 +303,11 @@ def serves_rows(backbone, rows, window=1, head=False):
         limit, fp16 = getattr(backbone, "max_rows", 64), backbone.output.weight.dtype == torch.float16 and rows > Z_MAX_ROWS
         return ("fp16" if fp16 else "max_rows", limit) if rows > limit else None
     weights, packed = getattr(backbone, "weights", None), getattr(backbone, "_packed", None)
-    limit = getattr(backbone, "max_rows", 64) if weights is not None else 64
-    if weights == "e4m3" and limit < rows <= WINDOW_MAX_ROWS and window <= 32:
+    (s, twin), limit = stream_of(weights), getattr(backbone, "max_rows", 64) if weights is not None else 64
+    if s is not None and s.max_rows > 64 and not twin and limit < rows <= WINDOW_MAX_ROWS and window <= 32:
         return "max_rows", limit
-    if weights in Q4_WEIGHTS + Q6_WEIGHTS and rows > Q4_MAX_ROWS:          # (neither the 4- / 6-bit copy nor its twin was packed for more: there is no other copy to serve them)
-        return ("max_rows", Q4_MAX_ROWS) if rows <= WINDOW_MAX_ROWS and window <= 32 else ("prefill", None)
+    if s is not None and rows > s.max_rows <= 64:          # (neither a copy without a wide form nor its twin was packed for more: there is no other copy to serve them)
+        return ("max_rows", s.max_rows) if rows <= WINDOW_MAX_ROWS and window <= 32 else ("prefill", None)
     if getattr(backbone, "_gemm", None) != "sjd" or rows > WINDOW_MAX_ROWS or (rows > 64 and window > 32) or (rows > Z_MAX_ROWS and not packed):
         return "prefill", None
     if rows <= Z_MAX_ROWS:
@@ -308,5 +333,5 @@ def gateup_silu_chunked_ok(T, inter, hidden, KC, packed_q4=True):
 
 
 def packed_nbytes(w):
-    """bytes of one packed weight: a tensor (pack_weight) or a PackedZ / PackedQ8, which know their own"""
+    """bytes of one packed weight: a tensor (pack_weight) or an ops.Packed (the 12-bit stream, a row of STREAMS), which knows its own"""
     return w.numel() * w.element_size() if isinstance(w, torch.Tensor) else w.nbytes()

@@ -363,7 +363,14 @@ def pack_weight(weight, KC, step_major=False):
     return torch.cat(out).contiguous()
 
 
-class PackedZ:
+class Packed:
+    """a packed weight that is more than pack_weight's tensor: PackedZ, or a copy of a row of LS.STREAMS (which names it in `weight_stream`: see streamed)"""
+
+    def numel(self):
+        return self.N * self.K
+
+
+class PackedZ(Packed):
     """A packed weight in the 12-bit lossless stream format of kernels G1z / G1sz (see pack_weight_z): `data` uint8 [N * K * 3 / 2] (1536-byte
     record pairs in pack_weight's record order), `exc` int32 [n_chunks, N / 32, cap, 2] (per-unit base / count and exceptions).  RAW units (round 6:
     more out-of-window weights than a header holds) are zero-filled in `data`; their weights travel verbatim in `raw_data` (pack_weight's 1-KiB
@@ -378,9 +385,6 @@ class PackedZ:
         self.n_raw = 0 if raw_data is None else int(raw_index.shape[0])
         self.n_raw_pairs = 0 if raw_tiles is None else int(raw_tiles.shape[0])
         self.stats = stats or {}
-
-    def numel(self):
-        return self.N * self.K
 
     def nbytes(self):
         return self.data.numel() + self.exc.numel() * 4 + (0 if self.raw_data is None else self.raw_data.numel() * 2)
@@ -512,17 +516,14 @@ def pack_weight_z(weight, KC, step_major=False, gateup=False):
     return PackedZ(data, exc, N, K, KC, step_major, total, raw_index, raw_tiles, raw_view, stats)
 
 
-class _PackedQuant:
+class _PackedQuant(Packed):
     """what the quantised stream formats share: `data` uint8 = the records, then the scales; LOSSY -- the kernels multiply by dequant(), exactly"""
 
-    dtype = torch.bfloat16          # the activation type the kernels take (and the type of dequant())
+    dtype = torch.bfloat16          # the activation type the kernels take (and the type of dequant()); a subclass adds `weight_stream`, its row of LS.STREAMS
 
     def __init__(self, data, N, K, KC, step_major, stats=None):
         self.data, self.N, self.K, self.KC, self.step_major = data, int(N), int(K), int(KC), bool(step_major)
         self.stats = stats or {}
-
-    def numel(self):
-        return self.N * self.K
 
     def nbytes(self):
         return self.data.numel()
@@ -538,6 +539,8 @@ def _rel_rms_error(weight, dequantised):
 class PackedQ8(_PackedQuant):
     """A packed weight in the 8-bit (OCP e4m3fn) stream format of kernels G1q / G1sq (see pack_weight_q8): `data` uint8 [N * K + 4 * N] = the
     records, one byte per weight, then the fp32 column scales [N] at byte offset N * K.  LOSSY: the kernels multiply by dequant(), exactly."""
+
+    weight_stream = LS.STREAMS[0]
 
     def reads_as(self, KC):
         """can a launch with split-K chunk KC stream this buffer?  The chunk it was packed with -- or, step-major with K and both chunks multiples of
@@ -634,7 +637,7 @@ def pack_weight_q8(weight, KC, step_major=False, gateup=False):
     return PackedQ8(data, N, K, KC, step_major, stats)
 
 
-Q4_GRANULE = 128            # K granule of the MXFP4 stream: K and every chunk are whole ring trips of eight k-steps = two records = one scale dword per column
+Q4_GRANULE = LS.Q4_GRANULE  # K granule of the MXFP4 stream (128): K and every chunk are whole ring trips of eight k-steps = two records = one scale dword per column
 Q4_MIN_SCALE_EXP = -125     # 0.5 (the smallest non-zero e2m1 magnitude) * 2^-125 = 2^-126: every dequantised value is a NORMAL bf16 number or zero
 Q4_MAX_SCALE_EXP = 125      # 6 (the largest) * 2^125 is a finite bf16 number; 4 * 2^126 would not be
 _E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
@@ -745,7 +748,7 @@ class PackedQ4(_PackedBlockQuant):
     """A packed weight in the MXFP4 stream format of kernels G1q4 / G1sq4 (see pack_weight_q4): `data` uint8 [N * K / 2 + N * K / 32] = the code
     records, four bits per weight, then the e8m0 scale bytes at byte offset N * K / 2.  LOSSY: the kernels multiply by dequant(), exactly."""
 
-    REC = 1024
+    weight_stream, REC = LS.STREAMS[1], 1024
 
     @staticmethod
     def _to_records(c, T):
@@ -856,7 +859,7 @@ class PackedQ6(_PackedBlockQuant):
     """A packed weight in the 6-bit (e2m3) stream format of kernels G1q6 / G1sq6 (see pack_weight_q6): `data` uint8 [N * K * 3 / 4 + N * K / 32] = the code
     records, six bits per weight, then the e8m0 scale bytes at byte offset N * K * 3 / 4.  LOSSY: the kernels multiply by dequant(), exactly."""
 
-    REC = 1536
+    weight_stream, REC = LS.STREAMS[2], 1536
 
     @staticmethod
     def _to_records(c, T):
@@ -904,17 +907,21 @@ def _prows(M):
     return ((int(M) + 31) // 32) * 32
 
 
+def streamed(w_packed):
+    """(stream, records, dtype flag) of a weight: a copy of a row of LS.STREAMS, else (None, the weight itself, 0) -- pack_weight's tensor, or a PackedZ"""
+    s = getattr(w_packed, "weight_stream", None)
+    return (None, w_packed, 0) if s is None else (s, w_packed.data, getattr(L, s.flag))
+
+
 def skinny_gemm(x, w_packed, N, K, KC, waves=4, step_major=False):
     """x [M <= LS.WINDOW_MAX_ROWS, K] bf16/fp16 -> Partials([n_chunks, 32 * ceil(M / 32), N] fp32).  waves = column tiles per workgroup: 1..16 up to 64 rows,
-    <= 8 up to 128 rows; above that (bf16 or fp16, uncompressed packing) kernel G1w takes LS.WIDE_TILES.  A PackedQ8 weight (bf16): up to 64 rows on kernel
-    G1q (min(KC, K) <= LS.CHUNK_CAP_32ROW up to 32 rows, <= LS.CHUNK_CAP_64ROW above); 65 rows and more on kernel G1wq with LS.WIDE_TILES (not 2 at 65..96
-    rows), K and KC multiples of 32 -- the planes of the same call on pack_weight(w_packed.dequant(), KC, step_major), bit for bit.  A PackedQ4 weight
-    (bf16) likewise: up to 64 rows on kernel G1q4 (the same chunk limits), 65 rows and more on kernel G1wq4 with the same tile counts; K and KC multiples of 128.
-    A PackedQ6 weight (bf16): up to LS.Q6_MAX_ROWS = 64 rows on kernel G1q6 (the same chunk limits; K and KC multiples of 128), no form for more rows."""
+    <= 8 up to 128 rows; above that (bf16 or fp16, uncompressed packing) kernel G1w takes LS.WIDE_TILES.  A copy of a row of LS.STREAMS (bf16; K and KC
+    multiples of its granule): up to 64 rows on G1q / G1q4 / G1q6 (min(KC, K) <= LS.CHUNK_CAP_32ROW up to 32 rows, <= LS.CHUNK_CAP_64ROW above); 65 rows and more
+    on G1wq / G1wq4 with LS.WIDE_TILES (not 2 at 65..96 rows), no form there for e2m3 -- the planes of the same call on pack_weight(w_packed.dequant(), KC, step_major), bit for bit."""
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N * K
     _same_16bit_type(x, w_packed, "skinny_gemm")
-    if isinstance(w_packed, (PackedZ, PackedQ8, PackedQ4, PackedQ6)):
+    if isinstance(w_packed, Packed):
         return skinny_gemm_cols(x, w_packed, N, K, KC, 0, N, waves, step_major)
     nc = (K + KC - 1) // KC
     out = torch.empty(nc, _prows(M), N, dtype=torch.float32, device=x.device)
@@ -923,20 +930,20 @@ def skinny_gemm(x, w_packed, N, K, KC, waves=4, step_major=False):
 
 
 def prefill_gemm(x, w_packed, N, K, row_scale=None, KC=None, step_major=None):
-    """G1p: x [M, K] bf16 (any M >= 1) -> y [M, N] bf16 = round16(row_scale[m] * x @ W^T) over a packed copy as it is packed -- a PackedQ8 / PackedQ4
-    (the chunk and record order they carry) or the plain pack_weight tensor (which carries neither: pass KC and step_major).  row_scale: fp32 [M] or None;
-    it multiplies the finished fp32 sum in front of the one rounding (the folded RMSNorm of F2 / F3).  A workgroup runs LS.PREFILL_ROW_BLOCK rows x the whole
+    """G1p: x [M, K] bf16 (any M >= 1) -> y [M, N] bf16 = round16(row_scale[m] * x @ W^T) over a packed copy as it is packed -- a copy of a stream that has
+    "prefill" (LS.STREAMS: PackedQ8 / PackedQ4; the chunk and record order they carry) or the plain pack_weight tensor (which carries neither: pass KC and
+    step_major).  row_scale: fp32 [M] or None; it multiplies the finished fp32 sum in front of the one rounding (the folded RMSNorm of F2 / F3).  A workgroup runs LS.PREFILL_ROW_BLOCK rows x the whole
     of K: no split-K planes.  A quantised copy gives the bits of prefill_gemm on pack_weight(w_packed.dequant(), KC, step_major); a row's output does not
-    depend on M or on its position.  K and KC multiples of LS.Q4_GRANULE (PackedQ4) / 32, N a multiple of 32, bf16: the library refuses the rest before
+    depend on M or on its position.  K and KC multiples of the stream's granule (plain: 32), N a multiple of 32, bf16: the library refuses the rest before
     any launch ("unsupported configuration")."""
     M = x.shape[0]
-    if isinstance(w_packed, PackedQ6):
-        raise ValueError("prefill_gemm: the e2m3 stream (PackedQ6) has no prefill kernel; prefill from the 16-bit weights")
+    s, data, flag = streamed(w_packed)
+    if s is not None and "prefill" not in s.has:
+        raise ValueError(f"prefill_gemm: the {s.names[0]} stream (Packed{s.tag.upper()}) has no prefill kernel; prefill from the 16-bit weights")
     assert x.dim() == 2 and x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N * K
-    flag, data = 0, w_packed
-    if isinstance(w_packed, (PackedQ8, PackedQ4)):
+    if s is not None:
         assert (w_packed.N, w_packed.K) == (N, K) and KC in (None, w_packed.KC) and step_major in (None, w_packed.step_major)
-        flag, data, KC, step_major = (L.G1_W4_MXFP4 if isinstance(w_packed, PackedQ4) else L.G1_W8_E4M3), w_packed.data, w_packed.KC, w_packed.step_major
+        KC, step_major = w_packed.KC, w_packed.step_major
     else:
         assert isinstance(w_packed, torch.Tensor) and KC is not None and step_major is not None, "a plain packing carries neither its chunk nor its record order"
     _same_16bit_type(x, w_packed, "prefill_gemm")
@@ -992,7 +999,7 @@ _PREFETCH_SINK = {}
 def weight_prefetch(w_packed, blocks=128, nbytes=None):
     """Read `w_packed` (a G1 packed weight) on the CURRENT stream and discard it: pulls the lines into the Infinity Cache ahead of
     the G1 launch that streams them (call it on a side stream forked from the forward, see ChameleonBackbone._prefetch)."""
-    if isinstance(w_packed, (PackedZ, PackedQ8, PackedQ4, PackedQ6)):
+    if isinstance(w_packed, Packed):
         w_packed = w_packed.data
     dev = w_packed.device
     sink = _PREFETCH_SINK.get(dev)
@@ -1090,8 +1097,7 @@ def _raw_units(w_packed, gateup=False):
 
 def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_major=True):
     """G1 over the vocabulary columns [col0, col0 + n_cols) (32-aligned) of a weight packed with N_packed columns -> Partials [n_chunks, R, n_cols].
-    Row counts and `waves` per packing as skinny_gemm (PackedZ: up to LS.Z_MAX_ROWS rows; PackedQ8 / PackedQ4: up to LS.WINDOW_MAX_ROWS, kernels G1q / G1wq
-    and G1q4 / G1wq4; PackedQ6: up to LS.Q6_MAX_ROWS, kernel G1q6)."""
+    Row counts and `waves` per packing as skinny_gemm (PackedZ: up to LS.Z_MAX_ROWS rows; a row of LS.STREAMS: where it has a wide kernel)."""
     M = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == K and w_packed.numel() == N_packed * K and col0 % 32 == 0 and n_cols % 32 == 0
     nc = (K + KC - 1) // KC
@@ -1102,23 +1108,11 @@ def skinny_gemm_cols(x, w_packed, N_packed, K, KC, col0, n_cols, waves=8, step_m
                                           _dtype_code(x.dtype), N_packed, col0 // 32, _raw_units(w_packed), _stream()), "sjd_skinny_gemm_z")
         return Partials(out, nc, n_cols)
     _same_16bit_type(x, w_packed, "skinny_gemm_cols")
-    if isinstance(w_packed, PackedQ8):          # G1q: the scales ride behind the records of the same buffer
+    s, records, flag = streamed(w_packed)
+    if s is not None:          # G1q / G1q4 / G1q6 and their wide forms: the scales ride behind the records of the same buffer
         assert (w_packed.N, w_packed.step_major) == (N_packed, bool(step_major)) and w_packed.reads_as(KC)
-        L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed.data), _ptr(out), M, n_cols, K, KC, waves, int(step_major),
-                                             _dtype_code(x.dtype) | L.G1_W8_E4M3, N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols (e4m3 weights)")
-        return Partials(out, nc, n_cols)
-    if isinstance(w_packed, PackedQ4):          # G1q4 / G1wq4: the block scales ride behind the records of the same buffer
-        assert (w_packed.N, w_packed.step_major) == (N_packed, bool(step_major)) and w_packed.reads_as(KC)
-        L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed.data), _ptr(out), M, n_cols, K, KC, waves, int(step_major),
-                                             _dtype_code(x.dtype) | L.G1_W4_MXFP4, N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols (mxfp4 weights)")
-        return Partials(out, nc, n_cols)
-    if isinstance(w_packed, PackedQ6):          # G1q6: the block scales ride behind the records of the same buffer
-        assert (w_packed.N, w_packed.step_major) == (N_packed, bool(step_major)) and w_packed.reads_as(KC)
-        L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed.data), _ptr(out), M, n_cols, K, KC, waves, int(step_major),
-                                             _dtype_code(x.dtype) | L.G1_W6_E2M3, N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols (e2m3 weights)")
-        return Partials(out, nc, n_cols)
-    L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(w_packed), _ptr(out), M, n_cols, K, KC, waves, int(step_major), _dtype_code(x.dtype),
-                                         N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols")
+    L.check(L.load().sjd_skinny_gemm_cols(_ptr(x), _ptr(records), _ptr(out), M, n_cols, K, KC, waves, int(step_major), _dtype_code(x.dtype) | flag,
+                                         N_packed, col0 // 32, _stream()), "sjd_skinny_gemm_cols" + (f" ({s.names[0]} weights)" if s else ""))
     return Partials(out, nc, n_cols)
 
 
@@ -1407,8 +1401,7 @@ def silu_mul(gate_up, rows=None, dtype=None, row_norm=None):
 def gateup_silu(x, w_packed, inter, hidden, step_major=False, row_norm=None):
     """G1s: silu(r * gate(x)) * (r * up(x)) [T, inter] in ONE launch -- the gate|up projection (w_packed = pack_weight([Wg; Wu], hidden / 2,
     step_major)) with F3 as its epilogue; bit-identical to silu_mul(skinny_gemm(x, w_packed, 2 * inter, hidden, hidden / 2), row_norm=...).
-    A PackedQ4 at hidden 8192 packed with KC = 2048 (LS.gateup_silu_chunked_ok: <= 32 rows) runs the four-chunk form: bit-identical to
-    silu_mul(skinny_gemm(x, w_packed, 2 * inter, 8192, 2048), row_norm=...) on the same buffer.  A PackedQ8 / PackedQ6 has no such form (PackedQ6: kernel G1sq6, <= 32 rows, hidden in {512, 1024, 2048, 4096})."""
+    A stream that has "gateup_k4" (LS.STREAMS: PackedQ4) packed with KC = 2048 at hidden 8192 (LS.gateup_silu_chunked_ok) runs in four chunks, skinny_gemm's."""
     T = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == hidden and w_packed.numel() == 2 * inter * hidden
     y = torch.empty(T, inter, dtype=x.dtype, device=x.device)
@@ -1418,30 +1411,19 @@ def gateup_silu(x, w_packed, inter, hidden, step_major=False, row_norm=None):
         L.check(L.load().sjd_gateup_silu_z(_ptr(x), _ptr(w_packed.data), _ptr(w_packed.exc), w_packed.cap, _ptr(y), T, inter, hidden, int(step_major),
                                           _dtype_code(x.dtype), _row_norm(row_norm), _raw_units(w_packed, gateup=True), _stream()), "sjd_gateup_silu_z")
         return y
-    if isinstance(w_packed, PackedQ8):          # G1sq
+    (s, records, flag), sm = streamed(w_packed), int(step_major)
+    if s is not None:          # G1sq / G1sq4 / G1sq6
         _same_16bit_type(x, w_packed, "gateup_silu")
-        assert (w_packed.N, w_packed.KC, w_packed.step_major) == (2 * inter, hidden // 2, bool(step_major))
-        L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed.data), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype) | L.G1_W8_E4M3,
-                                        _row_norm(row_norm), _stream()), "sjd_gateup_silu (e4m3 weights)")
-        return y
-    if isinstance(w_packed, PackedQ4):          # G1sq4
-        _same_16bit_type(x, w_packed, "gateup_silu")
-        assert (w_packed.N, w_packed.step_major) == (2 * inter, bool(step_major))
-        # packed in the two K halves, or (hidden 8192: the copy skinny_gemm streams in four chunks of 2048) the chunk count goes along; the library refuses the rest
-        assert hidden % w_packed.KC == 0
-        chunks = hidden // w_packed.KC
-        sm = int(step_major) | (0 if chunks == 2 else chunks << L.G1S_CHUNKS_SHIFT)
-        L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed.data), _ptr(y), T, inter, hidden, sm, _dtype_code(x.dtype) | L.G1_W4_MXFP4,
-                                        _row_norm(row_norm), _stream()), "sjd_gateup_silu (mxfp4 weights)")
-        return y
-    if isinstance(w_packed, PackedQ6):          # G1sq6
-        _same_16bit_type(x, w_packed, "gateup_silu")
-        assert (w_packed.N, w_packed.KC, w_packed.step_major) == (2 * inter, hidden // 2, bool(step_major))
-        L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed.data), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype) | L.G1_W6_E2M3,
-                                        _row_norm(row_norm), _stream()), "sjd_gateup_silu (e2m3 weights)")
-        return y
-    L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(w_packed), _ptr(y), T, inter, hidden, int(step_major), _dtype_code(x.dtype),
-                                    _row_norm(row_norm), _stream()), "sjd_gateup_silu")
+        if "gateup_k4" in s.has:
+            assert (w_packed.N, w_packed.step_major) == (2 * inter, bool(step_major))
+            # packed in the two K halves, or (hidden 8192: the copy skinny_gemm streams in four chunks of 2048) the chunk count goes along; the library refuses the rest
+            assert hidden % w_packed.KC == 0
+            chunks = hidden // w_packed.KC
+            sm |= 0 if chunks == 2 else chunks << L.G1S_CHUNKS_SHIFT
+        else:
+            assert (w_packed.N, w_packed.KC, w_packed.step_major) == (2 * inter, hidden // 2, bool(step_major))
+    L.check(L.load().sjd_gateup_silu(_ptr(x), _ptr(records), _ptr(y), T, inter, hidden, sm, _dtype_code(x.dtype) | flag, _row_norm(row_norm), _stream()),
+            "sjd_gateup_silu" + (f" ({s.names[0]} weights)" if s else ""))
     return y
 
 
