@@ -641,7 +641,15 @@ __global__ __launch_bounds__(SJD_TPB) void k4_verify_accept(
         k4_mirror_state(state, host_mirror, params->iter_seq);
         return;
     }
-    const int scheme = params->scheme;
+    const int scheme_word = params->scheme;
+    const int scheme = SJD_SCHEME_OF(scheme_word);
+    // lenient verification (LOSSY, opt-in; include/sjd_hip.h): every draft probability this kernel reads is divided by lambda, one IEEE fp32
+    // division per element, and everything behind it is the exact rule on q' = fp32(q / lambda).  The factor is decoded once per workgroup from
+    // the blob's word (a scalar load: wave-uniform); a field of 0 or of 1.0 skips the divisions, so lambda = 1 runs the instructions it ran
+    // before behind one scalar branch each.  lambda >= 1, finite, is the host's check (sjd_amd.engine.lenience_field).
+    const uint32_t lam_bits = SJD_LENIENCE_BITS_OF(scheme_word);
+    const bool lenient = lam_bits != 0u && lam_bits != 0x3f80u;               // (integer compares: the condition stays in scalar registers)
+    const float lam = lenient ? __uint_as_float(lam_bits << 16) : 1.0f;
     // phase 1: one lane per draft; ballot + find-first-zero = longest accepted prefix
     if (threadIdx.x < 64) {
         const int i = threadIdx.x;
@@ -653,7 +661,8 @@ __global__ __launch_bounds__(SJD_TPB) void k4_verify_accept(
                 float pa = probs[(size_t)(i - 1) * V + x];
                 int qs = state->q_src[i];
                 float qd = (qs >= 0) ? prev_probs[(size_t)qs * V + x] : 1.0f;
-                float ratio = pa / qd;                       // JL:286 (NaN compares false => reject)
+                if (lenient) qd = qd / lam;                  // q'(x): an implicit one-hot draft row holds 1 / lambda at x
+                float ratio = pa / qd;                     // JL:286 (NaN compares false => reject)
                 float uu;                                    // JL:282: rs[b, i, x] of torch.rand((1, n, V)); generated in place when
                 if (params->philox_blocks > 0)               // the noise is not handed over as tensors (15 uniforms instead of n * V)
                     uu = sjd_philox_rand(params->philox_seed, params->philox_offset[1],
@@ -708,6 +717,7 @@ __global__ __launch_bounds__(SJD_TPB) void k4_verify_accept(
                     int col = c0 + j;
                     if (col >= wlo && col < whi) {
                         float qv = qrow ? qrow[col] : ((long)col == x ? 1.0f : 0.0f);
+                        if (lenient) qv = qv / lam;          // (both staging forms: this loop is the only reader of the draft row)
                         float d = prow[col] - qv;
                         d = d > 0.0f ? d : 0.0f;
                         if (!rule_allows(rule, col)) d = 0.0f;

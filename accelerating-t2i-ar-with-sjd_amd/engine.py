@@ -81,6 +81,43 @@ class SJDConfig:
     #                                      and draws nothing (JL:127-129); the verify step's uniform and residual draws stay
     noise_device: Optional[str] = None   # None: the engine's device (what the reference does on a GPU);  "cpu": draw the noise
     #                                      from a CPU generator and upload it -- replays the reference's CPU run bit-exactly
+    lenience: float = 1.0                # LOSSY, off by default: the verify step accepts a draft with min(1, lenience * p / q) and resamples from
+    #                                      norm(max(p - q / lenience, 0)) (K4 on q' = fp32(q / lenience)).  >= 1, finite, exactly a
+    #                                      bf16 value (it travels as 16 bits of sjd_iter_params.scheme); speculative_jacobi only
+
+
+LENIENCE_SHIFT = 16        # sjd_iter_params.scheme: bits 0-7 the scheme, bits 16-31 the bf16 bits of the lenience factor (include/sjd_hip.h)
+
+
+def lenience_field(lenience, scheme_name="speculative_jacobi"):
+    """SJDConfig.lenience -> what goes into bits 16-31 of sjd_iter_params.scheme, already shifted; 0 for 1.0, so a blob written with the default is
+    byte for byte one written without the field.  Refuses (ValueError) a factor that is not finite, below 1, not exactly a bf16 value -- never
+    rounded silently -- or given with the plain Jacobi scheme, whose verify step has no p / q to relax."""
+    try:
+        lam = float(lenience)
+    except (TypeError, ValueError):
+        raise ValueError(f"lenience must be a number >= 1, but got {lenience!r}") from None
+    if not np.isfinite(lam) or lam < 1.0:
+        raise ValueError(f"lenience must be finite and >= 1 (1 is the exact verify rule), but got {lenience!r}")
+    as_float = lambda b: float(np.uint32(b).view(np.float32))
+    if lam > as_float(0x7f7f0000):
+        raise ValueError(f"lenience must be finite as a bf16 value (at most {as_float(0x7f7f0000)!r}), but got {lenience!r}")
+    bits = int(np.float32(lam).view(np.uint32))
+    if as_float(bits) != lam or bits & 0xffff:
+        below = (bits - 1 if as_float(bits) > lam else bits) & ~0xffff      # (positive values: dropping the low 16 bits rounds down)
+        lo, hi = as_float(below), as_float(below + 0x10000)
+        raise ValueError(f"lenience {lenience!r} is not exactly a bf16 value (it travels as the upper 16 bits of its fp32 pattern): "
+                         f"the two neighbours that are: {lo!r} and {hi!r}")
+    if lam != 1.0 and scheme_name == "jacobi":
+        raise ValueError(f"lenience={lenience!r} needs prefix_token_sampler_scheme='speculative_jacobi': plain Jacobi verifies by token equality, "
+                         "there is no acceptance probability to relax")
+    return 0 if lam == 1.0 else (bits >> 16) << LENIENCE_SHIFT
+
+
+def lenience_of(scheme_word):
+    """the lenience factor a sjd_iter_params.scheme word carries (a field of 0 is 1.0)"""
+    bits = (int(scheme_word) & 0xffffffff) >> LENIENCE_SHIFT
+    return float(np.uint32(bits << 16).view(np.float32)) if bits else 1.0
 
 
 @dataclass
@@ -195,6 +232,8 @@ class WindowLauncher:
     use_graph, hook, _rule_bytes, _rule_keep.  `s` below is whatever holds one prompt's buffers (params, state, probs, zero_state, scratch,
     tokens_ptr, amax_ptr, noise, rs, noise2): the solo engine itself, or a slot of the batch engine."""
 
+    _lenience_bits = 0                    # bits 16-31 of the blobs' scheme word (lenience_field); set per decode by _check_config
+
     def reset_graphs(self):
         """Call after the backbone's cache / weights were re-allocated."""
         self._graphs, self._graph_logits, self._eager_runs = {}, {}, {}
@@ -296,7 +335,7 @@ class WindowLauncher:
         """one prompt's sjd_iter_params for one iteration (host side; the caller uploads).  philox = (blocks, seed, off0, off1, off2): K2 / K4
         generate the multinomial / rand / residual noise torch would have drawn from a device generator at that state (None: tensors)."""
         p = blob.view
-        p.n_rows, p.kv_len, p.use_cfg, p.scheme, p.n_fresh = n, kv_len, int(use_cfg), scheme, len(fresh)
+        p.n_rows, p.kv_len, p.use_cfg, p.scheme, p.n_fresh = n, kv_len, int(use_cfg), scheme | self._lenience_bits, len(fresh)
         if philox is None:
             p.philox_blocks = 0
         else:
@@ -325,6 +364,9 @@ class WindowLauncher:
             raise ValueError(f"prefix_token_sampler_scheme: {cfg.prefix_token_sampler_scheme}")   # JL:1048
         if cfg.max_num_new_tokens > self.Lmax:
             raise ValueError("max_num_new_tokens exceeds the engine's max_window")
+        # the lenience factor of this decode: _fill_blob writes it beside the scheme into every blob, which is all a captured graph needs -- K4
+        # reads it from the blob, so no graph key carries it
+        self._lenience_bits = lenience_field(getattr(cfg, "lenience", 1.0), cfg.prefix_token_sampler_scheme)
         for g in grammars:
             warn_no_grid(cfg, g)
 

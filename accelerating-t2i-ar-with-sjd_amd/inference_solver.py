@@ -14,6 +14,7 @@ import torch
 
 from . import backbones as BB
 from . import ops
+from .engine import lenience_field
 
 
 IMAGE_START, IMAGE_END, IMAGE_NEW_LINE, GRID_BASE = 8197, 8196, 8803, 8804       # <racm3:break>, <eoss>, <reserved08799>, <reserved08800> + 4
@@ -48,8 +49,10 @@ class FlexARInferenceSolver:
 
     def __init__(self, model_path=None, precision="bf16", target_size=512, cache_dir=None, device="cpu", tokenizer=None,
                  model: Optional[BB.ChameleonBackbone] = None, item_processor=None, fused=True, gemm="sjd", vq_model=None, bpe_to_vq=None, weights=None, swin_quant=False,
-                 release_16bit=False):
-        """weights: passed to ChameleonBackbone.enable_fused: the name of a row of launch_shapes.STREAMS or its "_as_bf16" twin -- the window projections
+                 release_16bit=False, lenience=1.0):
+        """lenience: SJDConfig.lenience of every SJD decode of this solver once renew_pipeline_sampler made it one -- LOSSY, off by default (1.0 is
+        the exact verify rule); refused at once unless it is a finite bf16 value >= 1.
+        weights: passed to ChameleonBackbone.enable_fused: the name of a row of launch_shapes.STREAMS or its "_as_bf16" twin -- the window projections
         streamed from quantised weights, lossy; the table says which streams go with release_16bit and swin_quant; the prompt
         prefill keeps the 16-bit parameters unless release_16bit=True goes along, which runs the prefill on the packed copy as well and releases the 16-bit
         layer matrices; see there).  swin_quant=True goes along: a swin-norm backbone (30B class) is quantised too -- lossy and
@@ -58,6 +61,8 @@ class FlexARInferenceSolver:
         dropped) -- with it decode_image / decode_ids / generate_ids(decode=True) return PIL images without the reference's item processor.
         bpe_to_vq: the BPE id -> VQ code mapping of the image span, a length-V int64 table or a callable on an int64 tensor; default
         default_bpe_to_vq (id - 4 over 4..8195)."""
+        lenience_field(lenience)
+        self.lenience = float(lenience)
         self.dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[precision]
         self.device = torch.device(device)
         self.target_size = target_size

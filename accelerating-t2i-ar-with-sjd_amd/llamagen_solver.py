@@ -5,6 +5,7 @@ import torch
 from torch.nn import functional as F
 
 from . import launch_shapes as LS
+from .engine import lenience_field
 from .scheduler.logit_processor_3dim import TopKLogitsWarper, TopPLogitsWarper3d
 
 
@@ -170,8 +171,15 @@ def renew_llamagen(model_class):
 class LlamaGenSolver:
     """reference LS:349-470"""
 
-    def __init__(self, model, image_top_k, image_top_p, noise_device=None, prompts_per_forward=None):
+    def __init__(self, model, image_top_k, image_top_p, noise_device=None, prompts_per_forward=None, lenience=1.0):
         self.model = model
+        # LOSSY, off by default: SJDConfig.lenience of every generate() -- the verify step accepts a draft with min(1, lenience * p / q).  1.0 is
+        # the exact rule (a model renewed with a lenience of its own then keeps that); anything else is refused here unless it is a finite bf16
+        # value >= 1 on the speculative scheme
+        if lenience == 1.0:
+            lenience = getattr(model, "lenience", 1.0)
+        lenience_field(lenience, getattr(model, "prefix_token_sampler_scheme", "speculative_jacobi"))
+        self.lenience = float(lenience)
         # generate() with several prompts: how many share one window forward (None: as many as the kernels' row limit allows)
         self.prompts_per_forward = prompts_per_forward
         self.image_top_k = image_top_k
@@ -242,6 +250,7 @@ class LlamaGenSolver:
         else:
             model._sjd_key_start = None
         model.sjd_noise_device = self.noise_device
+        model.lenience = self.lenience
         next_token, T = self.prefill(cond_combined, cfg_scale, **sampling_kwargs)
         from transformers import GenerationConfig
         generation_config = GenerationConfig(max_new_tokens=T + max_new_tokens, max_length=T + max_new_tokens, temperature=1.0,
@@ -321,6 +330,7 @@ class LlamaGenSolver:
             e.reset_graphs()
         model._sjd_key_start = None
         model.sjd_noise_device = None
+        model.lenience = self.lenience
         specs = []
         for j in range(N):
             c = cond[j:j + 1]

@@ -104,8 +104,9 @@ def renew_pipeline_anole(model_class):
     return JacobiPipeline
 
 
-def renew_pipeline_sampler(pipe_line, processor, **kwargs):
-    """reference JA:318-330"""
+def renew_pipeline_sampler(pipe_line, processor, lenience=1.0, **kwargs):
+    """reference JA:318-330.  lenience: SJDConfig.lenience of every decode of the renewed model (LOSSY; 1.0, the default, is the exact verify rule)."""
+    kwargs["lenience"] = lenience
     if hasattr(pipe_line, "model"):
         pipe_line.model.__class__ = renew_backbone(pipe_line.model.__class__)
         if not hasattr(pipe_line.model, "image_seq_length") and processor is not None:

@@ -91,8 +91,10 @@ def renew_sampler_forward(model_class):
     return JacobiModel
 
 
-def renew_solver(model, processor, vq_model=None, **jacobi_param_dict):
-    """reference JE:370-412 -> (model, LogitsProcessorList).  vq_model: a sjd_amd.detokenizers.Emu3VisionVQ for model.decode_image_tokens."""
+def renew_solver(model, processor, vq_model=None, lenience=1.0, **jacobi_param_dict):
+    """reference JE:370-412 -> (model, LogitsProcessorList).  vq_model: a sjd_amd.detokenizers.Emu3VisionVQ for model.decode_image_tokens.
+    lenience: SJDConfig.lenience of every decode of the renewed model (LOSSY; 1.0, the default, is the exact verify rule)."""
+    jacobi_param_dict["lenience"] = lenience
     h = jacobi_param_dict.pop('h', None)
     w = jacobi_param_dict.pop('w', None)
     jacobi_param_dict.pop('neg_inputs', None)

@@ -24,7 +24,7 @@ import torch
 
 from .. import _lib as L
 from .. import ops
-from ..engine import SJDConfig, SJDEngine, WindowSpec
+from ..engine import SJDConfig, SJDEngine, WindowSpec, lenience_field
 from .logit_processor_3dim import (MultiTokensInterleavedTopKLogitsWarper, MultiTokensVLLogitsProcessor,
                                    get_double_cfg_input_ids, grammar_from_processors)
 
@@ -258,7 +258,7 @@ def renew_sampler(model_class):
         def _init_new_params(self, jacobi_loop_interval_l=1, jacobi_loop_interval_r=(768 // 16) ** 2 + 768 // 16,
                              max_num_new_tokens=16, guidance_scale=3.0, seed=42, multi_token_init_scheme='random',
                              do_cfg=True, prefix_token_sampler_scheme='speculative_jacobi', use_chameleon_tokenizer=True,
-                             _init_doubled_attn_mask_cfg=False, **kwargs):
+                             _init_doubled_attn_mask_cfg=False, lenience=1.0, **kwargs):
             # reference JL:865-910.  img_vocab = Chameleon image ids 4..8195 for every model family (SURVEY.md
             # Appendix D); the reference reads them from ./ckpts/chameleon/tokenizer/text_tokenizer.json
             self.img_vocab_range = (4, 8196)
@@ -271,6 +271,11 @@ def renew_sampler(model_class):
             self.multi_token_init_scheme = multi_token_init_scheme
             self.do_cfg = do_cfg
             self.prefix_token_sampler_scheme = prefix_token_sampler_scheme
+            # LOSSY, off by default (1.0): the verify step accepts with min(1, lenience * p / q) (SJDConfig.lenience); refused here already
+            # when it is not a finite bf16 value >= 1 or comes with the plain Jacobi scheme
+            if prefix_token_sampler_scheme in ("speculative_jacobi", "jacobi"):
+                lenience_field(lenience, prefix_token_sampler_scheme)
+            self.lenience = float(lenience)
             self._init_doubled_attn_mask_cfg = _init_doubled_attn_mask_cfg
             self._sjd_engines = {}
 
@@ -339,7 +344,7 @@ def renew_sampler(model_class):
                             do_cfg=do_cfg, prefix_token_sampler_scheme=self.prefix_token_sampler_scheme,
                             multi_token_init_scheme=self.multi_token_init_scheme, img_vocab_lo=self.img_vocab_range[0],
                             img_vocab_n=self.img_vocab_range[1] - self.img_vocab_range[0], max_length=max_len, eos_token_ids=eos,
-                            noise_device=getattr(self, "sjd_noise_device", None), do_sample=do_sample)
+                            noise_device=getattr(self, "sjd_noise_device", None), do_sample=do_sample, lenience=getattr(self, "lenience", 1.0))
             B = 2 if do_cfg else 1
             if max_len >= (1 << 30):
                 # no MaxLength criterion: bound the cache by the model's own context instead of asking for ~1e9 rows
@@ -403,7 +408,7 @@ def renew_sampler(model_class):
                             do_cfg=do_cfg, prefix_token_sampler_scheme=self.prefix_token_sampler_scheme,
                             multi_token_init_scheme=self.multi_token_init_scheme, img_vocab_lo=self.img_vocab_range[0],
                             img_vocab_n=self.img_vocab_range[1] - self.img_vocab_range[0], max_length=max_len, eos_token_ids=eos,
-                            do_sample=do_sample)
+                            do_sample=do_sample, lenience=getattr(self, "lenience", 1.0))
             B = 2 if do_cfg else 1
             need = specs[0].kv_base + max_len + self.max_num_new_tokens + 32
             if self.cache is None or self.cache.k.shape[1] != B * n_slots or self.cache.s_max < need:
@@ -477,8 +482,12 @@ def renew_pipeline(model_class):
     return JacobiPipeline
 
 
-def renew_pipeline_sampler(pipe_line, **kwargs):
-    """reference JL:1340-1346"""
+def renew_pipeline_sampler(pipe_line, lenience=1.0, **kwargs):
+    """reference JL:1340-1346.  lenience: SJDConfig.lenience of every decode of the renewed model (LOSSY; 1.0, the default, is the exact verify
+    rule); a solver built with FlexARInferenceSolver(lenience=...) keeps its own value unless this call names another."""
+    if lenience == 1.0:
+        lenience = getattr(pipe_line, "lenience", 1.0)
+    kwargs["lenience"] = pipe_line.lenience = lenience
     pipe_line.__class__ = renew_pipeline(pipe_line.__class__)
     pipe_line._init_new_params(**kwargs)
     pipe_line.model.__class__ = renew_sampler(pipe_line.model.__class__)

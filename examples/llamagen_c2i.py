@@ -46,8 +46,16 @@ def parse_args(argv=None):
     ap.add_argument("--compress", action="store_true",
                     help="with --fused: stream the layer projections and the output head from the LOSSLESS 12-bit copy (about 0.78 of the bytes, the same tokens; "
                          "at most 128 window rows per forward)")
+    ap.add_argument("--lenience", type=float, default=1.0,
+                    help="accept a draft with min(1, LENIENCE * p / q) in the verify step (LOSSY, opt-in; 1 is the exact rule; >= 1 and exactly a bf16 value, "
+                         "e.g. 1.25, 1.5, 2, 4; more tokens per step, image quality on a real checkpoint is not measured)")
     ap.add_argument("--out", default="sample.png")
     a = ap.parse_args(argv)
+    try:
+        from sjd_amd.engine import lenience_field
+        lenience_field(a.lenience)
+    except ValueError as e:
+        ap.error(f"--lenience: {e}")
     if a.weights and not a.fused:
         ap.error("--weights packs the weights of the fused HIP path: add --fused")
     if a.compress and not a.fused:
@@ -113,7 +121,9 @@ def main():
     gpt.__class__ = renew_sampler(gpt.__class__)
     gpt._init_new_params(**jac)
 
-    solver = LlamaGenSolver(model=gpt, image_top_k=a.top_k, image_top_p=a.top_p, prompts_per_forward=a.prompts_per_forward)
+    solver = LlamaGenSolver(model=gpt, image_top_k=a.top_k, image_top_p=a.top_p, prompts_per_forward=a.prompts_per_forward, lenience=a.lenience)
+    if a.lenience != 1.0:
+        print(f"--lenience {a.lenience}: LOSSY verify step, drafts accepted with min(1, {a.lenience} * p / q)")
     torch.manual_seed(a.seed)
     t0 = time.time()
     index_sample, images = solver.generate(torch.tensor(a.class_id, device=dev), latent ** 2, None, cfg_scale=a.cfg_scale, temperature=1.0,

@@ -151,7 +151,12 @@ typedef struct sjd_iter_params {
     int32_t n_rows;                 /* window length n of this iteration (1..SJD_MAX_WINDOW) */
     int32_t kv_len;                 /* cache rows already valid before this window */
     int32_t use_cfg;                /* 1: z = g*(c-u)+u ; 0: z = c  (check_is_force_no_cfg, JL:70-80) */
-    int32_t scheme;                 /* 0: speculative_jacobi ; 1: jacobi */
+    int32_t scheme;                 /* bits 0-7 (SJD_SCHEME_OF): 0: speculative_jacobi ; 1: jacobi.  Bits 16-31 (SJD_LENIENCE_BITS_OF): the
+                                       lenience factor lambda >= 1 of the verify step as the UPPER HALF of its fp32 pattern (its bf16 bits); 0
+                                       means 1.0, so a blob that never sets the field is the exact rule.  LOSSY and opt-in: sjd_verify_accept*
+                                       on (p, q, lambda) is by definition the exact rule on (p, q') with q' = fp32(q / lambda) per element --
+                                       accept u < min(1, p(x) / q'(x)), residual norm(max(p - q', 0)), an implicit one-hot draft row 1 / lambda
+                                       at x.  Scheme 1 ignores the field.  Every other reader takes SJD_SCHEME_OF only. */
     int32_t n_fresh;                /* trailing window rows filled with fresh random ids */
     int32_t batch_rows;             /* several prompts per launch: 0 = this blob governs every batch row; > 0 = `params` points at a
                                        contiguous ARRAY of blobs and blob i governs batch rows [i*batch_rows, (i+1)*batch_rows) of K1 /
@@ -169,6 +174,8 @@ typedef struct sjd_iter_params {
     sjd_row_rule rules[SJD_MAX_WINDOW];           /* rules of the sampling call, row j */
     sjd_row_rule resid_rules[SJD_MAX_WINDOW];     /* rule of the residual call if rejection happens at i=j+1 */
 } sjd_iter_params;
+#define SJD_SCHEME_OF(word) ((int)((uint32_t)(word) & 0xffu))
+#define SJD_LENIENCE_BITS_OF(word) ((uint32_t)(word) >> 16)        /* bf16 bits of lambda; 0 = 1.0 (0x3f80 is 1.0 as well) */
 
 #if defined(__HIPCC__)
 /* blob that governs batch row b (see batch_rows) */

@@ -146,7 +146,7 @@ def load_llamagen(cache_dir="./ckpts", model_name="llamagen", target_size=512, s
     if t5_model is None and gpt_model.model_type == 't2i':
         t5_model = T5Embedder(device=device, local_cache=True, cache_dir=os.path.join(cache_dir, backbone_params['t5_path']),
                               dir_or_name=backbone_params['t5_model_type'], torch_dtype=dtype, model_max_length=backbone_params['t5_feature_max_len'])
-    model = LlamaGenSolver(model=gpt_model, image_top_k=image_top_k, image_top_p=image_top_p)
+    model = LlamaGenSolver(model=gpt_model, image_top_k=image_top_k, image_top_p=image_top_p, lenience=kwargs.get("lenience", 1.0))
     return dict(model=model, gpt_model=gpt_model, t5_model=t5_model, vq_model=vq_model, vq_params=vq_params, backbone_params=backbone_params,
                 latent_size=latent_size, guidance_scale=guidance_scale, temperature=temperature, image_top_k=image_top_k, image_top_p=image_top_p)
 
