@@ -500,8 +500,8 @@ __device__ __forceinline__ float block_kth_largest_spread(Visit &&visit, int k, 
 // Returns K* = the largest uint32 key with canonical_sum{ p_i : w_i > 0, key(w_i) <= K* } <= thr (32 canonical sums).
 // Ties at the cut: every entry whose weight EQUALS the threshold weight is removed or kept together (the set is a function of the values
 // only), whereas the reference's sorted cumulative sum (logit_processor_3dim.py:406-419) splits a run of equal values by sort order --
-// which torch.sort does not define for equal keys.  With fp32 softmax outputs a tie exactly at the cut is a measure-zero event; the oracle
-// restates THIS rule (oracle/sjd_oracle.c) and is pinned against the reference's golden vectors, none of which hits one.
+// which torch.sort does not define for equal keys.  Ties at the cut DO occur: the head's logits are rounded to 16 bits, equal logits give equal
+// weights (tests/test_gpu_sampling_edges.py holds this rule on such rows); the oracle restates THIS rule and is pinned against golden vectors.
 __device__ unsigned block_top_p_cut_key(const float *w, int lo, int hi, float S, float thr, SjdShared &sh, int base = 0)
 {
     unsigned K = 0;

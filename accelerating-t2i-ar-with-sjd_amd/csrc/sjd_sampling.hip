@@ -919,7 +919,7 @@ __global__ void k5_reguess(const sjd_iter_params *__restrict__ params, sjd_state
 
 // dynamic LDS (in floats) K2 / K4 ask for to stage a row's window: what `cols` columns need, capped at what a CU has left beside SjdShared
 // (150 KiB: windows of up to 38400 columns -- Emu3's 32768 visual tokens fit, a whole text vocabulary does not and keeps the global staging)
-#define SJD_DRAW_LIST 2304          // entries of the draw list K2 / K4 ask LDS room for behind a staged row (top-k 2000 / 2048 + ties)
+#define SJD_DRAW_LIST 2304          // entries of the draw list K2 / K4 ask LDS room for behind a staged row (top-k 2000 / 2048 + 256 tied scores; the kept count is data-dependent: more fall to the sparse loop)
 static int sjd_stage_lds_floats(long cols)
 {
     const long cap = 150 * 1024 / 4;
