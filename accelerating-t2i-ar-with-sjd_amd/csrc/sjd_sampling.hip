@@ -211,7 +211,8 @@ __global__ __launch_bounds__(SJD_TPB) void k2_logits_to_probs_sample(
     }
     const int n_rows_dev = params->n_rows, use_cfg_dev = params->use_cfg;
     const uint32_t ph_blocks = (uint32_t)params->philox_blocks;
-    const uint64_t ph_seed = params->philox_seed, ph_off = params->philox_offset[0];
+    const uint64_t ph_seed = params->philox_seed, ph_off0 = params->philox_offset[0], ph_stride = params->philox_offset[1];
+    const int kv_len_dev = params->kv_len, scheme_dev = SJD_SCHEME_OF(params->scheme);      // (scheme 2: the row's noise is keyed by its position, below)
     // what this row of probs_out is known to hold: zeros outside [zlo, zhi) (zlo < 0: unknown) -- see sjd_head_partials::zero_state
     int *zst = (PART && hp.zero_state) ? hp.zero_state + 2 * (row < SJD_MAX_WINDOW ? row : 0) : nullptr;
     const int *zp = zst ? zst : reinterpret_cast<const int *>(params);        // (unconditional loads, as above)
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(SJD_TPB) void k2_logits_to_probs_sample(
     float rc = 1.0f, ru = 1.0f;
     // (the compiler sinks the rule's loads below the early return otherwise: a trip of their own; these empty statements need the values HERE,
     //  where the wait for n_rows stands anyway)
-    asm volatile("" :: "s"(zl), "s"(zh), "s"(use_cfg_dev), "s"(ph_blocks), "s"(ph_seed), "s"(ph_off), "s"(n_rows_dev),
+    asm volatile("" :: "s"(zl), "s"(zh), "s"(use_cfg_dev), "s"(ph_blocks), "s"(ph_seed), "s"(ph_off0), "s"(ph_stride), "s"(kv_len_dev), "s"(scheme_dev), "s"(n_rows_dev),
                  "s"(rule.n_ranges), "s"(rule.forced), "s"(rule.temperature), "s"(sv[0]), "s"(sv[1]), "s"(sv[2]), "s"(sv[3]), "s"(sv[4]),
                  "s"(sv[5]), "s"(sv[6]), "s"(sv[7]), "s"(sw[0]), "s"(sw[1]), "s"(sw[2]), "s"(sw[3]), "s"(sw[4]), "s"(sw[5]), "s"(sw[6]), "s"(sw[7]));
     if constexpr (SLOTS) asm volatile("" :: "s"(guidance));                 // (the slot's scale: wanted here too, with the same wait)
@@ -239,7 +240,14 @@ __global__ __launch_bounds__(SJD_TPB) void k2_logits_to_probs_sample(
     const float *e = noise + (size_t)row * V;
     // the Exp(1) noise of the draw: read from `noise`, or (params->philox_blocks > 0) generated here -- the elements torch's
     // empty(n_rows, V).exponential_(generator=g) would hold, for the columns that carry probability mass only (sjd_philox.h)
-    const uint32_t ph_T = ph_blocks ? sjd_philox_threads((uint64_t)n_rows_dev * (uint64_t)V, ph_blocks) : 0u;
+    // Scheme 2 (coupled Jacobi, include/sjd_hip.h): the row's noise belongs to its POSITION t = kv_len + row, not to this launch -- the elements of
+    // a [1, V] exponential_ at offset philox_offset[0] + t * philox_offset[1] (the generator form of K4's residual row: element = column), so the
+    // draw at a position is a function of that position's distribution alone, whichever window, iteration or batch the row stands in.  All of
+    // it is uniform for the workgroup (row = blockIdx.x): three scalar selects in front of the passes, nothing in the column loops.
+    const bool keyed = scheme_dev == 2;
+    const uint64_t ph_off = keyed ? ph_off0 + (uint64_t)(kv_len_dev + row) * ph_stride : ph_off0;
+    const uint64_t ph_e0 = keyed ? 0ull : (uint64_t)row * (uint64_t)V;           // element of column 0 of this row in the generated tensor
+    const uint32_t ph_T = ph_blocks ? sjd_philox_threads(keyed ? (uint64_t)V : (uint64_t)n_rows_dev * (uint64_t)V, ph_blocks) : 0u;
 
     if (rule.forced >= 0) {   // forced EOL / end-of-image row: softmax of (-inf,...,0,...,-inf) (LP:39-41)
         // (with a known state only the hull of the old window and the forced column needs rewriting)
@@ -486,7 +494,7 @@ __global__ __launch_bounds__(SJD_TPB) void k2_logits_to_probs_sample(
         unsigned long long cand = pack_vi(pv, col);
         best_p = cand > best_p ? cand : best_p;
         float r;
-        if (ph_blocks) r = pv > 0.0f ? pv / sjd_philox_exponential(ph_seed, ph_off, ph_T, (uint64_t)row * (uint64_t)V + (uint64_t)col) : 0.0f;   // (0 / e == 0: e is finite and > 0)
+        if (ph_blocks) r = pv > 0.0f ? pv / sjd_philox_exponential(ph_seed, ph_off, ph_T, ph_e0 + (uint64_t)col) : 0.0f;   // (0 / e == 0: e is finite and > 0)
         else r = pv / e[col];
         cand = pack_vi(r, col);
         best = cand > best ? cand : best;
@@ -560,7 +568,7 @@ __global__ __launch_bounds__(SJD_TPB) void k2_logits_to_probs_sample(
                 const unsigned long long en = klist[i];
                 const int col = (int)(unsigned)(en & 0xffffffffull);
                 const float pv = __uint_as_float((unsigned)(en >> 32));
-                const unsigned long long cand = pack_vi(pv / sjd_philox_exponential(ph_seed, ph_off, ph_T, (uint64_t)row * (uint64_t)V + (uint64_t)col), col);
+                const unsigned long long cand = pack_vi(pv / sjd_philox_exponential(ph_seed, ph_off, ph_T, ph_e0 + (uint64_t)col), col);
                 best = cand > best ? cand : best;
             }
         } else {                                    // (more entries with mass than the list holds -- rows without a top-k: the sparse form)
@@ -571,7 +579,7 @@ __global__ __launch_bounds__(SJD_TPB) void k2_logits_to_probs_sample(
                     if (col >= wlo && col < whi) {
                         const float pv = p[col];
                         if (pv > 0.0f) {
-                            const unsigned long long cand = pack_vi(pv / sjd_philox_exponential(ph_seed, ph_off, ph_T, (uint64_t)row * (uint64_t)V + (uint64_t)col), col);
+                            const unsigned long long cand = pack_vi(pv / sjd_philox_exponential(ph_seed, ph_off, ph_T, ph_e0 + (uint64_t)col), col);
                             best = cand > best ? cand : best;
                         }
                     }

@@ -65,7 +65,10 @@ class SJDConfig:
     guidance_scale: float = 3.0
     seed: Optional[int] = 42
     do_cfg: bool = True
-    prefix_token_sampler_scheme: str = "speculative_jacobi"
+    prefix_token_sampler_scheme: str = "speculative_jacobi"     # or "jacobi", or "coupled_jacobi": plain Jacobi whose sampling noise is keyed
+    #                                           by the token's POSITION (K2 scheme 2): lossless, and the sequence a seed gives
+    #                                           does not depend on the draft window, on acceptance or on the prompts sharing the forward.
+    #                                           Needs in-kernel noise (noise_device=None) and lenience 1
     multi_token_init_scheme: str = "random"   # 'repeat_horizon' / 'sample_horizon': PARITY UNPINNED -- the reference raises IndexError at
     #                                           JL:577 for both, so no reference run exists; implemented from the evident intent
     #                                           (spatial init).  Differences a fixed upstream might show: 'sample_horizon' draws its
@@ -84,6 +87,30 @@ class SJDConfig:
     lenience: float = 1.0                # LOSSY, off by default: the verify step accepts a draft with min(1, lenience * p / q) and resamples from
     #                                      norm(max(p - q / lenience, 0)) (K4 on q' = fp32(q / lenience)).  >= 1, finite, exactly a
     #                                      bf16 value (it travels as 16 bits of sjd_iter_params.scheme); speculative_jacobi only
+
+
+# the verify schemes by name -> bits 0-7 of sjd_iter_params.scheme (SJD_SCHEME_OF, include/sjd_hip.h)
+SCHEME_CODES = {"speculative_jacobi": 0, "jacobi": 1, "coupled_jacobi": 2}
+COUPLED = SCHEME_CODES["coupled_jacobi"]
+
+
+def scheme_code(name):
+    """prefix_token_sampler_scheme -> its code in the blob; anything else is refused as the reference does (JL:1048)"""
+    if name not in SCHEME_CODES:
+        raise ValueError(f"prefix_token_sampler_scheme: {name}")
+    return SCHEME_CODES[name]
+
+
+def check_coupled(scheme_name, noise_device):
+    """what the coupled scheme cannot be combined with, refused before anything is launched or assigned: its noise exists only inside K2 (a row's
+    noise is addressed by position, not drawn as this launch's tensor), so noise that is drawn on the host and handed over as tensors has no
+    meaning for it; and its verify step is token equality, which has no acceptance probability to relax (lenience_field says that)."""
+    if scheme_name != "coupled_jacobi":
+        return
+    nd = noise_device
+    if nd is not None and torch.device(nd).type == "cpu":
+        raise ValueError(f"prefix_token_sampler_scheme='coupled_jacobi' needs in-kernel noise: K2 generates a row's noise from the row's position, "
+                         f"but noise_device={nd!r} draws the noise on the host and hands it over as tensors; leave noise_device=None")
 
 
 LENIENCE_SHIFT = 16        # sjd_iter_params.scheme: bits 0-7 the scheme, bits 16-31 the bf16 bits of the lenience factor (include/sjd_hip.h)
@@ -110,6 +137,9 @@ def lenience_field(lenience, scheme_name="speculative_jacobi"):
                          f"the two neighbours that are: {lo!r} and {hi!r}")
     if lam != 1.0 and scheme_name == "jacobi":
         raise ValueError(f"lenience={lenience!r} needs prefix_token_sampler_scheme='speculative_jacobi': plain Jacobi verifies by token equality, "
+                         "there is no acceptance probability to relax")
+    if lam != 1.0 and scheme_name == "coupled_jacobi":
+        raise ValueError(f"lenience={lenience!r} needs prefix_token_sampler_scheme='speculative_jacobi': coupled Jacobi verifies by token equality, "
                          "there is no acceptance probability to relax")
     return 0 if lam == 1.0 else (bits >> 16) << LENIENCE_SHIFT
 
@@ -360,8 +390,8 @@ class WindowLauncher:
         if cfg.multi_token_init_scheme not in ("random", "repeat_horizon", "sample_horizon"):
             # JL:554-560, 592: anything else (incl. the 'vertical' variants) asserts in the reference
             raise ValueError(f"multi_token_init_scheme should be 'random', 'repeat_horizon' or 'sample_horizon', but got {cfg.multi_token_init_scheme}")
-        if cfg.prefix_token_sampler_scheme not in ("speculative_jacobi", "jacobi"):
-            raise ValueError(f"prefix_token_sampler_scheme: {cfg.prefix_token_sampler_scheme}")   # JL:1048
+        scheme_code(cfg.prefix_token_sampler_scheme)                                             # JL:1048
+        check_coupled(cfg.prefix_token_sampler_scheme, getattr(cfg, "noise_device", None))
         if cfg.max_num_new_tokens > self.Lmax:
             raise ValueError("max_num_new_tokens exceeds the engine's max_window")
         # the lenience factor of this decode: _fill_blob writes it beside the scheme into every blob, which is all a captured graph needs -- K4
@@ -409,12 +439,18 @@ class WindowLauncher:
             s.rs = torch.zeros(self.Lmax, self.V, dtype=torch.float32, device=dev)
             s.noise2 = torch.ones(1, self.V, dtype=torch.float32, device=dev)
 
-    def _observer_noise(self, s, gen, ph_off, n_rows, draws_rs):
-        """what the prompt's kernels generate, drawn by torch from the same generator state -- for observers only (the parity tests' hook)"""
+    def _observer_noise(self, s, gen, ph_off, n_rows, draws_rs, keyed=None):
+        """what the prompt's kernels generate, drawn by torch from the same generator state -- for observers only (the parity tests' hook).
+        keyed = (base, stride, kv_len): the coupled scheme's window -- row j holds the [1, V] exponential_ at offset base + (kv_len + j) * stride."""
         self._noise_tensors(s)
         gen.set_offset(ph_off)
         if getattr(self, "_greedy", False):
             s.noise[:n_rows].fill_(1.0)
+        elif keyed is not None:
+            base, stride, kv_len = keyed
+            for j in range(n_rows):
+                gen.set_offset(base + (kv_len + j) * stride)
+                s.noise[j:j + 1].exponential_(generator=gen)
         else:
             s.noise[:n_rows].exponential_(generator=gen)                 # == torch.multinomial (JL:118)
         if draws_rs:
@@ -534,7 +570,7 @@ class SJDEngine(WindowLauncher):
         host clock after the iteration's sync) per iteration."""
         self._check_config(cfg, [grammar])
         dev, B = self.device, self.B
-        scheme = 0 if cfg.prefix_token_sampler_scheme == "speculative_jacobi" else 1
+        scheme = scheme_code(cfg.prefix_token_sampler_scheme)
         do_cfg = cfg.do_cfg and (cfg.guidance_scale != 1)                          # JL:1005
         gen = None
         if cfg.seed is not None:                                                   # JL:1021-1023
@@ -582,7 +618,7 @@ class SJDEngine(WindowLauncher):
             if _TWO_STAGE and draws_rs:
                 resid = None
             two_stage = resid is None
-            self._fill_params(n_rows, kv_len, use_cfg, scheme, fresh, rules, resid or [], head_only=two_stage,
+            self._fill_params(n_rows, kv_len, use_cfg, loop.launch_scheme(scheme), fresh, rules, resid or [], head_only=two_stage,
                               philox=None if offs is None else (ph_blocks, ph_seed) + offs)
             # ---------------- noise tensors: only for host-drawn noise (the reference's CPU runs) and for observers ----------------
             e1, g_state = None, None
@@ -598,7 +634,7 @@ class SJDEngine(WindowLauncher):
                     g_state = gen.get_state()
                     self.noise2.copy_(torch.empty(1, self.V).exponential_(generator=gen))
             elif self.hook is not None:
-                self._observer_noise(self, gen, loop.ph_off, n_rows, draws_rs)
+                self._observer_noise(self, gen, loop.ph_off, n_rows, draws_rs, keyed=loop.keyed(scheme, kv_len))
                 e1 = self.noise[:n_rows]
             stats.host_seconds += time.perf_counter() - t_host0
             # ---------------- device work ----------------
@@ -670,7 +706,7 @@ class SJDEngine(WindowLauncher):
         torch.cuda.synchronize()
         check_reduce_timeouts()
         if philox:
-            gen.set_offset(loop.ph_off)                # leave the generator where the reference's draws would have left it
+            gen.set_offset(loop.end_offset())          # leave the generator where the reference's draws would have left it (coupled: behind the last position)
         stats.total_tokens, stats.total_seconds = len(X) - P, time.perf_counter() - t_decode0
         return X, stats
 

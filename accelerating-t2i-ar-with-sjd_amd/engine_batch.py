@@ -28,7 +28,7 @@ import torch
 from . import _lib as L
 from . import launch_shapes as LS
 from . import ops
-from .engine import SJDConfig, WindowLauncher, WindowSpec, cached_column_window, check_reduce_timeouts
+from .engine import SJDConfig, WindowLauncher, WindowSpec, cached_column_window, check_reduce_timeouts, scheme_code
 from .window_loop import PromptLoop
 
 
@@ -69,6 +69,12 @@ def per_prompt_configs(cfg, n_prompts):
     for j, c in enumerate(cfgs):
         if not isinstance(c, SJDConfig):
             raise ValueError(f"config of prompt {j} is {type(c).__name__}, not an SJDConfig")
+    names = [c.prefix_token_sampler_scheme for c in cfgs]
+    if "coupled_jacobi" in names and len(set(names)) > 1:
+        j = next(k for k, nm in enumerate(names) if nm != names[0])
+        raise ValueError(f"prefix_token_sampler_scheme='coupled_jacobi' cannot be mixed with another scheme in one decode_many (prompt 0 has {names[0]!r}, "
+                         f"prompt {j} has {names[j]!r}): the host keeps one noise bookkeeping for the lock-step iterations -- a position-keyed "
+                         "base and stride per prompt, or a cursor that advances per iteration")
     for f in dataclasses.fields(SJDConfig):
         if f.name in _PER_PROMPT_FIELDS:
             continue
@@ -307,7 +313,7 @@ class SJDBatchEngine(WindowLauncher):
         dev, nb = self.device, self.nb
         ph_blocks = ops.philox_max_blocks(dev)
         default_gen = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
-        scheme = 0 if cfg.prefix_token_sampler_scheme == "speculative_jacobi" else 1
+        scheme = scheme_code(cfg.prefix_token_sampler_scheme)
         do_cfg = cfg.do_cfg and (cfg.guidance_scale != 1)
         self._guidance = float(cfg.guidance_scale)
         prompt_seed = lambda j: cfgs[j].seed if cfgs is not None else (None if cfg.seed is None else cfg.seed + j)
@@ -377,7 +383,7 @@ class SJDBatchEngine(WindowLauncher):
             s.harvested, s.t_admit = False, time.perf_counter()
             self.pos_offset[i * nb:(i + 1) * nb].copy_(specs[j].pos_offset.to(device=dev, dtype=torch.int64))
             _, _, rules, _, _, use_cfg, _, offs = s.plan(cfg, s.grammar, s.cpu_gen, self.V, ph_blocks, greedy, scheme, do_cfg)
-            self._fill_blob(s.params, 1, s.kv_len, use_cfg, scheme, [], rules, [], (ph_blocks, s.ph_seed) + offs)
+            self._fill_blob(s.params, 1, s.kv_len, use_cfg, s.launch_scheme(scheme), [], rules, [], (ph_blocks, s.ph_seed) + offs)
             s.params.upload()
             if self.hook is not None:
                 self._observer_noise(s, s.gen, s.ph_off, 1, False)
@@ -431,7 +437,7 @@ class SJDBatchEngine(WindowLauncher):
             s.harvested = True
             s.stats.wall_seconds = time.perf_counter() - s.t_admit
             s.stats.tokens, s.stats.timed_nfe, s.stats.kv_len = len(s.X) - s.P, s.stats.nfe, s.kv_len
-            s.gen.set_offset(s.ph_off)                             # leave the generator where the reference's draws would have left it
+            s.gen.set_offset(s.end_offset())                       # leave the generator where the reference's draws would have left it (coupled: behind the last position)
             results[s.prompt_index] = (s.X, s.stats)
 
         # ---------------- iteration 0 of the first P prompts ----------------
@@ -490,13 +496,13 @@ class SJDBatchEngine(WindowLauncher):
                     rule_lists.append(rules)
                     if resid is None:                          # the grammar cannot name the residual rules before the launch
                         slow.append((s, win, len(metas)))
-                self._fill_blob(s.params, n_rows, s.kv_len, use_cfg, scheme, fresh, rules, resid or [], (ph_blocks, s.ph_seed) + offs)
+                self._fill_blob(s.params, n_rows, s.kv_len, use_cfg, s.launch_scheme(scheme), fresh, rules, resid or [], (ph_blocks, s.ph_seed) + offs)
                 metas.append([n_rows, rules, resid, use_cfg])
             self.params.upload()
             cols = cached_column_window(self, rule_lists) if rule_lists else None      # the union of the slots' output-head column windows
             if self.hook is not None:
                 for s in self.slots:
-                    self._observer_noise(s, s.gen, s.ph_off, s.n_rows, s.draws_rs)
+                    self._observer_noise(s, s.gen, s.ph_off, s.n_rows, s.draws_rs, keyed=s.keyed(scheme, s.kv_len))
             host_s += time.perf_counter() - t_h
             if slow:                                            # two stages: the missing residual rules are computed under the forward
                 logits = self._launch_forward(cols)

@@ -5,7 +5,7 @@ import torch
 from torch.nn import functional as F
 
 from . import launch_shapes as LS
-from .engine import lenience_field
+from .engine import check_coupled, lenience_field
 from .scheduler.logit_processor_3dim import TopKLogitsWarper, TopPLogitsWarper3d
 
 
@@ -186,6 +186,8 @@ class LlamaGenSolver:
         self.image_top_p = image_top_p
         # None: every draw on the model's device, as the reference does.  "cpu": the first-token draw and the SJD noise streams come
         # from CPU generators (the golden fixtures were produced by CPU runs of the reference)
+        # (a model renewed with prefix_token_sampler_scheme='coupled_jacobi' generates its noise in K2, by position: no host noise stream)
+        check_coupled(getattr(model, "prefix_token_sampler_scheme", "speculative_jacobi"), noise_device)
         self.noise_device = noise_device
 
     def create_logits_processor(self, top_k=None, top_p=None, temperature=None):
@@ -224,6 +226,9 @@ class LlamaGenSolver:
         (N, e_dim, h, w) of the latent; default: the codebook's width and a square of max_new_tokens codes.  With N > 1 every image is
         decoded on the batch engine's side stream as soon as its prompt ends, under the window forwards of the others."""
         model = self.model
+        scheme_name = getattr(model, "prefix_token_sampler_scheme", "speculative_jacobi")
+        check_coupled(scheme_name, self.noise_device)              # (the model may have been renewed since the solver was built)
+        lenience_field(self.lenience, scheme_name)
         if vq_model is not None:
             qzshape = self._qzshape(vq_model, qzshape, cond.shape[0], max_new_tokens)
         if cond.shape[0] > 1:

@@ -51,6 +51,14 @@ def philox_step(numel, max_blocks):
     return ((numel - 1) // (T * 4) + 1) * 4
 
 
+def philox_fill(numel, seed, offset, device, kind=1):
+    """-> fp32 [numel]: what K2 / K4 generate in place, written out -- the tensor torch would fill from a device generator at (seed, offset);
+    kind 1: exponential_(1), 0: uniform_(0, 1).  sjd_philox_fill (tests/test_gpu_philox.py holds it to torch bit for bit); observers and tests only."""
+    out = torch.empty(int(numel), dtype=torch.float32, device=device)
+    L.check(L.load().sjd_philox_fill(out.data_ptr(), int(numel), int(seed), int(offset), philox_max_blocks(device), int(kind), _stream()), "sjd_philox_fill")
+    return out
+
+
 _RULE_CACHE = {}
 
 

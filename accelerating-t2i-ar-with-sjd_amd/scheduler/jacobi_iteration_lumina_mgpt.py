@@ -24,7 +24,7 @@ import torch
 
 from .. import _lib as L
 from .. import ops
-from ..engine import SJDConfig, SJDEngine, WindowSpec, lenience_field
+from ..engine import SCHEME_CODES, SJDConfig, SJDEngine, WindowSpec, check_coupled, lenience_field, scheme_code
 from .logit_processor_3dim import (MultiTokensInterleavedTopKLogitsWarper, MultiTokensVLLogitsProcessor,
                                    get_double_cfg_input_ids, grammar_from_processors)
 
@@ -272,8 +272,8 @@ def renew_sampler(model_class):
             self.do_cfg = do_cfg
             self.prefix_token_sampler_scheme = prefix_token_sampler_scheme
             # LOSSY, off by default (1.0): the verify step accepts with min(1, lenience * p / q) (SJDConfig.lenience); refused here already
-            # when it is not a finite bf16 value >= 1 or comes with the plain Jacobi scheme
-            if prefix_token_sampler_scheme in ("speculative_jacobi", "jacobi"):
+            # when it is not a finite bf16 value >= 1 or comes with a scheme that verifies by token equality ('jacobi', 'coupled_jacobi')
+            if prefix_token_sampler_scheme in SCHEME_CODES:
                 lenience_field(lenience, prefix_token_sampler_scheme)
             self.lenience = float(lenience)
             self._init_doubled_attn_mask_cfg = _init_doubled_attn_mask_cfg
@@ -328,8 +328,10 @@ def renew_sampler(model_class):
             assert not getattr(generation_config, "return_dict_in_generate", False)       # JL:1164
             if input_ids.shape[0] != 1:
                 raise NotImplementedError("the reference supports one prompt per process (SURVEY.md Appendix B note 5)")
-            if self.prefix_token_sampler_scheme not in ("speculative_jacobi", "jacobi"):
-                raise ValueError(f"prefix_token_sampler_scheme: {self.prefix_token_sampler_scheme}")   # JL:1048
+            scheme_code(self.prefix_token_sampler_scheme)                                              # JL:1048
+            # 'coupled_jacobi' generates its noise in K2 by position: refused with a host noise stream before the cache or an engine is touched
+            check_coupled(self.prefix_token_sampler_scheme, getattr(self, "sjd_noise_device", None))
+            lenience_field(getattr(self, "lenience", 1.0), self.prefix_token_sampler_scheme)
             dev = input_ids.device
             do_cfg = bool(self.do_cfg) and (self.guidance_scale != 1)                                  # JL:1002-1005
             do_sample = bool(getattr(generation_config, "do_sample", True))                            # JL:969
@@ -387,8 +389,8 @@ def renew_sampler(model_class):
             detokenize: None, or a callable (prompt's ids, 1-d LongTensor on the device) -> image tensor, run on the engine's side stream as
             each prompt ends (SJDBatchEngine.decode_many); the return value is then (ids [N, tokens], [N images in prompt order])."""
             from ..engine_batch import SJDBatchEngine
-            if self.prefix_token_sampler_scheme not in ("speculative_jacobi", "jacobi"):
-                raise ValueError(f"prefix_token_sampler_scheme: {self.prefix_token_sampler_scheme}")
+            scheme_code(self.prefix_token_sampler_scheme)
+            lenience_field(getattr(self, "lenience", 1.0), self.prefix_token_sampler_scheme)
             if getattr(self, "sjd_noise_device", None) is not None:
                 raise ValueError("several prompts per forward draw their noise in the kernels: noise_device must be None (decode one prompt "
                                  "per call to replay a CPU noise stream)")

@@ -13,6 +13,8 @@ import torch
 from . import ops
 from .grammar import spatial_fresh_tokens
 
+COUPLED = 2          # engine.SCHEME_CODES["coupled_jacobi"]: K2 keys a row's noise by its position (include/sjd_hip.h)
+
 
 @dataclass
 class DecodeStats:
@@ -45,6 +47,9 @@ class PromptLoop:
         self.carried, self.carried_amax, self.last_amax = [], [], None
         self.first, self.finished = True, False
         self.ph_seed, self.ph_off = ph_seed, ph_off
+        # the coupled scheme (code 2): the offset of position 0's noise -- the generator's right behind the prefill's first-token draw, fixed for
+        # the whole decode -- and the step from one position to the next; None until the prefill iteration was absorbed / in the other schemes
+        self.ph_base, self.ph_stride = None, 0
         self.n_rows, self.ph_step, self.k2_step, self.ph_row, self.draws_rs = 1, 0, 0, 0, False      # the last plan's
         self.stats = DecodeStats()
 
@@ -78,6 +83,13 @@ class PromptLoop:
         self.n_rows, self.draws_rs = n_rows, n_rows > 1 and scheme == 0
         if ph_blocks is None:
             return n_rows, fresh, rules, win, resid, use_cfg, self.draws_rs, None
+        if scheme == COUPLED and not self.first:
+            # position-keyed noise: K2 takes row j's from offset base + (kv_len + j) * stride (word 0 the base, word 1 the stride, word 2 unused);
+            # nothing is consumed per iteration, the cursor stays where the prefill left it
+            if self.ph_base is None:
+                self.ph_base, self.ph_stride = self.ph_off, 0 if greedy else ops.philox_step(V, ph_blocks)
+            self.ph_step = self.k2_step = self.ph_row = 0
+            return n_rows, fresh, rules, win, resid, use_cfg, False, (self.ph_base, ops.philox_step(V, ph_blocks), 0)
         # what torch would consume: an [n, V] multinomial (greedy: sampling_logits2tokens draws nothing, JL:127-129), an [n, V] rand and --
         # only after a rejection -- the [1, V] residual multinomial
         self.ph_step = step = ops.philox_step(n_rows * V, ph_blocks)
@@ -85,6 +97,21 @@ class PromptLoop:
         self.ph_row = ops.philox_step(V, ph_blocks) if self.draws_rs else 0
         off = self.ph_off
         return n_rows, fresh, rules, win, resid, use_cfg, self.draws_rs, (off, off + k2, off + k2 + step)
+
+    def launch_scheme(self, scheme):
+        """the scheme code of the NEXT iteration's blob.  The coupled scheme's prefill iteration carries code 1: its one row is the first-token draw,
+        which stays the per-launch draw at the generator's own offset that every scheme makes (K4 short-circuits at n <= 1 whatever the code)."""
+        return 1 if scheme == COUPLED and self.ph_base is None else scheme
+
+    def keyed(self, scheme, kv_len):
+        """(base, stride, kv_len) of a coupled window iteration, None for anything else (the engines' observer noise)"""
+        return (self.ph_base, self.ph_stride, kv_len) if scheme == COUPLED and self.ph_base is not None else None
+
+    def end_offset(self):
+        """where the prompt's device generator is left when the decode ends: the cursor, or -- coupled -- behind the noise of the last position that
+        emitted a token (cache row kv_len - 1), base + kv_len * stride, so that no later draw of the generator reuses noise a token came from.  It
+        depends on the emitted sequence alone, not on the window.  (A greedy decode drew nothing: the stride is 0 and the base comes back.)"""
+        return self.ph_off if self.ph_base is None else self.ph_base + self.kv_len * self.ph_stride
 
     def absorb(self, m_dev, rejected, tokens, amax, win_len, cfg, grammar):
         """The read-back of the planned iteration: K4's accept length and rejection flag, the corrected tokens and the modes of the target

@@ -49,11 +49,15 @@ def parse_args(argv=None):
     ap.add_argument("--lenience", type=float, default=1.0,
                     help="accept a draft with min(1, LENIENCE * p / q) in the verify step (LOSSY, opt-in; 1 is the exact rule; >= 1 and exactly a bf16 value, "
                          "e.g. 1.25, 1.5, 2, 4; more tokens per step, image quality on a real checkpoint is not measured)")
+    ap.add_argument("--scheme", default="speculative_jacobi", choices=["speculative_jacobi", "jacobi", "coupled_jacobi"],
+                    help="the verify step: speculative_jacobi (default); jacobi (token equality, per-iteration noise); coupled_jacobi (token equality, "
+                         "sampling noise keyed by the token's position: lossless, and the image of a --seed does not depend on --window or on the "
+                         "labels sharing a forward)")
     ap.add_argument("--out", default="sample.png")
     a = ap.parse_args(argv)
     try:
         from sjd_amd.engine import lenience_field
-        lenience_field(a.lenience)
+        lenience_field(a.lenience, a.scheme)
     except ValueError as e:
         ap.error(f"--lenience: {e}")
     if a.weights and not a.fused:
@@ -115,7 +119,7 @@ def main():
     one_scale = a.cfg_scale if isinstance(a.cfg_scale, float) else a.cfg_scale[0]        # (a scale per label: this one only says "CFG on")
     jac = dict(jacobi_loop_interval_l=1, jacobi_loop_interval_r=latent ** 2 - a.window - 2, max_num_new_tokens=a.window,
                guidance_scale=one_scale, seed=a.seed, multi_token_init_scheme="random", do_cfg=True, image_top_k=a.top_k,
-               text_top_k=10, prefix_token_sampler_scheme="speculative_jacobi")
+               text_top_k=10, prefix_token_sampler_scheme=a.scheme)
     gpt.__class__ = renew_llamagen(gpt.__class__)
     gpt._init_new_params(**jac)
     gpt.__class__ = renew_sampler(gpt.__class__)

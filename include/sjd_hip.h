@@ -151,12 +151,20 @@ typedef struct sjd_iter_params {
     int32_t n_rows;                 /* window length n of this iteration (1..SJD_MAX_WINDOW) */
     int32_t kv_len;                 /* cache rows already valid before this window */
     int32_t use_cfg;                /* 1: z = g*(c-u)+u ; 0: z = c  (check_is_force_no_cfg, JL:70-80) */
-    int32_t scheme;                 /* bits 0-7 (SJD_SCHEME_OF): 0: speculative_jacobi ; 1: jacobi.  Bits 16-31 (SJD_LENIENCE_BITS_OF): the
+    int32_t scheme;                 /* bits 0-7 (SJD_SCHEME_OF): 0: speculative_jacobi ; 1: jacobi ; 2: coupled_jacobi -- for sjd_verify_accept*
+                                       exactly scheme 1 (token equality, no residual, no noise read, the lenience field ignored, n_rows <= 1
+                                       short-circuits), for sjd_logits_to_probs_sample* (every form: dense, _part, _slots, _slots_g; each slot
+                                       its own blob) with philox_blocks > 0 the noise of window row j is keyed by its POSITION t = kv_len + j:
+                                       the elements of a [1, V] exponential_ (element = column, the generator form of the residual row) at
+                                       offset philox_offset[0] + t * philox_offset[1].  The draw at a position is then a function of that
+                                       position's distribution alone, whatever window, iteration or batch the row stands in; rules, CFG, top-k,
+                                       top-p, temperature, forced rows, amax and the zero state are untouched.  With philox_blocks == 0 K2 reads
+                                       the noise tensor it is handed, as in every scheme.  Bits 16-31 (SJD_LENIENCE_BITS_OF): the
                                        lenience factor lambda >= 1 of the verify step as the UPPER HALF of its fp32 pattern (its bf16 bits); 0
                                        means 1.0, so a blob that never sets the field is the exact rule.  LOSSY and opt-in: sjd_verify_accept*
                                        on (p, q, lambda) is by definition the exact rule on (p, q') with q' = fp32(q / lambda) per element --
                                        accept u < min(1, p(x) / q'(x)), residual norm(max(p - q', 0)), an implicit one-hot draft row 1 / lambda
-                                       at x.  Scheme 1 ignores the field.  Every other reader takes SJD_SCHEME_OF only. */
+                                       at x.  Schemes 1 and 2 ignore the field.  Every other reader takes SJD_SCHEME_OF only. */
     int32_t n_fresh;                /* trailing window rows filled with fresh random ids */
     int32_t batch_rows;             /* several prompts per launch: 0 = this blob governs every batch row; > 0 = `params` points at a
                                        contiguous ARRAY of blobs and blob i governs batch rows [i*batch_rows, (i+1)*batch_rows) of K1 /
@@ -167,9 +175,13 @@ typedef struct sjd_iter_params {
                                                      with the seed / offsets below (Philox4x32-10, csrc/sjd_philox.h); the value is the
                                                      grid cap of ATen's launch, multiProcessorCount * (maxThreadsPerMultiProcessor / 256) */
     uint64_t philox_seed;                         /* torch.Generator.initial_seed() */
-    uint64_t philox_offset[3];                    /* the generator's offset before (0) the [n_rows, V] exponential_ of the multinomial
+    uint64_t philox_offset[3];                    /* schemes 0 and 1: the generator's offset before (0) the [n_rows, V] exponential_ of the multinomial
                                                      (JL:118), (1) the [1, n_rows, V] rand of the accept test (JL:260), (2) the [1, V]
-                                                     exponential_ of the residual multinomial (JL:237) */
+                                                     exponential_ of the residual multinomial (JL:237).
+                                                     Scheme 2: (0) the BASE, the offset of position 0's noise, fixed for the whole decode
+                                                     (the host takes the generator's offset right behind the prefill's first-token draw);
+                                                     (1) the STRIDE from one position to the next, sjd_philox_offset_increment(V,
+                                                     philox_blocks), written by the host; (2) unused, 0.  Both multiples of 4. */
     int64_t fresh_tok[SJD_MAX_WINDOW];            /* random re-guess ids (host global RNG, JL:505-509), packed */
     sjd_row_rule rules[SJD_MAX_WINDOW];           /* rules of the sampling call, row j */
     sjd_row_rule resid_rules[SJD_MAX_WINDOW];     /* rule of the residual call if rejection happens at i=j+1 */
