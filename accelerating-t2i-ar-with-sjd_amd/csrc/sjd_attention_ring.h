@@ -260,7 +260,10 @@ __global__ __launch_bounds__(64 * NWV) void k1_partial_ring(
             for (int i = 0; i < 4; ++i) pw[i] = k1_cvt_pk<DT>(pv[2 * i], pv[2 * i + 1]);
             const vec pfrag = as_frag<vec>(pw);
 #endif
-            // the running output is rescaled only when some row's maximum moved (alpha == 1 exactly otherwise: 2^0)
+            // the running output is rescaled only where alpha != 1.  NOT "whenever the maximum stayed": fma(m, c1, -fl(m c1)) is the rounding
+            // error delta of m c1, so alpha (and the maximum's own probability) is 2^delta, |delta| <= ulp(m c1) / 2, and exactly 1 only when
+            // m c1 is representable.  Numerator and l_run take the same factor, so one dominant key is unaffected; keys of tiles that lie T tiles
+            // apart are weighted 2^(T delta) against each other -- below 130 * 2^-19 at the |m c1| < 64 of real scores (tests/attention_probe_cases.py).
             const bool rescale = __builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0ull;
             if (rescale) {
 #pragma unroll

@@ -95,7 +95,8 @@ def attention_fp64(q, kc, vc, kv_len, n_rows, key_start, dtype=None):
     The bound restates the kernel's rounding points: scores and the softmax sum are fp32, each probability is rounded ONCE to the 16-bit
     MFMA operand type before P.V (relative error <= u = 2^-8 bf16 / 2^-11 fp16), the output is rounded once more, so element by element
         |out - exact| <= u * 1.05 * (sum_j p_j |v_jd| + |exact_d|) + 2e-6     (+ fp16: N * 2^-25 max|v| for subnormal probabilities)
-    -- about two output ulps; a wrong tile edge, mask bit, split merge or another slot's kv_len is orders of magnitude above it."""
+    -- about two output ulps.  Measured on Gaussian operands (tests/test_attention_probe_cases.py): a dropped 32-key tile puts about two thirds
+    of the output elements beyond it, ONE wrong key at the causal edge 2-4 % of them; tests/test_gpu_attention_probes.py holds K1 to exact answers."""
     dtype = dtype or q.dtype
     nb, _, H, D = q.shape
     Hkv = kc.shape[1]

@@ -334,8 +334,9 @@ def test_k1_k3_attention(dev, case, n_split):
     assert (got[~vis] == 0).all()
     # The kernel's rounding points restated (the fp8 test does the same for its P): scores and the softmax sum are
     # fp32, each probability is rounded ONCE to the 16-bit MFMA operand type before P.V, the output is rounded once more -- the element-wise
-    # bound of tests/blob_array_cases.py::attention_fp64 (about two output ulps; a wrong tile edge, mask bit or split merge is orders of
-    # magnitude above it, where the 3e-2 above would hide it).
+    # bound of tests/blob_array_cases.py::attention_fp64 (about two output ulps, where the 3e-2 above would hide every such error; measured on
+    # these inputs, a dropped 32-key tile puts two thirds of the elements beyond it and one wrong key at the causal edge 2-4 % of them -- the
+    # exact probes of tests/test_gpu_attention_probes.py name the key).
     exact, bound, _ = attention_fp64(q, ref_cache.k[0], ref_cache.v[0], kv_len, n, key_start, dtype)
     e = (got.double() - exact).abs()
     over = e > bound
