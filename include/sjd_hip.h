@@ -273,7 +273,9 @@ int sjd_logits_to_probs_sample_ex(const float *logits_c, const float *logits_u, 
  * (reference modeling_chameleon.py:1560-1561 computes 16-bit logits, then .float()).  Cond rows are part rows [0, max_rows), uncond
  * rows [urow_off, urow_off + max_rows) (urow_off <= 0: never CFG).  Everything after the load -- CFG combine, grammar, top-k / top-p,
  * softmax, draw -- is sjd_logits_to_probs_sample's code, so results are bit-identical to feeding it those logits.
- * dbg_c / dbg_u (optional, [max_rows, V] fp32): receive the derived logits of the columns inside each row's rule window (tests). */
+ * dbg_c / dbg_u (optional, [max_rows, V] fp32): receive the derived logits of the columns inside each row's rule window (tests); where
+ * sjd_head_combine runs first it writes them instead, for every column of the head's window below V.  dbg_u is written only when the launch
+ * combines (urow_off > 0 and params->use_cfg); rows >= params->n_rows are never written. */
 typedef struct sjd_head_partials {
     const float *part;              /* [n_chunks][prows][n_cols] fp32 */
     int32_t n_chunks;
